@@ -3,15 +3,19 @@
 
     python bench.py --gpus N --steps K --warmup W            # N > 1 without a launcher: bench.py starts its own N ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py --full                                   # + device-only figure, per-kernel roofline, CPU baselines
+    python bench.py --dump-outputs DIR                       # + the last timed step's outputs as DIR/<name>.npy
 
-A step = one pass of the hot path over one batch of synthetic 1080p frames already resident in HBM.  The line carries two
-measurements of the same batch:
+A step = one pass of the hot path over one batch of synthetic 1080p frames already resident in HBM (the same frames and weights
+on every run with the same arguments).
   value (value_kind "end_to_end", BASELINE.json's metric): K1 (frame -> bit image) -> speck filter -> D2H -> host contour corner
       search -> K2 (frame + homography -> 81 cells) -> K3 (cells -> logits, digits), software-pipelined over chunks of the batch
-      (sudoku-vision_amd/pipeline.py FramePipeline).  Three timed regions of exactly K steps each, every one bracketed by
-      barrier + synchronize, MAX over ranks; value and ms_per_step are the median region's and all three are listed.
-  value_device_only + roofline + kernels: K1 + K2 + K3 with the generator's corners (no host work in the timed region), K steps,
-      every hot kernel bracketed by HIP events on its launch stream inside the library.
+      (sudoku-vision_amd/pipeline.py FramePipeline).  One timed region of exactly K steps after W warm-up steps (and at least
+      1 s of them) and one untimed region like it, bracketed by barrier + synchronize, MAX over ranks; ms_per_step = that region / K.
+      --full: three timed regions of K steps each; value and ms_per_step are the median region's and all three are listed.
+  --full also measures value_device_only + roofline + kernels: K1 + K2 + K3 with the generator's corners (no host work in the
+      timed region), K steps, every hot kernel bracketed by HIP events on its launch stream inside the library; and the CPU
+      baselines.  --no-e2e: value = the device-only figure (per-kernel events and roofline still only with --full).
 
 Workloads
   configs1 (default)  BASELINE.json configs[1] per GPU: 256 synthetic 1080p frames per step, f32-grade CNN.
@@ -126,6 +130,31 @@ def cpu_baseline(frames_host, corners, sd, threads):
                       "C oracle K1+K2, one frame per thread, + torch-CPU DigitCNN on the same threads"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, out, res_e2e, rank):
+    """--dump-outputs: what a caller of the timed path receives for its last step, as DIR/<name>.npy in float32 (rank r > 0: <name>.rank<r>.npy).
+    Every step covers the whole resident pool, so after the timed steps `out` holds the last step's result for every pool frame.  End to end:
+    logits, digits, conf and the host search's corners and found flags; device-only (--no-e2e): logits, digits, conf.  Above 64 MB in all,
+    a fixed seeded sample of the frames is written instead, and its frame indices as frame_index.npy."""
+    import numpy as np
+    arrays = {k: out[k].cpu().numpy() for k in ("logits", "digits", "conf")}
+    if res_e2e is not None:
+        arrays["corners"], arrays["found"] = res_e2e["corners"], res_e2e["found"]
+    arrays = {k: v.astype(np.float32) for k, v in arrays.items()}
+    n = arrays["logits"].shape[0]
+    per_frame = sum(v[0].nbytes for v in arrays.values())
+    if n * per_frame > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.RandomState(0).choice(n, DUMP_LIMIT_BYTES // (per_frame + 4), replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["frame_index"] = idx.astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), v)
+
+
 def rank_identity(rank, local_rank, device_index):
     """What the driver needs to see that N ranks sat on N distinct GPUs: torch's device name, PCI address and UUID of this rank's GPU."""
     import torch
@@ -143,13 +172,19 @@ def main():
     ap.add_argument("--frames", type=int, default=256, help="frames in each GPU's resident pool (= frames per GPU per step in configs1)")
     ap.add_argument("--workload", choices=["configs1", "configs3"], default="configs1")
     ap.add_argument("--total-frames", type=int, default=100_000, help="configs3: frames dealt round-robin over the ranks per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--precision", choices=["f32", "bf16"], default="f32",
                     help="f32 = BASELINE configs[1] (headline); bf16 = configs[4]: conv2/fc1 on bf16 MFMA, digit-index parity only")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end measurement: value = the device-only figure, value_kind says so")
     ap.add_argument("--e2e-passes", type=int, default=None, help="deprecated: 0 = --no-e2e")
     ap.add_argument("--chunk", type=int, default=None, help="end-to-end pipeline: frames per chunk (default: largest of 256, 128, 64, ... dividing --frames)")
     ap.add_argument("--depth", type=int, default=None, help="end-to-end pipeline: chunks in flight")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the device-only measurement with per-kernel times and roofline, three end-to-end regions "
+                         "of `steps` steps each (value = the median one), the CPU baselines.  Without it a run times `steps` steps of the headline "
+                         "path once and reports that")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 100 if args.workload == "configs1" else 1
@@ -224,28 +259,32 @@ def main():
         torch.cuda.synchronize()
 
     # ---- device-only: the kernels' own rates (roofline) ------------------------------------------------------------------------------
-    # clock ramp: an idle MI355X needs some tens of milliseconds of load before it runs at its sustained clock (12 steps from idle run
-    # ~13 % slower than the same steps after 100 ms of load) -- untimed steps of the same work, before and apart from the W warm-up steps
-    preroll = 0
-    t_ramp = time.perf_counter()
-    while time.perf_counter() - t_ramp < 0.1:
-        batch(n)
-        torch.cuda.synchronize()
-        preroll += 1
-    for _ in range(args.warmup):
-        step()
-    barrier()
-    ctx.timing_begin()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    barrier()
-    elapsed_dev = time.perf_counter() - t0
-    per_kernel = ctx.timing_end()
-    elapsed_dev = sharding.max_over_ranks(elapsed_dev)
+    # --full, or the headline itself under --no-e2e; per-kernel HIP events only under --full
+    elapsed_dev, per_kernel, preroll = None, None, 0
+    if args.full or args.no_e2e:
+        # clock ramp: an idle MI355X needs some tens of milliseconds of load before it runs at its sustained clock (12 steps from idle run
+        # ~13 % slower than the same steps after 100 ms of load) -- untimed steps of the same work, before and apart from the W warm-up steps
+        t_ramp = time.perf_counter()
+        while time.perf_counter() - t_ramp < 0.1:
+            batch(n)
+            torch.cuda.synchronize()
+            preroll += 1
+        for _ in range(args.warmup):
+            step()
+        barrier()
+        if args.full:
+            ctx.timing_begin()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        elapsed_dev = time.perf_counter() - t0
+        if args.full:
+            per_kernel = ctx.timing_end()
+        elapsed_dev = sharding.max_over_ranks(elapsed_dev)
 
     # ---- end to end (BASELINE's metric): the same steps with the host corner search in the loop -----------------------------------
-    e2e = None
+    e2e = res_e2e = None
     if not args.no_e2e:
         from sudoku_vision_amd.pipeline import FramePipeline, host_cpu_budget
         # the box's CPU share is 16 cores per GPU, enforced as a cgroup quota: stay two under it (this thread + the HIP runtime's)
@@ -262,75 +301,37 @@ def main():
         pipe.run(frames, out=out, total=max(n, min(mine, n) * args.warmup))
         while time.perf_counter() - t_w < 1.0 and args.warmup > 0:
             pipe.run(frames, out=out, total=max(n, min(mine, 8 * n)))
-        # three timed regions of exactly K steps; value = their median and all three are listed: on a shared host a region now and then
-        # contains a 40-60 ms stall of one search call (tools/dev/search_outliers.py: with or without GPU work in flight), which says
-        # nothing about the pipeline
+        # --full: three timed regions of exactly K steps; value = their median and all three are listed: on a shared host a region now and
+        # then contains a 40-60 ms stall of one search call (tools/dev/search_outliers.py: with or without GPU work in flight), which says
+        # nothing about the pipeline.  Otherwise one timed region of exactly K steps, after one untimed region of the same kind: the first
+        # region after the warm-up runs slow whatever the warm-up's length (20 steps: 139-143 k frames/s against 198 k for the next ones,
+        # after 1 s or 2 s of warm-up alike), so it is streamed untimed, at most 100 pool passes' worth of frames of it
+        if not args.full:
+            barrier()
+            pipe.run(frames, out=out, total=mine * max(1, min(args.steps, 100 * n // mine)))
         regions = []
-        for _ in range(3):
+        for _ in range(3 if args.full else 1):
             barrier()
             t1 = time.perf_counter()
             res_e2e = pipe.run(frames, out=out, total=mine * args.steps)     # K steps streamed back to back, pipeline kept full
             barrier()
             regions.append(sharding.max_over_ranks(time.perf_counter() - t1))
-        dt = sorted(regions)[1]
+        dt = sorted(regions)[len(regions) // 2]
         seen = min(n, mine * args.steps)
         err = np.abs(res_e2e["corners"][:seen].astype(np.float32)[:, :, None, :] - corners[:seen, None, :, :]).sum(-1).min(-1).max()
         e2e = {"value": frames_per_step_job * args.steps / dt, "unit": "frames/s", "ms_per_step": dt / args.steps * 1e3, "host_threads_per_gpu": host_threads,
-               "regions": [frames_per_step_job * args.steps / t for t in regions], "aggregate": "median of three timed regions of `steps` steps each",
+               "regions": [frames_per_step_job * args.steps / t for t in regions],
+               "aggregate": "median of three timed regions of `steps` steps each" if args.full else "one timed region of `steps` steps",
                "grids_found": int(res_e2e["found"][:seen].sum()), "of": seen, "max_corner_error_px": float(err),
                "dense_fallbacks": pipe.dense_fallbacks, "note": pipe.describe()}
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, res_e2e, rank)
+
     if rank == 0:
         total_frames = frames_per_step_job * args.steps
-        fps_dev = total_frames / elapsed_dev
-        launched = frames_per_step_rank * args.steps               # frames rank 0 pushed through each kernel in the timed region
+        fps_dev = total_frames / elapsed_dev if elapsed_dev is not None else None
         conv_info = ctx.conv_kernel_info()
-        per_frame = {"k_preprocess": ("hbm", K1_BYTES_PER_FRAME), "k_warp_cells": ("hbm", K2_BYTES_PER_FRAME),
-                     "k_conv_features": ("mfma", CONV_FLOP_PER_CELL * 81), "k_fc_head": ("mfma", FC_FLOP_PER_CELL * 81)}
-        kernels = {}
-        for name, (ms, cnt) in per_kernel.items():
-            if not cnt or name not in per_frame:                    # a kernel id this script has no price for (e.g. the fused launch) is not on this path
-                continue
-            bound, units = per_frame[name]
-            avg = ms / cnt * 1e-3                                   # average launch duration (HIP events on the launch stream)
-            per_launch = units * launched / cnt                     # algorithmic bytes / FLOPs of an average launch
-            peak = HBM_PEAK if bound == "hbm" else (BF16_MFMA_PEAK if args.precision == "bf16" else FP32_MFMA_PEAK)
-            ach = per_launch / avg
-            scale = 1e9 if bound == "hbm" else 1e12
-            kernels[name] = {"bound": bound, "avg_ms": ms / cnt, "launches": cnt, "achieved": ach / scale, "peak": peak / scale,
-                             "unit": "GB/s" if bound == "hbm" else "TFLOP/s", "frac": ach / peak}
-        if args.precision == "f32":
-            # `frac` of the CNN kernels is priced on the FLOPs they ISSUE on the pipe they issue them on; the direct f32 convolution /
-            # matrix product the algorithmic figure counts is kept beside it as the f32-equivalent rate
-            conv_f, fc_f, pipe_peak = issued_flop_per_cell(conv_info)
-            for name, per_cell in (("k_conv_features", conv_f), ("k_fc_head", fc_f)):
-                if name not in kernels:
-                    continue
-                k = kernels[name]
-                k["algorithmic_equiv"], k["algorithmic_equiv_frac_of_f32_peak"] = k["achieved"], k["frac"]
-                issued = per_cell * 81 * launched / k["launches"] / (k["avg_ms"] * 1e-3)
-                k["achieved"], k["peak"], k["frac"] = issued / 1e12, pipe_peak / 1e12, issued / pipe_peak
-                k["issued_flop_per_cell"], k["algo"] = per_cell, conv_info["name"]
-                k["pipe"] = "v_mfma_f32_16x16x32_f16" if conv_info["mfma_f16_conv"] else "v_mfma_f32_16x16x4_f32"
-        dom = max(kernels, key=lambda k: kernels[k]["avg_ms"])
-        # HBM bytes per launch from the PMC counters (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, corrected as
-        # MI355X_MICROARCH.md prescribes).  NOT measured in this run: read from profiles/pmc_traffic.json, which tools/pmc_traffic.py
-        # writes from a rocprofv3 run of this same command at 256 frames -- traffic_source says which
-        traffic, traffic_source, tf = None, None, os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tf) and n == 256 and args.workload == "configs1":
-            pmc = json.load(open(tf))
-            sect = pmc if args.precision == "f32" else pmc.get("bf16", {})
-            traffic = sect.get(dom, {}).get("hbm_bytes_per_launch")
-            for k in kernels:
-                kernels[k]["traffic"] = sect.get(k, {}).get("hbm_bytes_per_launch")
-            traffic_source = ("profiles/pmc_traffic.json: " + str(pmc.get("_source", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `python bench.py` at 256 frames"))
-                              + " -- a constant from that profile, not measured by this run")
-        roofline = {"kernel": dom, **{k: kernels[dom][k] for k in ("bound", "achieved", "peak", "unit", "frac")}, "traffic": traffic,
-                    "traffic_source": traffic_source, "measured_in": "device-only steps of this run (HIP events on the launch stream)"}
-        if "algorithmic_equiv" in kernels[dom]:
-            roofline.update({k: kernels[dom][k] for k in ("algorithmic_equiv", "algorithmic_equiv_frac_of_f32_peak", "issued_flop_per_cell", "algo", "pipe")})
-            roofline["note"] = ("achieved/frac = FLOPs the kernel issues on its matrix pipe / kernel time / that pipe's dense peak; algorithmic_equiv = the direct "
-                                "f32 convolution / matrix product's FLOPs (SURVEY 8d) / kernel time")
         cfg_id = 3 if args.workload == "configs3" else (1 if args.precision == "f32" else 4)
         if args.workload == "configs3":
             wl = (f"configs[3]: {args.total_frames} synthetic 1080p frames per step dealt round-robin over {world} GPU(s) (frame i -> rank i mod N), "
@@ -343,28 +344,80 @@ def main():
         fps = e2e["value"] if e2e else fps_dev
         res = {
             "metric": "end-to-end frames/sec (1080p->81 digits)" if e2e else "frames/sec (1080p->81 digits), device-only",
-            "value": fps, "value_kind": "end_to_end" if e2e else "device_only",
-            "value_device_only": fps_dev, "value_end_to_end": e2e["value"] if e2e else None, "unit": "frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "clock_ramp_steps_before_warmup": preroll,
-            "ms_per_step": e2e["ms_per_step"] if e2e else elapsed_dev / args.steps * 1e3, "ms_per_step_device_only": elapsed_dev / args.steps * 1e3,
+            "value": fps, "value_kind": "end_to_end" if e2e else "device_only", "unit": "frames/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": e2e["ms_per_step"] if e2e else elapsed_dev / args.steps * 1e3,
             "higher_is_better": True, "scaling": "strong" if args.workload == "configs3" else "weak", "vs_baseline": None,
-            "dtype": args.precision, "data": "synthetic",
+            "dtype": args.precision, "data": "synthetic", "full": args.full,
             "arithmetic": (conv_info["name"] + "; logits within 1e-4 of the PyTorch-CPU f32 model (measured ~1e-6), digits equal"
                            if args.precision == "f32" else "bf16 operands, f32 accumulation; digit-index parity only"),
             "config": {"workload": wl, "frames_per_gpu": n if args.workload == "configs1" else frames_per_step_rank,
                        "frames_per_step": frames_per_step_job, "height": H, "width": W, "weights": "random-init DigitCNN (seed 1234)",
                        "parallelism": f"frames sharded over {world} GPU(s), one process per GPU, no data-path collective (gloo barrier for timing only)"},
-            "per_gpu_value": fps / world, "per_gpu_value_device_only": fps_dev / world,
+            "per_gpu_value": fps / world,
             "ranks": ranks,
-            "roofline": roofline,
-            "kernels": kernels,
-            "pipeline_hbm_frac": fps_dev / world * BYTES_PER_FRAME / HBM_PEAK,
             "end_to_end_with_host_corner_search": e2e,
-            # whole-step view of the CNN's ALGORITHMIC (f32-equivalent) FLOPs against the f32 MFMA peak -- a context figure, not a roofline
-            # fraction: the default kernels do this arithmetic on the f16 pipe (their own fractions are in "kernels", priced on issued FLOPs)
-            "pipeline_algorithmic_cnn_flops_vs_f32_mfma_peak": fps_dev / world * 81 * (CONV_FLOP_PER_CELL + FC_FLOP_PER_CELL) / FP32_MFMA_PEAK,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if elapsed_dev is not None:
+            res.update({"value_device_only": fps_dev, "value_end_to_end": e2e["value"] if e2e else None, "clock_ramp_steps_before_warmup": preroll,
+                        "ms_per_step_device_only": elapsed_dev / args.steps * 1e3, "per_gpu_value_device_only": fps_dev / world})
+        if args.full:
+            launched = frames_per_step_rank * args.steps               # frames rank 0 pushed through each kernel in the timed region
+            per_frame = {"k_preprocess": ("hbm", K1_BYTES_PER_FRAME), "k_warp_cells": ("hbm", K2_BYTES_PER_FRAME),
+                         "k_conv_features": ("mfma", CONV_FLOP_PER_CELL * 81), "k_fc_head": ("mfma", FC_FLOP_PER_CELL * 81)}
+            kernels = {}
+            for name, (ms, cnt) in per_kernel.items():
+                if not cnt or name not in per_frame:                    # a kernel id this script has no price for (e.g. the fused launch) is not on this path
+                    continue
+                bound, units = per_frame[name]
+                avg = ms / cnt * 1e-3                                   # average launch duration (HIP events on the launch stream)
+                per_launch = units * launched / cnt                     # algorithmic bytes / FLOPs of an average launch
+                peak = HBM_PEAK if bound == "hbm" else (BF16_MFMA_PEAK if args.precision == "bf16" else FP32_MFMA_PEAK)
+                ach = per_launch / avg
+                scale = 1e9 if bound == "hbm" else 1e12
+                kernels[name] = {"bound": bound, "avg_ms": ms / cnt, "launches": cnt, "achieved": ach / scale, "peak": peak / scale,
+                                 "unit": "GB/s" if bound == "hbm" else "TFLOP/s", "frac": ach / peak}
+            if args.precision == "f32":
+                # `frac` of the CNN kernels is priced on the FLOPs they ISSUE on the pipe they issue them on; the direct f32 convolution /
+                # matrix product the algorithmic figure counts is kept beside it as the f32-equivalent rate
+                conv_f, fc_f, pipe_peak = issued_flop_per_cell(conv_info)
+                for name, per_cell in (("k_conv_features", conv_f), ("k_fc_head", fc_f)):
+                    if name not in kernels:
+                        continue
+                    k = kernels[name]
+                    k["algorithmic_equiv"], k["algorithmic_equiv_frac_of_f32_peak"] = k["achieved"], k["frac"]
+                    issued = per_cell * 81 * launched / k["launches"] / (k["avg_ms"] * 1e-3)
+                    k["achieved"], k["peak"], k["frac"] = issued / 1e12, pipe_peak / 1e12, issued / pipe_peak
+                    k["issued_flop_per_cell"], k["algo"] = per_cell, conv_info["name"]
+                    k["pipe"] = "v_mfma_f32_16x16x32_f16" if conv_info["mfma_f16_conv"] else "v_mfma_f32_16x16x4_f32"
+            dom = max(kernels, key=lambda k: kernels[k]["avg_ms"])
+            # HBM bytes per launch from the PMC counters (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, corrected as
+            # MI355X_MICROARCH.md prescribes).  NOT measured in this run: read from profiles/pmc_traffic.json, which tools/pmc_traffic.py
+            # writes from a rocprofv3 run of this same command at 256 frames -- traffic_source says which
+            traffic, traffic_source, tf = None, None, os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tf) and n == 256 and args.workload == "configs1":
+                pmc = json.load(open(tf))
+                sect = pmc if args.precision == "f32" else pmc.get("bf16", {})
+                traffic = sect.get(dom, {}).get("hbm_bytes_per_launch")
+                for k in kernels:
+                    kernels[k]["traffic"] = sect.get(k, {}).get("hbm_bytes_per_launch")
+                traffic_source = ("profiles/pmc_traffic.json: " + str(pmc.get("_source", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `python bench.py` at 256 frames"))
+                                  + " -- a constant from that profile, not measured by this run")
+            roofline = {"kernel": dom, **{k: kernels[dom][k] for k in ("bound", "achieved", "peak", "unit", "frac")}, "traffic": traffic,
+                        "traffic_source": traffic_source, "measured_in": "device-only steps of this run (HIP events on the launch stream)"}
+            if "algorithmic_equiv" in kernels[dom]:
+                roofline.update({k: kernels[dom][k] for k in ("algorithmic_equiv", "algorithmic_equiv_frac_of_f32_peak", "issued_flop_per_cell", "algo", "pipe")})
+                roofline["note"] = ("achieved/frac = FLOPs the kernel issues on its matrix pipe / kernel time / that pipe's dense peak; algorithmic_equiv = the direct "
+                                    "f32 convolution / matrix product's FLOPs (SURVEY 8d) / kernel time")
+            res.update({
+                "roofline": roofline,
+                "kernels": kernels,
+                "pipeline_hbm_frac": fps_dev / world * BYTES_PER_FRAME / HBM_PEAK,
+                # whole-step view of the CNN's ALGORITHMIC (f32-equivalent) FLOPs against the f32 MFMA peak -- a context figure, not a roofline
+                # fraction: the default kernels do this arithmetic on the f16 pipe (their own fractions are in "kernels", priced on issued FLOPs)
+                "pipeline_algorithmic_cnn_flops_vs_f32_mfma_peak": fps_dev / world * 81 * (CONV_FLOP_PER_CELL + FC_FLOP_PER_CELL) / FP32_MFMA_PEAK,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = min(16, os.cpu_count() or 1)
             m = min(n, 2 * threads)
             res["cpu_baseline"] = cpu_baseline(frames[:m].cpu().numpy(), corners[:m], sd, threads)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/solver_golden.npz by running the REFERENCE solver (solver/src/sudoku.c, compiled as is into
-oracle/_ref/libsudoku_ref.so by `make -C oracle ref`) on seeded puzzles.  Run in the build container only."""
+"""Generates tests/golden/solver_golden.npz and solver_golden_seed99.npz by running the REFERENCE solver (solver/src/sudoku.c,
+compiled as is into oracle/_ref/libsudoku_ref.so by `make -C oracle ref`) on seeded puzzles.  Needs the reference tree."""
 import ctypes as C
 import os
 
@@ -41,17 +41,23 @@ def puzzles(seed=7, n=160):
     return np.stack(out).astype(np.int32)
 
 
-def main():
-    lib = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libsudoku_ref.so"))
-    P = puzzles()
+def solve_all(lib, P):
+    """-> (codes int32 [n], grids int32 [n,9,9]): the reference's return code and the grid it leaves behind, per puzzle"""
     codes, sols = [], []
     for g in P:
         w = np.ascontiguousarray(g.copy())
         codes.append(lib.solve_sudoku(w.ctypes.data_as(C.c_void_p)))
         sols.append(w)
-    codes = np.array(codes, np.int32)
-    print("codes:", {int(c): int((codes == c).sum()) for c in np.unique(codes)})
-    np.savez_compressed(os.path.join(HERE, "solver_golden.npz"), puzzles=P, codes=codes, solutions=np.stack(sols).astype(np.int32))
+    return np.array(codes, np.int32), np.stack(sols).astype(np.int32)
+
+
+def main():
+    lib = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libsudoku_ref.so"))
+    # solver_golden.npz: test_against_reference_goldens; solver_golden_seed99.npz: the set test_live_against_reference_library runs
+    for name, P in (("solver_golden.npz", puzzles()), ("solver_golden_seed99.npz", puzzles(seed=99, n=120))):
+        codes, sols = solve_all(lib, P)
+        print(name, "codes:", {int(c): int((codes == c).sum()) for c in np.unique(codes)})
+        np.savez_compressed(os.path.join(HERE, name), puzzles=P, codes=codes, solutions=sols)
 
 
 if __name__ == "__main__":

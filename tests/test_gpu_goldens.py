@@ -270,7 +270,7 @@ def _bench(args, env=None, timeout=600):
 def test_bench_starts_its_own_ranks(ctx):
     """`python bench.py --gpus 2` with no outer launcher: two ranks (both on cuda:0 under SV_BENCH_REHEARSE=1), n_gpus = 2 in
     the line, weak scaling counts both ranks' frames, `ranks` names each rank's GPU; configs[3]'s round-robin workload at a small total."""
-    res = _bench(["--gpus", "2", "--frames", "32", "--steps", "3", "--warmup", "1", "--no-e2e", "--no-cpu-baseline"],
+    res = _bench(["--full", "--gpus", "2", "--frames", "32", "--steps", "3", "--warmup", "1", "--no-e2e", "--no-cpu-baseline"],
                  env={"SV_BENCH_REHEARSE": "1"})
     assert res["n_gpus"] == 2 and res["steps"] == 3 and res["scaling"] == "weak" and res["value_kind"] == "device_only"
     assert res["config"]["frames_per_step"] == 64
@@ -278,7 +278,7 @@ def test_bench_starts_its_own_ranks(ctx):
     assert 0 < res["roofline"]["frac"] <= 1.0
     assert [r["rank"] for r in res["ranks"]] == [0, 1] and len({r["pid"] for r in res["ranks"]}) == 2
     assert all(r["pci_bus_id"] and r["device"] for r in res["ranks"])
-    res3 = _bench(["--gpus", "2", "--workload", "configs3", "--total-frames", "301", "--frames", "32", "--steps", "2", "--warmup", "1"],
+    res3 = _bench(["--full", "--gpus", "2", "--workload", "configs3", "--total-frames", "301", "--frames", "32", "--steps", "2", "--warmup", "1"],
                   env={"SV_BENCH_REHEARSE": "1"})
     assert res3["n_gpus"] == 2 and res3["scaling"] == "strong" and res3["config"]["frames_per_step"] == 301
     assert res3["config"]["frames_per_gpu"] == 151                        # rank 0 owns frames 0, 2, ..., 300
@@ -289,7 +289,7 @@ def test_bench_starts_its_own_ranks(ctx):
 def test_bench_single_gpu_line_is_honest(ctx):
     """--gpus 1 line: value = the end-to-end figure BASELINE's metric names, value_device_only beside it; roofline.frac <= 1 and
     reproducible from its own fields; the traffic constant says where it comes from."""
-    res = _bench(["--frames", "64", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    res = _bench(["--full", "--frames", "64", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
     rf = res["roofline"]
     e2e = res["end_to_end_with_host_corner_search"]
     assert res["n_gpus"] == 1 and res["value_kind"] == "end_to_end" and res["metric"].startswith("end-to-end")
@@ -303,10 +303,43 @@ def test_bench_single_gpu_line_is_honest(ctx):
         assert abs(rf["achieved"] * 1e12 - rf["issued_flop_per_cell"] * 81 * 64 / (k["avg_ms"] * 1e-3)) <= 1e-6 * rf["achieved"] * 1e12
 
 
+def test_bench_plain_line_and_dumped_outputs(ctx, tmp_path):
+    """A plain run (no --full) times exactly `steps` steps of the end-to-end path in one region and measures nothing beside it;
+    --dump-outputs writes what that path returned for its last step, the same on a second run, and equal to the device path run
+    in-process on the same seeded frames with the corners the host search found."""
+    import sudoku_vision_amd as sva
+    from sudoku_vision_amd.synth import random_state_dict, synth_frames
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        res = _bench(["--frames", "32", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert res["full"] is False and res["steps"] == 3 and res["value_kind"] == "end_to_end" and res["metric"].startswith("end-to-end")
+        assert res["unit"] == "frames/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+        assert abs(res["value"] - 32 * 3 / (res["ms_per_step"] * 3e-3)) <= 1e-6 * res["value"]
+        e2e = res["end_to_end_with_host_corner_search"]
+        assert len(e2e["regions"]) == 1 and e2e["value"] == res["value"] and e2e["grids_found"] == 32
+        assert not {"value_device_only", "kernels", "roofline", "cpu_baseline", "cpu_baseline_test_image"} & set(res)
+        arrays = {k: np.load(d / f"{k}.npy") for k in ("logits", "digits", "conf", "corners", "found")}
+        assert sorted(p.name for p in d.iterdir()) == sorted(f"{k}.npy" for k in arrays)
+        assert all(v.dtype == np.float32 for v in arrays.values())
+        assert [arrays[k].shape for k in ("logits", "digits", "conf", "corners", "found")] == [(32, 81, 10), (32, 81), (32, 81), (32, 4, 2), (32,)]
+        dumps.append(arrays)
+    for k in dumps[0]:
+        assert (dumps[0][k] == dumps[1][k]).all(), k
+    got = dumps[0]
+    assert (got["found"] == 1).all()
+    frames, _, _ = synth_frames(32, 1080, 1920, seed=1234, device="cuda")
+    ctx.load_state_dict(random_state_dict(1234))
+    want = ctx.frames_to_digits(frames, ctx.minv_to_device(sva.Context.corners_to_minv(got["corners"])))
+    assert (want["digits"].cpu().numpy() == got["digits"]).all()
+    assert np.abs(want["logits"].cpu().numpy() - got["logits"]).max() <= 1e-6
+    assert np.abs(want["conf"].cpu().numpy() - got["conf"]).max() <= 1e-6
+
+
 def test_bench_configs3_full_size(ctx):
     """BASELINE configs[3] at its stated size on one GPU: 100,000 frames through the 256-frame pool in one step.  Every kernel is
     launched ceil(100000/256) times, the step covers 100,000 frames, and the per-GPU device-only rate is that of configs[1]."""
-    res = _bench(["--workload", "configs3", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], timeout=900)
+    res = _bench(["--full", "--workload", "configs3", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], timeout=900)
     assert res["scaling"] == "strong" and res["config"]["frames_per_step"] == 100000 and res["config"]["frames_per_gpu"] == 100000
     launches = -(-100000 // 256)
     for k in ("k_preprocess", "k_warp_cells", "k_conv_features", "k_fc_head"):

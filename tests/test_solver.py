@@ -37,18 +37,22 @@ def test_against_reference_goldens(host, golden_dir):
     assert seen == {-1, 0, 1}
 
 
-def test_live_against_reference_library(host):
-    ref = os.path.join(ROOT, "oracle", "_ref", "libsudoku_ref.so")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref not built (no reference tree on this box)")
-    lib = C.CDLL(ref)
+def test_live_against_reference_library(host, golden_dir):
+    """A second seeded set: the reference library's answers as recorded in tests/golden/solver_golden_seed99.npz, and, where
+    oracle/_ref is built, the library itself live (which must still give the recorded answers)."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("mk", os.path.join(ROOT, "tests", "golden", "make_solver_goldens.py"))
     mk = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mk)
-    for p in mk.puzzles(seed=99, n=120):
-        w = np.ascontiguousarray(p.copy())
-        code = lib.solve_sudoku(w.ctypes.data_as(C.c_void_p))
+    g = np.load(os.path.join(golden_dir, "solver_golden_seed99.npz"))
+    P = mk.puzzles(seed=99, n=120)
+    assert (g["puzzles"] == P).all()
+    codes, grids = g["codes"], g["solutions"]
+    ref = os.path.join(ROOT, "oracle", "_ref", "libsudoku_ref.so")
+    if os.path.exists(ref):
+        live_codes, live_grids = mk.solve_all(C.CDLL(ref), P)
+        assert (live_codes == codes).all() and (live_grids == grids).all()
+    for p, code, w in zip(P, codes, grids):
         c, s = host.solve_sudoku(p)
         assert c == code and (code != 1 or (s == w).all())
 
