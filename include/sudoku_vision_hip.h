@@ -67,12 +67,15 @@ int sv_ctx_set_precision(sv_ctx *ctx, int precision);
 
 /* Which kernels compute the SV_PREC_F32 forward.  Nothing in the process environment influences this.
  *   SV_CNN_AUTO (default)  csrc/k3_cnn_h2.hip -- every f32 operand as a pair of f16 halves (22 significant bits) on the f16 matrix pipe,
- *                          f32 accumulation, logits ~1e-6 from an exact evaluation -- whenever that is safe, else csrc/k3_cnn.hip's f32-MFMA
- *                          kernels.  "Safe" = inputs, conv1 activations and features stay inside f16's range (|v| < 65,504):
- *                          sv_load_weights_f32 bounds the activations from the weights (worst case over inputs in [-1, 1], which is what
- *                          8-bit cells become), and an f32 input batch (sv_cnn_forward_f32) is range-checked on the device per call -- out
- *                          of range, NaN/Inf or all below 2^-10, it takes the f32 kernels, with no host synchronisation either way.  So
- *                          the entry points accept what ml/model.py:34-42 accepts: any f32.
+ *                          f32 accumulation -- whenever that is safe, else csrc/k3_cnn.hip's f32-MFMA kernels.  "Safe" = inputs, conv1
+ *                          activations and features stay inside f16's range (|v| < 65,504): sv_load_weights_f32 bounds the activations
+ *                          from the weights (worst case over inputs in [-1, 1], which is what 8-bit cells become; weights are carried times
+ *                          a power of two, as are activations whose bound is below 1), and an f32 input batch (sv_cnn_forward_f32) is
+ *                          range-checked on the device per call -- out of range, NaN/Inf or all below 2^-3 (where an unscaled pair loses
+ *                          bits), it takes the f32 kernels, with no host synchronisation either way.  So the entry points accept what
+ *                          ml/model.py:34-42 accepts: any finite f32 weights and inputs.  Accuracy, either way: the logits are as close
+ *                          to an exact (float64) evaluation of the model as PyTorch-CPU's own f32 forward is, within a small factor
+ *                          (tests/test_gpu_cnn_accuracy.py states the bound and the measured ratios), at any scale of weights and inputs.
  *   SV_CNN_F16PAIR         the f16-pair kernels unconditionally (inputs/activations beyond 65,504 then overflow to inf)
  *   SV_CNN_F32MFMA         the f32-MFMA kernels unconditionally (true f32 throughout; about 4x slower) */
 #define SV_CNN_AUTO 0

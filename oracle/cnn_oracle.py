@@ -9,6 +9,11 @@ Dropout (model.py:31,40) is identity in eval mode and is therefore absent here.
 Pinned: tests/golden/cnn_*.npz hold logits produced by importing the reference module itself
 (tests/golden/make_goldens.py); tests/test_oracle_cnn.py checks this restatement against them.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
+
+Besides the f32 forward: forward64 (the same model in float64, the accuracy tests' yardstick), and emulations of the two reduced-operand
+schemes of the GPU kernels -- forward_pair_emulated (csrc/k3_cnn_h2.hip: f16 hi/lo operand pairs) and forward_bf16_emulated (the bf16
+configuration, csrc/k3_cnn_bf16.hip) -- with float64 arithmetic wherever the kernels' own sums are not what is being emulated.  Their
+`mutate` arguments inject small, plausible kernel bugs, so that tests can show the tolerance rule below catches them.
 """
 import numpy as np
 import torch
@@ -59,3 +64,202 @@ def predict(sd, x):
     pred = logits.argmax(dim=1)
     conf = probs.gather(1, pred[:, None])[:, 0]
     return logits, pred.to(torch.uint8), conf
+
+
+# ---- float64 reference and the scale-free tolerance rule ---------------------------------------------------------------------------
+EPS32 = 2.0 ** -24
+
+
+def forward64(sd, x):
+    """forward() in float64 on the CPU, same op order: x float32/float64 [B,1,28,28] -> logits float64 [B,10] (tensor)."""
+    x = torch.as_tensor(np.asarray(x), device="cpu").to(torch.float64)
+    w = {k: torch.as_tensor(v).detach().cpu().to(torch.float64) for k, v in sd.items()}
+    with torch.no_grad():
+        x = F.max_pool2d(F.relu(F.conv2d(x, w["conv1.weight"], w["conv1.bias"], padding=1)), 2, 2)
+        x = F.max_pool2d(F.relu(F.conv2d(x, w["conv2.weight"], w["conv2.bias"], padding=1)), 2, 2)
+        x = F.relu(F.linear(x.reshape(x.size(0), -1), w["fc1.weight"], w["fc1.bias"]))
+        return F.linear(x, w["fc2.weight"], w["fc2.bias"])
+
+
+# c of the tolerance rule: the largest ratio max|gpu - reference| / noise measured over the whole matrix of tests/test_gpu_cnn_accuracy.py
+# on an MI355X, times at least 4 (that file's docstring has the measured ratios and where the largest ones come from)
+C_F32 = 56.0                    # f16 pairs, f32 MFMA, Winograd, split-bf16 Winograd, frame fc (measured: 13.1)
+C_BF16 = 52.0                   # bf16 configuration, noise = the f32-summing emulation's distance from the float64 one (measured: 12.6)
+# bf16 configuration with the run.py glue: measured up to 3e-4 of max|emu64| away from the emulation (trained weights), against a noise
+# term near 1e-6.  Its inputs are exactly +-1, so conv1's f32 sums often land exactly on a bf16 rounding tie; our explanation, not
+# verified, is that the kernel's conv1 misses the emulation's f32 value by a last bit at some of them (the configuration's known
+# run-to-run variation, k3_cnn_bf16.hip at conv1) and the tie goes the other way.  The bound adds this slack, times max|emu64|, for that glue.
+BF16_RUNPY_SLACK = 1e-3
+
+
+def tolerance(want64, noise, c):
+    """The accuracy tests' bound on max|got - want64| for one batch: c * noise + 2^-24 * max|want64|, noise = max|(another evaluation of the
+    same operands with f32 sums) - want64|.  Both terms scale with the weights and the inputs, so the rule holds at any magnitude."""
+    want64 = np.asarray(want64, np.float64)
+    return c * float(noise) + EPS32 * float(np.abs(want64).max())
+
+
+def glue(cells_u8, glue_mode=0):
+    """pipeline/run.py's glue in float32 operations: u8 [B,28,28] -> float32 [B,1,28,28] (glue_mode 1: preprocess_cell first)."""
+    import sv_oracle
+    c = np.asarray(cells_u8, np.uint8)
+    if glue_mode == 1:
+        c = sv_oracle.preprocess_cells(c)
+    t = (np.float32(255) - c.astype(np.float32)) / np.float32(255.0)
+    return ((t - np.float32(0.5)) / np.float32(0.5))[:, None].astype(np.float32)
+
+
+def _f32(t):
+    """Round a float64 tensor to float32 and back (one rounding)."""
+    return t.to(torch.float32).to(torch.float64)
+
+
+def _w64(sd):
+    return {k: torch.as_tensor(v).detach().cpu().to(torch.float32).to(torch.float64) for k, v in sd.items()}
+
+
+# fc1's last 32-feature K step in the GPU kernels' feature order k' = 64 * window + channel: window 48, channels 32..63, i.e. the
+# NCHW-flattened features 49 * channel + 48
+LAST_FC1_KSTEP = np.arange(32, 64) * 49 + 48
+MUTATED_CHANNEL = 10            # a conv2 channel that reaches the logits with both the trained and the seeded random weights
+
+
+# ---- f16 operand pairs (csrc/k3_cnn_h2.hip with the weight images of csrc/sv_api.cpp sv_load_weights_f32) ------------------------
+PAIR_CLAMP = (None, 120)        # sv_load_weights_f32's pow2_scale: weight exponents capped at 120, no floor
+
+
+def _h2(t):
+    """float64 tensor of float32 values -> (hi, lo) f16 halves as float64: hi = f16(v), lo = f16(v - hi)."""
+    hi = t.to(torch.float16).to(torch.float64)
+    lo = (t - hi).to(torch.float32).to(torch.float16).to(torch.float64)
+    return hi, lo
+
+
+def _pow2_exp(w, clamp):
+    m = float(np.abs(np.asarray(w, np.float32)).max())
+    if not (m > 0) or not np.isfinite(m):
+        return 0
+    e = 13 - int(np.frexp(np.float32(m))[1] - 1)
+    lo, hi = clamp
+    if lo is not None:
+        e = max(e, lo)
+    return min(e, hi) if hi is not None else e
+
+
+def pair_range(sd):
+    """sv_load_weights_f32's range decision for the f16-pair kernels, restated: -> dict(eA, eF, x_hi, x_lo, in_range)."""
+    w = {k: np.asarray(torch.as_tensor(v).detach().cpu().to(torch.float32).numpy(), np.float64) for k, v in sd.items()}
+    A1 = np.abs(w["conv1.weight"].reshape(32, 9)).sum(1).max()
+    B1 = np.abs(w["conv1.bias"]).max()
+    A2 = np.abs(w["conv2.weight"].reshape(64, 288)).sum(1).max()
+    B2 = np.abs(w["conv2.bias"]).max()
+    LIM = 6.0e4
+    with np.errstate(all="ignore"):
+        U1 = A1 + B1
+        U2 = A2 * U1 + B2
+        eA = min(-int(np.frexp(U1)[1] - 1), 120) if 0 < U1 < 1 else 0
+        eF = min(-int(np.frexp(U2)[1] - 1), 120) if 0 < U2 < 1 else 0
+        sA, sF = 2.0 ** eA, 2.0 ** eF
+        hi = LIM
+        if A1 > 0:
+            hi = min(hi, (LIM / sA - B1) / A1)
+        elif B1 * sA > LIM:
+            hi = -1.0
+        if A2 > 0 and A1 > 0:
+            hi = min(hi, ((LIM / sF - B2) / A2 - B1) / A1)
+        elif (A2 * B1 + B2) * sF > LIM:
+            hi = -1.0
+        if not all(np.isfinite(v) for v in (A1, A2, B1, B2)) or hi != hi:
+            hi = -1.0
+    e0, e2, e1 = (_pow2_exp(w[k], PAIR_CLAMP) for k in ("conv1.weight", "conv2.weight", "fc1.weight"))
+    folded_ok = all(-126 <= e <= 127 for e in (eA - e0, eF - eA - e2, -eF - e1))
+    return {"eA": eA, "eF": eF, "x_hi": float(np.float32(hi)), "x_lo": 2.0 ** -3, "in_range": hi >= 1.0 and folded_ok}
+
+
+def forward_pair_emulated(sd, x, clamp=PAIR_CLAMP, act_scale=True, mutate=None):
+    """The f16-pair kernels' operand treatment on the CPU: weights times 2^e (pow2_scale, with `clamp` on e) and inputs, conv1 activations and
+    features (times 2^eA / 2^eF when act_scale) split into f16 pairs; every product as ah*wh + ah*wl + al*wh; the matrix sums exact (float64),
+    rounded to f32 where the kernels store them (accumulator -> max -> scale and bias -> ReLU).  clamp=(-14, 40), act_scale=False is the
+    loader before the weight-range fix.  mutate: None, "drop_al_wh", "drop_ah_wl", "conv2_bias" (channel 10's bias moved by 1e-3 of the
+    largest |bias|), "drop_fc1_kstep" (fc1's last K step skipped).  -> logits float64 [B,10] (tensor)."""
+    w = _w64(sd)
+    r = pair_range(sd) if act_scale else {"eA": 0, "eF": 0}
+    sA, sF = 2.0 ** r["eA"], 2.0 ** r["eF"]
+    e0, e2, e1 = (_pow2_exp(w[k].numpy(), clamp) for k in ("conv1.weight", "conv2.weight", "fc1.weight"))
+    use_lw = mutate != "drop_ah_wl"        # the  a_hi * w_lo  term
+    use_la = mutate != "drop_al_wh"        # the  a_lo * w_hi  term
+
+    def wsplit(t, e):
+        return _h2(_f32(t * 2.0 ** e))
+
+    def conv(ah, al, wh, wl):
+        y = F.conv2d(ah, wh + wl if use_lw else wh, None, padding=1)
+        return y + F.conv2d(al, wh, None, padding=1) if use_la else y
+
+    x = torch.as_tensor(np.asarray(x, np.float32)).to(torch.float64)
+    with torch.no_grad():
+        xh, xl = _h2(x)
+        y = F.max_pool2d(_f32(conv(xh, xl, *wsplit(w["conv1.weight"], e0))), 2, 2)
+        a1 = F.relu(_f32(y * 2.0 ** (r["eA"] - e0) + (w["conv1.bias"] * sA).view(1, -1, 1, 1)))
+        ah, al = _h2(a1)
+        b2 = w["conv2.bias"].clone()
+        if mutate == "conv2_bias":
+            b2[MUTATED_CHANNEL] += 1e-3 * float(b2.abs().max())
+        y = F.max_pool2d(_f32(conv(ah, al, *wsplit(w["conv2.weight"], e2))), 2, 2)
+        feat = F.relu(_f32(y * 2.0 ** (r["eF"] - r["eA"] - e2) + (b2 * sF).view(1, -1, 1, 1))).reshape(x.shape[0], -1)
+        fh, fl = _h2(feat)
+        wh, wl = wsplit(w["fc1.weight"], e1)
+        if mutate == "drop_fc1_kstep":
+            fh, fl = fh.clone(), fl.clone()
+            fh[:, LAST_FC1_KSTEP] = 0
+            fl[:, LAST_FC1_KSTEP] = 0
+        acc_h = _f32(fh @ wh.T)
+        acc_l = _f32((fh @ wl.T if use_lw else 0) + (fl @ wh.T if use_la else 0))
+        h = F.relu(_f32(_f32(acc_h + acc_l) * 2.0 ** (-r["eF"] - e1) + w["fc1.bias"]))
+        return _f32(h @ w["fc2.weight"].T + w["fc2.bias"])
+
+
+# ---- bf16 configuration (csrc/k3_cnn_bf16.hip; weight images: csrc/sv_api.cpp, the bf16 lambda) ----------------------------------
+def _bf16(t, truncate=False):
+    """float64 tensor of float32 values -> bf16 (round to nearest even; or by truncation) as float64."""
+    if not truncate:
+        return t.to(torch.float32).to(torch.bfloat16).to(torch.float64)
+    b = t.to(torch.float32).numpy().view(np.uint32) & np.uint32(0xFFFF0000)
+    return torch.from_numpy(b.view(np.float32).astype(np.float64))
+
+
+def forward_bf16_emulated(sd, cells_u8, glue_mode=0, acc=torch.float64, mutate=None):
+    """The bf16 configuration's rounding points, float64 arithmetic elsewhere:
+      glue in f32 operations; conv1 in f32, bias first and then the nine taps as fused multiply-adds (emulated as float64 product + sum rounded
+      to f32: a double rounding, which can differ from the kernel's FMA only on a tie of the float64 sum, i.e. essentially never); max-pool,
+      ReLU, RNE to bf16; conv2 on bf16 weights (RNE) as an exact sum, max-pool, + bias in f32, ReLU, RNE to bf16 features; fc1 on bf16
+      weights, exact sum, + bias in f32, ReLU; fc2.
+    acc=torch.float32 sums conv2, fc1 and fc2 in f32 instead (PyTorch's order, not the MFMA's): another f32-accumulating evaluation of the
+    same operands, whose distance from the float64 one is the noise term of the bf16 tolerance.
+    mutate: None, "truncate" (bf16 by truncation instead of RNE), "conv2_channel" (channel 10 of conv2 moved by 1e-3), "drop_fc1_kstep".
+    -> logits float64 [B,10] (tensor)."""
+    w = _w64(sd)
+    trunc = mutate == "truncate"
+    x = torch.from_numpy(glue(cells_u8, glue_mode).astype(np.float64))
+    B = x.shape[0]
+    with torch.no_grad():
+        # conv1: acc = bias; for ky, kx: acc = fma(w, x[y+ky-1][x+kx-1], acc)
+        xp = F.pad(x, (1, 1, 1, 1))
+        a = w["conv1.bias"].view(1, 32, 1, 1).expand(B, 32, 28, 28).clone()
+        w1 = w["conv1.weight"]
+        for ky in range(3):
+            for kx in range(3):
+                a = _f32(a + w1[:, 0, ky, kx].view(1, 32, 1, 1) * xp[:, :, ky:ky + 28, kx:kx + 28])
+        a1 = _bf16(F.relu(F.max_pool2d(a, 2, 2)), trunc)
+        w2 = _bf16(w["conv2.weight"], trunc)
+        y = _f32(F.conv2d(a1.to(acc), w2.to(acc), None, padding=1).to(torch.float64))
+        if mutate == "conv2_channel":
+            y[:, MUTATED_CHANNEL] += 1e-3
+        feat = _bf16(F.relu(_f32(F.max_pool2d(y, 2, 2) + w["conv2.bias"].view(1, -1, 1, 1))), trunc).reshape(B, -1)
+        wf = _bf16(w["fc1.weight"], trunc)
+        if mutate == "drop_fc1_kstep":
+            feat = feat.clone()
+            feat[:, LAST_FC1_KSTEP] = 0
+        h = F.relu(_f32(_f32((feat.to(acc) @ wf.to(acc).T).to(torch.float64)) + w["fc1.bias"]))
+        out = h.to(acc) @ w["fc2.weight"].to(acc).T + w["fc2.bias"].to(acc)
+        return out.to(torch.float64)

@@ -849,8 +849,9 @@ __global__ __launch_bounds__(256) void k_fc_head(const float *__restrict__ feat,
 __global__ __launch_bounds__(512) void k_fc_head_frame(const float *__restrict__ feat, long B, const float *__restrict__ w1reg,
                                                        const float *__restrict__ b1, const float *__restrict__ w2,
                                                        const float *__restrict__ b2, float *__restrict__ logits,
-                                                       u8 *__restrict__ digits, float *__restrict__ conf)
+                                                       u8 *__restrict__ digits, float *__restrict__ conf, const int *__restrict__ run_if_set)
 {
+    if (run_if_set && *run_if_set == 0) return;                       // (as k_fc_head: under SV_CNN_AUTO the f16-pair kernels took this batch)
     constexpr int CELLS = 81, ROWS = 96, CH = 4, WPT = CH * 8 * 64 / 512;   // WPT float4 of weights per thread per stage                      // cells per workgroup, padded rows, 16-wide chunks per stage
     __shared__ __attribute__((aligned(16))) f32x4 wt[2][CH * 8 * 64]; // 2 x 32 KB weight stages
     __shared__ float hs[ROWS][129];
@@ -1159,7 +1160,7 @@ int svk_cnn_forward(sv_ctx *ctx, const void *x, bool x_is_u8, int glue, long B, 
     sv_time_scope ts(ctx, SVK_FC_HEAD, s);
 #ifdef SV_XCHECK
     if (ctx->x_fc_frame && B >= 81 * 64)       // enough frames to give most CUs a workgroup
-        hipLaunchKernelGGL(k_fc_head_frame, dim3((unsigned)((B + 80) / 81)), dim3(512), 0, s, ctx->features, B, w.fc1_wreg, w.fc1_b, w.fc2_w, w.fc2_b, logits, digits, conf);
+        hipLaunchKernelGGL(k_fc_head_frame, dim3((unsigned)((B + 80) / 81)), dim3(512), 0, s, ctx->features, B, w.fc1_wreg, w.fc1_b, w.fc2_w, w.fc2_b, logits, digits, conf, flag);
     else
 #endif
     hipLaunchKernelGGL(k_fc_head, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, ctx->features, B, w.fc1_wreg, w.fc1_b, w.fc2_w, w.fc2_b, logits, digits, conf, flag);

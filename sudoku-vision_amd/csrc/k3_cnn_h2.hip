@@ -8,7 +8,7 @@
 // products  ah*wh + ah*wl + al*wh  accumulated in f32 by the MFMA (f16 x f16 products are exact in f32; the dropped al*wl
 // is < 2^-22 of the product).  What this does to the logits, measured against an exact (f64) evaluation of the same model on
 // the golden inputs: max error 1e-6, the same as PyTorch-CPU's own f32 forward (1.4e-6) -- tests/test_oracle_cnn.py holds the
-// simulation, tests/test_gpu_parity.py the measured kernel (<= 1e-4 is the contract, ~1e-6 is what comes out).
+// simulation, tests/test_gpu_cnn_accuracy.py the measured kernels against a float64 evaluation at every scale of weights and inputs.
 // bias, ReLU, pooling, fc2 and the softmax stay in f32 on the VALU.
 //
 //   k_conv_features_h2 : persistent, one 512-thread workgroup per CU, producer waves (input staging, conv1) and consumer waves
@@ -28,10 +28,10 @@
 //        through double-buffered LDS, A fragments straight from global memory) for larger batches.
 //
 // Range: inputs and activations are carried as f16 pairs, so their magnitudes must stay below 65,504 (and a pair holds 22 significant bits
-// only while its low half is a normal f16; below that the absolute error is f16's subnormal step, 2^-24).  sv_load_weights_f32 bounds the
-// activations from the weights
-// and svk_cnn_forward (k3_cnn.hip) routes anything outside to the f32-MFMA kernels; `run_if_clear` is that decision for f32 inputs, made
-// on the device.  SV_DEV builds (tools/dev) add an ablation switch and s_memtime stamps; the product is compiled without them.
+// only while its low half is a normal f16, |v| >= 2^-3; below that the absolute error is f16's subnormal step, 2^-24).  sv_load_weights_f32
+// bounds the activations from the weights, scales conv1's activations and the features by powers of two when their bounds are below 1
+// (folded into b1, b2 and the scale_inv factors), and svk_cnn_forward (k3_cnn.hip) routes anything outside to the f32-MFMA kernels;
+// `run_if_clear` is that decision for f32 inputs, made on the device.  SV_DEV builds (tools/dev) add an ablation switch and s_memtime stamps; the product is compiled without them.
 #include "sv_device.h"
 #include "sv_internal.h"
 
@@ -684,10 +684,10 @@ int svk_cnn_forward_h2(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *
     {
         sv_time_scope ts(ctx, SVK_CONV_FEATURES, s);
         if (x_is_u8)
-            hipLaunchKernelGGL(k_conv_features_h2<true>, dim3(grid), dim3(512), 0, s, x, B, (const uint4 *)w.conv1_h2, w.conv1_b, w.conv1_h2_scale_inv, (const uint4 *)w.conv2_h2, w.conv2_b,
+            hipLaunchKernelGGL(k_conv_features_h2<true>, dim3(grid), dim3(512), 0, s, x, B, (const uint4 *)w.conv1_h2, w.conv1_b_h2, w.conv1_h2_scale_inv, (const uint4 *)w.conv2_h2, w.conv2_b_h2,
                                w.conv2_h2_scale_inv, ctx->features, run_if_clear SV_ABLATE_ARG);
         else
-            hipLaunchKernelGGL(k_conv_features_h2<false>, dim3(grid), dim3(512), 0, s, x, B, (const uint4 *)w.conv1_h2, w.conv1_b, w.conv1_h2_scale_inv, (const uint4 *)w.conv2_h2, w.conv2_b,
+            hipLaunchKernelGGL(k_conv_features_h2<false>, dim3(grid), dim3(512), 0, s, x, B, (const uint4 *)w.conv1_h2, w.conv1_b_h2, w.conv1_h2_scale_inv, (const uint4 *)w.conv2_h2, w.conv2_b_h2,
                                w.conv2_h2_scale_inv, ctx->features, run_if_clear SV_ABLATE_ARG);
     }
 #undef SV_ABLATE_ARG

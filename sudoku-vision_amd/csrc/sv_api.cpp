@@ -1,5 +1,6 @@
 // Host side of libsudokuvision_hip.so: context, weight packing, fp64 homography, argument checks.
 // Everything exported here is declared in include/sudoku_vision_hip.h.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -41,7 +42,7 @@ extern "C" int sv_ctx_create(int device, sv_ctx **out)
 
 static void free_weights(sv_weights &w)
 {
-    float **ps[] = {&w.conv1_w, &w.conv1_b, &w.conv2_wreg, &w.conv2_wino, &w.conv2_b, &w.fc1_wreg, &w.fc1_b, &w.fc2_w, &w.fc2_b};
+    float **ps[] = {&w.conv1_w, &w.conv1_b, &w.conv2_wreg, &w.conv2_wino, &w.conv2_b, &w.fc1_wreg, &w.fc1_b, &w.fc2_w, &w.fc2_b, &w.conv1_b_h2, &w.conv2_b_h2};
     for (float **p : ps) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -244,14 +245,42 @@ extern "C" int sv_load_weights_f32(sv_ctx *ctx, const float *blob)
                     const int kp = 32 * st + 8 * (lane >> 4) + j, win = kp >> 6, oc = kp & 63, n = 16 * t + (lane & 15);
                     fc1b[(((size_t)st * 8 + t) * 64 + lane) * 8 + j] = bf16(f1w[(size_t)n * 3136 + oc * 49 + win]);
                 }
+    // Range of the f16-pair kernels for these weights (k3_cnn_h2.hip carries inputs, conv1 activations and features as f16 pairs: each
+    // must stay below f16's 65,504).  Worst case over inputs of magnitude <= xm:  |conv1| <= A1*xm + B1,  |features| <= A2*(A1*xm + B1) + B2
+    // with A = the largest absolute row sum of a layer's weights, B = its largest |bias|.  A pair holds 22 significant bits only while its lo
+    // half is a normal f16 (|v| >= 2^-3); so when a layer's bound at xm = 1 is below 1, the kernels carry its activations times 2^eA (conv1) or
+    // 2^eF (features), which puts that bound in [1, 2).  Such a power of two is exact; the kernels fold it into the biases and the scale_inv
+    // factors below, and for bounds of 1 or more (every ordinary set of weights) eA = eF = 0.  h2_x_hi = the largest xm all bounds allow,
+    // after the scaling; 8-bit cells are in [-1, 1] after the glue, so the f16-pair kernels serve them iff h2_x_hi >= 1.  An f32 input batch
+    // is not scaled: below 2^-3 its values' low halves are f16-subnormal, and such batches take the f32 kernels too.
+    int eA = 0, eF = 0;
+    {
+        auto row_sum_max = [](const float *wt, int rows, int cols) { double m = 0; for (int r = 0; r < rows; r++) { double a = 0; for (int c = 0; c < cols; c++) a += std::fabs((double)wt[(size_t)r * cols + c]); m = std::fmax(m, a); } return m; };
+        auto abs_max = [](const float *v, int n) { double m = 0; for (int i = 0; i < n; i++) m = std::fmax(m, std::fabs((double)v[i])); return m; };
+        const double LIM = 6.0e4, A1 = row_sum_max(c1w, 32, 9), B1 = abs_max(c1b, 32), A2 = row_sum_max(c2w, 64, 288), B2 = abs_max(c2b, 64);
+        const double U1 = A1 + B1, U2 = A2 * U1 + B2;
+        if (U1 > 0 && U1 < 1) eA = std::min(-std::ilogb(U1), 120);
+        if (U2 > 0 && U2 < 1) eF = std::min(-std::ilogb(U2), 120);
+        const double sA = std::ldexp(1.0, eA), sF = std::ldexp(1.0, eF);
+        double hi = LIM;
+        if (A1 > 0) hi = std::fmin(hi, (LIM / sA - B1) / A1);
+        else if (B1 * sA > LIM) hi = -1;
+        if (A2 > 0 && A1 > 0) hi = std::fmin(hi, ((LIM / sF - B2) / A2 - B1) / A1);
+        else if ((A2 * B1 + B2) * sF > LIM) hi = -1;
+        if (!std::isfinite(A1) || !std::isfinite(A2) || !std::isfinite(B1) || !std::isfinite(B2) || !(hi == hi)) hi = -1;
+        ctx->w.h2_x_hi = (float)hi;
+        ctx->w.h2_x_lo = 0x1p-3f;
+        ctx->w.h2_in_range = hi >= 1.0;
+    }
     // k3_cnn_h2.hip: w * 2^e = hi + lo, both f16 (round to nearest), e chosen so that max|w| * 2^e lies in [2^13, 2^14): hi is far
-    // from f16's overflow (65504) and lo (~2^-11 of hi) stays a normal f16 for all but the tiniest weights
+    // from f16's overflow (65504) and lo (~2^-11 of hi) stays a normal f16.  Every finite weight has e >= -114; e is capped at 120 (weights below
+    // ~2^-107), where 2^e would approach the end of f32's range.
     auto pow2_scale = [](const float *v, size_t n) -> int {
         float m = 0.f;
         for (size_t i = 0; i < n; i++) m = std::fmax(m, std::fabs(v[i]));
         if (!(m > 0.f) || !std::isfinite(m)) return 0;
         const int e = 13 - std::ilogb(m);
-        return e < -14 ? -14 : (e > 40 ? 40 : e);
+        return e > 120 ? 120 : e;
     };
     auto split_h2 = [](float ws, uint16_t &hi, uint16_t &lo) {
         const _Float16 h = (_Float16)ws;
@@ -261,8 +290,8 @@ extern "C" int sv_load_weights_f32(sv_ctx *ctx, const float *blob)
     };
     const int e2 = pow2_scale(c2w, 18432), e1 = pow2_scale(f1w, 401408);
     const float s2 = std::ldexp(1.f, e2), s1 = std::ldexp(1.f, e1);
-    ctx->w.conv2_h2_scale_inv = std::ldexp(1.f, -e2);
-    ctx->w.fc1_h2_scale_inv = std::ldexp(1.f, -e1);
+    ctx->w.conv2_h2_scale_inv = std::ldexp(1.f, eF - eA - e2);     // conv2 reads conv1's activations x 2^eA and writes the features x 2^eF
+    ctx->w.fc1_h2_scale_inv = std::ldexp(1.f, -eF - e1);
     std::vector<uint16_t> c2h((size_t)9 * 2 * 2 * 2 * 64 * 8), f1h((size_t)98 * 8 * 2 * 64 * 8);
     for (int tap = 0; tap < 9; tap++)
         for (int np = 0; np < 2; np++)
@@ -287,7 +316,13 @@ extern "C" int sv_load_weights_f32(sv_ctx *ctx, const float *blob)
     // MFMA 0 multiplies [xh | xl] by [wh | wh], MFMA 1 by [wl | 0]:  xh*wh + xl*wh + xh*wl.
     const int e0 = pow2_scale(c1w, 288);
     const float s0 = std::ldexp(1.f, e0);
-    ctx->w.conv1_h2_scale_inv = std::ldexp(1.f, -e0);
+    ctx->w.conv1_h2_scale_inv = std::ldexp(1.f, eA - e0);
+    // the folded factors must be normal floats (only weights or biases spanning ~2^250 could push them out; the f32 kernels take those)
+    for (int e : {eA - e0, eF - eA - e2, -eF - e1})
+        if (e < -126 || e > 127) ctx->w.h2_in_range = false;
+    std::vector<float> c1bs(c1b, c1b + 32), c2bs(c2b, c2b + 64);
+    for (float &b : c1bs) b = std::ldexp(b, eA);
+    for (float &b : c2bs) b = std::ldexp(b, eF);
     std::vector<uint16_t> c1h((size_t)2 * 4 * 2 * 64 * 8);
     for (int chalf = 0; chalf < 2; chalf++)
         for (int pos = 0; pos < 4; pos++)
@@ -321,29 +356,12 @@ extern "C" int sv_load_weights_f32(sv_ctx *ctx, const float *blob)
     if ((rc = upload(&ctx->w.conv1_b, std::vector<float>(c1b, c1b + 32)))) return rc;
     if ((rc = upload(&ctx->w.conv2_wreg, w2))) return rc;
     if ((rc = upload(&ctx->w.conv2_b, std::vector<float>(c2b, c2b + 64)))) return rc;
+    if ((rc = upload(&ctx->w.conv1_b_h2, c1bs))) return rc;
+    if ((rc = upload(&ctx->w.conv2_b_h2, c2bs))) return rc;
     if ((rc = upload(&ctx->w.fc1_wreg, f1))) return rc;
     if ((rc = upload(&ctx->w.fc1_b, std::vector<float>(f1b, f1b + 128)))) return rc;
     if ((rc = upload(&ctx->w.fc2_w, std::vector<float>(f2w, f2w + 1280)))) return rc;
     if ((rc = upload(&ctx->w.fc2_b, std::vector<float>(f2b, f2b + 10)))) return rc;
-    // Range of the f16-pair kernels for these weights (k3_cnn_h2.hip carries inputs, conv1 activations and features as f16 pairs: each
-    // must stay below f16's 65,504).  Worst case over inputs of magnitude <= xm:  |conv1| <= A1*xm + B1,  |features| <= A2*(A1*xm + B1) + B2
-    // with A = the largest absolute row sum of a layer's weights, B = its largest |bias|.  h2_x_hi = the largest xm all three bounds allow;
-    // 8-bit cells are in [-1, 1] after the glue, so the f16-pair kernels serve them iff h2_x_hi >= 1.  Below 2^-10 an input's low halves
-    // are all f16-subnormal; such batches take the f32 kernels too.
-    {
-        auto row_sum_max = [](const float *wt, int rows, int cols) { double m = 0; for (int r = 0; r < rows; r++) { double a = 0; for (int c = 0; c < cols; c++) a += std::fabs((double)wt[(size_t)r * cols + c]); m = std::fmax(m, a); } return m; };
-        auto abs_max = [](const float *v, int n) { double m = 0; for (int i = 0; i < n; i++) m = std::fmax(m, std::fabs((double)v[i])); return m; };
-        const double LIM = 6.0e4, A1 = row_sum_max(c1w, 32, 9), B1 = abs_max(c1b, 32), A2 = row_sum_max(c2w, 64, 288), B2 = abs_max(c2b, 64);
-        double hi = LIM;
-        if (A1 > 0) hi = std::fmin(hi, (LIM - B1) / A1);
-        else if (B1 > LIM) hi = -1;
-        if (A2 > 0 && A1 > 0) hi = std::fmin(hi, ((LIM - B2) / A2 - B1) / A1);
-        else if (A2 * B1 + B2 > LIM) hi = -1;
-        if (!std::isfinite(A1) || !std::isfinite(A2) || !std::isfinite(B1) || !std::isfinite(B2) || !(hi == hi)) hi = -1;
-        ctx->w.h2_x_hi = (float)hi;
-        ctx->w.h2_x_lo = 0x1p-10f;
-        ctx->w.h2_in_range = hi >= 1.0;
-    }
     ctx->w.loaded = true;
     return SV_OK;
 }

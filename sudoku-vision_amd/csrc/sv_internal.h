@@ -30,6 +30,10 @@ struct sv_weights {
     unsigned short *fc1_h2 = nullptr;     // [98 step][8 t][2 part][64 lane][8] f16: n = 16t + (lane&15), feature = 64*(step/2) + 16*(lane>>4) + 8*(step%2) + j
     unsigned short *conv1_h2 = nullptr;   // [2 chalf][4 pos][2 mfma][64 lane][8] f16: conv1 as a GEMM over the 4x4 patch of a pooling window (k3_cnn_h2.hip)
     float conv1_h2_scale_inv = 1.f, conv2_h2_scale_inv = 1.f, fc1_h2_scale_inv = 1.f;
+    // the f16-pair kernels carry conv1's activations and the features times powers of two (1 unless a layer's worst-case bound is below 1,
+    // sv_load_weights_f32); the scale_inv factors above fold them in, and these are the biases of conv1 and conv2 with the same factors
+    float *conv1_b_h2 = nullptr;          // [32]
+    float *conv2_b_h2 = nullptr;          // [64]
     // range of the f16-pair kernels for THESE weights (sv_load_weights_f32): with inputs in [-1, 1] (8-bit cells after the glue) every activation
     // stays below the f16 range iff h2_in_range; an f32 input batch is inside it iff h2_x_lo <= max|x| <= h2_x_hi (0 > hi: never)
     bool h2_in_range = true;

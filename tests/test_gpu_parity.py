@@ -441,7 +441,8 @@ def test_despeckle_preserves_grid_search(ctx):
 
 
 def test_bf16_configuration_digit_parity(golden_dir):
-    """BASELINE configs[4]: bf16 MFMA conv2/fc1.  Parity target = digit indices; logits are compared loosely."""
+    """BASELINE configs[4]: bf16 MFMA conv2/fc1.  Parity target = digit indices; logits are compared loosely with the f32 model, and tightly
+    with the emulation of the configuration's own rounding points (cnn_oracle.forward_bf16_emulated, the bound of test_gpu_cnn_accuracy.py)."""
     import sudoku_vision_amd as sva
     g2 = np.load(os.path.join(golden_dir, "cnn_coreml_fp16.npz"))
     sd = {k: torch.from_numpy(g2[k.replace(".", "_")].astype(np.float32)) for k in cnn_oracle.KEYS}
@@ -460,6 +461,11 @@ def test_bf16_configuration_digit_parity(golden_dir):
         clear = (top2[:, 1] - top2[:, 0]) > 4 * err.max()
         assert clear.mean() > 0.7
         assert (digits.cpu().numpy()[clear] == ed.numpy()[clear]).all()
+        emu = cnn_oracle.forward_bf16_emulated(sd, cells, glue).numpy()
+        noise = np.abs(cnn_oracle.forward_bf16_emulated(sd, cells, glue, acc=torch.float32).numpy() - emu).max()
+        emu_err = np.abs(logits.cpu().numpy() - emu).max()
+        slack = cnn_oracle.BF16_RUNPY_SLACK * np.abs(emu).max() if glue == 1 else 0.0
+        assert emu_err <= cnn_oracle.tolerance(emu, noise, cnn_oracle.C_BF16) + slack, (glue, emu_err, noise)
     # the two fc kernels of this configuration against each other: a cell's logits do not depend on the batch it sits in, and both kernels add the
     # 98 K steps in the same order -- 97 cells per CU runs k_fc_head_bf16, its first 256 frames' worth alone runs k_fc_head_bf16p
     big = np.random.RandomState(6).randint(0, 256, (97 * 256, 28, 28)).astype(np.uint8)
