@@ -362,6 +362,32 @@ int sv_jpeg_reconstruct_sparse_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, con
                                       const uint32_t *offsets /*dev*/, const int16_t *values /*dev*/,
                                       const uint16_t *quant /*dev, 192*/, uint8_t *bgr /*dev*/, ptrdiff_t pitch, void *stream);
 
+/* ---- quality gate: the per-pixel statistics of cv/grid_quality.py (pipeline/run_v2.py:299-311) ------------------------- */
+
+/* The integer sums behind compute_sharpness (cv/grid_quality.py:48-62) and compute_contrast (:65-87) for n frames:
+ * gray = cv2.cvtColor(BGR2GRAY) (channels 3; channels 1: the frame is the gray image), L = cv2.Laplacian(gray, CV_64F)
+ * (3x3 [0 1 0; 1 -4 1; 0 1 0], BORDER_REFLECT_101; on a 1-pixel axis the neighbour is the pixel itself).
+ * Per frame: lap_sum = sum(L), lap_sqsum = sum(L^2) (|L| <= 1020), hist[256] = cv2.calcHist of gray.  Any H, W >= 1, any
+ * pitch >= W*channels and frame stride img_stride.  Integer accumulation only: the result does not depend on the order of
+ * the partial sums.  The outputs are zeroed on `stream` first. */
+int sv_frame_quality_stats_u8(sv_ctx *ctx, const uint8_t *img /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
+                              int channels, int64_t *lap_sum /*dev, n*/, int64_t *lap_sqsum /*dev, n*/, uint32_t *hist /*dev, n*256*/,
+                              void *stream);
+
+/* compute_completeness (cv/grid_quality.py:90-149) without the 450x450 warp: per frame and band, how many warped pixels of
+ * the band are > 0.  Band 2i = warped rows, band 2i+1 = warped columns [max(0,c-2), min(450,c+3)), c = min(50i, 449),
+ * i = 0..9 (the order of the reference's line_scores); every band spans all 450 pixels the other way (41,400 warped pixels
+ * per frame).  Each warped pixel is cv2.warpPerspective's (INTER_LINEAR, 1/32-px coordinates, 15-bit weights, constant-0
+ * border), minv = sv_corners_to_minv_batch(corners, 450, 0) (the same getPerspectiveTransform as compute_completeness).
+ * binary: n 8-bit images (pitch, img_stride). */
+int sv_grid_line_coverage_u8(sv_ctx *ctx, const uint8_t *binary /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
+                             const double *minv /*dev, n*9*/, uint32_t *counts /*dev, n*20*/, void *stream);
+
+/* The same on bit images (sv_preprocess_bits_u8's layout: 1 bit per pixel, LSB = leftmost, W/32 words per row, rows and
+ * frames dense; a set bit is 255).  W % 32 == 0. */
+int sv_grid_line_coverage_bits(sv_ctx *ctx, const uint32_t *bits /*dev, n*H*W/32*/, int n, int H, int W,
+                               const double *minv /*dev, n*9*/, uint32_t *counts /*dev, n*20*/, void *stream);
+
 /* ---- the whole device-resident path ----------------------------------------------------------- */
 
 /* frames + homographies -> 81 digits per frame: K2 then K3 on `stream`, no host sync.

@@ -69,6 +69,9 @@ SIGNATURES = {
     "sv_cnn_forward_f32": [_p, _p, _l, _p, _p, _p, _p],
     "sv_cnn_forward_cells_u8": [_p, _p, _l, _i, _p, _p, _p, _p],
     "sv_frames_to_digits": [_p, _p, _i, _i, _i, _pd, _pd, _p, _i, _p, _p, _p, _p, _p],
+    "sv_frame_quality_stats_u8": [_p, _p, _i, _i, _i, _pd, _pd, _i, _p, _p, _p, _p],
+    "sv_grid_line_coverage_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p, _p],
+    "sv_grid_line_coverage_bits": [_p, _p, _i, _i, _i, _p, _p, _p],
 }
 _RESTYPES = {"sv_last_error": C.c_char_p, "sv_sparse_bits_record_bytes": C.c_long}
 # what libsudokuvision_xcheck.so exports on top of SIGNATURES (include/sudoku_vision_xcheck.h)

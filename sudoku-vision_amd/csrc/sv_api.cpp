@@ -707,6 +707,34 @@ extern "C" int sv_softmax_topk_f32(sv_ctx *ctx, const float *logits, long B, int
     return svk_softmax_topk(logits, B, k, index, prob, S(stream));
 }
 
+extern "C" int sv_frame_quality_stats_u8(sv_ctx *ctx, const uint8_t *img, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int channels,
+                                         int64_t *lap_sum, int64_t *lap_sqsum, uint32_t *hist, void *stream)
+{
+    REQUIRE(ctx && img && lap_sum && lap_sqsum && hist, "NULL argument");
+    REQUIRE(channels == 1 || channels == 3, "channels must be 1 or 3");
+    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= (ptrdiff_t)W * channels, "bad shape");
+    REQUIRE(n == 1 || img_stride >= pitch * (H - 1) + (ptrdiff_t)W * channels, "frames overlap (img_stride too small)");
+    REQUIRE((((uintptr_t)lap_sum | (uintptr_t)lap_sqsum) & 7) == 0 && ((uintptr_t)hist & 3) == 0, "misaligned output");
+    return svk_frame_quality_stats(img, n, H, W, pitch, img_stride, channels, (long long *)lap_sum, (long long *)lap_sqsum, hist, S(stream));
+}
+
+extern "C" int sv_grid_line_coverage_u8(sv_ctx *ctx, const uint8_t *binary, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const double *minv,
+                                        uint32_t *counts, void *stream)
+{
+    REQUIRE(ctx && binary && minv && counts, "NULL argument");
+    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= (ptrdiff_t)W, "bad shape");
+    REQUIRE(((uintptr_t)minv & 7) == 0 && ((uintptr_t)counts & 3) == 0, "misaligned argument");
+    return svk_grid_line_coverage(binary, false, n, H, W, pitch, img_stride, minv, counts, S(stream));
+}
+
+extern "C" int sv_grid_line_coverage_bits(sv_ctx *ctx, const uint32_t *bits, int n, int H, int W, const double *minv, uint32_t *counts, void *stream)
+{
+    REQUIRE(ctx && bits && minv && counts, "NULL argument");
+    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && W % 32 == 0, "bad shape (W must be a multiple of 32)");
+    REQUIRE((((uintptr_t)bits | (uintptr_t)counts) & 3) == 0 && ((uintptr_t)minv & 7) == 0, "misaligned argument");
+    return svk_grid_line_coverage(bits, true, n, H, W, 0, 0, minv, counts, S(stream));
+}
+
 static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *fn)
 {
     const char *what = nullptr;

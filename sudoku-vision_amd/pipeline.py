@@ -64,7 +64,8 @@ def gpu_local_cpus(device):
 
 
 class FramePipeline:
-    def __init__(self, ctx: Context, H: int, W: int, chunk: int = 32, host_threads=None, min_area_ratio=0.1, glue=0, despeckle=True, sparse=True, depth=5, cpu_affinity="auto", bits_direct=True):
+    def __init__(self, ctx: Context, H: int, W: int, chunk: int = 32, host_threads=None, min_area_ratio=0.1, glue=0, despeckle=True, sparse=True, depth=5, cpu_affinity="auto", bits_direct=True,
+                 quality=False):
         self.ctx, self.H, self.W, self.chunk = ctx, H, W, chunk
         # chunks in flight.  A chunk's chain is K1 -> D2H -> search -> K2/K3, and chunk i's K1 is only issued once chunk i-depth+1's search has
         # returned: with too few in flight the period is (K1 + D2H + search) / (depth - 1), not the slowest stage
@@ -112,6 +113,11 @@ class FramePipeline:
             host.set_pool_affinity(self.cpus)
         self.pool = ThreadPoolExecutor(1, initializer=(lambda: os.sched_setaffinity(0, self.cpus)) if self.cpus and hasattr(os, "sched_setaffinity") else None)
         self.dense_fallbacks = 0
+        # quality=True: run() also returns run_v2's quality scores (cv/grid_quality.py): the frame statistics on s_pre, and the grid line
+        # coverage on s_cls once the corners are known, from a per-slot copy of K1's output taken before the speck filter erases digits
+        self.quality = bool(quality)
+        if self.quality:
+            self.q_bin = [None] * depth           # shaped on first use like K1's output (bit or byte image)
         ctx.reserve(chunk * 81)
 
     def _search(self, slot, m, ev):
@@ -147,7 +153,8 @@ class FramePipeline:
 
     def run(self, frames, out=None, repeat=1, total=None):
         """frames u8 [n,H,W,3] on the context's device -> dict(digits u8[n,81], logits f32[n,81,10], conf f32[n,81],
-        corners int32[n,4,2] (host), found bool[n] (host)).  repeat > 1 streams the pool that many times through the
+        corners int32[n,4,2] (host), found bool[n] (host)); with quality=True also quality f32[n,6] (host: overall, sharpness, contrast,
+        completeness, geometry, size -- cv/grid_quality.py's scores of each frame, NaN in the corner-dependent columns where found is False).  repeat > 1 streams the pool that many times through the
         pipeline without draining it in between (steady-state throughput measurement); total = k streams exactly k frames,
         cycling the pool (the k-th frame is pool frame k mod n: BASELINE configs[3]'s shard of 100,000 frames); both need chunk | n."""
         n = frames.shape[0]
@@ -169,6 +176,14 @@ class FramePipeline:
                        and self.H >= 16 and self.W >= 16)
         if not bits_direct and self.dev_bin is None:
             self.dev_bin = [torch.empty((self.chunk, self.H, self.W), dtype=torch.uint8, device=dev) for _ in range(self.depth)]
+        if self.quality:
+            qshape, qtype = ((self.chunk, self.H, self.W // 32), torch.int32) if bits_direct else ((self.chunk, self.H, self.W), torch.uint8)
+            if self.q_bin[0] is None or tuple(self.q_bin[0].shape) != qshape or self.q_bin[0].dtype != qtype:
+                self.q_bin = [torch.empty(qshape, dtype=qtype, device=dev) for _ in range(self.depth)]
+            q_s1 = torch.empty((n,), dtype=torch.int64, device=dev)
+            q_s2 = torch.empty((n,), dtype=torch.int64, device=dev)
+            q_hist = torch.empty((n, 256), dtype=torch.int32, device=dev)
+            q_cnt = torch.zeros((n, 20), dtype=torch.int32, device=dev)
         if total is None:
             starts = [(s0, min(self.chunk, n - s0)) for _ in range(repeat) for s0 in range(0, n, self.chunk)]
         else:
@@ -184,6 +199,8 @@ class FramePipeline:
                 self.minv_dev[slot][:m].copy_(self.minv_pin[slot][:m], non_blocking=True)
                 sub = {k: out[k][s:s + m] for k in ("logits", "digits", "conf")}
                 self.ctx.frames_to_digits(frames[s:s + m], self.minv_dev[slot][:m], out=sub, glue=self.glue)
+                if self.quality:
+                    self.ctx.grid_line_coverage(self.q_bin[slot][:m], self.minv_dev[slot][:m], out=q_cnt[s:s + m])
                 if not found.all():
                     out["digits"][s:s + m][torch.from_numpy(~found).to(dev)] = 0
                 ev = torch.cuda.Event(blocking=True)      # the waiting thread sleeps instead of spinning: the box's CPU quota is for the search
@@ -199,9 +216,14 @@ class FramePipeline:
                 # grows) stalls the whole pipeline for tens of milliseconds
                 if bits_direct:
                     # K1 writes the bit image itself and the speck filter works on it in place: no byte image at all
-                    b = self.ctx.despeckle_bits(self.ctx.preprocess_bits(frames[s:s + m], out=self.dev_bits[slot][:m]))
+                    b = self.ctx.preprocess_bits(frames[s:s + m], out=self.dev_bits[slot][:m])
+                    if self.quality:
+                        self.q_bin[slot][:m].copy_(b)
+                    b = self.ctx.despeckle_bits(b)
                 else:
                     b = self.ctx.preprocess(frames[s:s + m], out=self.dev_bin[slot][:m])
+                    if self.quality:
+                        self.q_bin[slot][:m].copy_(b)
                 # exact accelerator for the host search: erase the specks that cannot matter (csrc/k4_despeckle.hip), in place
                 if self.packed:
                     if not bits_direct:
@@ -212,6 +234,8 @@ class FramePipeline:
                     b = self.ctx.despeckle(b, out=b)
                 ready = torch.cuda.Event()
                 ready.record(self.s_pre)
+                if self.quality:                  # after `ready`: the D2H copy does not wait for it
+                    self.ctx.frame_quality_stats(frames[s:s + m], out=(q_s1[s:s + m], q_s2[s:s + m], q_hist[s:s + m]))
             with torch.cuda.stream(self.s_d2h):
                 self.s_d2h.wait_event(ready)
                 self.pinned[slot][:m].copy_(b, non_blocking=True)
@@ -224,13 +248,20 @@ class FramePipeline:
             classify(pending.pop(0))
         cur.wait_stream(self.s_cls)
         out["corners"], out["found"] = corners_all, found_all
+        if self.quality:
+            from .cv.grid_quality import scores_from_stats
+            cur.wait_stream(self.s_pre)
+            s1, s2, hist, cnt = (t.cpu().numpy() for t in (q_s1, q_s2, q_hist, q_cnt))
+            out["quality"] = scores_from_stats(s1, s2, hist, cnt, corners_all, found_all, self.H * self.W).astype(np.float32)
         return out
 
 
-def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0):
+def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False):
     """One BGR image (numpy uint8 [H,W,3], or a CUDA uint8 tensor of that shape) -> dict(grid 9x9 list, digits, confidences, corners) or None when no
     grid is found -- the call order of pipeline/run.py:261-312, preprocess_cell (:73-95) included by default.
-    top_k > 1 adds run_v2's per-cell `alternatives` (pipeline/run_v2.py:165-178): 81 lists of (digit, prob), best excluded."""
+    top_k > 1 adds run_v2's per-cell `alternatives` (pipeline/run_v2.py:165-178): 81 lists of (digit, prob), best excluded.
+    quality=True adds run_v2's quality check (pipeline/run_v2.py:299-311): `quality` (a cv.grid_quality.QualityScore) and
+    `quality_feedback` (get_user_feedback); comparing quality.overall with a minimum is left to the caller, as run_v2 does."""
     from .runtime import default_context
     ctx = ctx or default_context()
     if model_state_dict is not None:
@@ -239,7 +270,8 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
         frames = image.contiguous()[None]
     else:
         frames = torch.from_numpy(np.ascontiguousarray(image)).to(ctx.device)[None]
-    binary = ctx.preprocess(frames)[0].cpu().numpy()
+    binary_dev = ctx.preprocess(frames)[0]
+    binary = binary_dev.cpu().numpy()
     corners = host.find_grid_corners(binary)
     if corners is None:
         return None
@@ -252,6 +284,10 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
         idx, prob = ctx.softmax_topk(out["logits"][0], top_k)
         idx, prob = idx.cpu().numpy(), prob.cpu().numpy()
         res["alternatives"] = [[(int(idx[i, j]), float(prob[i, j])) for j in range(1, top_k)] for i in range(81)]
+    if quality:
+        from .cv import grid_quality
+        q = grid_quality.assess_grid_quality(frames[0], binary_dev, corners, ctx=ctx)
+        res["quality"], res["quality_feedback"] = q, grid_quality.get_user_feedback(q)
     return res
 
 

@@ -469,6 +469,59 @@ class Context:
                                                         _ptr(out["conf"]), _stream_ptr()), "sv_frames_to_digits")
         return out
 
+    # ---- quality gate (cv/grid_quality.py) ------------------------------------------------------
+    def frame_quality_stats(self, frames, out=None):
+        """frames u8 [n,H,W,3] (BGR) or [n,H,W] (gray) on device, rows may be padded -> (lap_sum int64 [n], lap_sqsum int64 [n],
+        hist int32 [n,256]) on device: the integer sums of cv2.Laplacian(gray, CV_64F) and its square, and calcHist of gray
+        (sv_frame_quality_stats_u8).  out: optional tuple of three such tensors to write into."""
+        if frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
+            raise TypeError("expected a uint8 tensor of shape [n,H,W,3] or [n,H,W]")
+        if frames.dim() == 4:
+            frames, pitch, fstride = _frame_layout(frames)
+            ch = 3
+        else:
+            n, H, W = frames.shape
+            st = frames.stride()
+            if not (st[2] == 1 and st[1] >= W and (n == 1 or st[0] >= st[1] * (H - 1) + W)):
+                frames = frames.contiguous()
+                st = frames.stride()
+            pitch, fstride, ch = st[1], (st[0] if n > 1 else st[1] * H), 1
+        n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+        if out is None:
+            out = (torch.empty((n,), dtype=torch.int64, device=self.device), torch.empty((n,), dtype=torch.int64, device=self.device),
+                   torch.empty((n, 256), dtype=torch.int32, device=self.device))
+        else:
+            out = (self._out(out[0], (n,), torch.int64, "lap_sum"), self._out(out[1], (n,), torch.int64, "lap_sqsum"),
+                   self._out(out[2], (n, 256), torch.int32, "hist"))
+        self._check(self._lib.sv_frame_quality_stats_u8(self._h, _ptr(frames), n, H, W, pitch, fstride, ch, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                                        _stream_ptr()), "sv_frame_quality_stats_u8")
+        return out
+
+    def grid_line_coverage(self, binary_or_bits, minv_dev, out=None):
+        """binary u8 [n,H,W] (any value > 0 is ink) or a bit image int32 [n,H,W//32] (preprocess_bits), minv_dev f64 [n,3,3] from
+        corners_to_minv_batch(corners, 450) on device -> counts int32 [n,20] on device: the warped pixels > 0 of compute_completeness's
+        bands, band 2i = grid row line i, 2i+1 = grid column line i (sv_grid_line_coverage_u8 / _bits)."""
+        x = binary_or_bits
+        if x.dim() != 3 or x.dtype not in (torch.uint8, torch.int32):
+            raise TypeError("expected a uint8 [n,H,W] binary or an int32 [n,H,W//32] bit image")
+        n = x.shape[0]
+        if minv_dev.dtype != torch.float64 or minv_dev.numel() != 9 * n or not minv_dev.is_contiguous() or minv_dev.device != self.device:
+            raise TypeError(f"minv_dev must be a contiguous float64 [{n},3,3] tensor on {self.device}")
+        out = torch.empty((n, 20), dtype=torch.int32, device=self.device) if out is None else self._out(out, (n, 20), torch.int32, "out")
+        if x.dtype == torch.uint8:
+            H, W = x.shape[1], x.shape[2]
+            st = x.stride()
+            if not (st[2] == 1 and st[1] >= W and (n == 1 or st[0] >= st[1] * (H - 1) + W)):
+                x = x.contiguous()
+                st = x.stride()
+            rc = self._lib.sv_grid_line_coverage_u8(self._h, _ptr(x), n, H, W, st[1], (st[0] if n > 1 else st[1] * H), _ptr(minv_dev), _ptr(out),
+                                                    _stream_ptr())
+        else:
+            x = x.contiguous()
+            rc = self._lib.sv_grid_line_coverage_bits(self._h, _ptr(x), n, x.shape[1], x.shape[2] * 32, _ptr(minv_dev), _ptr(out), _stream_ptr())
+        self._check(rc, "sv_grid_line_coverage")
+        return out
+
 
 _default = {}
 _lock = threading.Lock()
