@@ -139,6 +139,19 @@ def warp_perspective(img, corners, output_size=450, inset_ratio=0.0):
     return out
 
 
+def warp_perspective_minv(img, Minv, output_size):
+    """svo_warp_perspective_u8 with the destination -> source map given directly (any 3x3 matrix, not only a quad's)."""
+    img, p = _u8(img)
+    H, W = img.shape[:2]
+    Cn = 1 if img.ndim == 2 else img.shape[2]
+    Minv = np.ascontiguousarray(Minv, np.float64).reshape(9)
+    shape = (output_size, output_size) if img.ndim == 2 else (output_size, output_size, Cn)
+    out = np.empty(shape, np.uint8)
+    lib().svo_warp_perspective_u8(p, H, W, C.c_long(W * Cn), Cn, Minv.ctypes.data_as(C.c_void_p), int(output_size),
+                                  out.ctypes.data_as(C.c_void_p))
+    return out
+
+
 def resize_linear(img, dsize):
     img, p = _u8(img)
     sh, sw = img.shape

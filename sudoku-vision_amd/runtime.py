@@ -28,10 +28,45 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
-def _frame_layout(frames):
+def _dev_tensor(t, name, dtype, device, shape=None, ndim=None):
+    """Check a tensor argument before anything reaches the library, which sees only its data pointer: a torch.Tensor of `dtype`
+    (a dtype, a tuple of them, or None for any) on `device`, of `shape` (None entries match any size) or with `ndim` dimensions
+    (an int or a tuple of them).  TypeError for the kind, dtype or device; ValueError for the shape.  Returns t."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    if dtype is not None and t.dtype not in (dtype if isinstance(dtype, tuple) else (dtype,)):
+        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    if t.device != torch.device(device):
+        raise TypeError(f"{name} must be on {device}, got {t.device}")
+    if shape is not None:
+        if t.dim() != len(shape) or any(want is not None and got != want for got, want in zip(t.shape, shape)):
+            raise ValueError(f"{name} must have shape [{','.join('*' if v is None else str(v) for v in shape)}], got {list(t.shape)}")
+    elif ndim is not None and t.dim() not in (ndim if isinstance(ndim, tuple) else (ndim,)):
+        raise ValueError(f"{name} must have {ndim} dimensions, got {list(t.shape)}")
+    return t
+
+
+def _image_layout(img):
+    """img u8 [H,W] or [H,W,C]: (tensor, row pitch in bytes).  A view whose rows are dense (cropped columns, padded rows) is passed
+    through with its own row stride; anything else is made contiguous first."""
+    H, W = img.shape[0], img.shape[1]
+    ch = 1 if img.dim() == 2 else img.shape[2]
+    st = img.stride()
+    dense_rows = st[1] == ch and (img.dim() == 2 or st[2] == 1 or ch == 1)
+    if H == 1 and dense_rows:
+        return img, W * ch
+    if not (dense_rows and st[0] >= W * ch):
+        img = img.contiguous()
+        st = img.stride()
+    return img, st[0]
+
+
+def _frame_layout(frames, device=None):
     """frames u8 [n,H,W,3]: (tensor, row pitch, frame stride) in bytes.  Row padding and gaps between frames are passed through to
     the library (camera buffers are rarely dense); anything else is made contiguous first."""
-    if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
+    if device is not None:
+        _dev_tensor(frames, "frames", torch.uint8, device, shape=(None, None, None, 3))
+    elif frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
         raise TypeError("expected a uint8 tensor of shape [n,H,W,3]")
     n, H, W, _ = frames.shape
     st = frames.stride()
@@ -61,6 +96,13 @@ class Context:
         if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
             raise TypeError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)} on {self.device}")
         return t
+
+    def _minv(self, minv_dev, n):
+        """minv_dev: n destination -> source maps, float64 [n,3,3] (or any shape of 9n elements) on this device."""
+        _dev_tensor(minv_dev, "minv_dev", torch.float64, self.device)
+        if minv_dev.numel() != 9 * n:
+            raise ValueError(f"minv_dev must hold {n} 3x3 matrices, got shape {list(minv_dev.shape)}")
+        return minv_dev.contiguous()
 
     def close(self):
         if self._h:
@@ -133,19 +175,21 @@ class Context:
 
     # ---- K1 -----------------------------------------------------------------------------------
     def gray(self, bgr):
-        bgr, pitch, fstride = _frame_layout(bgr)
+        bgr, pitch, fstride = _frame_layout(bgr, self.device)
         n, H, W = bgr.shape[0], bgr.shape[1], bgr.shape[2]
         out = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
         self._check(self._lib.sv_gray_u8(self._h, _ptr(bgr), n, H, W, pitch, fstride, _ptr(out), _stream_ptr()), "sv_gray_u8")
         return out
 
     def blur(self, gray, ksize):
+        gray = _dev_tensor(gray, "gray", torch.uint8, self.device, ndim=3).contiguous()
         n, H, W = gray.shape
         out = torch.empty_like(gray)
         self._check(self._lib.sv_blur_u8(self._h, _ptr(gray), n, H, W, int(ksize), _ptr(out), _stream_ptr()), "sv_blur_u8")
         return out
 
     def adaptive_threshold(self, gray, block_size, c, inv=True):
+        gray = _dev_tensor(gray, "gray", torch.uint8, self.device, ndim=3).contiguous()
         n, H, W = gray.shape
         out = torch.empty_like(gray)
         self._check(self._lib.sv_adaptive_threshold_u8(self._h, _ptr(gray), n, H, W, int(block_size), float(c), int(bool(inv)),
@@ -155,7 +199,7 @@ class Context:
     def preprocess(self, frames, out=None):
         """frames u8 [n,H,W,3] on device (rows may be padded, frames may have gaps) -> binary u8 [n,H,W]
         (preprocess_for_grid_detection).  out: optional contiguous u8 [n,H,W] tensor to write into."""
-        frames, pitch, fstride = _frame_layout(frames)
+        frames, pitch, fstride = _frame_layout(frames, self.device)
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
         if out is None:
             out = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
@@ -167,8 +211,9 @@ class Context:
     def preprocess_and_warp_cells(self, frames, minv_dev, binary=None, cells=None):
         """K1 and K2 of the same frames in one launch (sv_preprocess_warp_cells_u8; BASELINE configs[4]'s fused threshold/warp for callers
         that know the corners beforehand) -> (binary u8 [n,H,W], cells u8 [n,81,28,28])."""
-        frames, pitch, fstride = _frame_layout(frames)
+        frames, pitch, fstride = _frame_layout(frames, self.device)
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+        minv_dev = self._minv(minv_dev, n)
         binary = torch.empty((n, H, W), dtype=torch.uint8, device=self.device) if binary is None else self._out(binary, (n, H, W), torch.uint8, "binary")
         cells = torch.empty((n, 81, 28, 28), dtype=torch.uint8, device=self.device) if cells is None else self._out(cells, (n, 81, 28, 28), torch.uint8, "cells")
         self._check(self._lib.sv_preprocess_warp_cells_u8(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(binary), _ptr(minv_dev), _ptr(cells),
@@ -179,7 +224,7 @@ class Context:
         """preprocess() through the matrix-pipe formulation of K1 (sv_preprocess_mm_u8): the same binary, an independent implementation.
         Only on a Context of the test-only library (Context(library=_native.lib_xcheck())).
         want_mean: also return the kernel's approximate local mean per pixel (f32 [n,H,W])."""
-        frames, pitch, fstride = _frame_layout(frames)
+        frames, pitch, fstride = _frame_layout(frames, self.device)
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
         out = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
         mean = torch.zeros((n, H, W), dtype=torch.float32, device=self.device) if want_mean else None
@@ -197,7 +242,7 @@ class Context:
     def preprocess_bits(self, frames, out=None):
         """K1 with the binary as 1 bit per pixel: frames u8 [n,H,W,3] -> int32 [n,H,W//32] (LSB = leftmost pixel).  Needs W % 32 == 0 and
         4-byte aligned rows (NativeError SV_ERR_UNSUPPORTED otherwise: use preprocess + despeckle(packed=...))."""
-        frames, pitch, fstride = _frame_layout(frames)
+        frames, pitch, fstride = _frame_layout(frames, self.device)
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
         if W % 32:
             raise ValueError("preprocess_bits needs W % 32 == 0")
@@ -207,6 +252,7 @@ class Context:
 
     def despeckle_bits(self, bits):
         """despeckle on a bit image int32 [n,H,W//32], in place."""
+        self._out(_dev_tensor(bits, "bits", torch.int32, self.device, ndim=3), bits.shape, torch.int32, "bits")
         n, H, wpr = bits.shape
         self._check(self._lib.sv_despeckle_bits(self._h, _ptr(bits), n, H, wpr * 32, _stream_ptr()), "sv_despeckle_bits")
         return bits
@@ -215,8 +261,11 @@ class Context:
         """binary u8 [n,H,W] in {0,255} -> the same with every component that fits strictly inside a 64x64 tile erased
         (find_grid_contour-equivalent; used only to make the host corner search cheaper).  packed: optional int32 [n,H,W//32]
         tensor receiving the result as 1 bit per pixel (then `out` is scratch)."""
+        binary = _dev_tensor(binary, "binary", torch.uint8, self.device, ndim=3).contiguous()
         n, H, W = binary.shape
-        out = torch.empty_like(binary) if out is None else out
+        out = torch.empty_like(binary) if out is None else self._out(out, (n, H, W), torch.uint8, "out")
+        if packed is not None:
+            self._out(packed, (n, H, W // 32), torch.int32, "packed")
         self._check(self._lib.sv_despeckle_u8(self._h, _ptr(binary), n, H, W, _ptr(out), _ptr(packed) if packed is not None else None,
                                                     _stream_ptr()), "sv_despeckle_u8")
         return out if packed is None else packed
@@ -225,6 +274,8 @@ class Context:
         """bits int32 [n,H,W//32] (despeckle's packed output) -> records uint8 [n,stride] (device): per frame the row masks of its
         non-zero words and those words (sv_pack_sparse_bits; layout in include/sudoku_vision_hip.h).  A third to a quarter of the
         dense image for the D2H copy; host.find_grid_corners_sparse_batch reads it."""
+        _dev_tensor(bits, "bits", torch.int32, self.device, ndim=3)
+        _dev_tensor(records, "records", torch.uint8, self.device, ndim=2)
         n, H, wpr = bits.shape
         if records.dtype != torch.uint8 or records.dim() != 2 or records.shape[0] < n or not records.is_contiguous() or not bits.is_contiguous():
             raise TypeError("records must be a contiguous uint8 [>=n, stride] device tensor")
@@ -236,6 +287,7 @@ class Context:
         """src (device tensor) -> dst (pinned host tensor of the same byte size) by a copy kernel on the current stream: about twice
         the PCIe rate of the DMA engine tensor.copy_(non_blocking=True) uses (sv_copy_to_pinned_host).  Stream-ordered; synchronise
         (an event, the stream) before reading dst."""
+        _dev_tensor(src, "src", None, self.device)
         if not dst.is_pinned() or not dst.is_contiguous() or not src.is_contiguous():
             raise TypeError("copy_to_pinned needs a contiguous device tensor and a contiguous pinned host tensor")
         nbytes = src.numel() * src.element_size()
@@ -269,25 +321,37 @@ class Context:
         return torch.from_numpy(np.ascontiguousarray(minv, np.float64)).to(self.device)
 
     def warp_perspective(self, img, minv_dev, output_size):
+        """img u8 [H,W] or [H,W,1|3] on device (rows may be padded: cropped views are read in place) -> the output_size square."""
+        _dev_tensor(img, "img", torch.uint8, self.device, ndim=(2, 3))
+        if img.dim() == 3 and img.shape[2] not in (1, 3):
+            raise ValueError(f"img must have 1 or 3 channels, got {list(img.shape)}")
+        minv_dev = self._minv(minv_dev, 1)
+        img, pitch = _image_layout(img)
         H, W = img.shape[0], img.shape[1]
         ch = 1 if img.dim() == 2 else img.shape[2]
         shape = (output_size, output_size) if img.dim() == 2 else (output_size, output_size, ch)
         out = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        self._check(self._lib.sv_warp_perspective_u8(self._h, _ptr(img), H, W, W * ch, ch, _ptr(minv_dev), int(output_size), _ptr(out),
+        self._check(self._lib.sv_warp_perspective_u8(self._h, _ptr(img), H, W, pitch, ch, _ptr(minv_dev), int(output_size), _ptr(out),
                                                            _stream_ptr()), "sv_warp_perspective_u8")
         return out
 
     def extract_cells(self, grid, cell_size, margin_h, margin_w):
+        """grid u8 [h,w] or [h,w,1|3] on device (rows may be padded) -> 81 cells u8 [81,cell_size,cell_size]."""
+        _dev_tensor(grid, "grid", torch.uint8, self.device, ndim=(2, 3))
+        if grid.dim() == 3 and grid.shape[2] not in (1, 3):
+            raise ValueError(f"grid must have 1 or 3 channels, got {list(grid.shape)}")
+        grid, pitch = _image_layout(grid)
         h, w = grid.shape[0], grid.shape[1]
         ch = 1 if grid.dim() == 2 else grid.shape[2]
         out = torch.empty((81, cell_size, cell_size), dtype=torch.uint8, device=self.device)
-        self._check(self._lib.sv_extract_cells_u8(self._h, _ptr(grid), h, w, w * ch, ch, int(cell_size), int(margin_h), int(margin_w),
+        self._check(self._lib.sv_extract_cells_u8(self._h, _ptr(grid), h, w, pitch, ch, int(cell_size), int(margin_h), int(margin_w),
                                                         _ptr(out), _stream_ptr()), "sv_extract_cells_u8")
         return out
 
     def warp_cells(self, frames, minv_dev):
-        frames, pitch, fstride = _frame_layout(frames)
+        frames, pitch, fstride = _frame_layout(frames, self.device)
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+        minv_dev = self._minv(minv_dev, n)
         out = torch.empty((n, 81, 28, 28), dtype=torch.uint8, device=self.device)
         self._check(self._lib.sv_warp_cells_u8(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(minv_dev), _ptr(out), _stream_ptr()),
                       "sv_warp_cells_u8")
@@ -298,14 +362,16 @@ class Context:
 
     def resize_linear(self, img, dsize):
         """cv2.resize(img, dsize=(w, h)) INTER_LINEAR on a gray u8 image."""
+        img, pitch = _image_layout(_dev_tensor(img, "img", torch.uint8, self.device, ndim=2))
         dw, dh = dsize
         out = torch.empty((dh, dw), dtype=torch.uint8, device=self.device)
-        self._check(self._lib.sv_resize_linear_u8(self._h, _ptr(img), img.shape[0], img.shape[1], img.shape[1], _ptr(out), dh, dw, _stream_ptr()),
+        self._check(self._lib.sv_resize_linear_u8(self._h, _ptr(img), img.shape[0], img.shape[1], pitch, _ptr(out), dh, dw, _stream_ptr()),
                       "sv_resize_linear_u8")
         return out
 
     def cell_ink_ratio(self, cells):
         """cells u8 [B,h,w] -> (ratio f32 [B], otsu i32 [B]): is_cell_empty's Otsu ink share, batched."""
+        cells = _dev_tensor(cells, "cells", torch.uint8, self.device, ndim=3).contiguous()
         B = cells.shape[0]
         ratio = torch.empty((B,), dtype=torch.float32, device=self.device)
         otsu = torch.empty((B,), dtype=torch.int32, device=self.device)
@@ -424,7 +490,7 @@ class Context:
 
     def softmax_topk(self, logits, k=3):
         """F.softmax(logits, 1).topk(k) (pipeline/run_v2.py:165-178): (index u8 [B,k], prob f32 [B,k]), best first."""
-        logits = logits.reshape(-1, 10).contiguous()
+        logits = _dev_tensor(logits, "logits", torch.float32, self.device).reshape(-1, 10).contiguous()
         B = logits.shape[0]
         index = torch.empty((B, k), dtype=torch.uint8, device=self.device)
         prob = torch.empty((B, k), dtype=torch.float32, device=self.device)
@@ -433,6 +499,7 @@ class Context:
 
     def preprocess_cells(self, cells):
         """run.py's preprocess_cell on u8 cells [B,28,28] -> u8 {0,255} [B,28,28]."""
+        cells = _dev_tensor(cells, "cells", torch.uint8, self.device, shape=(None, 28, 28)).contiguous()
         out = torch.empty_like(cells)
         self._check(self._lib.sv_preprocess_cells_u8(self._h, _ptr(cells), cells.shape[0], _ptr(out), _stream_ptr()), "sv_preprocess_cells_u8")
         return out
@@ -440,6 +507,12 @@ class Context:
     def cnn_forward(self, x, want_digits=False, glue=0):
         """x f32 [B,1,28,28], or u8 [B,28,28] cells with the run.py glue fused in (glue=GLUE_NORMALIZE: invert+normalise;
         GLUE_RUNPY: preprocess_cell (CLAHE + adaptive threshold) first) -> logits [B,10] (, digits, conf)."""
+        _dev_tensor(x, "x", (torch.uint8, torch.float32), self.device)
+        if x.dtype == torch.uint8:
+            _dev_tensor(x, "x", torch.uint8, self.device, shape=(None, 28, 28))
+        elif not (x.dim() in (3, 4) and tuple(x.shape[-2:]) == (28, 28) and (x.dim() == 3 or x.shape[1] == 1)):
+            raise ValueError(f"x must have shape [B,1,28,28], got {list(x.shape)}")
+        x = x.contiguous()
         B = x.shape[0]
         logits = torch.empty((B, 10), dtype=torch.float32, device=self.device)
         digits = torch.empty((B,), dtype=torch.uint8, device=self.device) if want_digits else None
@@ -455,8 +528,9 @@ class Context:
     # ---- whole path ---------------------------------------------------------------------------
     def frames_to_digits(self, frames, minv_dev, out=None, keep_cells=False, glue=0):
         """frames u8 [n,H,W,3], minv_dev f64 [n,3,3] on device -> dict(logits [n,81,10], digits [n,81], conf [n,81])."""
-        frames, pitch, fstride = _frame_layout(frames)
+        frames, pitch, fstride = _frame_layout(frames, self.device)
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+        minv_dev = self._minv(minv_dev, n)
         if out is None:
             out = {"logits": torch.empty((n, 81, 10), dtype=torch.float32, device=self.device),
                    "digits": torch.empty((n, 81), dtype=torch.uint8, device=self.device),
@@ -474,10 +548,9 @@ class Context:
         """frames u8 [n,H,W,3] (BGR) or [n,H,W] (gray) on device, rows may be padded -> (lap_sum int64 [n], lap_sqsum int64 [n],
         hist int32 [n,256]) on device: the integer sums of cv2.Laplacian(gray, CV_64F) and its square, and calcHist of gray
         (sv_frame_quality_stats_u8).  out: optional tuple of three such tensors to write into."""
-        if frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
-            raise TypeError("expected a uint8 tensor of shape [n,H,W,3] or [n,H,W]")
+        _dev_tensor(frames, "frames", torch.uint8, self.device, ndim=(3, 4))
         if frames.dim() == 4:
-            frames, pitch, fstride = _frame_layout(frames)
+            frames, pitch, fstride = _frame_layout(frames, self.device)
             ch = 3
         else:
             n, H, W = frames.shape
@@ -501,12 +574,9 @@ class Context:
         """binary u8 [n,H,W] (any value > 0 is ink) or a bit image int32 [n,H,W//32] (preprocess_bits), minv_dev f64 [n,3,3] from
         corners_to_minv_batch(corners, 450) on device -> counts int32 [n,20] on device: the warped pixels > 0 of compute_completeness's
         bands, band 2i = grid row line i, 2i+1 = grid column line i (sv_grid_line_coverage_u8 / _bits)."""
-        x = binary_or_bits
-        if x.dim() != 3 or x.dtype not in (torch.uint8, torch.int32):
-            raise TypeError("expected a uint8 [n,H,W] binary or an int32 [n,H,W//32] bit image")
+        x = _dev_tensor(binary_or_bits, "binary_or_bits", (torch.uint8, torch.int32), self.device, ndim=3)
         n = x.shape[0]
-        if minv_dev.dtype != torch.float64 or minv_dev.numel() != 9 * n or not minv_dev.is_contiguous() or minv_dev.device != self.device:
-            raise TypeError(f"minv_dev must be a contiguous float64 [{n},3,3] tensor on {self.device}")
+        minv_dev = self._minv(minv_dev, n)
         out = torch.empty((n, 20), dtype=torch.int32, device=self.device) if out is None else self._out(out, (n, 20), torch.int32, "out")
         if x.dtype == torch.uint8:
             H, W = x.shape[1], x.shape[2]
