@@ -124,8 +124,8 @@ LAST_FC1_KSTEP = np.arange(32, 64) * 49 + 48
 MUTATED_CHANNEL = 10            # a conv2 channel that reaches the logits with both the trained and the seeded random weights
 
 
-# ---- f16 operand pairs (csrc/k3_cnn_h2.hip with the weight images of csrc/sv_api.cpp sv_load_weights_f32) ------------------------
-PAIR_CLAMP = (None, 120)        # sv_load_weights_f32's pow2_scale: weight exponents capped at 120, no floor
+# ---- f16 operand pairs (csrc/k3_cnn_h2.hip with its weight images, svk_pack_weights_h2) ------------------------------------------
+PAIR_CLAMP = (None, 120)        # svk_pack_weights_h2's pow2_scale: weight exponents capped at 120, no floor
 
 
 def _h2(t):
@@ -147,7 +147,7 @@ def _pow2_exp(w, clamp):
 
 
 def pair_range(sd):
-    """sv_load_weights_f32's range decision for the f16-pair kernels, restated: -> dict(eA, eF, x_hi, x_lo, in_range)."""
+    """svk_pack_weights_h2's range decision for the f16-pair kernels, restated: -> dict(eA, eF, x_hi, x_lo, in_range)."""
     w = {k: np.asarray(torch.as_tensor(v).detach().cpu().to(torch.float32).numpy(), np.float64) for k, v in sd.items()}
     A1 = np.abs(w["conv1.weight"].reshape(32, 9)).sum(1).max()
     B1 = np.abs(w["conv1.bias"]).max()
@@ -219,7 +219,7 @@ def forward_pair_emulated(sd, x, clamp=PAIR_CLAMP, act_scale=True, mutate=None):
         return _f32(h @ w["fc2.weight"].T + w["fc2.bias"])
 
 
-# ---- bf16 configuration (csrc/k3_cnn_bf16.hip; weight images: csrc/sv_api.cpp, the bf16 lambda) ----------------------------------
+# ---- bf16 configuration (csrc/k3_cnn_bf16.hip; weight images: svk_pack_weights_bf16, the bf16 lambda) -----------------------------
 def _bf16(t, truncate=False):
     """float64 tensor of float32 values -> bf16 (round to nearest even; or by truncation) as float64."""
     if not truncate:

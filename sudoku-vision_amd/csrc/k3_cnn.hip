@@ -1,6 +1,6 @@
 // K3 -- DigitCNN.forward (ml/model.py:34-42, eval mode) on MI355X: the f32-MFMA kernels and the small stages around the CNN.
-// (The default conv/fc pair -- f32-grade arithmetic on the f16 matrix pipe -- is k3_cnn_h2.hip; svk_cnn_forward at the end of this file
-// picks between the two, see sv_ctx_set_cnn_kernels.)
+// (The default conv/fc pair -- f32-grade arithmetic on the f16 matrix pipe -- is k3_cnn_h2.hip, the bf16 configuration k3_cnn_bf16.hip;
+// svk_cnn_forward at the end of this file picks the family, see sv_ctx_set_precision and sv_ctx_set_cnn_kernels.)
 //
 //   k_conv_features_pc : true f32 throughout, the reference's own numeric range: what runs when the loaded weights or an f32 input
 //        leave the range the f16-pair kernels carry exactly (and for misaligned 8-bit buffers).  Persistent, one 512-thread workgroup per
@@ -18,8 +18,10 @@
 //   Under SV_XCHECK (libsudokuvision_xcheck.so, test-only): k_conv_features_wstream / _wsplit (round 1's Winograd stream on f32 and on
 //        split-bf16 MFMA) and k_fc_head_frame -- independent implementations the tests compare the product with.
 //
-// Weight images are packed on the host by sv_load_weights_f32 (sv_api.cpp) into exactly the
+// Weight images are packed on the host by svk_pack_weights_f32mfma (below) into exactly the
 // per-lane register order the kernels load.
+#include <cstring>
+
 #include "sv_device.h"
 #include "sv_internal.h"
 
@@ -508,7 +510,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_features_wstream(const void *__
 // f32 operand is therefore split, without error, into three bf16 parts (x = h + m + l, each the next 8 mantissa bits, by
 // truncation: one v_and + one exact v_sub per part), and a product a*b becomes the six partial products
 // ah*bh + ah*bm + am*bh + ah*bl + al*bh + am*bm accumulated in f32 -- what is dropped (am*bl, al*bm, al*bl) is below 2^-23 of
-// the product, i.e. below f32's own rounding.  U is split once on the host (sv_load_weights_f32), V when the input transform
+// the product, i.e. below f32's own rounding.  U is split once on the host (svk_pack_weights_f32mfma), V when the input transform
 // writes it.  6 MFMAs of K = 32 replace 8 of K = 4: 96 matrix-pipe cycles per (M tile, N tile, xi) instead of 256.
 //
 // All 8 waves do everything (no producer/consumer split; the 96-register B image of a wave is (N tile nt, half of the xi)):
@@ -771,7 +773,7 @@ __global__ __launch_bounds__(256) void k_fc_head(const float *__restrict__ feat,
     const f32x4 *ap = (const f32x4 *)(feat + crow * FEAT + 4 * q);
     const f32x4 *bp = (const f32x4 *)w1reg + lane;
 
-    for (int i = tid; i < 1280; i += 256) w2s[i >> 7][i & 127] = w2[i];
+    sv_fc2_stage<256>(w2s, w2, tid);
 
     f32x4 acc[8];
 #pragma unroll
@@ -816,25 +818,13 @@ __global__ __launch_bounds__(256) void k_fc_head(const float *__restrict__ feat,
     for (int jj = 0; jj < 3; jj++) {
         const int j = q + 4 * jj;
         if (j < 10) {
-            float s = b2[j];
-            for (int n = 0; n < 128; n++) s = __builtin_fmaf(hs[wave][r][n], w2s[j][n], s);
+            const float s = sv_fc2_logit(hs[wave][r], w2s, b2, j);
             lg[wave][r][j] = s;
             if (cell0 + r < B) logits[(cell0 + r) * 10 + j] = s;
         }
     }
     __syncthreads();
-    if (q == 0 && cell0 + r < B && (digits || conf)) {
-        float best = lg[wave][r][0];
-        int arg = 0;
-        for (int j = 1; j < 10; j++)
-            if (lg[wave][r][j] > best) { best = lg[wave][r][j]; arg = j; }
-        if (digits) digits[cell0 + r] = (u8)arg;
-        if (conf) {
-            float den = 0.f;
-            for (int j = 0; j < 10; j++) den += expf(lg[wave][r][j] - best);
-            conf[cell0 + r] = 1.0f / den;
-        }
-    }
+    if (q == 0 && cell0 + r < B) sv_digit_conf(lg[wave][r], cell0 + r, digits, conf);
 }
 
 #ifdef SV_XCHECK
@@ -871,7 +861,7 @@ __global__ __launch_bounds__(512) void k_fc_head_frame(const float *__restrict__
     const f32x4 *ap = (const f32x4 *)(feat + crow * FEAT + 4 * q);
     const f32x4 *wp = (const f32x4 *)w1reg;                           // [196][8][64] float4
 
-    for (int i = tid; i < 1280; i += 512) w2s[i >> 7][i & 127] = w2[i];
+    sv_fc2_stage<512>(w2s, w2, tid);
 
     f32x4 acc[8];
 #pragma unroll
@@ -937,24 +927,12 @@ __global__ __launch_bounds__(512) void k_fc_head_frame(const float *__restrict__
     __syncthreads();
     for (int it = tid; it < CELLS * 10; it += 512) {                  // fc2
         const int cl = it / 10, j = it - 10 * cl;
-        float sacc = b2[j];
-        for (int n = 0; n < 128; n++) sacc = __builtin_fmaf(hs[cl][n], w2s[j][n], sacc);
+        const float sacc = sv_fc2_logit(hs[cl], w2s, b2, j);
         lg[cl][j] = sacc;
         if (cellbase + cl < B) logits[(cellbase + cl) * 10 + j] = sacc;
     }
     __syncthreads();
-    if (tid < CELLS && cellbase + tid < B && (digits || conf)) {
-        float best = lg[tid][0];
-        int arg = 0;
-        for (int j = 1; j < 10; j++)
-            if (lg[tid][j] > best) { best = lg[tid][j]; arg = j; }
-        if (digits) digits[cellbase + tid] = (u8)arg;
-        if (conf) {
-            float den = 0.f;
-            for (int j = 0; j < 10; j++) den += expf(lg[tid][j] - best);
-            conf[cellbase + tid] = 1.0f / den;
-        }
-    }
+    if (tid < CELLS && cellbase + tid < B) sv_digit_conf(lg[tid], cellbase + tid, digits, conf);
 }
 
 #endif  // SV_XCHECK
@@ -976,6 +954,67 @@ __global__ __launch_bounds__(256) void k_preprocess_cells(const u8 *__restrict__
 }
 
 }  // namespace
+
+int svk_pack_weights_f32mfma(sv_weights &w, const float *c2w, const float *f1w)
+{
+    // conv2: [np][t][ks][lane]; lane -> oc = 32np + 16t + (lane&15), ic = icb + 8*(lane>>4); ks = tap*8 + icb
+    std::vector<float> w2(2 * 2 * 72 * 64);
+    for (int np = 0; np < 2; np++)
+        for (int t = 0; t < 2; t++)
+            for (int ks = 0; ks < 72; ks++)
+                for (int lane = 0; lane < 64; lane++) {
+                    const int oc = 32 * np + 16 * t + (lane & 15), tap = ks >> 3, ic = (ks & 7) + 8 * (lane >> 4);
+                    w2[((np * 2 + t) * 72 + ks) * 64 + lane] = c2w[(oc * 32 + ic) * 9 + tap];
+                }
+    // fc1: [chunk][t][lane][e]; feature index k' = 16*chunk + 4*(lane>>4) + e = window*64 + oc;
+    // the reference flattens NCHW: k = oc*49 + window (ml/model.py:38)
+    std::vector<float> f1((size_t)196 * 8 * 64 * 4);
+    for (int c = 0; c < 196; c++)
+        for (int t = 0; t < 8; t++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int e = 0; e < 4; e++) {
+                    const int kp = 16 * c + 4 * (lane >> 4) + e, win = kp >> 6, oc = kp & 63, n = 16 * t + (lane & 15);
+                    f1[(((size_t)c * 8 + t) * 64 + lane) * 4 + e] = f1w[(size_t)n * 3136 + oc * 49 + win];
+                }
+    int rc;
+    if ((rc = sv_upload(w, &w.conv2_wreg, w2.data(), w2.size()))) return rc;
+    if ((rc = sv_upload(w, &w.fc1_wreg, f1.data(), f1.size()))) return rc;
+#ifdef SV_XCHECK
+    // Winograd F(2x2,3x3) weights U = G g G^T (computed in double), as [nt][xi][ks][lane]: oc = 16nt + (lane&15), ic = 4ks + (lane>>4)
+    std::vector<float> wino((size_t)4 * 16 * 8 * 64);
+    // the same U split without error into three bf16 parts (each the next 8 mantissa bits, by truncation) for
+    // k_conv_features_wsplit: [nt][xi][part][lane][j], oc = 16nt + (lane&15), ic = 8*(lane>>4) + j
+    std::vector<uint16_t> wsplit((size_t)4 * 16 * 3 * 64 * 8);
+    const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+    for (int oc = 0; oc < 64; oc++)
+        for (int ic = 0; ic < 32; ic++) {
+            const float *g = c2w + (oc * 32 + ic) * 9;
+            double Gg[4][3], U[4][4];
+            for (int i = 0; i < 4; i++)
+                for (int j = 0; j < 3; j++) Gg[i][j] = G[i][0] * g[j] + G[i][1] * g[3 + j] + G[i][2] * g[6 + j];
+            for (int i = 0; i < 4; i++)
+                for (int j = 0; j < 4; j++) U[i][j] = Gg[i][0] * G[j][0] + Gg[i][1] * G[j][1] + Gg[i][2] * G[j][2];
+            const int nt = oc >> 4, lane = (oc & 15) + 16 * (ic & 3), ks = ic >> 2;
+            for (int xi = 0; xi < 16; xi++) {
+                const float u = (float)U[xi >> 2][xi & 3];
+                wino[(((size_t)nt * 16 + xi) * 8 + ks) * 64 + lane] = u;
+                float rest = u;
+                for (int part = 0; part < 3; part++) {
+                    uint32_t bits;
+                    memcpy(&bits, &rest, 4);
+                    bits &= 0xffff0000u;
+                    float piece;
+                    memcpy(&piece, &bits, 4);
+                    rest -= piece;                                        // exact
+                    wsplit[((((size_t)nt * 16 + xi) * 3 + part) * 64 + (oc & 15) + 16 * (ic >> 3)) * 8 + (ic & 7)] = (uint16_t)(bits >> 16);
+                }
+            }
+        }
+    if ((rc = sv_upload(w, &w.conv2_wino, wino.data(), wino.size()))) return rc;
+    if ((rc = sv_upload(w, &w.conv2_wsplit, wsplit.data(), wsplit.size()))) return rc;
+#endif
+    return SV_OK;
+}
 
 int svk_preprocess_cells(const u8 *cells, long B, u8 *out, hipStream_t s)
 {
@@ -1020,21 +1059,21 @@ int svk_softmax_topk(const float *logits, long B, int k, u8 *index, float *prob,
 
 // Which conv/fc kernels run (sv_ctx_set_cnn_kernels; include/sudoku_vision_hip.h):
 //   SV_CNN_AUTO (default)  the f16 hi/lo operand-pair kernels (k3_cnn_h2.hip) whenever the loaded weights keep every activation inside their
-//                          range, else the f32-MFMA kernels below, which have the reference's own range (sv_load_weights_f32 decides; f32
+//                          range, else the f32-MFMA kernels below, which have the reference's own range (svk_pack_weights_h2 decides; f32
 //                          inputs are range-checked on the device per call)
 //   SV_CNN_F16PAIR / SV_CNN_F32MFMA   one of the two, unconditionally
 //   (libsudokuvision_xcheck.so only) SV_CNN_X_WINOGRAD, SV_CNN_X_WSPLIT: the round-1 Winograd stream on f32 / on split-bf16 MFMA, and
 //   SV_FC_X_FRAME for the one-workgroup-per-frame fc kernel -- independent implementations the tests compare the product with
-static int effective_algo(const sv_ctx *ctx)
+static sv_cnn_algo effective_algo(const sv_ctx *ctx)
 {
     switch (ctx->cnn_kernels) {
-    case SV_CNN_F16PAIR: return 4;
-    case SV_CNN_F32MFMA: return 0;
+    case SV_CNN_F16PAIR: return SV_ALGO_F16PAIR;
+    case SV_CNN_F32MFMA: return SV_ALGO_F32MFMA;
 #ifdef SV_XCHECK
-    case SV_CNN_X_WINOGRAD: return 2;
-    case SV_CNN_X_WSPLIT: return 3;
+    case SV_CNN_X_WINOGRAD: return SV_ALGO_X_WINOGRAD;
+    case SV_CNN_X_WSPLIT: return SV_ALGO_X_WSPLIT;
 #endif
-    default: return ctx->w.h2_in_range ? 4 : 0;
+    default: return ctx->w.h2_in_range ? SV_ALGO_F16PAIR : SV_ALGO_F32MFMA;
     }
 }
 
@@ -1064,14 +1103,14 @@ extern "C" int sv_conv_kernel_info(sv_ctx *ctx, int *algo, int *mfma_f32_conv2_p
 {
     if (!ctx || !algo || !mfma_f32_conv2_per_cell || !mfma_f32_conv1_per_cell || !mfma_f16_conv_per_cell || !mfma_f16_fc_per_cell)
         return sv_fail(SV_ERR_BAD_ARG, "sv_conv_kernel_info: NULL argument");
-    const int a = effective_algo(ctx);
+    const sv_cnn_algo a = effective_algo(ctx);
     *algo = a;
     // f32 Winograd: 49 tiles x 16 xi x 8 k-steps x 4 N tiles / 16 tiles per M tile; f32 direct: 196 positions / 16 x 72 k-steps x 4 N tiles
-    *mfma_f32_conv2_per_cell = a == 2 ? 1568 : ((a == 3 || a == 4) ? 0 : 3600);
+    *mfma_f32_conv2_per_cell = a == SV_ALGO_X_WINOGRAD ? 1568 : (a == SV_ALGO_F32MFMA ? 3600 : 0);
     *mfma_f32_conv1_per_cell = 0;
     // f16 pairs: conv2 13 M tiles x 9 taps x 4 N tiles x 3 products + conv1 13 M tiles x 8 N tiles x 2; fc1 98 k-steps x 8 N tiles x 3 per 16 cells
-    *mfma_f16_conv_per_cell = a == 4 ? 13 * 9 * 4 * 3 + 13 * 8 * 2 : 0;
-    *mfma_f16_fc_per_cell = a == 4 ? 98 * 8 * 3 / 16 : 0;
+    *mfma_f16_conv_per_cell = a == SV_ALGO_F16PAIR ? 13 * 9 * 4 * 3 + 13 * 8 * 2 : 0;
+    *mfma_f16_fc_per_cell = a == SV_ALGO_F16PAIR ? 98 * 8 * 3 / 16 : 0;
     return SV_OK;
 }
 
@@ -1102,21 +1141,26 @@ __global__ void k_input_range_finish(int *flag)                     // flag[0] |
     if (flag[1] == 0) flag[0] = 1;
 }
 
+// The whole CNN forward of a batch: run.py's preprocess_cell pass when asked for, then the bf16 configuration or the SV_PREC_F32 family
+// effective_algo names.
 int svk_cnn_forward(sv_ctx *ctx, const void *x, bool x_is_u8, int glue, long B, float *logits, u8 *digits, float *conf, hipStream_t s)
 {
     const sv_weights &w = ctx->w;
     const long npairs = (B + 1) / 2;
+    if (ctx->precision == SV_PREC_BF16 && !x_is_u8)
+        return sv_fail(SV_ERR_UNSUPPORTED, "sv_cnn_forward_f32: the bf16 configuration takes 8-bit cells (sv_cnn_forward_cells_u8 / sv_frames_to_digits)");
     if (x_is_u8 && glue == SV_GLUE_RUNPY) {      // run.py's preprocess_cell as its own pass; its {0,255} output then takes the plain glue
         int rc = svk_preprocess_cells((const u8 *)x, B, ctx->cells2, s);
         if (rc) return rc;
         x = ctx->cells2;
     }
-    int conv_algo = effective_algo(ctx);
+    if (ctx->precision == SV_PREC_BF16) return svk_cnn_forward_bf16(ctx, (const u8 *)x, B, logits, digits, conf, s);
+    sv_cnn_algo conv_algo = effective_algo(ctx);
     // (the kernels that read 8-bit cells as dwords need a 4-byte-aligned buffer; a misaligned one takes the direct f32 kernel)
-    if (x_is_u8 && ((uintptr_t)x & 3)) conv_algo = 0;
+    if (x_is_u8 && ((uintptr_t)x & 3)) conv_algo = SV_ALGO_F32MFMA;
     const int *flag = nullptr;                   // device flag: 0 = the f16-pair kernels run, 1 = the f32-MFMA kernels (both are launched)
-    if (conv_algo == 4 && !x_is_u8 && ctx->cnn_kernels == SV_CNN_AUTO) {
-        // 8-bit cells are in [-1, 1] after the glue (what sv_load_weights_f32 sized the activations for); f32 input can be anything
+    if (conv_algo == SV_ALGO_F16PAIR && !x_is_u8 && ctx->cnn_kernels == SV_CNN_AUTO) {
+        // 8-bit cells are in [-1, 1] after the glue (what svk_pack_weights_h2 sized the activations for); f32 input can be anything
         if (!ctx->range_flag) SV_HIP(hipMalloc((void **)&ctx->range_flag, 2 * sizeof(int)));
         SV_HIP(hipMemsetAsync(ctx->range_flag, 0, 2 * sizeof(int), s));
         const long n = B * 784;
@@ -1125,17 +1169,17 @@ int svk_cnn_forward(sv_ctx *ctx, const void *x, bool x_is_u8, int glue, long B, 
         SV_LAUNCH_CHECK("k_input_range");
         flag = ctx->range_flag;
     }
-    if (conv_algo == 4) {
+    if (conv_algo == SV_ALGO_F16PAIR) {
         const int rc = svk_cnn_forward_h2(ctx, x, x_is_u8, B, logits, digits, conf, flag, s);
         if (rc || !flag) return rc;
     }
 #ifdef SV_XCHECK
-    if (conv_algo == 3 || conv_algo == 2) {
+    if (conv_algo == SV_ALGO_X_WSPLIT || conv_algo == SV_ALGO_X_WINOGRAD) {
         long cpw = (B + ctx->num_cus - 1) / ctx->num_cus;
         if (cpw < 1) cpw = 1;
         const int grid_s = (int)((B + cpw - 1) / cpw);
         sv_time_scope ts(ctx, SVK_CONV_FEATURES, s);
-        if (conv_algo == 3) {
+        if (conv_algo == SV_ALGO_X_WSPLIT) {
             if (x_is_u8)
                 hipLaunchKernelGGL(k_conv_features_wsplit<true>, dim3(grid_s), dim3(512), 0, s, x, B, cpw, w.conv1_w, w.conv1_b, (const uint4 *)w.conv2_wsplit, w.conv2_b, ctx->features);
             else

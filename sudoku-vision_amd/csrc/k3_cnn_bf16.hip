@@ -9,6 +9,8 @@
 //        instead of 288 in f32.  N tiles are interleaved (column c of tile t = channel 4c + t) so that a lane ends up with
 //        4 consecutive channels of one pooled window: one 8-byte store of bf16 features.
 //   k_fc_head_bf16       : fc1 on the same MFMA (K = 3136 = 98 steps), fc2/argmax/softmax epilogue in f32 as in k_fc_head.
+#include <cstring>
+
 #include "sv_device.h"
 #include "sv_internal.h"
 
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(256) void k_fc_head_bf16(const unsigned short *__re
     const uint4 *ap = (const uint4 *)(feat + crow * FEAT) + q;      // step s: + 4*s
     const uint4 *bp = w1img + lane;                                 // [98][8][64]
 
-    for (int i = tid; i < 1280; i += 256) w2s[i >> 7][i & 127] = w2[i];
+    sv_fc2_stage<256>(w2s, w2, tid);
 
     f32x4 acc[8];
 #pragma unroll
@@ -202,25 +204,13 @@ __global__ __launch_bounds__(256) void k_fc_head_bf16(const unsigned short *__re
     for (int jj = 0; jj < 3; jj++) {
         const int j = q + 4 * jj;
         if (j < 10) {
-            float sacc = b2[j];
-            for (int n = 0; n < 128; n++) sacc = __builtin_fmaf(hs[wave][r][n], w2s[j][n], sacc);
+            const float sacc = sv_fc2_logit(hs[wave][r], w2s, b2, j);
             lg[wave][r][j] = sacc;
             if (cell0 + r < B) logits[(cell0 + r) * 10 + j] = sacc;
         }
     }
     __syncthreads();
-    if (q == 0 && cell0 + r < B && (digits || conf)) {
-        float best = lg[wave][r][0];
-        int arg = 0;
-        for (int j = 1; j < 10; j++)
-            if (lg[wave][r][j] > best) { best = lg[wave][r][j]; arg = j; }
-        if (digits) digits[cell0 + r] = (u8)arg;
-        if (conf) {
-            float den = 0.f;
-            for (int j = 0; j < 10; j++) den += expf(lg[wave][r][j] - best);
-            conf[cell0 + r] = 1.0f / den;
-        }
-    }
+    if (q == 0 && cell0 + r < B) sv_digit_conf(lg[wave][r], cell0 + r, digits, conf);
 }
 
 
@@ -256,7 +246,7 @@ __global__ __launch_bounds__(64 * BFP_WAVES, 1) void k_fc_head_bf16p(const unsig
     const int r = lane & 15, q = lane >> 4;
     const int mt = wave % BFP_MT, nh = wave / BFP_MT;
     const bool loader = wave < 8;
-    for (int i = tid; i < 1280; i += 64 * BFP_WAVES) w2s[i >> 7][i & 127] = w2[i];
+    sv_fc2_stage<64 * BFP_WAVES>(w2s, w2, tid);
 
     // this lane's A fragments in a feature stage: row 16 mt + r, step ss = unit 4 ss + q, in slot unit ^ (r >> 1 & 7)
     unsigned a_off[2];
@@ -321,29 +311,43 @@ __global__ __launch_bounds__(64 * BFP_WAVES, 1) void k_fc_head_bf16p(const unsig
         for (int jj = 0; jj < 3; jj++) {
             const int j = q + 4 * jj;
             if (j < 10) {
-                float sacc = b2[j];
-                for (int n = 0; n < 128; n++) sacc = __builtin_fmaf(hs[16 * mt + r][n], w2s[j][n], sacc);
+                const float sacc = sv_fc2_logit(hs[16 * mt + r], w2s, b2, j);
                 lg[mt][r][j] = sacc;
                 if (cell0 + r < c_end) logits[(cell0 + r) * 10 + j] = sacc;
             }
         }
     }
     __syncthreads();
-    if (nh == 0 && q == 0 && cell0 + r < c_end && (digits || conf)) {
-        float best = lg[mt][r][0];
-        int arg = 0;
-        for (int j = 1; j < 10; j++)
-            if (lg[mt][r][j] > best) { best = lg[mt][r][j]; arg = j; }
-        if (digits) digits[cell0 + r] = (u8)arg;
-        if (conf) {
-            float den = 0.f;
-            for (int j = 0; j < 10; j++) den += expf(lg[mt][r][j] - best);
-            conf[cell0 + r] = 1.0f / den;
-        }
-    }
+    if (nh == 0 && q == 0 && cell0 + r < c_end) sv_digit_conf(lg[mt][r], cell0 + r, digits, conf);
 }
 
 }  // namespace
+
+// Round-to-nearest-even images for v_mfma_f32_16x16x32_bf16.
+//   conv2 [tap][t][lane][j]: oc = 4*(lane&15) + t, ic = 8*(lane>>4) + j
+//   fc1   [step][t][lane][j]: n = 16t + (lane&15), feature k' = 32*step + 8*(lane>>4) + j = window*64 + oc
+int svk_pack_weights_bf16(sv_weights &w, const float *c2w, const float *f1w)
+{
+    auto bf16 = [](float f) -> uint16_t { uint32_t u; memcpy(&u, &f, 4); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); };
+    std::vector<uint16_t> w2b((size_t)9 * 4 * 64 * 8), fc1b((size_t)98 * 8 * 64 * 8);
+    for (int tap = 0; tap < 9; tap++)
+        for (int t = 0; t < 4; t++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int j = 0; j < 8; j++) {
+                    const int oc = 4 * (lane & 15) + t, ic = 8 * (lane >> 4) + j;
+                    w2b[(((size_t)tap * 4 + t) * 64 + lane) * 8 + j] = bf16(c2w[(oc * 32 + ic) * 9 + tap]);
+                }
+    for (int st = 0; st < 98; st++)
+        for (int t = 0; t < 8; t++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int j = 0; j < 8; j++) {
+                    const int kp = 32 * st + 8 * (lane >> 4) + j, win = kp >> 6, oc = kp & 63, n = 16 * t + (lane & 15);
+                    fc1b[(((size_t)st * 8 + t) * 64 + lane) * 8 + j] = bf16(f1w[(size_t)n * 3136 + oc * 49 + win]);
+                }
+    int rc;
+    if ((rc = sv_upload(w, &w.conv2_bf16, w2b.data(), w2b.size()))) return rc;
+    return sv_upload(w, &w.fc1_bf16, fc1b.data(), fc1b.size());
+}
 
 int svk_cnn_forward_bf16(sv_ctx *ctx, const u8 *cells, long B, float *logits, u8 *digits, float *conf, hipStream_t s)
 {

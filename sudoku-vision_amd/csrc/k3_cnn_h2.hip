@@ -28,7 +28,7 @@
 //        through double-buffered LDS, A fragments straight from global memory) for larger batches.
 //
 // Range: inputs and activations are carried as f16 pairs, so their magnitudes must stay below 65,504 (and a pair holds 22 significant bits
-// only while its low half is a normal f16, |v| >= 2^-3; below that the absolute error is f16's subnormal step, 2^-24).  sv_load_weights_f32
+// only while its low half is a normal f16, |v| >= 2^-3; below that the absolute error is f16's subnormal step, 2^-24).  svk_pack_weights_h2
 // bounds the activations from the weights, scales conv1's activations and the features by powers of two when their bounds are below 1
 // (folded into b1, b2 and the scale_inv factors), and svk_cnn_forward (k3_cnn.hip) routes anything outside to the f32-MFMA kernels;
 // `run_if_clear` is that decision for f32 inputs, made on the device.  SV_DEV builds (tools/dev) add an ablation switch and s_memtime stamps; the product is compiled without them.
@@ -69,8 +69,8 @@ __device__ __forceinline__ unsigned pack2h(_Float16 a, _Float16 b)
     return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
 }
 
-// v -> (hi, lo) with hi + lo = v to 22 bits
-__device__ __forceinline__ void split_h2(float v, _Float16 &hi, _Float16 &lo)
+// v -> (hi, lo) with hi + lo = v to 22 bits (the kernels' activations and, on the host, the weights of svk_pack_weights_h2)
+__host__ __device__ __forceinline__ void split_h2(float v, _Float16 &hi, _Float16 &lo)
 {
     hi = (_Float16)v;
     lo = (_Float16)(v - (float)hi);
@@ -410,7 +410,7 @@ __global__ __launch_bounds__(256, 2) void k_fc_head_h2(const float *__restrict__
     // per stage, and what arrives are the MFMA operands themselves
     const uint4 *ap = (const uint4 *)(feat + crow * FEAT + 16 * q);     // stage S: + 16*S uint4; [2 ss] = hi, [2 ss + 1] = lo
 
-    for (int i = tid; i < 1280; i += 256) w2s[i >> 7][i & 127] = w2[i];
+    sv_fc2_stage<256>(w2s, w2, tid);
 
     f32x4 acc_h[8], acc_l[8];
 #pragma unroll
@@ -469,25 +469,13 @@ __global__ __launch_bounds__(256, 2) void k_fc_head_h2(const float *__restrict__
     for (int jj = 0; jj < 3; jj++) {                                  // fc2: lane (cell r, class group q) -> classes q, q+4, q+8
         const int j = q + 4 * jj;
         if (j < 10) {
-            float s = b2[j];
-            for (int n = 0; n < 128; n++) s = __builtin_fmaf(hs[wave][r][n], w2s[j][n], s);
+            const float s = sv_fc2_logit(hs[wave][r], w2s, b2, j);
             lg[wave][r][j] = s;
             if (cell0 + r < B) logits[(cell0 + r) * 10 + j] = s;
         }
     }
     __syncthreads();
-    if (q == 0 && cell0 + r < B && (digits || conf)) {
-        float best = lg[wave][r][0];
-        int arg = 0;
-        for (int j = 1; j < 10; j++)
-            if (lg[wave][r][j] > best) { best = lg[wave][r][j]; arg = j; }
-        if (digits) digits[cell0 + r] = (u8)arg;
-        if (conf) {
-            float den = 0.f;
-            for (int j = 0; j < 10; j++) den += expf(lg[wave][r][j] - best);
-            conf[cell0 + r] = 1.0f / den;
-        }
-    }
+    if (q == 0 && cell0 + r < B) sv_digit_conf(lg[wave][r], cell0 + r, digits, conf);
 }
 
 
@@ -541,7 +529,7 @@ __global__ __launch_bounds__(64 * FCP_WAVES, 1) void k_fc_head_h2p(const float *
     const int r = lane & 15, q = lane >> 4;
     const int mt = wave % FCP_MT, nh = wave / FCP_MT;                                  // M tile, N half (hidden units 64 nh ..)
     const bool loader = wave < 8;
-    for (int i = tid; i < 1280; i += 64 * FCP_WAVES) w2s[i >> 7][i & 127] = w2[i];
+    sv_fc2_stage<64 * FCP_WAVES>(w2s, w2, tid);
 
     // this lane's A fragments in a feature stage: row 16 mt + r; (step ss, part) = unit 4 q + 2 ss + part, in slot unit ^ g(r)
     const unsigned g_r = ((unsigned)(r & 3) << 2) | (unsigned)(r >> 2);
@@ -640,30 +628,121 @@ __global__ __launch_bounds__(64 * FCP_WAVES, 1) void k_fc_head_h2p(const float *
             for (int jj = 0; jj < 3; jj++) {                                            // fc2: lane (cell r, class group q) -> classes q, q+4, q+8
                 const int j = q + 4 * jj;
                 if (j < 10) {
-                    float s = b2[j];
-                    for (int n = 0; n < 128; n++) s = __builtin_fmaf(hs[16 * mt + r][n], w2s[j][n], s);
+                    const float s = sv_fc2_logit(hs[16 * mt + r], w2s, b2, j);
                     lg[mt][r][j] = s;
                     if (cell0 + r < c_end) logits[(cell0 + r) * 10 + j] = s;
                 }
             }
         }
         __syncthreads();
-        if (nh == 0 && q == 0 && cell0 + r < c_end && (digits || conf)) {
-            float best = lg[mt][r][0];
-            int arg = 0;
-            for (int j = 1; j < 10; j++)
-                if (lg[mt][r][j] > best) { best = lg[mt][r][j]; arg = j; }
-            if (digits) digits[cell0 + r] = (u8)arg;
-            if (conf) {
-                float den = 0.f;
-                for (int j = 0; j < 10; j++) den += expf(lg[mt][r][j] - best);
-                conf[cell0 + r] = 1.0f / den;
-            }
-        }
+        if (nh == 0 && q == 0 && cell0 + r < c_end) sv_digit_conf(lg[mt][r], cell0 + r, digits, conf);
     }
 }
 
 }  // namespace
+
+int svk_pack_weights_h2(sv_weights &w, const float *c1w, const float *c1b, const float *c2w, const float *c2b, const float *f1w)
+{
+    // Range of the f16-pair kernels for these weights (inputs, conv1 activations and features are carried as f16 pairs: each must stay
+    // below f16's 65,504).  Worst case over inputs of magnitude <= xm:  |conv1| <= A1*xm + B1,  |features| <= A2*(A1*xm + B1) + B2
+    // with A = the largest absolute row sum of a layer's weights, B = its largest |bias|.  A pair holds 22 significant bits only while its lo
+    // half is a normal f16 (|v| >= 2^-3); so when a layer's bound at xm = 1 is below 1, the kernels carry its activations times 2^eA (conv1) or
+    // 2^eF (features), which puts that bound in [1, 2).  Such a power of two is exact; the kernels fold it into the biases and the scale_inv
+    // factors below, and for bounds of 1 or more (every ordinary set of weights) eA = eF = 0.  h2_x_hi = the largest xm all bounds allow,
+    // after the scaling; 8-bit cells are in [-1, 1] after the glue, so the f16-pair kernels serve them iff h2_x_hi >= 1.  An f32 input batch
+    // is not scaled: below 2^-3 its values' low halves are f16-subnormal, and such batches take the f32 kernels too.
+    int eA = 0, eF = 0;
+    {
+        auto row_sum_max = [](const float *wt, int rows, int cols) { double m = 0; for (int r = 0; r < rows; r++) { double a = 0; for (int c = 0; c < cols; c++) a += std::fabs((double)wt[(size_t)r * cols + c]); m = std::fmax(m, a); } return m; };
+        auto abs_max = [](const float *v, int n) { double m = 0; for (int i = 0; i < n; i++) m = std::fmax(m, std::fabs((double)v[i])); return m; };
+        const double LIM = 6.0e4, A1 = row_sum_max(c1w, 32, 9), B1 = abs_max(c1b, 32), A2 = row_sum_max(c2w, 64, 288), B2 = abs_max(c2b, 64);
+        const double U1 = A1 + B1, U2 = A2 * U1 + B2;
+        if (U1 > 0 && U1 < 1) eA = std::min(-std::ilogb(U1), 120);
+        if (U2 > 0 && U2 < 1) eF = std::min(-std::ilogb(U2), 120);
+        const double sA = std::ldexp(1.0, eA), sF = std::ldexp(1.0, eF);
+        double hi = LIM;
+        if (A1 > 0) hi = std::fmin(hi, (LIM / sA - B1) / A1);
+        else if (B1 * sA > LIM) hi = -1;
+        if (A2 > 0 && A1 > 0) hi = std::fmin(hi, ((LIM / sF - B2) / A2 - B1) / A1);
+        else if ((A2 * B1 + B2) * sF > LIM) hi = -1;
+        if (!std::isfinite(A1) || !std::isfinite(A2) || !std::isfinite(B1) || !std::isfinite(B2) || !(hi == hi)) hi = -1;
+        w.h2_x_hi = (float)hi;
+        w.h2_x_lo = 0x1p-3f;
+        w.h2_in_range = hi >= 1.0;
+    }
+    // w * 2^e = hi + lo, both f16 (round to nearest), e chosen so that max|w| * 2^e lies in [2^13, 2^14): hi is far from f16's overflow
+    // (65504) and lo (~2^-11 of hi) stays a normal f16.  Every finite weight has e >= -114; e is capped at 120 (weights below ~2^-107),
+    // where 2^e would approach the end of f32's range.
+    auto pow2_scale = [](const float *v, size_t n) -> int {
+        float m = 0.f;
+        for (size_t i = 0; i < n; i++) m = std::fmax(m, std::fabs(v[i]));
+        if (!(m > 0.f) || !std::isfinite(m)) return 0;
+        const int e = 13 - std::ilogb(m);
+        return e > 120 ? 120 : e;
+    };
+    auto split_bits = [](float ws, uint16_t &hi, uint16_t &lo) {
+        _Float16 h, l;
+        split_h2(ws, h, l);
+        hi = __builtin_bit_cast(uint16_t, h);
+        lo = __builtin_bit_cast(uint16_t, l);
+    };
+    const int e2 = pow2_scale(c2w, 18432), e1 = pow2_scale(f1w, 401408);
+    const float s2 = std::ldexp(1.f, e2), s1 = std::ldexp(1.f, e1);
+    w.conv2_h2_scale_inv = std::ldexp(1.f, eF - eA - e2);     // conv2 reads conv1's activations x 2^eA and writes the features x 2^eF
+    w.fc1_h2_scale_inv = std::ldexp(1.f, -eF - e1);
+    // conv2 [tap][np][t][part][lane][j]: oc = 32np + 2*(lane&15) + t, ic = 8*(lane>>4) + j (k_conv_features_h2's breg)
+    // fc1 [step][t][part][lane][j]: n = 16t + (lane&15); k-slot (q = lane>>4, j) of step st = feature 64*(st/2) + 16q + 8*(st%2) + j, so that
+    // a lane's operands of a 2-step stage are contiguous (k_fc_head_h2, k_fc_head_h2p)
+    std::vector<uint16_t> c2h((size_t)9 * 2 * 2 * 2 * 64 * 8), f1h((size_t)98 * 8 * 2 * 64 * 8);
+    for (int tap = 0; tap < 9; tap++)
+        for (int np = 0; np < 2; np++)
+            for (int t = 0; t < 2; t++)
+                for (int lane = 0; lane < 64; lane++)
+                    for (int j = 0; j < 8; j++) {
+                        const int oc = 32 * np + 2 * (lane & 15) + t, ic = 8 * (lane >> 4) + j;
+                        const size_t base = ((((size_t)tap * 2 + np) * 2 + t) * 2) * 64 * 8;
+                        split_bits(c2w[(oc * 32 + ic) * 9 + tap] * s2, c2h[base + (size_t)lane * 8 + j], c2h[base + 512 + (size_t)lane * 8 + j]);
+                    }
+    for (int st = 0; st < 98; st++)
+        for (int t = 0; t < 8; t++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int j = 0; j < 8; j++) {
+                    const int kp = 64 * (st >> 1) + 16 * (lane >> 4) + 8 * (st & 1) + j, win = kp >> 6, oc = kp & 63, n = 16 * t + (lane & 15);
+                    const size_t base = (((size_t)st * 8 + t) * 2) * 64 * 8;
+                    split_bits(f1w[(size_t)n * 3136 + oc * 49 + win] * s1, f1h[base + (size_t)lane * 8 + j], f1h[base + 512 + (size_t)lane * 8 + j]);
+                }
+    // conv1 as a GEMM over the 4x4 input patch of a pooling window, [chalf][pos][mfma][lane][j]: k = 16*part + 4r + c (part 0: hi plane of
+    // the input, 1: lo plane), column = channel 16*chalf + (lane&15) at conv position (dy, dx) of the window; B = w1[ch][r-dy][c-dx] (0 outside
+    // the 3x3).  MFMA 0 multiplies [xh | xl] by [wh | wh], MFMA 1 by [wl | 0]:  xh*wh + xl*wh + xh*wl.
+    const int e0 = pow2_scale(c1w, 288);
+    const float s0 = std::ldexp(1.f, e0);
+    w.conv1_h2_scale_inv = std::ldexp(1.f, eA - e0);
+    // the folded factors must be normal floats (only weights or biases spanning ~2^250 could push them out; the f32 kernels take those)
+    for (int e : {eA - e0, eF - eA - e2, -eF - e1})
+        if (e < -126 || e > 127) w.h2_in_range = false;
+    std::vector<float> c1bs(c1b, c1b + 32), c2bs(c2b, c2b + 64);
+    for (float &b : c1bs) b = std::ldexp(b, eA);
+    for (float &b : c2bs) b = std::ldexp(b, eF);
+    std::vector<uint16_t> c1h((size_t)2 * 4 * 2 * 64 * 8);
+    for (int chalf = 0; chalf < 2; chalf++)
+        for (int pos = 0; pos < 4; pos++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int j = 0; j < 8; j++) {
+                    const int kk = 8 * (lane >> 4) + j, part = kk >> 4, pp = kk & 15, r = pp >> 2, c = pp & 3;
+                    const int ky = r - (pos >> 1), kx = c - (pos & 1), ch = 16 * chalf + (lane & 15);
+                    uint16_t hi = 0, lo = 0;
+                    if (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) split_bits(c1w[ch * 9 + ky * 3 + kx] * s0, hi, lo);
+                    const size_t base = (((size_t)chalf * 4 + pos) * 2) * 64 * 8 + (size_t)lane * 8 + j;
+                    c1h[base] = hi;
+                    c1h[base + 512] = part == 0 ? lo : 0;
+                }
+    int rc;
+    if ((rc = sv_upload(w, &w.conv1_h2, c1h.data(), c1h.size()))) return rc;
+    if ((rc = sv_upload(w, &w.conv2_h2, c2h.data(), c2h.size()))) return rc;
+    if ((rc = sv_upload(w, &w.fc1_h2, f1h.data(), f1h.size()))) return rc;
+    if ((rc = sv_upload(w, &w.conv1_b_h2, c1bs.data(), c1bs.size()))) return rc;
+    return sv_upload(w, &w.conv2_b_h2, c2bs.data(), c2bs.size());
+}
 
 #ifdef SV_DEV
 // development builds (make FLAGS+=-DSV_DEV): the ablation / stamp bits of k_conv_features_h2, see svk_cnn_forward_h2

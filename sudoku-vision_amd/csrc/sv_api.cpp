@@ -1,4 +1,4 @@
-// Host side of libsudokuvision_hip.so: context, weight packing, fp64 homography, argument checks.
+// Host side of libsudokuvision_hip.so: context, weight loading, fp64 homography, argument checks.
 // Everything exported here is declared in include/sudoku_vision_hip.h.
 #include <algorithm>
 #include <cmath>
@@ -42,22 +42,8 @@ extern "C" int sv_ctx_create(int device, sv_ctx **out)
 
 static void free_weights(sv_weights &w)
 {
-    float **ps[] = {&w.conv1_w, &w.conv1_b, &w.conv2_wreg, &w.conv2_wino, &w.conv2_b, &w.fc1_wreg, &w.fc1_b, &w.fc2_w, &w.fc2_b, &w.conv1_b_h2, &w.conv2_b_h2};
-    for (float **p : ps) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    if (w.conv2_wsplit) (void)hipFree(w.conv2_wsplit);
-    w.conv2_wsplit = nullptr;
-    if (w.conv2_bf16) (void)hipFree(w.conv2_bf16);
-    if (w.fc1_bf16) (void)hipFree(w.fc1_bf16);
-    w.conv2_bf16 = w.fc1_bf16 = nullptr;
-    if (w.conv1_h2) (void)hipFree(w.conv1_h2);
-    w.conv1_h2 = nullptr;
-    if (w.conv2_h2) (void)hipFree(w.conv2_h2);
-    if (w.fc1_h2) (void)hipFree(w.fc1_h2);
-    w.conv2_h2 = w.fc1_h2 = nullptr;
-    w.loaded = false;
+    for (void *p : w.allocs) (void)hipFree(p);
+    w = sv_weights();
 }
 
 extern "C" int sv_ctx_destroy(sv_ctx *ctx)
@@ -159,13 +145,6 @@ extern "C" int sv_timing_end(sv_ctx *ctx, double *ms_total, long *launches, int 
 }
 
 // ---- weights --------------------------------------------------------------------------------------
-static int upload(float **dst, const std::vector<float> &v)
-{
-    SV_HIP(hipMalloc((void **)dst, v.size() * sizeof(float)));
-    SV_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-    return SV_OK;
-}
-
 extern "C" int sv_load_weights_f32(sv_ctx *ctx, const float *blob)
 {
     if (!ctx || !blob) return sv_fail(SV_ERR_BAD_ARG, "sv_load_weights_f32: NULL argument");
@@ -173,196 +152,18 @@ extern "C" int sv_load_weights_f32(sv_ctx *ctx, const float *blob)
     free_weights(ctx->w);
     const float *c1w = blob, *c1b = c1w + 288, *c2w = c1b + 32, *c2b = c2w + 18432, *f1w = c2b + 64,
                 *f1b = f1w + 401408, *f2w = f1b + 128, *f2b = f2w + 1280;
-    // conv2: [np][t][ks][lane]; lane -> oc = 32np + 16t + (lane&15), ic = icb + 8*(lane>>4); ks = tap*8 + icb
-    std::vector<float> w2(2 * 2 * 72 * 64);
-    for (int np = 0; np < 2; np++)
-        for (int t = 0; t < 2; t++)
-            for (int ks = 0; ks < 72; ks++)
-                for (int lane = 0; lane < 64; lane++) {
-                    const int oc = 32 * np + 16 * t + (lane & 15), tap = ks >> 3, ic = (ks & 7) + 8 * (lane >> 4);
-                    w2[((np * 2 + t) * 72 + ks) * 64 + lane] = c2w[(oc * 32 + ic) * 9 + tap];
-                }
-    // fc1: [chunk][t][lane][e]; feature index k' = 16*chunk + 4*(lane>>4) + e = window*64 + oc;
-    // the reference flattens NCHW: k = oc*49 + window (ml/model.py:38)
-    std::vector<float> f1((size_t)196 * 8 * 64 * 4);
-    for (int c = 0; c < 196; c++)
-        for (int t = 0; t < 8; t++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int e = 0; e < 4; e++) {
-                    const int kp = 16 * c + 4 * (lane >> 4) + e, win = kp >> 6, oc = kp & 63, n = 16 * t + (lane & 15);
-                    f1[(((size_t)c * 8 + t) * 64 + lane) * 4 + e] = f1w[(size_t)n * 3136 + oc * 49 + win];
-                }
-#ifdef SV_XCHECK
-    // Winograd F(2x2,3x3) weights U = G g G^T (computed in double), as [nt][xi][ks][lane]: oc = 16nt + (lane&15), ic = 4ks + (lane>>4)
-    std::vector<float> wino((size_t)4 * 16 * 8 * 64);
-    // the same U split without error into three bf16 parts (each the next 8 mantissa bits, by truncation) for
-    // k_conv_features_wsplit: [nt][xi][part][lane][j], oc = 16nt + (lane&15), ic = 8*(lane>>4) + j
-    std::vector<uint16_t> wsplit((size_t)4 * 16 * 3 * 64 * 8);
-    {
-        const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-        for (int oc = 0; oc < 64; oc++)
-            for (int ic = 0; ic < 32; ic++) {
-                const float *g = c2w + (oc * 32 + ic) * 9;
-                double Gg[4][3], U[4][4];
-                for (int i = 0; i < 4; i++)
-                    for (int j = 0; j < 3; j++) Gg[i][j] = G[i][0] * g[j] + G[i][1] * g[3 + j] + G[i][2] * g[6 + j];
-                for (int i = 0; i < 4; i++)
-                    for (int j = 0; j < 4; j++) U[i][j] = Gg[i][0] * G[j][0] + Gg[i][1] * G[j][1] + Gg[i][2] * G[j][2];
-                const int nt = oc >> 4, lane = (oc & 15) + 16 * (ic & 3), ks = ic >> 2;
-                for (int xi = 0; xi < 16; xi++) {
-                    const float u = (float)U[xi >> 2][xi & 3];
-                    wino[(((size_t)nt * 16 + xi) * 8 + ks) * 64 + lane] = u;
-                    float rest = u;
-                    for (int part = 0; part < 3; part++) {
-                        uint32_t bits;
-                        memcpy(&bits, &rest, 4);
-                        bits &= 0xffff0000u;
-                        float piece;
-                        memcpy(&piece, &bits, 4);
-                        rest -= piece;                                        // exact
-                        wsplit[((((size_t)nt * 16 + xi) * 3 + part) * 64 + (oc & 15) + 16 * (ic >> 3)) * 8 + (ic & 7)] = (uint16_t)(bits >> 16);
-                    }
-                }
-            }
-    }
-#endif
-    // bf16 configuration: round-to-nearest-even images for v_mfma_f32_16x16x32_bf16.
-    //   conv2 [tap][t][lane][j]: oc = 4*(lane&15) + t, ic = 8*(lane>>4) + j
-    //   fc1   [step][t][lane][j]: n = 16t + (lane&15), feature k' = 32*step + 8*(lane>>4) + j = window*64 + oc
-    auto bf16 = [](float f) -> uint16_t { uint32_t u; memcpy(&u, &f, 4); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); };
-    std::vector<uint16_t> w2b((size_t)9 * 4 * 64 * 8), fc1b((size_t)98 * 8 * 64 * 8);
-    for (int tap = 0; tap < 9; tap++)
-        for (int t = 0; t < 4; t++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    const int oc = 4 * (lane & 15) + t, ic = 8 * (lane >> 4) + j;
-                    w2b[(((size_t)tap * 4 + t) * 64 + lane) * 8 + j] = bf16(c2w[(oc * 32 + ic) * 9 + tap]);
-                }
-    for (int st = 0; st < 98; st++)
-        for (int t = 0; t < 8; t++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    const int kp = 32 * st + 8 * (lane >> 4) + j, win = kp >> 6, oc = kp & 63, n = 16 * t + (lane & 15);
-                    fc1b[(((size_t)st * 8 + t) * 64 + lane) * 8 + j] = bf16(f1w[(size_t)n * 3136 + oc * 49 + win]);
-                }
-    // Range of the f16-pair kernels for these weights (k3_cnn_h2.hip carries inputs, conv1 activations and features as f16 pairs: each
-    // must stay below f16's 65,504).  Worst case over inputs of magnitude <= xm:  |conv1| <= A1*xm + B1,  |features| <= A2*(A1*xm + B1) + B2
-    // with A = the largest absolute row sum of a layer's weights, B = its largest |bias|.  A pair holds 22 significant bits only while its lo
-    // half is a normal f16 (|v| >= 2^-3); so when a layer's bound at xm = 1 is below 1, the kernels carry its activations times 2^eA (conv1) or
-    // 2^eF (features), which puts that bound in [1, 2).  Such a power of two is exact; the kernels fold it into the biases and the scale_inv
-    // factors below, and for bounds of 1 or more (every ordinary set of weights) eA = eF = 0.  h2_x_hi = the largest xm all bounds allow,
-    // after the scaling; 8-bit cells are in [-1, 1] after the glue, so the f16-pair kernels serve them iff h2_x_hi >= 1.  An f32 input batch
-    // is not scaled: below 2^-3 its values' low halves are f16-subnormal, and such batches take the f32 kernels too.
-    int eA = 0, eF = 0;
-    {
-        auto row_sum_max = [](const float *wt, int rows, int cols) { double m = 0; for (int r = 0; r < rows; r++) { double a = 0; for (int c = 0; c < cols; c++) a += std::fabs((double)wt[(size_t)r * cols + c]); m = std::fmax(m, a); } return m; };
-        auto abs_max = [](const float *v, int n) { double m = 0; for (int i = 0; i < n; i++) m = std::fmax(m, std::fabs((double)v[i])); return m; };
-        const double LIM = 6.0e4, A1 = row_sum_max(c1w, 32, 9), B1 = abs_max(c1b, 32), A2 = row_sum_max(c2w, 64, 288), B2 = abs_max(c2b, 64);
-        const double U1 = A1 + B1, U2 = A2 * U1 + B2;
-        if (U1 > 0 && U1 < 1) eA = std::min(-std::ilogb(U1), 120);
-        if (U2 > 0 && U2 < 1) eF = std::min(-std::ilogb(U2), 120);
-        const double sA = std::ldexp(1.0, eA), sF = std::ldexp(1.0, eF);
-        double hi = LIM;
-        if (A1 > 0) hi = std::fmin(hi, (LIM / sA - B1) / A1);
-        else if (B1 * sA > LIM) hi = -1;
-        if (A2 > 0 && A1 > 0) hi = std::fmin(hi, ((LIM / sF - B2) / A2 - B1) / A1);
-        else if ((A2 * B1 + B2) * sF > LIM) hi = -1;
-        if (!std::isfinite(A1) || !std::isfinite(A2) || !std::isfinite(B1) || !std::isfinite(B2) || !(hi == hi)) hi = -1;
-        ctx->w.h2_x_hi = (float)hi;
-        ctx->w.h2_x_lo = 0x1p-3f;
-        ctx->w.h2_in_range = hi >= 1.0;
-    }
-    // k3_cnn_h2.hip: w * 2^e = hi + lo, both f16 (round to nearest), e chosen so that max|w| * 2^e lies in [2^13, 2^14): hi is far
-    // from f16's overflow (65504) and lo (~2^-11 of hi) stays a normal f16.  Every finite weight has e >= -114; e is capped at 120 (weights below
-    // ~2^-107), where 2^e would approach the end of f32's range.
-    auto pow2_scale = [](const float *v, size_t n) -> int {
-        float m = 0.f;
-        for (size_t i = 0; i < n; i++) m = std::fmax(m, std::fabs(v[i]));
-        if (!(m > 0.f) || !std::isfinite(m)) return 0;
-        const int e = 13 - std::ilogb(m);
-        return e > 120 ? 120 : e;
-    };
-    auto split_h2 = [](float ws, uint16_t &hi, uint16_t &lo) {
-        const _Float16 h = (_Float16)ws;
-        const _Float16 l = (_Float16)(ws - (float)h);
-        memcpy(&hi, &h, 2);
-        memcpy(&lo, &l, 2);
-    };
-    const int e2 = pow2_scale(c2w, 18432), e1 = pow2_scale(f1w, 401408);
-    const float s2 = std::ldexp(1.f, e2), s1 = std::ldexp(1.f, e1);
-    ctx->w.conv2_h2_scale_inv = std::ldexp(1.f, eF - eA - e2);     // conv2 reads conv1's activations x 2^eA and writes the features x 2^eF
-    ctx->w.fc1_h2_scale_inv = std::ldexp(1.f, -eF - e1);
-    std::vector<uint16_t> c2h((size_t)9 * 2 * 2 * 2 * 64 * 8), f1h((size_t)98 * 8 * 2 * 64 * 8);
-    for (int tap = 0; tap < 9; tap++)
-        for (int np = 0; np < 2; np++)
-            for (int t = 0; t < 2; t++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int j = 0; j < 8; j++) {
-                        const int oc = 32 * np + 2 * (lane & 15) + t, ic = 8 * (lane >> 4) + j;
-                        const size_t base = ((((size_t)tap * 2 + np) * 2 + t) * 2) * 64 * 8;
-                        split_h2(c2w[(oc * 32 + ic) * 9 + tap] * s2, c2h[base + (size_t)lane * 8 + j], c2h[base + 512 + (size_t)lane * 8 + j]);
-                    }
-    for (int st = 0; st < 98; st++)
-        for (int t = 0; t < 8; t++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    // k-slot (q, j) of step st = feature 64*(st/2) + 16q + 8*(st%2) + j: a lane's operands of a 2-step stage are contiguous
-                    const int kp = 64 * (st >> 1) + 16 * (lane >> 4) + 8 * (st & 1) + j, win = kp >> 6, oc = kp & 63, n = 16 * t + (lane & 15);
-                    const size_t base = (((size_t)st * 8 + t) * 2) * 64 * 8;
-                    split_h2(f1w[(size_t)n * 3136 + oc * 49 + win] * s1, f1h[base + (size_t)lane * 8 + j], f1h[base + 512 + (size_t)lane * 8 + j]);
-                }
-    // conv1 as a GEMM over the 4x4 input patch of a pooling window: k = 16*part + 4r + c (part 0: hi plane of the input, 1: lo plane),
-    // column = channel 16*chalf + (lane&15) at conv position (dy, dx) of the window; B = w1[ch][r-dy][c-dx] (0 outside the 3x3).
-    // MFMA 0 multiplies [xh | xl] by [wh | wh], MFMA 1 by [wl | 0]:  xh*wh + xl*wh + xh*wl.
-    const int e0 = pow2_scale(c1w, 288);
-    const float s0 = std::ldexp(1.f, e0);
-    ctx->w.conv1_h2_scale_inv = std::ldexp(1.f, eA - e0);
-    // the folded factors must be normal floats (only weights or biases spanning ~2^250 could push them out; the f32 kernels take those)
-    for (int e : {eA - e0, eF - eA - e2, -eF - e1})
-        if (e < -126 || e > 127) ctx->w.h2_in_range = false;
-    std::vector<float> c1bs(c1b, c1b + 32), c2bs(c2b, c2b + 64);
-    for (float &b : c1bs) b = std::ldexp(b, eA);
-    for (float &b : c2bs) b = std::ldexp(b, eF);
-    std::vector<uint16_t> c1h((size_t)2 * 4 * 2 * 64 * 8);
-    for (int chalf = 0; chalf < 2; chalf++)
-        for (int pos = 0; pos < 4; pos++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int j = 0; j < 8; j++) {
-                    const int kk = 8 * (lane >> 4) + j, part = kk >> 4, pp = kk & 15, r = pp >> 2, c = pp & 3;
-                    const int ky = r - (pos >> 1), kx = c - (pos & 1), ch = 16 * chalf + (lane & 15);
-                    uint16_t hi = 0, lo = 0;
-                    if (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) split_h2(c1w[ch * 9 + ky * 3 + kx] * s0, hi, lo);
-                    const size_t base = (((size_t)chalf * 4 + pos) * 2) * 64 * 8 + (size_t)lane * 8 + j;
-                    c1h[base] = hi;
-                    c1h[base + 512] = part == 0 ? lo : 0;
-                }
-    SV_HIP(hipMalloc((void **)&ctx->w.conv1_h2, c1h.size() * 2));
-    SV_HIP(hipMemcpy(ctx->w.conv1_h2, c1h.data(), c1h.size() * 2, hipMemcpyHostToDevice));
-    SV_HIP(hipMalloc((void **)&ctx->w.conv2_h2, c2h.size() * 2));
-    SV_HIP(hipMemcpy(ctx->w.conv2_h2, c2h.data(), c2h.size() * 2, hipMemcpyHostToDevice));
-    SV_HIP(hipMalloc((void **)&ctx->w.fc1_h2, f1h.size() * 2));
-    SV_HIP(hipMemcpy(ctx->w.fc1_h2, f1h.data(), f1h.size() * 2, hipMemcpyHostToDevice));
-#ifdef SV_XCHECK
-    SV_HIP(hipMalloc((void **)&ctx->w.conv2_wsplit, wsplit.size() * 2));
-    SV_HIP(hipMemcpy(ctx->w.conv2_wsplit, wsplit.data(), wsplit.size() * 2, hipMemcpyHostToDevice));
-    if (int rcx = upload(&ctx->w.conv2_wino, wino)) return rcx;
-#endif
-    SV_HIP(hipMalloc((void **)&ctx->w.conv2_bf16, w2b.size() * 2));
-    SV_HIP(hipMemcpy(ctx->w.conv2_bf16, w2b.data(), w2b.size() * 2, hipMemcpyHostToDevice));
-    SV_HIP(hipMalloc((void **)&ctx->w.fc1_bf16, fc1b.size() * 2));
-    SV_HIP(hipMemcpy(ctx->w.fc1_bf16, fc1b.data(), fc1b.size() * 2, hipMemcpyHostToDevice));
+    sv_weights &w = ctx->w;
     int rc;
-    if ((rc = upload(&ctx->w.conv1_w, std::vector<float>(c1w, c1w + 288)))) return rc;
-    if ((rc = upload(&ctx->w.conv1_b, std::vector<float>(c1b, c1b + 32)))) return rc;
-    if ((rc = upload(&ctx->w.conv2_wreg, w2))) return rc;
-    if ((rc = upload(&ctx->w.conv2_b, std::vector<float>(c2b, c2b + 64)))) return rc;
-    if ((rc = upload(&ctx->w.conv1_b_h2, c1bs))) return rc;
-    if ((rc = upload(&ctx->w.conv2_b_h2, c2bs))) return rc;
-    if ((rc = upload(&ctx->w.fc1_wreg, f1))) return rc;
-    if ((rc = upload(&ctx->w.fc1_b, std::vector<float>(f1b, f1b + 128)))) return rc;
-    if ((rc = upload(&ctx->w.fc2_w, std::vector<float>(f2w, f2w + 1280)))) return rc;
-    if ((rc = upload(&ctx->w.fc2_b, std::vector<float>(f2b, f2b + 10)))) return rc;
-    ctx->w.loaded = true;
+    if ((rc = svk_pack_weights_h2(w, c1w, c1b, c2w, c2b, f1w))) return rc;
+    if ((rc = svk_pack_weights_bf16(w, c2w, f1w))) return rc;
+    if ((rc = svk_pack_weights_f32mfma(w, c2w, f1w))) return rc;
+    if ((rc = sv_upload(w, &w.conv1_w, c1w, 288))) return rc;
+    if ((rc = sv_upload(w, &w.conv1_b, c1b, 32))) return rc;
+    if ((rc = sv_upload(w, &w.conv2_b, c2b, 64))) return rc;
+    if ((rc = sv_upload(w, &w.fc1_b, f1b, 128))) return rc;
+    if ((rc = sv_upload(w, &w.fc2_w, f2w, 1280))) return rc;
+    if ((rc = sv_upload(w, &w.fc2_b, f2b, 10))) return rc;
+    w.loaded = true;
     return SV_OK;
 }
 
@@ -657,15 +458,6 @@ static int cnn_common(sv_ctx *ctx, const void *x, bool u8in, int glue, long B, f
     int rc = sv_ensure_scratch(ctx, B);
     if (rc) return rc;
     if (glue != SV_GLUE_NORMALIZE && glue != SV_GLUE_RUNPY) return sv_fail(SV_ERR_BAD_ARG, "sv_cnn_forward: glue %d", glue);
-    if (ctx->precision == SV_PREC_BF16) {
-        if (!u8in) return sv_fail(SV_ERR_UNSUPPORTED, "sv_cnn_forward_f32: the bf16 configuration takes 8-bit cells (sv_cnn_forward_cells_u8 / sv_frames_to_digits)");
-        const uint8_t *c = (const uint8_t *)x;
-        if (glue == SV_GLUE_RUNPY) {
-            if ((rc = svk_preprocess_cells(c, B, ctx->cells2, S(stream)))) return rc;
-            c = ctx->cells2;
-        }
-        return svk_cnn_forward_bf16(ctx, c, B, logits, digits, conf, S(stream));
-    }
     return svk_cnn_forward(ctx, x, u8in, glue, B, logits, digits, conf, S(stream));
 }
 

@@ -1,4 +1,4 @@
-// Device-side building blocks shared by the K1/K2 kernels.  Integer stages are exact by
+// Device-side building blocks shared by the K1/K2 kernels and the K3 fc heads.  Integer stages are exact by
 // construction; float/double stages use the _rn intrinsics so that no multiply-add is ever fused
 // (the arithmetic being matched rounds after every operation).
 #pragma once
@@ -116,4 +116,36 @@ __device__ __forceinline__ void sv_resize_axis(int s_len, int d_len, int d, int 
     ofs = s;
     w0 = __float2int_rn(__fmul_rn(__fsub_rn(1.f, f), 2048.f));
     w1 = __float2int_rn(__fmul_rn(f, 2048.f));
+}
+
+// ---- the fc2 -> argmax -> softmax[argmax] epilogue of every fc head (pipeline/run.py:139-143), in f32 on the VALU ----
+// fc2.weight [10][128] -> w2s (LDS), by the NTHREADS threads of the workgroup
+template <int NTHREADS>
+__device__ __forceinline__ void sv_fc2_stage(float (*w2s)[128], const float *w2, int tid)
+{
+    for (int i = tid; i < 1280; i += NTHREADS) w2s[i >> 7][i & 127] = w2[i];
+}
+
+// logit j of a cell from its 128 hidden activations h: b2[j] + h . w2s[j], one fmaf per term in order n = 0..127
+__device__ __forceinline__ float sv_fc2_logit(const float *h, const float (*w2s)[128], const float *b2, int j)
+{
+    float s = b2[j];
+    for (int n = 0; n < 128; n++) s = __builtin_fmaf(h[n], w2s[j][n], s);
+    return s;
+}
+
+// digit (first maximum of the 10 logits lg) and confidence (its softmax probability, 1 / sum exp(lg - best)) of cell `cell`
+__device__ __forceinline__ void sv_digit_conf(const float *lg, long cell, u8 *digits, float *conf)
+{
+    if (!digits && !conf) return;
+    float best = lg[0];
+    int arg = 0;
+    for (int j = 1; j < 10; j++)
+        if (lg[j] > best) { best = lg[j]; arg = j; }
+    if (digits) digits[cell] = (u8)arg;
+    if (conf) {
+        float den = 0.f;
+        for (int j = 0; j < 10; j++) den += expf(lg[j] - best);
+        conf[cell] = 1.0f / den;
+    }
 }

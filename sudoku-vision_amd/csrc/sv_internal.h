@@ -13,7 +13,7 @@
 
 typedef uint8_t u8;
 
-// Packed DigitCNN weights as the kernels consume them (see k3_cnn.hip for the layouts).
+// Packed DigitCNN weights as the kernels consume them (each family's packer, next to its kernels, has the layouts).
 struct sv_weights {
     float *conv1_w = nullptr;   // [32][9]
     float *conv1_b = nullptr;   // [32]
@@ -31,16 +31,17 @@ struct sv_weights {
     unsigned short *conv1_h2 = nullptr;   // [2 chalf][4 pos][2 mfma][64 lane][8] f16: conv1 as a GEMM over the 4x4 patch of a pooling window (k3_cnn_h2.hip)
     float conv1_h2_scale_inv = 1.f, conv2_h2_scale_inv = 1.f, fc1_h2_scale_inv = 1.f;
     // the f16-pair kernels carry conv1's activations and the features times powers of two (1 unless a layer's worst-case bound is below 1,
-    // sv_load_weights_f32); the scale_inv factors above fold them in, and these are the biases of conv1 and conv2 with the same factors
+    // svk_pack_weights_h2); the scale_inv factors above fold them in, and these are the biases of conv1 and conv2 with the same factors
     float *conv1_b_h2 = nullptr;          // [32]
     float *conv2_b_h2 = nullptr;          // [64]
-    // range of the f16-pair kernels for THESE weights (sv_load_weights_f32): with inputs in [-1, 1] (8-bit cells after the glue) every activation
+    // range of the f16-pair kernels for THESE weights (svk_pack_weights_h2): with inputs in [-1, 1] (8-bit cells after the glue) every activation
     // stays below the f16 range iff h2_in_range; an f32 input batch is inside it iff h2_x_lo <= max|x| <= h2_x_hi (0 > hi: never)
     bool h2_in_range = true;
     float h2_x_lo = 0.f, h2_x_hi = 0.f;
     float *fc2_w = nullptr;     // [10][128]
     float *fc2_b = nullptr;     // [10]
     bool loaded = false;
+    std::vector<void *> allocs; // every device buffer above (sv_upload), freed together
 };
 
 struct sv_ctx {
@@ -92,6 +93,19 @@ int sv_fail(int code, const char *fmt, ...);
 
 int sv_ensure_scratch(sv_ctx *ctx, long cells);
 
+// n elements of src -> a new device buffer *dst, recorded in w.allocs
+template <class T>
+int sv_upload(sv_weights &w, T **dst, const T *src, size_t n)
+{
+    SV_HIP(hipMalloc((void **)dst, n * sizeof(T)));
+    w.allocs.push_back(*dst);
+    SV_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return SV_OK;
+}
+
+// The conv/fc kernel family of an SV_PREC_F32 forward (svk_cnn_forward).  The values are ABI: sv_conv_kernel_info reports them.
+enum sv_cnn_algo { SV_ALGO_F32MFMA = 0, SV_ALGO_X_WINOGRAD = 2, SV_ALGO_X_WSPLIT = 3, SV_ALGO_F16PAIR = 4 };
+
 // kernel launchers (one per .hip file)
 int svk_gray(const u8 *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, u8 *gray, hipStream_t s);
 int svk_blur(const u8 *src, int n, int H, int W, int ksize, u8 *dst, hipStream_t s);
@@ -114,6 +128,10 @@ int svk_warp_cells(sv_ctx *ctx, const u8 *frames, int n, int H, int W, ptrdiff_t
                    u8 *cells, hipStream_t s);
 int svk_cnn_forward(sv_ctx *ctx, const void *x, bool x_is_u8, int glue, long B, float *logits, u8 *digits, float *conf,
                     hipStream_t s);
+// weight images of one kernel family from the PyTorch-layout tensors of the blob (sv_load_weights_f32), uploaded into w
+int svk_pack_weights_f32mfma(sv_weights &w, const float *c2w, const float *f1w);
+int svk_pack_weights_bf16(sv_weights &w, const float *c2w, const float *f1w);
+int svk_pack_weights_h2(sv_weights &w, const float *c1w, const float *c1b, const float *c2w, const float *c2b, const float *f1w);
 
 int svk_despeckle(const u8 *src, int n, int H, int W, u8 *dst, unsigned *packed, hipStream_t s);
 int svk_pack_sparse_bits(const uint32_t *bits, int n, int H, int W, u8 *records, long stride, hipStream_t s);

@@ -1,6 +1,8 @@
 """MI355X drop-in for the reference's ml/model.py: `DigitCNN` keeps the attributes, state_dict keys
-and call protocol pipeline/run.py:98-143 relies on; forward() runs the hand-written HIP kernels of
-csrc/k3_cnn.hip (fp32, MFMA implicit-GEMM conv2 + fc1).  Inference only, GPU only."""
+and call protocol pipeline/run.py:98-143 relies on; forward() runs the hand-written HIP kernels: by
+default the f16-pair family of csrc/k3_cnn_h2.hip (f32-grade conv2 + fc1 on the f16 matrix pipe), with
+the f32-MFMA kernels of csrc/k3_cnn.hip as the fallback for weights or inputs outside its range.
+Inference only, GPU only."""
 import os
 import sys
 
