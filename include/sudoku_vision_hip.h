@@ -388,6 +388,74 @@ int sv_grid_line_coverage_u8(sv_ctx *ctx, const uint8_t *binary /*dev*/, int n, 
 int sv_grid_line_coverage_bits(sv_ctx *ctx, const uint32_t *bits /*dev, n*H*W/32*/, int n, int H, int W,
                                const double *minv /*dev, n*9*/, uint32_t *counts /*dev, n*20*/, void *stream);
 
+/* ---- K7: run_v2's preprocessing, cv/preprocess_v2.py (pipeline/run_v2.py:278-280) -------------------------------------
+ * Every entry takes n gray frames of H x W (any `pitch` >= W, `img_stride` bytes between frames, any alignment) and writes
+ * dense [n][H][W] outputs that must not overlap the inputs.  cv2 is not available to pin these against: the arithmetic
+ * stated here is the contract (tests/preprocess_v2_ref.py restates it in numpy), parity with OpenCV is unpinned as for K1/K2.
+ * Stages with intermediates keep them in the context's grow-on-demand scratch. */
+
+/* cv2.dilate / cv2.erode / cv2.morphologyEx(MORPH_CLOSE | MORPH_OPEN) with cv2.getStructuringElement(shape, (k, k)),
+ * cv/preprocess_v2.py:52-53, 108-109, 190-200.  ELLIPSE: r = c = k/2, row i (dy = i - r) covers columns
+ * [max(c-dx,0), min(c+dx+1,k)), dx = round_half_even(c * sqrt((r*r - dy*dy) * (1/(r*r)))) in double; RECT: all ones.  Anchor
+ * (k/2, k/2).  dst = max | min of src over the element's ones placed unreflected on the pixel; pixels outside the image do
+ * not take part.  CLOSE = dilate then erode, OPEN = erode then dilate.  1 <= ksize <= 4095 (larger than the image included). */
+#define SV_MORPH_DILATE 0
+#define SV_MORPH_ERODE 1
+#define SV_MORPH_CLOSE 2
+#define SV_MORPH_OPEN 3
+#define SV_SHAPE_RECT 0
+#define SV_SHAPE_ELLIPSE 1
+int sv_morphology_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int op, int shape,
+                     int ksize, uint8_t *dst /*dev, n*H*W*/, void *stream);
+
+/* cv2.blur(gray, (k, k)) on u8, cv/preprocess_v2.py:93: S = the integer sum over the k x k window (BORDER_REFLECT_101,
+ * reflected repeatedly when the window is larger than the image), dst = (2*S + k*k) / (2*k*k): the mean rounded to nearest
+ * (k*k is odd: no ties).  ksize odd, <= 1023. */
+int sv_box_mean_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int ksize,
+                   uint8_t *dst /*dev, n*H*W*/, void *stream);
+
+/* cv2.GaussianBlur(img, (21, 21), 0) on u8, cv/preprocess_v2.py:112 (sv_blur_u8 stops at 7): sigma 3.5, taps in 8 fractional
+ * bits 0 2 2 4 6 11 15 20 25 28 30 28 25 20 15 11 6 4 2 2 0 (sum 256), horizontal pass exact, vertical pass (sum + 2^15) >> 16,
+ * BORDER_REFLECT_101. */
+int sv_gaussian_blur21_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
+                          uint8_t *dst /*dev, n*H*W*/, void *stream);
+
+/* (gray.astype(float32) / maximum(background, 1).astype(float32) * 255).clip(0, 255).astype(uint8), cv/preprocess_v2.py:56-60
+ * and :115-119: one IEEE float32 division, one float32 multiplication, truncation. */
+int sv_divide_normalize_u8(sv_ctx *ctx, const uint8_t *gray /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
+                           const uint8_t *background /*dev, n*H*W dense*/, uint8_t *dst /*dev, n*H*W*/, void *stream);
+
+/* cv2.createCLAHE(clip_limit, (tiles_x, tiles_y)).apply(gray), cv/preprocess_v2.py:128-129 and :325-326, any size: when H or W
+ * does not divide by the grid the image is extended at the bottom / right by tiles - size % tiles pixels (BORDER_REFLECT_101) and
+ * tile size, histograms, LUTs and blend weights come from the extended size.  Per tile: histogram, clip at
+ * max(1, int(clip * area / 256)), clipped mass spread evenly (+1 every max(256 / residual, 1) bins for the residual),
+ * LUT[i] = round_half_even(cumsum[i] * (255.f / area)); per pixel the float32 bilinear blend of the four nearest tiles' LUTs,
+ * one rounding per operation, round_half_even.  sv_preprocess_cells_u8 remains the fused 28x28 special case. */
+int sv_clahe_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, double clip_limit,
+                int tiles_x, int tiles_y, uint8_t *dst /*dev, n*H*W*/, void *stream);
+
+/* threshold_sauvola(gray, window, k), cv/preprocess_v2.py:152-175: S1, S2 = the window sums of g and g*g as integers
+ * (BORDER_REFLECT_101); mean = float32(double(S1) * (1.0 / w^2)), sq likewise from S2; then float32, one rounding each:
+ * var = max(sq - mean*mean, 0), sd = sqrt(var), t = mean * (1 + float32(k) * (sd / 128 - 1)); dst = float32(g) < t ? 255 : 0.
+ * window odd, <= 1023. */
+int sv_threshold_sauvola_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int window,
+                            double k, uint8_t *dst /*dev, n*H*W*/, void *stream);
+
+/* A fixed threshold and the count of the pixels it sets: dst = g > thresh ? 255 : 0 (type_inv 0: detect_glare's mask,
+ * cv/preprocess_v2.py:73) or g > thresh ? 0 : 255 (type_inv 1: THRESH_BINARY_INV at the Otsu threshold, :148, which the caller
+ * computes from sv_frame_quality_stats_u8's histogram); counts[f] = pixels of frame f set to 255. */
+int sv_threshold_count_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int thresh,
+                          int type_inv, uint8_t *dst /*dev, n*H*W*/, uint32_t *counts /*dev, n*/, void *stream);
+
+/* detect_shadow's mask, cv/preprocess_v2.py:96: mask = int(gray) - int(local_mean) < delta ? 255 : 0 (delta = -30), and its count. */
+int sv_shadow_mask_u8(sv_ctx *ctx, const uint8_t *gray /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
+                      const uint8_t *local_mean /*dev, n*H*W dense*/, int delta, uint8_t *mask /*dev, n*H*W*/, uint32_t *counts /*dev, n*/,
+                      void *stream);
+
+/* counts[f] = pixels != 0 of frame f: what score_binary's np.mean(b) / 255 needs of a {0,255} image, cv/preprocess_v2.py:285-290. */
+int sv_count_nonzero_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
+                        uint32_t *counts /*dev, n*/, void *stream);
+
 /* ---- the whole device-resident path ----------------------------------------------------------- */
 
 /* frames + homographies -> 81 digits per frame: K2 then K3 on `stream`, no host sync.

@@ -72,6 +72,15 @@ SIGNATURES = {
     "sv_frame_quality_stats_u8": [_p, _p, _i, _i, _i, _pd, _pd, _i, _p, _p, _p, _p],
     "sv_grid_line_coverage_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p, _p],
     "sv_grid_line_coverage_bits": [_p, _p, _i, _i, _i, _p, _p, _p],
+    "sv_morphology_u8": [_p, _p, _i, _i, _i, _pd, _pd, _i, _i, _i, _p, _p],
+    "sv_box_mean_u8": [_p, _p, _i, _i, _i, _pd, _pd, _i, _p, _p],
+    "sv_gaussian_blur21_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p],
+    "sv_divide_normalize_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p, _p],
+    "sv_clahe_u8": [_p, _p, _i, _i, _i, _pd, _pd, _d, _i, _i, _p, _p],
+    "sv_threshold_sauvola_u8": [_p, _p, _i, _i, _i, _pd, _pd, _i, _d, _p, _p],
+    "sv_threshold_count_u8": [_p, _p, _i, _i, _i, _pd, _pd, _i, _i, _p, _p, _p],
+    "sv_shadow_mask_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _i, _p, _p, _p],
+    "sv_count_nonzero_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p],
 }
 _RESTYPES = {"sv_last_error": C.c_char_p, "sv_sparse_bits_record_bytes": C.c_long}
 # what libsudokuvision_xcheck.so exports on top of SIGNATURES (include/sudoku_vision_xcheck.h)

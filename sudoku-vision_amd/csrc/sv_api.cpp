@@ -55,6 +55,7 @@ extern "C" int sv_ctx_destroy(sv_ctx *ctx)
     if (ctx->cells) (void)hipFree(ctx->cells);
     if (ctx->cells2) (void)hipFree(ctx->cells2);
     if (ctx->jpeg_planes) (void)hipFree(ctx->jpeg_planes);
+    if (ctx->pp2) (void)hipFree(ctx->pp2);
     if (ctx->k1_list) (void)hipFree(ctx->k1_list);
     if (ctx->range_flag) (void)hipFree(ctx->range_flag);
     for (auto &t : ctx->timeline) { (void)hipEventDestroy(t.t0); (void)hipEventDestroy(t.t1); }
@@ -525,6 +526,92 @@ extern "C" int sv_grid_line_coverage_bits(sv_ctx *ctx, const uint32_t *bits, int
     REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && W % 32 == 0, "bad shape (W must be a multiple of 32)");
     REQUIRE((((uintptr_t)bits | (uintptr_t)counts) & 3) == 0 && ((uintptr_t)minv & 7) == 0, "misaligned argument");
     return svk_grid_line_coverage(bits, true, n, H, W, 0, 0, minv, counts, S(stream));
+}
+
+// ---- K7: cv/preprocess_v2.py ---------------------------------------------------------------------------
+// one gray plane set: n frames of H x W, `pitch` bytes between rows, `img_stride` between frames; 65535 = the grid's y / z limit
+#define REQUIRE_PLANES(src) \
+    do { \
+        REQUIRE(n > 0 && n < 65536 && H > 0 && H < 65536 && W > 0 && pitch >= (ptrdiff_t)W, "bad shape"); \
+        REQUIRE(n == 1 || img_stride >= pitch * (H - 1) + (ptrdiff_t)W, "frames overlap (img_stride too small)"); \
+    } while (0)
+
+extern "C" int sv_morphology_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int op, int shape, int ksize,
+                                uint8_t *dst, void *stream)
+{
+    REQUIRE(ctx && src && dst, "NULL argument");
+    REQUIRE_PLANES(src);
+    REQUIRE(op >= SV_MORPH_DILATE && op <= SV_MORPH_OPEN, "op must be SV_MORPH_DILATE, _ERODE, _CLOSE or _OPEN");
+    REQUIRE(shape == SV_SHAPE_RECT || shape == SV_SHAPE_ELLIPSE, "shape must be SV_SHAPE_RECT or SV_SHAPE_ELLIPSE");
+    REQUIRE(ksize >= 1, "ksize must be positive");
+    return svk_morphology(ctx, src, n, H, W, pitch, img_stride, op, shape, ksize, dst, S(stream));
+}
+
+extern "C" int sv_box_mean_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int ksize, uint8_t *dst, void *stream)
+{
+    REQUIRE(ctx && src && dst, "NULL argument");
+    REQUIRE_PLANES(src);
+    REQUIRE(ksize > 0 && (ksize & 1), "ksize must be odd and positive");
+    return svk_box_mean(src, n, H, W, pitch, img_stride, ksize, dst, S(stream));
+}
+
+extern "C" int sv_gaussian_blur21_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint8_t *dst, void *stream)
+{
+    REQUIRE(ctx && src && dst, "NULL argument");
+    REQUIRE_PLANES(src);
+    return svk_gaussian_blur21(src, n, H, W, pitch, img_stride, dst, S(stream));
+}
+
+extern "C" int sv_divide_normalize_u8(sv_ctx *ctx, const uint8_t *gray, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const uint8_t *background,
+                                      uint8_t *dst, void *stream)
+{
+    REQUIRE(ctx && gray && background && dst, "NULL argument");
+    REQUIRE_PLANES(gray);
+    return svk_divide_normalize(gray, n, H, W, pitch, img_stride, background, dst, S(stream));
+}
+
+extern "C" int sv_clahe_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, double clip_limit, int tiles_x, int tiles_y,
+                           uint8_t *dst, void *stream)
+{
+    REQUIRE(ctx && src && dst, "NULL argument");
+    REQUIRE_PLANES(src);
+    REQUIRE(tiles_x > 0 && tiles_y > 0 && tiles_x * tiles_y <= 65535 && clip_limit == clip_limit, "bad tile grid or clip limit");
+    return svk_clahe(ctx, src, n, H, W, pitch, img_stride, clip_limit, tiles_x, tiles_y, dst, S(stream));
+}
+
+extern "C" int sv_threshold_sauvola_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int window, double k,
+                                       uint8_t *dst, void *stream)
+{
+    REQUIRE(ctx && src && dst, "NULL argument");
+    REQUIRE_PLANES(src);
+    REQUIRE(window > 0 && (window & 1), "window must be odd and positive");
+    return svk_threshold_sauvola(src, n, H, W, pitch, img_stride, window, k, dst, S(stream));
+}
+
+extern "C" int sv_threshold_count_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int thresh, int type_inv,
+                                     uint8_t *dst, uint32_t *counts, void *stream)
+{
+    REQUIRE(ctx && src && dst && counts, "NULL argument");
+    REQUIRE_PLANES(src);
+    REQUIRE(((uintptr_t)counts & 3) == 0, "misaligned counts");
+    return svk_threshold_count(src, n, H, W, pitch, img_stride, thresh, type_inv ? 1 : 0, dst, counts, S(stream));
+}
+
+extern "C" int sv_shadow_mask_u8(sv_ctx *ctx, const uint8_t *gray, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const uint8_t *local_mean, int delta,
+                                 uint8_t *mask, uint32_t *counts, void *stream)
+{
+    REQUIRE(ctx && gray && local_mean && mask && counts, "NULL argument");
+    REQUIRE_PLANES(gray);
+    REQUIRE(((uintptr_t)counts & 3) == 0, "misaligned counts");
+    return svk_shadow_mask(gray, n, H, W, pitch, img_stride, local_mean, delta, mask, counts, S(stream));
+}
+
+extern "C" int sv_count_nonzero_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint32_t *counts, void *stream)
+{
+    REQUIRE(ctx && src && counts, "NULL argument");
+    REQUIRE_PLANES(src);
+    REQUIRE(((uintptr_t)counts & 3) == 0, "misaligned counts");
+    return svk_count_nonzero(src, n, H, W, pitch, img_stride, counts, S(stream));
 }
 
 static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *fn)

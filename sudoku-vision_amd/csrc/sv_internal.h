@@ -55,6 +55,8 @@ struct sv_ctx {
     long cap_cells = 0;
     u8 *jpeg_planes = nullptr;  // decoded component planes (MCU-padded) between the IDCT and the colour kernel
     size_t cap_jpeg = 0;
+    u8 *pp2 = nullptr;          // k7_preprocess_v2.hip: element rows + doubling planes + the close/open intermediate, or CLAHE's tile histograms + LUTs
+    size_t cap_pp2 = 0;
     void *k1_list = nullptr;    // k1_threshold_mm.hip: optional diagnostic counter (pixels decided by the exact evaluation), sv_preprocess_stats
     int precision = 0;          // SV_PREC_F32 / SV_PREC_BF16 (sv_ctx_set_precision)
     int cnn_kernels = 0;        // SV_CNN_AUTO / _F16PAIR / _F32MFMA (sv_ctx_set_cnn_kernels)
@@ -148,6 +150,16 @@ int svk_frame_quality_stats(const u8 *img, int n, int H, int W, ptrdiff_t pitch,
                             uint32_t *hist, hipStream_t s);
 int svk_grid_line_coverage(const void *src, bool bits, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const double *minv, uint32_t *counts,
                            hipStream_t s);
+// k7_preprocess_v2.hip
+int svk_morphology(sv_ctx *ctx, const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int op, int shape, int k, u8 *dst, hipStream_t s);
+int svk_box_mean(const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int k, u8 *dst, hipStream_t s);
+int svk_threshold_sauvola(const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int window, double k, u8 *dst, hipStream_t s);
+int svk_gaussian_blur21(const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, u8 *dst, hipStream_t s);
+int svk_clahe(sv_ctx *ctx, const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, double clip, int tiles_x, int tiles_y, u8 *dst, hipStream_t s);
+int svk_divide_normalize(const u8 *gray, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const u8 *background, u8 *dst, hipStream_t s);
+int svk_threshold_count(const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int thresh, int type_inv, u8 *dst, uint32_t *counts, hipStream_t s);
+int svk_shadow_mask(const u8 *gray, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const u8 *local_mean, int delta, u8 *mask, uint32_t *counts, hipStream_t s);
+int svk_count_nonzero(const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint32_t *counts, hipStream_t s);
 
 // host helpers
 void sv_gaussian_taps_f32(int n, float *out);

@@ -256,13 +256,18 @@ class FramePipeline:
         return out
 
 
-def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False):
+def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1"):
     """One BGR image (numpy uint8 [H,W,3], or a CUDA uint8 tensor of that shape) -> dict(grid 9x9 list, digits, confidences, corners) or None when no
     grid is found -- the call order of pipeline/run.py:261-312, preprocess_cell (:73-95) included by default.
     top_k > 1 adds run_v2's per-cell `alternatives` (pipeline/run_v2.py:165-178): 81 lists of (digit, prob), best excluded.
     quality=True adds run_v2's quality check (pipeline/run_v2.py:299-311): `quality` (a cv.grid_quality.QualityScore) and
-    `quality_feedback` (get_user_feedback); comparing quality.overall with a minimum is left to the caller, as run_v2 does."""
+    `quality_feedback` (get_user_feedback); comparing quality.overall with a minimum is left to the caller, as run_v2 does.
+    preprocess="v2": the binary the corner search reads is run_v2's (pipeline/run_v2.py:278-280),
+    cv.preprocess_v2.preprocess_multi_strategy(image).binary, and the result carries what run_v2 prints of it (:283-284):
+    `preprocess_method`, `has_shadow`, `has_glare`.  It runs on the default context of the current device."""
     from .runtime import default_context
+    if preprocess not in ("v1", "v2"):
+        raise ValueError(f"preprocess must be 'v1' or 'v2', got {preprocess!r}")
     ctx = ctx or default_context()
     if model_state_dict is not None:
         ctx.load_state_dict(model_state_dict)
@@ -270,7 +275,13 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
         frames = image.contiguous()[None]
     else:
         frames = torch.from_numpy(np.ascontiguousarray(image)).to(ctx.device)[None]
-    binary_dev = ctx.preprocess(frames)[0]
+    pre = None
+    if preprocess == "v2":
+        from .cv import preprocess_v2
+        pre = preprocess_v2.preprocess_multi_strategy(frames[0])
+        binary_dev = pre.binary
+    else:
+        binary_dev = ctx.preprocess(frames)[0]
     binary = binary_dev.cpu().numpy()
     corners = host.find_grid_corners(binary)
     if corners is None:
@@ -288,6 +299,8 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
         from .cv import grid_quality
         q = grid_quality.assess_grid_quality(frames[0], binary_dev, corners, ctx=ctx)
         res["quality"], res["quality_feedback"] = q, grid_quality.get_user_feedback(q)
+    if pre is not None:
+        res["preprocess_method"], res["has_shadow"], res["has_glare"] = pre.method_used, pre.has_shadow, pre.has_glare
     return res
 
 

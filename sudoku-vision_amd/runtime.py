@@ -77,6 +77,18 @@ def _frame_layout(frames, device=None):
     return frames, st[1], (st[0] if n > 1 else st[1] * H)
 
 
+def _plane_layout(x, device, name="gray"):
+    """x u8 [n,H,W] on device: (tensor, row pitch, frame stride) in bytes.  Padded rows, gaps between frames and any base alignment are
+    passed through to the library; anything else is made contiguous first."""
+    _dev_tensor(x, name, torch.uint8, device, ndim=3)
+    n, H, W = x.shape
+    st = x.stride()
+    if not (st[2] == 1 and st[1] >= W and (n == 1 or st[0] >= st[1] * (H - 1) + W)):
+        x = x.contiguous()
+        st = x.stride()
+    return x, st[1], (st[0] if n > 1 else st[1] * H)
+
+
 class Context:
     def __init__(self, device=None, library=None):
         """library: a handle from _native (default: the product library).  Tests pass _native.lib_xcheck() to run the cross-check kernels of
@@ -591,6 +603,79 @@ class Context:
             rc = self._lib.sv_grid_line_coverage_bits(self._h, _ptr(x), n, x.shape[1], x.shape[2] * 32, _ptr(minv_dev), _ptr(out), _stream_ptr())
         self._check(rc, "sv_grid_line_coverage")
         return out
+
+    # ---- run_v2's preprocessing (cv/preprocess_v2.py, csrc/k7_preprocess_v2.hip) -------------------
+    # Every method takes gray u8 [n,H,W] on device (rows may be padded, frames may have gaps) and returns new dense tensors.
+    MORPH_DILATE, MORPH_ERODE, MORPH_CLOSE, MORPH_OPEN = 0, 1, 2, 3
+    SHAPE_RECT, SHAPE_ELLIPSE = 0, 1
+
+    def _planes_call(self, fn, what, x, *args, name="gray"):
+        """fn(ctx, x, n, H, W, pitch, stride, *args, stream) with x laid out by _plane_layout."""
+        x, pitch, fstride = _plane_layout(x, self.device, name)
+        n, H, W = x.shape
+        self._check(fn(self._h, _ptr(x), n, H, W, pitch, fstride, *args, _stream_ptr()), what)
+
+    def _dense_like(self, x, name):
+        """A second image argument the kernels read densely: u8, same [n,H,W] as the first."""
+        return _dev_tensor(x[1], name, torch.uint8, self.device, shape=tuple(x[0].shape)).contiguous()
+
+    def morphology(self, gray, op, shape, ksize):
+        """cv2.dilate / erode / morphologyEx(CLOSE | OPEN) with getStructuringElement(shape, (ksize, ksize)) (sv_morphology_u8)."""
+        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
+        self._planes_call(self._lib.sv_morphology_u8, "sv_morphology_u8", gray, int(op), int(shape), int(ksize), _ptr(out))
+        return out
+
+    def box_mean(self, gray, ksize):
+        """cv2.blur(gray, (ksize, ksize)) on u8 (sv_box_mean_u8)."""
+        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
+        self._planes_call(self._lib.sv_box_mean_u8, "sv_box_mean_u8", gray, int(ksize), _ptr(out))
+        return out
+
+    def gaussian_blur21(self, gray):
+        """cv2.GaussianBlur(gray, (21, 21), 0) on u8 (sv_gaussian_blur21_u8)."""
+        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
+        self._planes_call(self._lib.sv_gaussian_blur21_u8, "sv_gaussian_blur21_u8", gray, _ptr(out))
+        return out
+
+    def divide_normalize(self, gray, background):
+        """(gray / max(background, 1) * 255) in float32, clipped and truncated to u8 (sv_divide_normalize_u8)."""
+        background = self._dense_like((gray, background), "background")
+        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
+        self._planes_call(self._lib.sv_divide_normalize_u8, "sv_divide_normalize_u8", gray, _ptr(background), _ptr(out))
+        return out
+
+    def clahe(self, gray, clip_limit=2.0, tiles=(8, 8)):
+        """cv2.createCLAHE(clip_limit, tiles).apply(gray), tiles = (tiles_x, tiles_y), any image size (sv_clahe_u8)."""
+        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
+        self._planes_call(self._lib.sv_clahe_u8, "sv_clahe_u8", gray, float(clip_limit), int(tiles[0]), int(tiles[1]), _ptr(out))
+        return out
+
+    def threshold_sauvola(self, gray, window=25, k=0.2):
+        """Sauvola's threshold from exact integer window sums (sv_threshold_sauvola_u8) -> u8 {0,255}."""
+        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
+        self._planes_call(self._lib.sv_threshold_sauvola_u8, "sv_threshold_sauvola_u8", gray, int(window), float(k), _ptr(out))
+        return out
+
+    def threshold_count(self, gray, thresh, inv=False):
+        """gray > thresh ? 255 : 0 (inv: ? 0 : 255) -> (mask u8 [n,H,W], count int32 [n] of the pixels set), sv_threshold_count_u8."""
+        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
+        counts = torch.empty((gray.shape[0],), dtype=torch.int32, device=self.device)
+        self._planes_call(self._lib.sv_threshold_count_u8, "sv_threshold_count_u8", gray, int(thresh), int(bool(inv)), _ptr(out), _ptr(counts))
+        return out, counts
+
+    def shadow_mask(self, gray, local_mean, delta=-30):
+        """int(gray) - int(local_mean) < delta ? 255 : 0 -> (mask u8 [n,H,W], count int32 [n]), sv_shadow_mask_u8."""
+        local_mean = self._dense_like((gray, local_mean), "local_mean")
+        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
+        counts = torch.empty((gray.shape[0],), dtype=torch.int32, device=self.device)
+        self._planes_call(self._lib.sv_shadow_mask_u8, "sv_shadow_mask_u8", gray, _ptr(local_mean), int(delta), _ptr(out), _ptr(counts))
+        return out, counts
+
+    def count_nonzero(self, img):
+        """Pixels != 0 per frame -> int32 [n] (sv_count_nonzero_u8)."""
+        counts = torch.empty((img.shape[0],), dtype=torch.int32, device=self.device)
+        self._planes_call(self._lib.sv_count_nonzero_u8, "sv_count_nonzero_u8", img, _ptr(counts), name="img")
+        return counts
 
 
 _default = {}
