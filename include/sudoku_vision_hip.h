@@ -311,6 +311,46 @@ int sv_cnn_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells /*dev, B*784*/, lo
                             float *logits /*dev*/, uint8_t *digits /*dev or NULL*/,
                             float *conf /*dev or NULL*/, void *stream);
 
+/* ---- K8: DigitCNNv3 forward (ml/model_v3.py), the model pipeline/run_v2.py:95-128 loads ------------------------------------------ */
+
+/* Floats in the weight blob of sv_load_weights_v3_f32: DigitCNNv3(use_se=True) and DigitCNNv3(use_se=False). */
+#define SV_CNN3_PARAMS_SE 700587
+#define SV_CNN3_PARAMS_NOSE 679595
+#define SV_CNN3_FEATURES 128
+/* The v3 forward keeps its activations in context scratch, 3 * 32*28*28 floats (301,056 bytes) per cell, for at most this many cells: a
+ * larger batch runs as consecutive sub-batches, so the scratch never exceeds SV_V3_SUBBATCH * 301,056 bytes = 147 MiB. */
+#define SV_V3_SUBBATCH 512
+
+/* blob: the state_dict of DigitCNNv3 (ml/model_v3.py:113-149) flattened in key order, the int64 num_batches_tracked entries skipped:
+ * temperature[1] stem.0.weight[32,1,3,3] stem.1.{weight,bias,running_mean,running_var}[32], then per layer1..5
+ * conv1.weight bn1.{...} conv2.weight bn2.{...} [se.excite.0.weight se.excite.2.weight] [shortcut.0.weight shortcut.1.{...}],
+ * fc.weight[10,128] fc.bias[10].  n_floats must be SV_CNN3_PARAMS_SE (use_se != 0) or SV_CNN3_PARAMS_NOSE, else SV_ERR_BAD_ARG.
+ * Every BatchNorm is folded into its convolution here, in double, with eps = 1e-5.
+ * Replaces DigitCNNv3() + load_state_dict + model.to(device), pipeline/run_v2.py:99-121.  Synchronous.  Independent of
+ * sv_load_weights_f32: a context may hold both models.  If sv_ctx_reserve was called before, the v3 scratch is sized here. */
+int sv_load_weights_v3_f32(sv_ctx *ctx, const float *blob /*host*/, long n_floats, int use_se);
+
+/* DigitCNNv3.forward, ml/model_v3.py:163-184 (eval mode), in true f32 on v_mfma_f32_16x16x4_f32: x f32 [B,1,28,28] -> logits f32 [B,10].
+ * features: what forward(x, return_features=True) returns (:175-178).  digits: argmax of the logits.  conf: softmax(logits / temperature)
+ * at that digit, get_confidence (:216-225).  Each may be NULL.  A cell's results do not depend on the rest of the batch, and a cell
+ * holding NaN/Inf does not disturb the others (its own logits are unspecified: ReLU here is IEEE maxNum, which drops a NaN).
+ * SV_ERR_NO_WEIGHTS before sv_load_weights_v3_f32; SV_ERR_UNSUPPORTED on a context set to SV_PREC_BF16 (f32 is the only arithmetic).
+ * After sv_ctx_reserve (with the v3 weights loaded, in either order) no v3 entry allocates, so they can be captured in a hipGraph. */
+int sv_cnn3_forward_f32(sv_ctx *ctx, const float *x /*dev, B*784*/, long B, float *logits /*dev, B*10*/,
+                        float *features /*dev, B*128, or NULL*/, uint8_t *digits /*dev, B, or NULL*/, float *conf /*dev, B, or NULL*/,
+                        void *stream);
+
+/* The same on 8-bit cells with the glue of pipeline/run_v2.py:131-146 + :161-163 fused in: SV_GLUE_RUNPY is exactly what run_v2 feeds
+ * the model (its preprocess_cell is run.py's), SV_GLUE_NORMALIZE the invert + normalise alone. */
+int sv_cnn3_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells /*dev, B*784*/, long B, int glue, float *logits /*dev, B*10*/,
+                             uint8_t *digits /*dev or NULL*/, float *conf /*dev or NULL*/, void *stream);
+
+/* sv_frames_to_digits with the v3 model: K2, then sv_cnn3_forward_cells_u8 (pipeline/run_v2.py:149-163 after the warp). */
+int sv_frames_to_digits_v3(sv_ctx *ctx, const uint8_t *frames /*dev*/, int n, int H, int W,
+                           ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv /*dev, n*9*/, int glue,
+                           uint8_t *cells /*dev n*81*784 or NULL*/, float *logits /*dev, n*81*10*/,
+                           uint8_t *digits /*dev, n*81*/, float *conf /*dev n*81 or NULL*/, void *stream);
+
 /* F.softmax(output, dim=1) then probs.topk(top_k), pipeline/run_v2.py:165-178 (predict_cells_with_alternatives):
  * per cell the k most probable classes, most probable first (index[.,0] = the predicted digit, prob[.,0] = its
  * confidence, the rest = run_v2's `alternatives`).  Equal probabilities: lower class index first.  1 <= k <= 10. */

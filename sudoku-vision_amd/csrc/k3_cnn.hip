@@ -35,12 +35,7 @@ constexpr int C1_CELL = 32 * PLANE;      // conv1 output of one cell
 constexpr int IN_W = 30, IN_CELL = 900;  // zero-padded 30x30 input
 constexpr int FEAT = 3136;
 
-__device__ __forceinline__ float glue_norm(u8 c)
-{
-    // x = ((255 - cell)/255 - 0.5)/0.5, one rounding per operation (pipeline/run.py:129-135)
-    const float t = __fdiv_rn((float)(255 - (int)c), 255.0f);
-    return __fdiv_rn(__fsub_rn(t, 0.5f), 0.5f);
-}
+__device__ __forceinline__ float glue_norm(u8 c) { return sv_glue_norm(c); }     // sv_device.h: shared with k8_cnn_v3.hip
 
 // ---------------------------------------------------------------------------------------------------
 // N1 -- the per-cell glue of pipeline/run.py:73-95 (preprocess_cell), one wave per cell (k_preprocess_cells):

@@ -46,11 +46,19 @@ static void free_weights(sv_weights &w)
     w = sv_weights();
 }
 
+static void free_weights(sv_weights3 &w)
+{
+    for (void *p : w.allocs) (void)hipFree(p);
+    w = sv_weights3();
+}
+
 extern "C" int sv_ctx_destroy(sv_ctx *ctx)
 {
     if (!ctx) return SV_OK;
     (void)hipSetDevice(ctx->device);
     free_weights(ctx->w);
+    free_weights(ctx->w3);
+    if (ctx->v3_act) (void)hipFree(ctx->v3_act);
     if (ctx->features) (void)hipFree(ctx->features);
     if (ctx->cells) (void)hipFree(ctx->cells);
     if (ctx->cells2) (void)hipFree(ctx->cells2);
@@ -82,6 +90,20 @@ int sv_ensure_scratch(sv_ctx *ctx, long cells)
     return SV_OK;
 }
 
+// the v3 forward's activation buffers for batches of `cells` cells (at most SV_V3_SUBBATCH of them are in flight)
+static int sv_ensure_scratch_v3(sv_ctx *ctx, long cells)
+{
+    const long want = cells < SV_V3_SUBBATCH ? cells : SV_V3_SUBBATCH;
+    if (want <= ctx->cap_v3) return SV_OK;
+    SV_HIP(hipSetDevice(ctx->device));
+    if (ctx->v3_act) SV_HIP(hipFree(ctx->v3_act));
+    ctx->v3_act = nullptr;
+    ctx->cap_v3 = 0;
+    SV_HIP(hipMalloc((void **)&ctx->v3_act, svk_v3_scratch_bytes(want)));
+    ctx->cap_v3 = want;
+    return SV_OK;
+}
+
 extern "C" int sv_ctx_set_precision(sv_ctx *ctx, int precision)
 {
     if (!ctx || (precision != SV_PREC_F32 && precision != SV_PREC_BF16)) return sv_fail(SV_ERR_BAD_ARG, "sv_ctx_set_precision: bad argument");
@@ -94,7 +116,9 @@ extern "C" int sv_ctx_reserve(sv_ctx *ctx, long max_cells)
     if (!ctx || max_cells <= 0) return sv_fail(SV_ERR_BAD_ARG, "sv_ctx_reserve: bad argument");
     SV_HIP(hipSetDevice(ctx->device));
     if (!ctx->range_flag) SV_HIP(hipMalloc((void **)&ctx->range_flag, 2 * sizeof(int)));     // sv_cnn_forward_f32's per-call range flag: no hipMalloc after reserve
-    return sv_ensure_scratch(ctx, max_cells);
+    int rc = sv_ensure_scratch(ctx, max_cells);
+    if (rc) return rc;
+    return ctx->w3.loaded ? sv_ensure_scratch_v3(ctx, max_cells) : SV_OK;    // v1-only contexts do not pay for the v3 activations
 }
 
 // ---- per-kernel timing -------------------------------------------------------------------------------
@@ -166,6 +190,19 @@ extern "C" int sv_load_weights_f32(sv_ctx *ctx, const float *blob)
     if ((rc = sv_upload(w, &w.fc2_b, f2b, 10))) return rc;
     w.loaded = true;
     return SV_OK;
+}
+
+extern "C" int sv_load_weights_v3_f32(sv_ctx *ctx, const float *blob, long n_floats, int use_se)
+{
+    if (!ctx || !blob) return sv_fail(SV_ERR_BAD_ARG, "sv_load_weights_v3_f32: NULL argument");
+    if (n_floats != svk_v3_blob_floats(use_se != 0))
+        return sv_fail(SV_ERR_BAD_ARG, "sv_load_weights_v3_f32: %ld floats, DigitCNNv3(use_se=%s) has %ld", n_floats, use_se ? "True" : "False", svk_v3_blob_floats(use_se != 0));
+    SV_HIP(hipSetDevice(ctx->device));
+    SV_HIP(hipDeviceSynchronize());                  // a forward still running on the old images
+    free_weights(ctx->w3);
+    int rc = svk_pack_weights_v3(ctx->w3, blob, use_se != 0);
+    if (rc) { free_weights(ctx->w3); return rc; }
+    return ctx->cap_cells > 0 ? sv_ensure_scratch_v3(ctx, ctx->cap_cells) : SV_OK;
 }
 
 // ---- host math ------------------------------------------------------------------------------------
@@ -472,6 +509,33 @@ extern "C" int sv_cnn_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells, long B
     return cnn_common(ctx, cells, true, glue, B, logits, digits, conf, stream);
 }
 
+static int cnn3_common(sv_ctx *ctx, const void *x, bool u8in, int glue, long B, float *logits, float *features, uint8_t *digits, float *conf, void *stream)
+{
+    if (!ctx || !x || !logits) return sv_fail(SV_ERR_BAD_ARG, "sv_cnn3_forward: NULL argument");
+    if (B <= 0) return sv_fail(SV_ERR_BAD_ARG, "sv_cnn3_forward: B = %ld", B);
+    if (!ctx->w3.loaded) return sv_fail(SV_ERR_NO_WEIGHTS, "sv_cnn3_forward: call sv_load_weights_v3_f32 first");
+    if (ctx->precision != SV_PREC_F32) return sv_fail(SV_ERR_UNSUPPORTED, "sv_cnn3_forward: the DigitCNNv3 forward has f32 arithmetic only (context is set to SV_PREC_BF16)");
+    if (glue != SV_GLUE_NORMALIZE && glue != SV_GLUE_RUNPY) return sv_fail(SV_ERR_BAD_ARG, "sv_cnn3_forward: glue %d", glue);
+    int rc = sv_ensure_scratch_v3(ctx, B);
+    if (rc) return rc;
+    if (u8in && glue == SV_GLUE_RUNPY) {             // preprocess_cell as its own pass; its {0,255} output then takes the plain glue
+        if ((rc = sv_ensure_scratch(ctx, B))) return rc;
+        if ((rc = svk_preprocess_cells((const uint8_t *)x, B, ctx->cells2, S(stream)))) return rc;
+        x = ctx->cells2;
+    }
+    return svk_cnn3_forward(ctx, x, u8in, B, logits, features, digits, conf, S(stream));
+}
+
+extern "C" int sv_cnn3_forward_f32(sv_ctx *ctx, const float *x, long B, float *logits, float *features, uint8_t *digits, float *conf, void *stream)
+{
+    return cnn3_common(ctx, x, false, SV_GLUE_NORMALIZE, B, logits, features, digits, conf, stream);
+}
+
+extern "C" int sv_cnn3_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells, long B, int glue, float *logits, uint8_t *digits, float *conf, void *stream)
+{
+    return cnn3_common(ctx, cells, true, glue, B, logits, nullptr, digits, conf, stream);
+}
+
 extern "C" int sv_resize_linear_u8(sv_ctx *ctx, const uint8_t *src, int sh, int sw, ptrdiff_t pitch, uint8_t *dst, int dh, int dw, void *stream)
 {
     REQUIRE(ctx && src && dst, "NULL argument");
@@ -657,4 +721,17 @@ extern "C" int sv_frames_to_digits(sv_ctx *ctx, const uint8_t *frames, int n, in
     uint8_t *c = cells ? cells : ctx->cells;
     if ((rc = svk_warp_cells(ctx, frames, n, H, W, pitch, frame_stride, minv, c, S(stream)))) return rc;
     return cnn_common(ctx, c, true, glue, B, logits, digits, conf, stream);
+}
+
+extern "C" int sv_frames_to_digits_v3(sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv, int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)
+{
+    REQUIRE(ctx && frames && minv && logits && digits, "NULL argument");
+    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W, "bad shape");
+    if (!ctx->w3.loaded) return sv_fail(SV_ERR_NO_WEIGHTS, "sv_frames_to_digits_v3: call sv_load_weights_v3_f32 first");
+    const long B = (long)n * SV_CELLS;
+    int rc = sv_ensure_scratch(ctx, B);
+    if (rc) return rc;
+    uint8_t *c = cells ? cells : ctx->cells;
+    if ((rc = svk_warp_cells(ctx, frames, n, H, W, pitch, frame_stride, minv, c, S(stream)))) return rc;
+    return cnn3_common(ctx, c, true, glue, B, logits, nullptr, digits, conf, stream);
 }

@@ -15,6 +15,14 @@ __device__ __forceinline__ int sv_gray_px(int b, int g, int r)
 
 __device__ __forceinline__ int sv_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// The normalise glue between an 8-bit cell and the CNN input: x = ((255 - cell)/255 - 0.5)/0.5, one rounding per operation
+// (pipeline/run.py:129-135, pipeline/run_v2.py:161-163)
+__device__ __forceinline__ float sv_glue_norm(u8 c)
+{
+    const float t = __fdiv_rn((float)(255 - (int)c), 255.0f);
+    return __fdiv_rn(__fsub_rn(t, 0.5f), 0.5f);
+}
+
 // cv2 BORDER_REFLECT_101
 __device__ __forceinline__ int sv_reflect101(int p, int len)
 {

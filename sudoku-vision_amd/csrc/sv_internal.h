@@ -44,10 +44,24 @@ struct sv_weights {
     std::vector<void *> allocs; // every device buffer above (sv_upload), freed together
 };
 
+// Packed DigitCNNv3 weights (k8_cnn_v3.hip: svk_pack_weights_v3 has the layouts), BatchNorm folded into every conv
+struct sv_conv3 { float *w = nullptr, *b = nullptr; };   // MFMA B-operand image [cout/16][cin/4][taps][64 lane], folded bias [cout]
+struct sv_weights3 {
+    sv_conv3 stem, conv1[5], conv2[5], shortcut[5];      // shortcut: layers 2 and 4 only (1x1, stride 2)
+    float *se1[5] = {}, *se2[5] = {};                    // se.excite.0.weight [C/4][C], se.excite.2.weight [C][C/4]; NULL without SE
+    float *fc_w = nullptr, *fc_b = nullptr;              // [10][128], [10]
+    float temperature = 1.f;
+    bool use_se = true, loaded = false;
+    std::vector<void *> allocs;
+};
+
 struct sv_ctx {
     int device = 0;
     int num_cus = 256;
     sv_weights w;
+    sv_weights3 w3;
+    float *v3_act = nullptr;    // k8_cnn_v3.hip: three activation buffers of [cap_v3][32*784] floats
+    long cap_v3 = 0;            // cells, at most SV_V3_SUBBATCH
     // grow-only scratch
     float *features = nullptr;  // [cells][49][64] pooled conv2 output
     u8 *cells = nullptr;        // [cells][784]
@@ -160,6 +174,12 @@ int svk_divide_normalize(const u8 *gray, int n, int H, int W, ptrdiff_t pitch, p
 int svk_threshold_count(const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int thresh, int type_inv, u8 *dst, uint32_t *counts, hipStream_t s);
 int svk_shadow_mask(const u8 *gray, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const u8 *local_mean, int delta, u8 *mask, uint32_t *counts, hipStream_t s);
 int svk_count_nonzero(const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint32_t *counts, hipStream_t s);
+
+// k8_cnn_v3.hip
+int svk_pack_weights_v3(sv_weights3 &w, const float *blob, bool use_se);
+long svk_v3_blob_floats(bool use_se);
+size_t svk_v3_scratch_bytes(long cells);
+int svk_cnn3_forward(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *logits, float *features, u8 *digits, float *conf, hipStream_t s);
 
 // host helpers
 void sv_gaussian_taps_f32(int n, float *out);

@@ -256,7 +256,7 @@ class FramePipeline:
         return out
 
 
-def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1"):
+def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1"):
     """One BGR image (numpy uint8 [H,W,3], or a CUDA uint8 tensor of that shape) -> dict(grid 9x9 list, digits, confidences, corners) or None when no
     grid is found -- the call order of pipeline/run.py:261-312, preprocess_cell (:73-95) included by default.
     top_k > 1 adds run_v2's per-cell `alternatives` (pipeline/run_v2.py:165-178): 81 lists of (digit, prob), best excluded.
@@ -264,13 +264,18 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     `quality_feedback` (get_user_feedback); comparing quality.overall with a minimum is left to the caller, as run_v2 does.
     preprocess="v2": the binary the corner search reads is run_v2's (pipeline/run_v2.py:278-280),
     cv.preprocess_v2.preprocess_multi_strategy(image).binary, and the result carries what run_v2 prints of it (:283-284):
-    `preprocess_method`, `has_shadow`, `has_glare`.  It runs on the default context of the current device."""
+    `preprocess_method`, `has_shadow`, `has_glare`.  It runs on the default context of the current device.
+    model="v3": the model run_v2 loads (pipeline/run_v2.py:95-128), DigitCNNv3; model_state_dict is then its state_dict and the same
+    call order runs with the v3 forward.  `confidence` is softmax(logits / temperature) at the digit; the top_k alternatives come from
+    softmax(logits), without the temperature, as at run_v2.py:166-180."""
     from .runtime import default_context
     if preprocess not in ("v1", "v2"):
         raise ValueError(f"preprocess must be 'v1' or 'v2', got {preprocess!r}")
+    if model not in ("v1", "v3"):
+        raise ValueError(f"model must be 'v1' or 'v3', got {model!r}")
     ctx = ctx or default_context()
     if model_state_dict is not None:
-        ctx.load_state_dict(model_state_dict)
+        (ctx.load_state_dict_v3 if model == "v3" else ctx.load_state_dict)(model_state_dict)
     if isinstance(image, torch.Tensor):             # already in HBM (imgcodecs.imread(..., device=True))
         frames = image.contiguous()[None]
     else:
@@ -287,7 +292,7 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     if corners is None:
         return None
     minv = ctx.minv_to_device(Context.corners_to_minv(corners[None].astype(np.float32)))
-    out = ctx.frames_to_digits(frames, minv, glue=glue)
+    out = (ctx.frames_to_digits_v3 if model == "v3" else ctx.frames_to_digits)(frames, minv, glue=glue)
     digits = out["digits"][0].cpu().numpy()
     res = {"grid": [[int(digits[r * 9 + c]) for c in range(9)] for r in range(9)], "digits": digits,
            "confidence": out["conf"][0].cpu().numpy(), "logits": out["logits"][0].cpu().numpy(), "corners": corners}

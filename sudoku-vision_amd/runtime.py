@@ -15,6 +15,26 @@ _KEYS = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight
 _SHAPES = ((32, 1, 3, 3), (32,), (64, 32, 3, 3), (64,), (128, 3136), (128,), (10, 128), (10,))
 
 
+# DigitCNNv3 (ml/model_v3.py): (in, out, stride) of layer1..5
+_V3_BLOCKS = ((32, 32, 1), (32, 64, 2), (64, 64, 1), (64, 128, 2), (128, 128, 1))
+
+
+def v3_layout(use_se=True):
+    """(key, shape) of every float entry of a DigitCNNv3 state_dict, in key order: the blob sv_load_weights_v3_f32 takes.  The int64
+    num_batches_tracked entries are not part of it."""
+    def bn(prefix, c):
+        return [(f"{prefix}.{n}", (c,)) for n in ("weight", "bias", "running_mean", "running_var")]
+    out = [("temperature", (1,)), ("stem.0.weight", (32, 1, 3, 3))] + bn("stem.1", 32)
+    for i, (cin, c, stride) in enumerate(_V3_BLOCKS, 1):
+        L = f"layer{i}"
+        out += [(f"{L}.conv1.weight", (c, cin, 3, 3))] + bn(f"{L}.bn1", c) + [(f"{L}.conv2.weight", (c, c, 3, 3))] + bn(f"{L}.bn2", c)
+        if use_se:
+            out += [(f"{L}.se.excite.0.weight", (c // 4, c)), (f"{L}.se.excite.2.weight", (c, c // 4))]
+        if stride != 1 or cin != c:
+            out += [(f"{L}.shortcut.0.weight", (c, cin, 1, 1))] + bn(f"{L}.shortcut.1", c)
+    return out + [("fc.weight", (10, 128)), ("fc.bias", (10,))]
+
+
 def _require_gpu():
     if not torch.cuda.is_available():
         raise _native.NativeError("no ROCm GPU visible: the sudoku-vision hot path runs on MI355X only (no CPU fallback)")
@@ -99,6 +119,7 @@ class Context:
         self._h = C.c_void_p()
         self._check(self._lib.sv_ctx_create(self.device.index, C.byref(self._h)), "sv_ctx_create")
         self._weights_key = None
+        self._weights_v3_key = None
 
     def _check(self, rc, what):
         _native.check(rc, what, self._lib)
@@ -141,6 +162,31 @@ class Context:
         assert blob.size == 421642
         self._check(self._lib.sv_load_weights_f32(self._h, blob.ctypes.data_as(C.c_void_p)), "sv_load_weights_f32")
         self._weights_key = key
+
+    def load_state_dict_v3(self, sd, use_se=None, key=None):
+        """sd: DigitCNNv3 state_dict (ml/model_v3.py) -- tensors or arrays, any device; num_batches_tracked entries are ignored.
+        use_se: None = inferred from the keys.  Independent of load_state_dict: one context holds both models."""
+        has_se = any(".se.excite." in k for k in sd)
+        if use_se is None:
+            use_se = has_se
+        elif bool(use_se) != has_se:
+            raise ValueError(f"use_se={use_se} but the state_dict {'has' if has_se else 'has no'} se.excite weights")
+        layout = v3_layout(bool(use_se))
+        extra = [k for k in sd if not k.endswith("num_batches_tracked") and k not in dict(layout)]
+        if extra:
+            raise ValueError(f"not DigitCNNv3 keys: {extra[:4]}")
+        parts = []
+        for k, shape in layout:
+            if k not in sd:
+                raise KeyError(f"DigitCNNv3 state_dict lacks {k}")
+            v = sd[k]
+            v = v.detach().to("cpu", torch.float32).numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)
+            if tuple(v.shape) != shape:
+                raise ValueError(f"{k}: shape {tuple(v.shape)} != {shape}")
+            parts.append(np.ascontiguousarray(v).reshape(-1))
+        blob = np.concatenate(parts)
+        self._check(self._lib.sv_load_weights_v3_f32(self._h, blob.ctypes.data_as(C.c_void_p), blob.size, int(bool(use_se))), "sv_load_weights_v3_f32")
+        self._weights_v3_key = key
 
     PREC_F32, PREC_BF16 = 0, 1
 
@@ -537,6 +583,34 @@ class Context:
         self._check(rc, "sv_cnn_forward")
         return (logits, digits, conf) if want_digits else logits
 
+    def cnn3_forward(self, x, want_digits=False, want_features=False, glue=0):
+        """DigitCNNv3.forward (ml/model_v3.py): x f32 [B,1,28,28], or u8 [B,28,28] cells with the run_v2.py glue fused in (as cnn_forward)
+        -> logits [B,10]; with want_digits (logits, digits, conf), conf = softmax(logits / temperature)[digit]; with want_features the
+        128 pooled features [B,128] come last (f32 input only)."""
+        _dev_tensor(x, "x", (torch.uint8, torch.float32), self.device)
+        if x.dtype == torch.uint8:
+            _dev_tensor(x, "x", torch.uint8, self.device, shape=(None, 28, 28))
+            if want_features:
+                raise ValueError("want_features needs f32 input (sv_cnn3_forward_f32)")
+        elif not (x.dim() in (3, 4) and tuple(x.shape[-2:]) == (28, 28) and (x.dim() == 3 or x.shape[1] == 1)):
+            raise ValueError(f"x must have shape [B,1,28,28], got {list(x.shape)}")
+        x = x.contiguous()
+        B = x.shape[0]
+        logits = torch.empty((B, 10), dtype=torch.float32, device=self.device)
+        digits = torch.empty((B,), dtype=torch.uint8, device=self.device) if want_digits else None
+        conf = torch.empty((B,), dtype=torch.float32, device=self.device) if want_digits else None
+        feats = torch.empty((B, 128), dtype=torch.float32, device=self.device) if want_features else None
+        dg, cf = (_ptr(digits) if want_digits else None), (_ptr(conf) if want_digits else None)
+        if x.dtype == torch.uint8:
+            rc = self._lib.sv_cnn3_forward_cells_u8(self._h, _ptr(x), B, int(glue), _ptr(logits), dg, cf, _stream_ptr())
+        else:
+            rc = self._lib.sv_cnn3_forward_f32(self._h, _ptr(x), B, _ptr(logits), _ptr(feats) if want_features else None, dg, cf, _stream_ptr())
+        self._check(rc, "sv_cnn3_forward")
+        out = (logits, digits, conf) if want_digits else (logits,)
+        if want_features:
+            out += (feats,)
+        return out if len(out) > 1 else logits
+
     # ---- whole path ---------------------------------------------------------------------------
     def frames_to_digits(self, frames, minv_dev, out=None, keep_cells=False, glue=0):
         """frames u8 [n,H,W,3], minv_dev f64 [n,3,3] on device -> dict(logits [n,81,10], digits [n,81], conf [n,81])."""
@@ -553,6 +627,23 @@ class Context:
         self._check(self._lib.sv_frames_to_digits(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(minv_dev), int(glue),
                                                         _ptr(cells) if cells is not None else None, _ptr(out["logits"]), _ptr(out["digits"]),
                                                         _ptr(out["conf"]), _stream_ptr()), "sv_frames_to_digits")
+        return out
+
+    def frames_to_digits_v3(self, frames, minv_dev, out=None, keep_cells=False, glue=0):
+        """frames_to_digits with the DigitCNNv3 forward (load_state_dict_v3): same arguments, same dict."""
+        frames, pitch, fstride = _frame_layout(frames, self.device)
+        n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+        minv_dev = self._minv(minv_dev, n)
+        if out is None:
+            out = {"logits": torch.empty((n, 81, 10), dtype=torch.float32, device=self.device),
+                   "digits": torch.empty((n, 81), dtype=torch.uint8, device=self.device),
+                   "conf": torch.empty((n, 81), dtype=torch.float32, device=self.device)}
+            if keep_cells:
+                out["cells"] = torch.empty((n, 81, 28, 28), dtype=torch.uint8, device=self.device)
+        cells = out.get("cells")
+        self._check(self._lib.sv_frames_to_digits_v3(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(minv_dev), int(glue),
+                                                           _ptr(cells) if cells is not None else None, _ptr(out["logits"]), _ptr(out["digits"]),
+                                                           _ptr(out["conf"]), _stream_ptr()), "sv_frames_to_digits_v3")
         return out
 
     # ---- quality gate (cv/grid_quality.py) ------------------------------------------------------
