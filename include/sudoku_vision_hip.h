@@ -150,10 +150,14 @@ int sv_preprocess_bits_u8(sv_ctx *ctx, const uint8_t *bgr /*dev*/, int n, int H,
 /* sv_despeckle_u8 on a bit image, in place (same filter, same precondition, same result as its `packed` output). */
 int sv_despeckle_bits(sv_ctx *ctx, uint32_t *bits /*dev, n*H*W/32*/, int n, int H, int W, void *stream);
 
-/* Accelerator for the host corner search, not a reference stage: erases every connected component of a {0,255}
- * image that lies strictly inside a 64x64 tile (two offset tile grids).  Such components can neither be nor
- * influence the result of find_grid_contour (argument in csrc/k4_despeckle.hip), so
+/* Accelerator for the host corner search, not a reference stage: erases connected components of a {0,255}
+ * image that lie strictly inside a 64x64 tile (two passes, the second with the tile grid offset by (32,32)).  Such
+ * components can neither be nor influence the result of find_grid_contour (argument in csrc/k4_despeckle.hip), so
  * sv_find_grid_corners_u8(despeckled) == sv_find_grid_corners_u8(binary).  out may equal binary.
+ * A pass erases every such component of a tile unless the tile's flood fill has not settled within its iteration cap
+ * (MAX_IT = 96 in csrc/k4_despeckle.hip; thin diagonal paths that wind through a tile need more, natural images come
+ * close: DESIGN.md, K4): that tile is left exactly as it is for that pass.  So the filter erases a subset of the
+ * strictly-inside components, always whole ones; the equality above holds for any subset.
  * packed (optional, needs W % 32 == 0): the result as 1 bit per pixel (LSB = leftmost, W/32 words per row) for a
  * cheap D2H copy -- when given, `out` is scratch (first pass only) and `packed` holds the result; feed it to
  * sv_find_grid_corners_bits_batch.

@@ -316,7 +316,8 @@ class Context:
         return bits
 
     def despeckle(self, binary, out=None, packed=None):
-        """binary u8 [n,H,W] in {0,255} -> the same with every component that fits strictly inside a 64x64 tile erased
+        """binary u8 [n,H,W] in {0,255} -> the same with the components that lie strictly inside a 64x64 tile erased (all of them,
+        except in a tile whose flood fill hits its iteration cap: that tile is left as it is for that pass; sv_despeckle_u8 in the header)
         (find_grid_contour-equivalent; used only to make the host corner search cheaper).  packed: optional int32 [n,H,W//32]
         tensor receiving the result as 1 bit per pixel (then `out` is scratch)."""
         binary = _dev_tensor(binary, "binary", torch.uint8, self.device, ndim=3).contiguous()

@@ -315,7 +315,9 @@ def test_tiny_and_odd_images(ctx):
 
 def _despeckle_np(img):
     """numpy/scipy statement of sv_despeckle_u8: two passes over 64x64 tiles (grid origin (0,0), then (-32,-32)); in every tile the
-    8-connected components of the tile's own pixels that touch none of the tile's outermost pixels are erased."""
+    8-connected components of the tile's own pixels that touch none of the tile's outermost pixels are erased.  It does not model the
+    kernel's iteration cap (a tile whose fill needs more than MAX_IT iterations is left untouched): for inputs that come near it use
+    tests/despeckle_ref.py, which does (tests/test_gpu_despeckle_topology.py)."""
     from scipy import ndimage
     out = (img > 0).copy()
     H, W = out.shape
