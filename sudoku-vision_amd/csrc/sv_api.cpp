@@ -40,16 +40,11 @@ extern "C" int sv_ctx_create(int device, sv_ctx **out)
     return SV_OK;
 }
 
-static void free_weights(sv_weights &w)
+template <class W>   // sv_weights or sv_weights3
+static void free_weights(W &w)
 {
     for (void *p : w.allocs) (void)hipFree(p);
-    w = sv_weights();
-}
-
-static void free_weights(sv_weights3 &w)
-{
-    for (void *p : w.allocs) (void)hipFree(p);
-    w = sv_weights3();
+    w = W();
 }
 
 extern "C" int sv_ctx_destroy(sv_ctx *ctx)
@@ -343,15 +338,20 @@ extern "C" int sv_corners_to_minv_batch(const float *corners, int n, int out_siz
 }
 
 // ---- argument checks + dispatch ---------------------------------------------------------------------
-#define REQUIRE(cond, what) \
-    do { if (!(cond)) return sv_fail(SV_ERR_BAD_ARG, "%s: %s", __func__, what); } while (0)
+#define REQUIRE_AS(fn, cond, what) \
+    do { if (!(cond)) return sv_fail(SV_ERR_BAD_ARG, "%s: %s", fn, what); } while (0)
+#define REQUIRE(cond, what) REQUIRE_AS(__func__, cond, what)
 
 static inline hipStream_t S(void *s) { return (hipStream_t)s; }
+
+// one BGR frame batch: n frames of H x W pixels, `pitch` bytes between rows; 65535 = the grid's z limit
+static inline bool frames_ok(int n, int H, int W, ptrdiff_t pitch) { return n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W; }
+#define REQUIRE_FRAMES() REQUIRE(frames_ok(n, H, W, pitch), "bad shape")
 
 extern "C" int sv_gray_u8(sv_ctx *ctx, const uint8_t *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint8_t *gray, void *stream)
 {
     REQUIRE(ctx && bgr && gray, "NULL argument");
-    REQUIRE(n > 0 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W, "bad shape");
+    REQUIRE_FRAMES();
     return svk_gray(bgr, n, H, W, pitch, img_stride, gray, S(stream));
 }
 
@@ -379,7 +379,7 @@ extern "C" int sv_adaptive_threshold_u8(sv_ctx *ctx, const uint8_t *src, int n, 
 extern "C" int sv_preprocess_u8(sv_ctx *ctx, const uint8_t *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint8_t *binary, void *stream)
 {
     REQUIRE(ctx && bgr && binary, "NULL argument");
-    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W, "bad shape");
+    REQUIRE_FRAMES();
     return svk_preprocess(ctx, bgr, n, H, W, pitch, img_stride, binary, S(stream));
 }
 
@@ -387,7 +387,7 @@ extern "C" int sv_preprocess_warp_cells_u8(sv_ctx *ctx, const uint8_t *bgr, int 
                                            const double *minv, uint8_t *cells, void *stream)
 {
     REQUIRE(ctx && bgr && binary && minv && cells, "NULL argument");
-    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W, "bad shape");
+    REQUIRE_FRAMES();
     return svk_preprocess_warp_fused(ctx, bgr, n, H, W, pitch, img_stride, binary, minv, cells, S(stream));
 }
 
@@ -395,7 +395,7 @@ extern "C" int sv_preprocess_warp_cells_u8(sv_ctx *ctx, const uint8_t *bgr, int 
 extern "C" int sv_preprocess_mm_u8(sv_ctx *ctx, const uint8_t *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint8_t *binary, float *mean, void *stream)
 {
     REQUIRE(ctx && bgr && binary, "NULL argument");
-    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W, "bad shape");
+    REQUIRE_FRAMES();
     if (!svk_preprocess_mm_supported(bgr, H, W, pitch, img_stride, binary, false))
         return sv_fail(SV_ERR_UNSUPPORTED, "sv_preprocess_mm_u8: needs H, W >= 16, W %% 16 == 0, 4-byte aligned frames and a 16-byte aligned output");
     return svk_preprocess_mm(ctx, bgr, n, H, W, pitch, img_stride, binary, false, mean, S(stream));
@@ -413,7 +413,7 @@ extern "C" int sv_preprocess_stats(sv_ctx *ctx, unsigned *ambiguous, unsigned lo
 extern "C" int sv_preprocess_bits_u8(sv_ctx *ctx, const uint8_t *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint32_t *bits, void *stream)
 {
     REQUIRE(ctx && bgr && bits, "NULL argument");
-    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W, "bad shape");
+    REQUIRE_FRAMES();
     REQUIRE(((uintptr_t)bits & 3) == 0, "bits must be 4-byte aligned");
     return svk_preprocess_bits(ctx, bgr, n, H, W, pitch, img_stride, bits, S(stream));
 }
@@ -484,18 +484,30 @@ extern "C" int sv_extract_cells_u8(sv_ctx *ctx, const uint8_t *grid, int h, int 
 extern "C" int sv_warp_cells_u8(sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv, uint8_t *cells, void *stream)
 {
     REQUIRE(ctx && frames && minv && cells, "NULL argument");
-    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W, "bad shape");
+    REQUIRE_FRAMES();
     return svk_warp_cells(ctx, frames, n, H, W, pitch, frame_stride, minv, cells, S(stream));
+}
+
+// the argument checks the two forwards share, reported under `fn`; `loaded`: the model's weights are there, else `loader` is what to call
+static int cnn_args_ok(const char *fn, const sv_ctx *ctx, const void *x, long B, const float *logits, bool loaded, const char *loader)
+{
+    if (!ctx || !x || !logits) return sv_fail(SV_ERR_BAD_ARG, "%s: NULL argument", fn);
+    if (B <= 0) return sv_fail(SV_ERR_BAD_ARG, "%s: B = %ld", fn, B);
+    if (!loaded) return sv_fail(SV_ERR_NO_WEIGHTS, "%s: call %s first", fn, loader);
+    return SV_OK;
+}
+
+static int glue_ok(const char *fn, int glue)
+{
+    return glue == SV_GLUE_NORMALIZE || glue == SV_GLUE_RUNPY ? SV_OK : sv_fail(SV_ERR_BAD_ARG, "%s: glue %d", fn, glue);
 }
 
 static int cnn_common(sv_ctx *ctx, const void *x, bool u8in, int glue, long B, float *logits, uint8_t *digits, float *conf, void *stream)
 {
-    if (!ctx || !x || !logits) return sv_fail(SV_ERR_BAD_ARG, "sv_cnn_forward: NULL argument");
-    if (B <= 0) return sv_fail(SV_ERR_BAD_ARG, "sv_cnn_forward: B = %ld", B);
-    if (!ctx->w.loaded) return sv_fail(SV_ERR_NO_WEIGHTS, "sv_cnn_forward: call sv_load_weights_f32 first");
-    int rc = sv_ensure_scratch(ctx, B);
+    int rc = cnn_args_ok("sv_cnn_forward", ctx, x, B, logits, ctx && ctx->w.loaded, "sv_load_weights_f32");
     if (rc) return rc;
-    if (glue != SV_GLUE_NORMALIZE && glue != SV_GLUE_RUNPY) return sv_fail(SV_ERR_BAD_ARG, "sv_cnn_forward: glue %d", glue);
+    if ((rc = sv_ensure_scratch(ctx, B))) return rc;
+    if ((rc = glue_ok("sv_cnn_forward", glue))) return rc;
     return svk_cnn_forward(ctx, x, u8in, glue, B, logits, digits, conf, S(stream));
 }
 
@@ -511,13 +523,11 @@ extern "C" int sv_cnn_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells, long B
 
 static int cnn3_common(sv_ctx *ctx, const void *x, bool u8in, int glue, long B, float *logits, float *features, uint8_t *digits, float *conf, void *stream)
 {
-    if (!ctx || !x || !logits) return sv_fail(SV_ERR_BAD_ARG, "sv_cnn3_forward: NULL argument");
-    if (B <= 0) return sv_fail(SV_ERR_BAD_ARG, "sv_cnn3_forward: B = %ld", B);
-    if (!ctx->w3.loaded) return sv_fail(SV_ERR_NO_WEIGHTS, "sv_cnn3_forward: call sv_load_weights_v3_f32 first");
-    if (ctx->precision != SV_PREC_F32) return sv_fail(SV_ERR_UNSUPPORTED, "sv_cnn3_forward: the DigitCNNv3 forward has f32 arithmetic only (context is set to SV_PREC_BF16)");
-    if (glue != SV_GLUE_NORMALIZE && glue != SV_GLUE_RUNPY) return sv_fail(SV_ERR_BAD_ARG, "sv_cnn3_forward: glue %d", glue);
-    int rc = sv_ensure_scratch_v3(ctx, B);
+    int rc = cnn_args_ok("sv_cnn3_forward", ctx, x, B, logits, ctx && ctx->w3.loaded, "sv_load_weights_v3_f32");
     if (rc) return rc;
+    if (ctx->precision != SV_PREC_F32) return sv_fail(SV_ERR_UNSUPPORTED, "sv_cnn3_forward: the DigitCNNv3 forward has f32 arithmetic only (context is set to SV_PREC_BF16)");
+    if ((rc = glue_ok("sv_cnn3_forward", glue))) return rc;
+    if ((rc = sv_ensure_scratch_v3(ctx, B))) return rc;
     if (u8in && glue == SV_GLUE_RUNPY) {             // preprocess_cell as its own pass; its {0,255} output then takes the plain glue
         if ((rc = sv_ensure_scratch(ctx, B))) return rc;
         if ((rc = svk_preprocess_cells((const uint8_t *)x, B, ctx->cells2, S(stream)))) return rc;
@@ -594,7 +604,7 @@ extern "C" int sv_grid_line_coverage_bits(sv_ctx *ctx, const uint32_t *bits, int
 
 // ---- K7: cv/preprocess_v2.py ---------------------------------------------------------------------------
 // one gray plane set: n frames of H x W, `pitch` bytes between rows, `img_stride` between frames; 65535 = the grid's y / z limit
-#define REQUIRE_PLANES(src) \
+#define REQUIRE_PLANES() \
     do { \
         REQUIRE(n > 0 && n < 65536 && H > 0 && H < 65536 && W > 0 && pitch >= (ptrdiff_t)W, "bad shape"); \
         REQUIRE(n == 1 || img_stride >= pitch * (H - 1) + (ptrdiff_t)W, "frames overlap (img_stride too small)"); \
@@ -604,7 +614,7 @@ extern "C" int sv_morphology_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, i
                                 uint8_t *dst, void *stream)
 {
     REQUIRE(ctx && src && dst, "NULL argument");
-    REQUIRE_PLANES(src);
+    REQUIRE_PLANES();
     REQUIRE(op >= SV_MORPH_DILATE && op <= SV_MORPH_OPEN, "op must be SV_MORPH_DILATE, _ERODE, _CLOSE or _OPEN");
     REQUIRE(shape == SV_SHAPE_RECT || shape == SV_SHAPE_ELLIPSE, "shape must be SV_SHAPE_RECT or SV_SHAPE_ELLIPSE");
     REQUIRE(ksize >= 1, "ksize must be positive");
@@ -614,7 +624,7 @@ extern "C" int sv_morphology_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, i
 extern "C" int sv_box_mean_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int ksize, uint8_t *dst, void *stream)
 {
     REQUIRE(ctx && src && dst, "NULL argument");
-    REQUIRE_PLANES(src);
+    REQUIRE_PLANES();
     REQUIRE(ksize > 0 && (ksize & 1), "ksize must be odd and positive");
     return svk_box_mean(src, n, H, W, pitch, img_stride, ksize, dst, S(stream));
 }
@@ -622,7 +632,7 @@ extern "C" int sv_box_mean_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int
 extern "C" int sv_gaussian_blur21_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint8_t *dst, void *stream)
 {
     REQUIRE(ctx && src && dst, "NULL argument");
-    REQUIRE_PLANES(src);
+    REQUIRE_PLANES();
     return svk_gaussian_blur21(src, n, H, W, pitch, img_stride, dst, S(stream));
 }
 
@@ -630,7 +640,7 @@ extern "C" int sv_divide_normalize_u8(sv_ctx *ctx, const uint8_t *gray, int n, i
                                       uint8_t *dst, void *stream)
 {
     REQUIRE(ctx && gray && background && dst, "NULL argument");
-    REQUIRE_PLANES(gray);
+    REQUIRE_PLANES();
     return svk_divide_normalize(gray, n, H, W, pitch, img_stride, background, dst, S(stream));
 }
 
@@ -638,7 +648,7 @@ extern "C" int sv_clahe_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W,
                            uint8_t *dst, void *stream)
 {
     REQUIRE(ctx && src && dst, "NULL argument");
-    REQUIRE_PLANES(src);
+    REQUIRE_PLANES();
     REQUIRE(tiles_x > 0 && tiles_y > 0 && tiles_x * tiles_y <= 65535 && clip_limit == clip_limit, "bad tile grid or clip limit");
     return svk_clahe(ctx, src, n, H, W, pitch, img_stride, clip_limit, tiles_x, tiles_y, dst, S(stream));
 }
@@ -647,7 +657,7 @@ extern "C" int sv_threshold_sauvola_u8(sv_ctx *ctx, const uint8_t *src, int n, i
                                        uint8_t *dst, void *stream)
 {
     REQUIRE(ctx && src && dst, "NULL argument");
-    REQUIRE_PLANES(src);
+    REQUIRE_PLANES();
     REQUIRE(window > 0 && (window & 1), "window must be odd and positive");
     return svk_threshold_sauvola(src, n, H, W, pitch, img_stride, window, k, dst, S(stream));
 }
@@ -656,7 +666,7 @@ extern "C" int sv_threshold_count_u8(sv_ctx *ctx, const uint8_t *src, int n, int
                                      uint8_t *dst, uint32_t *counts, void *stream)
 {
     REQUIRE(ctx && src && dst && counts, "NULL argument");
-    REQUIRE_PLANES(src);
+    REQUIRE_PLANES();
     REQUIRE(((uintptr_t)counts & 3) == 0, "misaligned counts");
     return svk_threshold_count(src, n, H, W, pitch, img_stride, thresh, type_inv ? 1 : 0, dst, counts, S(stream));
 }
@@ -665,7 +675,7 @@ extern "C" int sv_shadow_mask_u8(sv_ctx *ctx, const uint8_t *gray, int n, int H,
                                  uint8_t *mask, uint32_t *counts, void *stream)
 {
     REQUIRE(ctx && gray && local_mean && mask && counts, "NULL argument");
-    REQUIRE_PLANES(gray);
+    REQUIRE_PLANES();
     REQUIRE(((uintptr_t)counts & 3) == 0, "misaligned counts");
     return svk_shadow_mask(gray, n, H, W, pitch, img_stride, local_mean, delta, mask, counts, S(stream));
 }
@@ -673,7 +683,7 @@ extern "C" int sv_shadow_mask_u8(sv_ctx *ctx, const uint8_t *gray, int n, int H,
 extern "C" int sv_count_nonzero_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint32_t *counts, void *stream)
 {
     REQUIRE(ctx && src && counts, "NULL argument");
-    REQUIRE_PLANES(src);
+    REQUIRE_PLANES();
     REQUIRE(((uintptr_t)counts & 3) == 0, "misaligned counts");
     return svk_count_nonzero(src, n, H, W, pitch, img_stride, counts, S(stream));
 }
@@ -710,28 +720,27 @@ extern "C" int sv_jpeg_reconstruct_sparse_bgr_u8(sv_ctx *ctx, const sv_jpeg_info
     return svk_jpeg_reconstruct(ctx, info, nullptr, masks, offsets, values, quant, bgr, pitch, S(stream));
 }
 
-extern "C" int sv_frames_to_digits(sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv, int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)
+// K2 into the caller's cells (or the context's), then the forward `v3` selects
+static int frames_to_digits(const char *fn, bool v3, sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv,
+                            int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)
 {
-    REQUIRE(ctx && frames && minv && logits && digits, "NULL argument");
-    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W, "bad shape");
-    if (!ctx->w.loaded) return sv_fail(SV_ERR_NO_WEIGHTS, "sv_frames_to_digits: call sv_load_weights_f32 first");
+    REQUIRE_AS(fn, ctx && frames && minv && logits && digits, "NULL argument");
+    REQUIRE_AS(fn, frames_ok(n, H, W, pitch), "bad shape");
+    if (!(v3 ? ctx->w3.loaded : ctx->w.loaded)) return sv_fail(SV_ERR_NO_WEIGHTS, "%s: call %s first", fn, v3 ? "sv_load_weights_v3_f32" : "sv_load_weights_f32");
     const long B = (long)n * SV_CELLS;
     int rc = sv_ensure_scratch(ctx, B);
     if (rc) return rc;
     uint8_t *c = cells ? cells : ctx->cells;
     if ((rc = svk_warp_cells(ctx, frames, n, H, W, pitch, frame_stride, minv, c, S(stream)))) return rc;
-    return cnn_common(ctx, c, true, glue, B, logits, digits, conf, stream);
+    return v3 ? cnn3_common(ctx, c, true, glue, B, logits, nullptr, digits, conf, stream) : cnn_common(ctx, c, true, glue, B, logits, digits, conf, stream);
+}
+
+extern "C" int sv_frames_to_digits(sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv, int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)
+{
+    return frames_to_digits("sv_frames_to_digits", false, ctx, frames, n, H, W, pitch, frame_stride, minv, glue, cells, logits, digits, conf, stream);
 }
 
 extern "C" int sv_frames_to_digits_v3(sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv, int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)
 {
-    REQUIRE(ctx && frames && minv && logits && digits, "NULL argument");
-    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W, "bad shape");
-    if (!ctx->w3.loaded) return sv_fail(SV_ERR_NO_WEIGHTS, "sv_frames_to_digits_v3: call sv_load_weights_v3_f32 first");
-    const long B = (long)n * SV_CELLS;
-    int rc = sv_ensure_scratch(ctx, B);
-    if (rc) return rc;
-    uint8_t *c = cells ? cells : ctx->cells;
-    if ((rc = svk_warp_cells(ctx, frames, n, H, W, pitch, frame_stride, minv, c, S(stream)))) return rc;
-    return cnn3_common(ctx, c, true, glue, B, logits, nullptr, digits, conf, stream);
+    return frames_to_digits("sv_frames_to_digits_v3", true, ctx, frames, n, H, W, pitch, frame_stride, minv, glue, cells, logits, digits, conf, stream);
 }

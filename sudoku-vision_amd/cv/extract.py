@@ -3,21 +3,12 @@ import os
 import sys
 
 import numpy as np
-import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from _bootstrap import package  # noqa: E402
 sys.path.pop(0)
 _rt = package().runtime
-
-
-def _to_dev(a, ctx):
-    if isinstance(a, torch.Tensor):
-        return a.contiguous(), True
-    a = np.asarray(a)
-    if a.dtype != np.uint8:
-        raise TypeError(f"expected uint8 image, got {a.dtype}")
-    return torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device), False
+_to_dev = _rt._to_dev
 
 
 def extract_cells(grid_image, cell_size: int = 28, margin_ratio: float = 0.1):

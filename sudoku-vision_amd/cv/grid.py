@@ -51,15 +51,7 @@ def order_points(pts):
 def warp_perspective(image, corners, output_size: int = 450, inset_ratio: float = 0.0):
     """Warp the grid region to an output_size square (reference cv/grid.py:94-133)."""
     ctx = _rt.default_context()
-    was_tensor = isinstance(image, torch.Tensor)
-    if was_tensor:
-        d = image.contiguous()
-    else:
-        image = np.asarray(image)
-        if image.dtype != np.uint8:
-            raise TypeError(f"expected uint8 image, got {image.dtype}")
-        d = torch.from_numpy(np.ascontiguousarray(image)).to(ctx.device)
+    d, was_tensor = _rt._to_dev(image, ctx)
     corners = np.asarray(corners.cpu() if isinstance(corners, torch.Tensor) else corners).astype(np.float32).reshape(1, 4, 2)
     minv = ctx.minv_to_device(_rt.Context.corners_to_minv(corners, output_size, inset_ratio))
-    out = ctx.warp_perspective(d, minv, output_size)
-    return out if was_tensor else out.cpu().numpy()
+    return _rt._back(ctx.warp_perspective(d, minv, output_size), was_tensor)

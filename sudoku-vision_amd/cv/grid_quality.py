@@ -186,17 +186,6 @@ def get_user_feedback(quality: QualityScore) -> str:
 
 
 # ---- the reference's functions, on the GPU --------------------------------------------------------------------------
-def _dev_image(a, ctx):
-    if isinstance(a, torch.Tensor):
-        if a.dtype != torch.uint8 or not a.is_cuda:
-            raise TypeError("expected a uint8 CUDA tensor or a numpy uint8 array")
-        return a
-    a = np.asarray(a)
-    if a.dtype != np.uint8:
-        raise TypeError(f"expected uint8 image, got {a.dtype}")
-    return torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device)
-
-
 def _host_corners(corners):
     c = corners.cpu().numpy() if isinstance(corners, torch.Tensor) else np.asarray(corners)
     return c.astype(np.float32).reshape(-1, 4, 2)
@@ -204,7 +193,7 @@ def _host_corners(corners):
 
 def _stats(image, ctx):
     """image [H,W] gray or [H,W,3] BGR -> (lap_sum, lap_sqsum, hist, H*W) on the host."""
-    d = _dev_image(image, ctx)
+    d, _ = _rt._to_dev(image, ctx)
     s1, s2, h = ctx.frame_quality_stats(d[None])
     return int(s1.item()), int(s2.item()), h[0].cpu().numpy(), d.shape[0] * d.shape[1]
 
@@ -212,7 +201,7 @@ def _stats(image, ctx):
 def _coverage(binary, corners, ctx):
     """-> (counts int [20], ok) for one binary image and one quad."""
     minv, ok = _rt.Context.corners_to_minv_batch(_host_corners(corners), GRID_SIZE)
-    counts = ctx.grid_line_coverage(_dev_image(binary, ctx)[None], ctx.minv_to_device(minv))
+    counts = ctx.grid_line_coverage(_rt._to_dev(binary, ctx)[0][None], ctx.minv_to_device(minv))
     return counts[0].cpu().numpy(), bool(ok[0])
 
 

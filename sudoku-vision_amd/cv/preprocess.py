@@ -6,28 +6,11 @@ tensor out with no host round trip.  All arithmetic runs in the HIP kernels of c
 import os
 import sys
 
-import numpy as np
-import torch
-
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from _bootstrap import package  # noqa: E402
 sys.path.pop(0)
 _rt = package().runtime
-
-
-def _to_dev(a, ctx):
-    if isinstance(a, torch.Tensor):
-        if a.dtype != torch.uint8 or not a.is_cuda:
-            raise TypeError("expected a uint8 CUDA tensor or a numpy uint8 array")
-        return a.contiguous(), True
-    a = np.asarray(a)
-    if a.dtype != np.uint8:
-        raise TypeError(f"expected uint8 image, got {a.dtype}")
-    return torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device), False
-
-
-def _back(t, was_tensor):
-    return t if was_tensor else t.cpu().numpy()
+_to_dev, _back = _rt._to_dev, _rt._back
 
 
 def grayscale(image):

@@ -26,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from _bootstrap import package  # noqa: E402
 sys.path.pop(0)
 _rt = package().runtime
+_to_dev, _back = _rt._to_dev, _rt._back
 
 METHODS = ("adaptive", "otsu", "sauvola")
 
@@ -115,21 +116,6 @@ def choose_strategy(counts, npx):
 
 
 # ---- device plumbing ------------------------------------------------------------------------------------------------------
-def _to_dev(a, ctx):
-    if isinstance(a, torch.Tensor):
-        if a.dtype != torch.uint8 or not a.is_cuda:
-            raise TypeError("expected a uint8 CUDA tensor or a numpy uint8 array")
-        return a, True
-    a = np.asarray(a)
-    if a.dtype != np.uint8:
-        raise TypeError(f"expected uint8 image, got {a.dtype}")
-    return torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device), False
-
-
-def _back(t, was_tensor):
-    return t if was_tensor else t.cpu().numpy()
-
-
 def _gray_planes(image, ctx, what):
     """A single-channel image -> (u8 [1,H,W] on device, was_tensor)."""
     d, was = _to_dev(image, ctx)
@@ -144,7 +130,7 @@ def _grayscale_dev(d, ctx):
         return d[None]
     if d.dim() != 3 or d.shape[2] != 3:
         raise ValueError(f"expected an [H,W] or [H,W,3] image, got {list(d.shape)}")
-    return ctx.gray(d.contiguous()[None])
+    return ctx.gray(d[None])
 
 
 def _normalize_illumination(ctx, g):
@@ -230,7 +216,7 @@ def threshold_adaptive(gray, block_size: int = 11, c: int = 2):
     """Adaptive Gaussian threshold, inverted binary (cv/preprocess_v2.py:132-143)."""
     ctx = _rt.default_context()
     g, was = _gray_planes(gray, ctx, "threshold_adaptive")
-    return _back(ctx.adaptive_threshold(g.contiguous(), block_size, c, inv=True)[0], was)
+    return _back(ctx.adaptive_threshold(g, block_size, c, inv=True)[0], was)
 
 
 def threshold_otsu(gray):
@@ -266,7 +252,7 @@ def preprocess_for_grid_detection(image, use_illumination_norm: bool = True, use
     if use_illumination_norm:
         enhanced = _normalize_illumination(ctx, enhanced)
     enhanced = ctx.clahe(enhanced, 2.0, (8, 8))
-    binary = ctx.adaptive_threshold(ctx.blur(enhanced.contiguous(), 5), 11, 2, inv=True)
+    binary = ctx.adaptive_threshold(ctx.blur(enhanced, 5), 11, 2, inv=True)
     return _back(_cleanup(ctx, binary, 3, 2)[0], was)
 
 

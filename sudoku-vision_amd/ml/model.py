@@ -33,13 +33,7 @@ class DigitCNN(nn.Module):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if self.training:
-            raise NotImplementedError("DigitCNN (MI355X): inference only -- call .eval() (dropout is identity in eval mode)")
-        if not x.is_cuda:
-            raise RuntimeError("DigitCNN (MI355X): input must be a CUDA tensor; there is no CPU fallback")
-        if x.dim() != 4 or tuple(x.shape[1:]) != (1, 28, 28):
-            raise ValueError(f"expected input of shape (batch, 1, 28, 28), got {tuple(x.shape)}")
-        ctx = _rt.default_context(x.device)
+        ctx = _rt._model_context(x, self.training, "DigitCNN", "dropout is identity")
         key = (id(self), self._weights_key())
         if ctx._weights_key != key:
             ctx.load_state_dict(self.state_dict(), key=key)

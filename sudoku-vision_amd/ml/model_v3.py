@@ -61,13 +61,7 @@ class DigitCNNv3(nn.Module):
         return tuple((v.data_ptr(), v._version) for v in self.state_dict(keep_vars=True).values())
 
     def _context(self, x):
-        if self.training:
-            raise NotImplementedError("DigitCNNv3 (MI355X): inference only -- call .eval() (dropout is identity and BatchNorm uses its running statistics in eval mode)")
-        if not x.is_cuda:
-            raise RuntimeError("DigitCNNv3 (MI355X): input must be a CUDA tensor; there is no CPU fallback")
-        if x.dim() != 4 or tuple(x.shape[1:]) != (1, 28, 28):
-            raise ValueError(f"expected input of shape (batch, 1, 28, 28), got {tuple(x.shape)}")
-        ctx = _rt.default_context(x.device)
+        ctx = _rt._model_context(x, self.training, "DigitCNNv3", "dropout is identity and BatchNorm uses its running statistics")
         key = (id(self), self._weights_key())
         if ctx._weights_v3_key != key:
             ctx.load_state_dict_v3(self.state_dict(), use_se=self.use_se, key=key)

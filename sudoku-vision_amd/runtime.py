@@ -11,8 +11,9 @@ import torch
 
 from . import _native
 
-_KEYS = ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
-_SHAPES = ((32, 1, 3, 3), (32,), (64, 32, 3, 3), (64,), (128, 3136), (128,), (10, 128), (10,))
+# (key, shape) of a DigitCNN state_dict (ml/model.py) in the order of the blob sv_load_weights_f32 takes
+_V1_LAYOUT = (("conv1.weight", (32, 1, 3, 3)), ("conv1.bias", (32,)), ("conv2.weight", (64, 32, 3, 3)), ("conv2.bias", (64,)),
+              ("fc1.weight", (128, 3136)), ("fc1.bias", (128,)), ("fc2.weight", (10, 128)), ("fc2.bias", (10,)))
 
 
 # DigitCNNv3 (ml/model_v3.py): (in, out, stride) of layer1..5
@@ -35,6 +36,21 @@ def v3_layout(use_se=True):
     return out + [("fc.weight", (10, 128)), ("fc.bias", (10,))]
 
 
+def _state_blob(sd, layout, model):
+    """sd: a state_dict of `model` -- tensors or arrays, any device -> its `layout` entries ((key, shape) pairs) as one float32 host
+    array in that order.  KeyError for a missing key, ValueError for a wrong shape; entries outside the layout are not looked at."""
+    parts = []
+    for k, shape in layout:
+        if k not in sd:
+            raise KeyError(f"{model} state_dict lacks {k}")
+        v = sd[k]
+        v = v.detach().to("cpu", torch.float32).numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)
+        if tuple(v.shape) != shape:
+            raise ValueError(f"{k}: shape {tuple(v.shape)} != {shape}")
+        parts.append(np.ascontiguousarray(v).reshape(-1))
+    return np.concatenate(parts)
+
+
 def _require_gpu():
     if not torch.cuda.is_available():
         raise _native.NativeError("no ROCm GPU visible: the sudoku-vision hot path runs on MI355X only (no CPU fallback)")
@@ -46,6 +62,11 @@ def _stream_ptr():
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr())
+
+
+def _opt_ptr(t):
+    """_ptr of an output the caller may not want: NULL for None."""
+    return None if t is None else _ptr(t)
 
 
 def _dev_tensor(t, name, dtype, device, shape=None, ndim=None):
@@ -81,32 +102,56 @@ def _image_layout(img):
     return img, st[0]
 
 
-def _frame_layout(frames, device=None):
-    """frames u8 [n,H,W,3]: (tensor, row pitch, frame stride) in bytes.  Row padding and gaps between frames are passed through to
-    the library (camera buffers are rarely dense); anything else is made contiguous first."""
-    if device is not None:
-        _dev_tensor(frames, "frames", torch.uint8, device, shape=(None, None, None, 3))
-    elif frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
-        raise TypeError("expected a uint8 tensor of shape [n,H,W,3]")
-    n, H, W, _ = frames.shape
-    st = frames.stride()
-    ok = st[3] == 1 and st[2] == 3 and st[1] >= 3 * W and (n == 1 or st[0] >= st[1] * (H - 1) + 3 * W)
-    if not ok:
-        frames = frames.contiguous()
-        st = frames.stride()
-    return frames, st[1], (st[0] if n > 1 else st[1] * H)
-
-
-def _plane_layout(x, device, name="gray"):
-    """x u8 [n,H,W] on device: (tensor, row pitch, frame stride) in bytes.  Padded rows, gaps between frames and any base alignment are
-    passed through to the library; anything else is made contiguous first."""
-    _dev_tensor(x, name, torch.uint8, device, ndim=3)
-    n, H, W = x.shape
+def _batch_layout(x, device, name, ch):
+    """x u8 [n,H,W] (ch = 1) or [n,H,W,ch] on device: (tensor, row pitch, frame stride) in bytes.  Row padding, gaps between frames and any
+    base alignment are passed through to the library (camera buffers are rarely dense); anything else is made contiguous first."""
+    _dev_tensor(x, name, torch.uint8, device, shape=(None, None, None, ch) if ch > 1 else (None, None, None))
+    n, H, row = x.shape[0], x.shape[1], x.shape[2] * ch                # a row of W pixels is W * ch dense bytes
     st = x.stride()
-    if not (st[2] == 1 and st[1] >= W and (n == 1 or st[0] >= st[1] * (H - 1) + W)):
+    # st[2] is the pixel stride and st[-1] the channel stride; for planes both name the pixel stride
+    if not (st[-1] == 1 and st[2] == ch and st[1] >= row and (n == 1 or st[0] >= st[1] * (H - 1) + row)):
         x = x.contiguous()
         st = x.stride()
     return x, st[1], (st[0] if n > 1 else st[1] * H)
+
+
+def _frame_layout(frames, device):
+    """frames u8 [n,H,W,3] on device: _batch_layout of BGR frames."""
+    return _batch_layout(frames, device, "frames", 3)
+
+
+def _plane_layout(x, device, name="gray"):
+    """x u8 [n,H,W] on device: _batch_layout of gray planes."""
+    return _batch_layout(x, device, name, 1)
+
+
+def _to_dev(a, ctx):
+    """An image argument of a drop-in (cv/*.py) -> (u8 tensor on ctx's device, was_tensor).  A numpy uint8 array is uploaded; a uint8 CUDA
+    tensor is passed as it is, views included: the Context methods deal with layout.  Anything else is a TypeError."""
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.uint8 or not a.is_cuda:
+            raise TypeError("expected a uint8 CUDA tensor or a numpy uint8 array")
+        return a, True
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        raise TypeError(f"expected uint8 image, got {a.dtype}")
+    return torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device), False
+
+
+def _back(t, was_tensor):
+    """A drop-in's result in the kind its argument had: the tensor itself, or a numpy array on the host."""
+    return t if was_tensor else t.cpu().numpy()
+
+
+def _model_context(x, training, name, eval_note):
+    """The preamble of the drop-in models' forward (ml/*.py): inference only, CUDA only, x [batch,1,28,28] -> the context of x's device."""
+    if training:
+        raise NotImplementedError(f"{name} (MI355X): inference only -- call .eval() ({eval_note} in eval mode)")
+    if not x.is_cuda:
+        raise RuntimeError(f"{name} (MI355X): input must be a CUDA tensor; there is no CPU fallback")
+    if x.dim() != 4 or tuple(x.shape[1:]) != (1, 28, 28):
+        raise ValueError(f"expected input of shape (batch, 1, 28, 28), got {tuple(x.shape)}")
+    return default_context(x.device)
 
 
 class Context:
@@ -125,7 +170,10 @@ class Context:
         _native.check(rc, what, self._lib)
 
     def _out(self, t, shape, dtype, name):
-        """A caller-provided output tensor: the kernels write shape-many elements through its raw pointer, so it has to be exactly that."""
+        """An output tensor: a new one, or the caller's `t`.  The kernels write shape-many elements through its raw pointer, so `t` has to
+        be exactly that."""
+        if t is None:
+            return torch.empty(tuple(shape), dtype=dtype, device=self.device)
         if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
             raise TypeError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)} on {self.device}")
         return t
@@ -151,15 +199,7 @@ class Context:
     # ---- weights ------------------------------------------------------------------------------
     def load_state_dict(self, sd, key=None):
         """sd: DigitCNN state_dict (ml/model.py) -- tensors or arrays, any device."""
-        parts = []
-        for k, shape in zip(_KEYS, _SHAPES):
-            v = sd[k]
-            v = v.detach().to("cpu", torch.float32).numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)
-            if tuple(v.shape) != shape:
-                raise ValueError(f"{k}: shape {tuple(v.shape)} != {shape}")
-            parts.append(np.ascontiguousarray(v).reshape(-1))
-        blob = np.concatenate(parts)
-        assert blob.size == 421642
+        blob = _state_blob(sd, _V1_LAYOUT, "DigitCNN")
         self._check(self._lib.sv_load_weights_f32(self._h, blob.ctypes.data_as(C.c_void_p)), "sv_load_weights_f32")
         self._weights_key = key
 
@@ -175,16 +215,7 @@ class Context:
         extra = [k for k in sd if not k.endswith("num_batches_tracked") and k not in dict(layout)]
         if extra:
             raise ValueError(f"not DigitCNNv3 keys: {extra[:4]}")
-        parts = []
-        for k, shape in layout:
-            if k not in sd:
-                raise KeyError(f"DigitCNNv3 state_dict lacks {k}")
-            v = sd[k]
-            v = v.detach().to("cpu", torch.float32).numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32)
-            if tuple(v.shape) != shape:
-                raise ValueError(f"{k}: shape {tuple(v.shape)} != {shape}")
-            parts.append(np.ascontiguousarray(v).reshape(-1))
-        blob = np.concatenate(parts)
+        blob = _state_blob(sd, layout, "DigitCNNv3")
         self._check(self._lib.sv_load_weights_v3_f32(self._h, blob.ctypes.data_as(C.c_void_p), blob.size, int(bool(use_se))), "sv_load_weights_v3_f32")
         self._weights_v3_key = key
 
@@ -259,10 +290,7 @@ class Context:
         (preprocess_for_grid_detection).  out: optional contiguous u8 [n,H,W] tensor to write into."""
         frames, pitch, fstride = _frame_layout(frames, self.device)
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
-        if out is None:
-            out = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
-        else:
-            self._out(out, (n, H, W), torch.uint8, "out")
+        out = self._out(out, (n, H, W), torch.uint8, "out")
         self._check(self._lib.sv_preprocess_u8(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(out), _stream_ptr()), "sv_preprocess_u8")
         return out
 
@@ -272,8 +300,8 @@ class Context:
         frames, pitch, fstride = _frame_layout(frames, self.device)
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
         minv_dev = self._minv(minv_dev, n)
-        binary = torch.empty((n, H, W), dtype=torch.uint8, device=self.device) if binary is None else self._out(binary, (n, H, W), torch.uint8, "binary")
-        cells = torch.empty((n, 81, 28, 28), dtype=torch.uint8, device=self.device) if cells is None else self._out(cells, (n, 81, 28, 28), torch.uint8, "cells")
+        binary = self._out(binary, (n, H, W), torch.uint8, "binary")
+        cells = self._out(cells, (n, 81, 28, 28), torch.uint8, "cells")
         self._check(self._lib.sv_preprocess_warp_cells_u8(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(binary), _ptr(minv_dev), _ptr(cells),
                                                                 _stream_ptr()), "sv_preprocess_warp_cells_u8")
         return binary, cells
@@ -286,7 +314,7 @@ class Context:
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
         out = torch.empty((n, H, W), dtype=torch.uint8, device=self.device)
         mean = torch.zeros((n, H, W), dtype=torch.float32, device=self.device) if want_mean else None
-        self._check(self._lib.sv_preprocess_mm_u8(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(out), _ptr(mean) if want_mean else None,
+        self._check(self._lib.sv_preprocess_mm_u8(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(out), _opt_ptr(mean),
                                                         _stream_ptr()), "sv_preprocess_mm_u8")
         return (out, mean) if want_mean else out
 
@@ -304,7 +332,7 @@ class Context:
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
         if W % 32:
             raise ValueError("preprocess_bits needs W % 32 == 0")
-        out = torch.empty((n, H, W // 32), dtype=torch.int32, device=self.device) if out is None else self._out(out, (n, H, W // 32), torch.int32, "out")
+        out = self._out(out, (n, H, W // 32), torch.int32, "out")
         self._check(self._lib.sv_preprocess_bits_u8(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(out), _stream_ptr()), "sv_preprocess_bits_u8")
         return out
 
@@ -322,10 +350,10 @@ class Context:
         tensor receiving the result as 1 bit per pixel (then `out` is scratch)."""
         binary = _dev_tensor(binary, "binary", torch.uint8, self.device, ndim=3).contiguous()
         n, H, W = binary.shape
-        out = torch.empty_like(binary) if out is None else self._out(out, (n, H, W), torch.uint8, "out")
+        out = self._out(out, (n, H, W), torch.uint8, "out")
         if packed is not None:
             self._out(packed, (n, H, W // 32), torch.int32, "packed")
-        self._check(self._lib.sv_despeckle_u8(self._h, _ptr(binary), n, H, W, _ptr(out), _ptr(packed) if packed is not None else None,
+        self._check(self._lib.sv_despeckle_u8(self._h, _ptr(binary), n, H, W, _ptr(out), _opt_ptr(packed),
                                                     _stream_ptr()), "sv_despeckle_u8")
         return out if packed is None else packed
 
@@ -336,7 +364,7 @@ class Context:
         _dev_tensor(bits, "bits", torch.int32, self.device, ndim=3)
         _dev_tensor(records, "records", torch.uint8, self.device, ndim=2)
         n, H, wpr = bits.shape
-        if records.dtype != torch.uint8 or records.dim() != 2 or records.shape[0] < n or not records.is_contiguous() or not bits.is_contiguous():
+        if records.shape[0] < n or not records.is_contiguous() or not bits.is_contiguous():
             raise TypeError("records must be a contiguous uint8 [>=n, stride] device tensor")
         self._check(self._lib.sv_pack_sparse_bits(self._h, _ptr(bits), n, H, wpr * 32, _ptr(records), records.shape[1], _stream_ptr()),
                       "sv_pack_sparse_bits")
@@ -454,6 +482,22 @@ class Context:
             self._jpeg_sets[self._jpeg_turn] = cur
         return cur
 
+    @staticmethod
+    def _jpeg_layout(info, base, dense):
+        """Where one image's coefficients lie in a staging buffer, from byte offset `base`: ((masks, offsets, values, capacity in values),
+        the 64-byte aligned end).  dense: plain int16 blocks, no masks or offsets."""
+        ncoef, nb = int(info.coef_count), int(info.coef_count) // 64
+        if dense:
+            return (0, 0, base, ncoef), base + (2 * ncoef + 63) // 64 * 64
+        cap = int(info.sparse_capacity)
+        return (base, base + 8 * nb, base + 12 * nb, cap), base + (12 * nb + 2 * cap + 63) // 64 * 64
+
+    def _jpeg_reconstruct(self, info, db, lay, qoff, out, dense, stream):
+        """Coefficients staged at device address db as _jpeg_layout `lay`, quantisation tables at db + qoff -> BGR in `out`, on `stream`."""
+        p = [C.c_void_p(db + lay[2])] if dense else [C.c_void_p(db + o) for o in lay[:3]]
+        fn = self._lib.sv_jpeg_reconstruct_bgr_u8 if dense else self._lib.sv_jpeg_reconstruct_sparse_bgr_u8
+        self._check(fn(self._h, C.byref(info), *p, C.c_void_p(db + qoff), _ptr(out), out.stride(0), stream), "sv_jpeg_reconstruct")
+
     def imdecode_batch(self, datas, threads=16, dense=False):
         """A batch of JPEG files -> uint8 CUDA tensor [n,H,W,3] when all share a shape, else a list of [H,W,3] tensors.
         Images are Huffman-decoded on `threads` host threads (sv_jpeg_entropy_decode_batch) into pinned memory in the compact
@@ -463,16 +507,11 @@ class Context:
         n = len(datas)
         datas = [bytes(d) for d in datas]
         infos = [host.jpeg_parse(d) for d in datas]
-        lay, total = [], 0                                             # per image: (base, masks, offsets, values, capacity) byte offsets
+        base, lay, total = [], [], 0
         for info in infos:
-            nb = int(info.coef_count) // 64
-            base = total
-            if dense:
-                lay.append((base, 0, 0, base, int(info.coef_count)))
-                total += (2 * int(info.coef_count) + 63) // 64 * 64
-            else:
-                lay.append((base, base, base + 8 * nb, base + 12 * nb, int(info.sparse_capacity)))
-                total += (12 * nb + 2 * int(info.sparse_capacity) + 63) // 64 * 64
+            base.append(total)
+            l, total = self._jpeg_layout(info, total, dense)
+            lay.append(l)
         qoff = total
         total += 384 * n
         pin, dev, ev = self._jpeg_staging(total)
@@ -483,10 +522,10 @@ class Context:
         status = (C.c_int * n)()
         used = (C.c_long * n)()
         if dense:
-            args = (VP(*[pb + l[3] for l in lay]), None, None, None, None, None)
+            args = (VP(*[pb + l[2] for l in lay]), None, None, None, None, None)
         else:
-            args = (None, VP(*[pb + l[1] for l in lay]), VP(*[pb + l[2] for l in lay]), VP(*[pb + l[3] for l in lay]),
-                    (C.c_long * n)(*[l[4] for l in lay]), used)
+            args = (None, VP(*[pb + l[0] for l in lay]), VP(*[pb + l[1] for l in lay]), VP(*[pb + l[2] for l in lay]),
+                    (C.c_long * n)(*[l[3] for l in lay]), used)
         self._check(self._lib.sv_jpeg_entropy_decode_batch(bufs, sizes, n, *args, C.c_void_p(pb + qoff), int(threads), status),
                       "sv_jpeg_entropy_decode_batch")
         same = all((i.out_height, i.out_width) == (infos[0].out_height, infos[0].out_width) for i in infos)
@@ -496,19 +535,14 @@ class Context:
         else:
             outs = [torch.empty((i.out_height, i.out_width, 3), dtype=torch.uint8, device=self.device) for i in infos]
         dev[qoff:qoff + 384 * n].copy_(pin[qoff:qoff + 384 * n], non_blocking=True)
-        lib, stream = self._lib, _stream_ptr()
+        sent, stream = 0, _stream_ptr()
         for i, (info, l) in enumerate(zip(infos, lay)):
-            end = l[3] + 2 * (int(info.coef_count) if dense else used[i])
-            dev[l[0]:end].copy_(pin[l[0]:end], non_blocking=True)
-            q = C.c_void_p(db + qoff + 384 * i)
-            if dense:
-                rc = lib.sv_jpeg_reconstruct_bgr_u8(self._h, C.byref(info), C.c_void_p(db + l[3]), q, _ptr(outs[i]), outs[i].stride(0), stream)
-            else:
-                rc = lib.sv_jpeg_reconstruct_sparse_bgr_u8(self._h, C.byref(info), C.c_void_p(db + l[1]), C.c_void_p(db + l[2]), C.c_void_p(db + l[3]), q,
-                                                           _ptr(outs[i]), outs[i].stride(0), stream)
-            self._check(rc, "sv_jpeg_reconstruct")
+            end = l[2] + 2 * (int(info.coef_count) if dense else used[i])
+            dev[base[i]:end].copy_(pin[base[i]:end], non_blocking=True)
+            self._jpeg_reconstruct(info, db, l, qoff + 384 * i, outs[i], dense, stream)
+            sent += end - base[i]
         ev.record(torch.cuda.current_stream(self.device))
-        self._jpeg_last_bytes = sum((l[3] - l[0]) + 2 * (int(i.coef_count) if dense else used[k]) for k, (i, l) in enumerate(zip(infos, lay))) / max(n, 1)
+        self._jpeg_last_bytes = sent / max(n, 1)
         return out if same else outs
 
     def imdecode(self, data: bytes, threads=1, out=None, dense=False):
@@ -520,30 +554,22 @@ class Context:
         from . import host
         data = bytes(data)
         info = host.jpeg_parse(data)
-        nb, ncoef, cap = int(info.coef_count) // 64, int(info.coef_count), int(info.sparse_capacity)
-        voff = 0 if dense else 12 * nb
-        qoff = (voff + 2 * (ncoef if dense else cap) + 63) // 64 * 64
+        lay, qoff = self._jpeg_layout(info, 0, dense)
         pin, dev, ev = self._jpeg_staging(qoff + 384)
         pb, db = pin.data_ptr(), dev.data_ptr()
-        lib = self._lib
         if dense:
-            self._check(lib.sv_jpeg_entropy_decode(data, len(data), C.c_void_p(pb), C.c_void_p(pb + qoff), int(threads)), "sv_jpeg_entropy_decode")
-            end = 2 * ncoef
+            self._check(self._lib.sv_jpeg_entropy_decode(data, len(data), C.c_void_p(pb), C.c_void_p(pb + qoff), int(threads)), "sv_jpeg_entropy_decode")
+            end = 2 * int(info.coef_count)
         else:
             used = C.c_long()
-            self._check(lib.sv_jpeg_entropy_decode_sparse(data, len(data), C.c_void_p(pb), C.c_void_p(pb + 8 * nb), C.c_void_p(pb + voff), cap, C.byref(used),
-                                                            C.c_void_p(pb + qoff), int(threads)), "sv_jpeg_entropy_decode_sparse")
-            end = voff + 2 * used.value
+            self._check(self._lib.sv_jpeg_entropy_decode_sparse(data, len(data), *[C.c_void_p(pb + o) for o in lay[:3]], lay[3], C.byref(used),
+                                                                C.c_void_p(pb + qoff), int(threads)), "sv_jpeg_entropy_decode_sparse")
+            end = lay[2] + 2 * used.value
         dev[:end].copy_(pin[:end], non_blocking=True)
         dev[qoff:qoff + 384].copy_(pin[qoff:qoff + 384], non_blocking=True)
         if out is None:
             out = torch.empty((info.out_height, info.out_width, 3), dtype=torch.uint8, device=self.device)
-        if dense:
-            rc = lib.sv_jpeg_reconstruct_bgr_u8(self._h, C.byref(info), C.c_void_p(db), C.c_void_p(db + qoff), _ptr(out), out.stride(0), _stream_ptr())
-        else:
-            rc = lib.sv_jpeg_reconstruct_sparse_bgr_u8(self._h, C.byref(info), C.c_void_p(db), C.c_void_p(db + 8 * nb), C.c_void_p(db + voff), C.c_void_p(db + qoff),
-                                                       _ptr(out), out.stride(0), _stream_ptr())
-        self._check(rc, "sv_jpeg_reconstruct")
+        self._jpeg_reconstruct(info, db, lay, qoff, out, dense, _stream_ptr())
         ev.record(torch.cuda.current_stream(self.device))
         return out
 
@@ -563,24 +589,29 @@ class Context:
         self._check(self._lib.sv_preprocess_cells_u8(self._h, _ptr(cells), cells.shape[0], _ptr(out), _stream_ptr()), "sv_preprocess_cells_u8")
         return out
 
-    def cnn_forward(self, x, want_digits=False, glue=0):
-        """x f32 [B,1,28,28], or u8 [B,28,28] cells with the run.py glue fused in (glue=GLUE_NORMALIZE: invert+normalise;
-        GLUE_RUNPY: preprocess_cell (CLAHE + adaptive threshold) first) -> logits [B,10] (, digits, conf)."""
+    def _cnn_args(self, x, want_digits):
+        """The argument of a CNN forward, checked: x f32 [B,1,28,28] or u8 [B,28,28] cells on this device -> (x contiguous, logits [B,10],
+        digits u8 [B], conf f32 [B]); digits and conf are None unless wanted."""
         _dev_tensor(x, "x", (torch.uint8, torch.float32), self.device)
         if x.dtype == torch.uint8:
             _dev_tensor(x, "x", torch.uint8, self.device, shape=(None, 28, 28))
         elif not (x.dim() in (3, 4) and tuple(x.shape[-2:]) == (28, 28) and (x.dim() == 3 or x.shape[1] == 1)):
             raise ValueError(f"x must have shape [B,1,28,28], got {list(x.shape)}")
-        x = x.contiguous()
         B = x.shape[0]
         logits = torch.empty((B, 10), dtype=torch.float32, device=self.device)
         digits = torch.empty((B,), dtype=torch.uint8, device=self.device) if want_digits else None
         conf = torch.empty((B,), dtype=torch.float32, device=self.device) if want_digits else None
-        dg, cf = (_ptr(digits) if want_digits else None), (_ptr(conf) if want_digits else None)
+        return x.contiguous(), logits, digits, conf
+
+    def cnn_forward(self, x, want_digits=False, glue=0):
+        """x f32 [B,1,28,28], or u8 [B,28,28] cells with the run.py glue fused in (glue=GLUE_NORMALIZE: invert+normalise;
+        GLUE_RUNPY: preprocess_cell (CLAHE + adaptive threshold) first) -> logits [B,10] (, digits, conf)."""
+        x, logits, digits, conf = self._cnn_args(x, want_digits)
+        B = x.shape[0]
         if x.dtype == torch.uint8:
-            rc = self._lib.sv_cnn_forward_cells_u8(self._h, _ptr(x), B, int(glue), _ptr(logits), dg, cf, _stream_ptr())
+            rc = self._lib.sv_cnn_forward_cells_u8(self._h, _ptr(x), B, int(glue), _ptr(logits), _opt_ptr(digits), _opt_ptr(conf), _stream_ptr())
         else:
-            rc = self._lib.sv_cnn_forward_f32(self._h, _ptr(x), B, _ptr(logits), dg, cf, _stream_ptr())
+            rc = self._lib.sv_cnn_forward_f32(self._h, _ptr(x), B, _ptr(logits), _opt_ptr(digits), _opt_ptr(conf), _stream_ptr())
         self._check(rc, "sv_cnn_forward")
         return (logits, digits, conf) if want_digits else logits
 
@@ -588,24 +619,15 @@ class Context:
         """DigitCNNv3.forward (ml/model_v3.py): x f32 [B,1,28,28], or u8 [B,28,28] cells with the run_v2.py glue fused in (as cnn_forward)
         -> logits [B,10]; with want_digits (logits, digits, conf), conf = softmax(logits / temperature)[digit]; with want_features the
         128 pooled features [B,128] come last (f32 input only)."""
-        _dev_tensor(x, "x", (torch.uint8, torch.float32), self.device)
-        if x.dtype == torch.uint8:
-            _dev_tensor(x, "x", torch.uint8, self.device, shape=(None, 28, 28))
-            if want_features:
-                raise ValueError("want_features needs f32 input (sv_cnn3_forward_f32)")
-        elif not (x.dim() in (3, 4) and tuple(x.shape[-2:]) == (28, 28) and (x.dim() == 3 or x.shape[1] == 1)):
-            raise ValueError(f"x must have shape [B,1,28,28], got {list(x.shape)}")
-        x = x.contiguous()
+        x, logits, digits, conf = self._cnn_args(x, want_digits)
         B = x.shape[0]
-        logits = torch.empty((B, 10), dtype=torch.float32, device=self.device)
-        digits = torch.empty((B,), dtype=torch.uint8, device=self.device) if want_digits else None
-        conf = torch.empty((B,), dtype=torch.float32, device=self.device) if want_digits else None
+        if want_features and x.dtype == torch.uint8:
+            raise ValueError("want_features needs f32 input (sv_cnn3_forward_f32)")
         feats = torch.empty((B, 128), dtype=torch.float32, device=self.device) if want_features else None
-        dg, cf = (_ptr(digits) if want_digits else None), (_ptr(conf) if want_digits else None)
         if x.dtype == torch.uint8:
-            rc = self._lib.sv_cnn3_forward_cells_u8(self._h, _ptr(x), B, int(glue), _ptr(logits), dg, cf, _stream_ptr())
+            rc = self._lib.sv_cnn3_forward_cells_u8(self._h, _ptr(x), B, int(glue), _ptr(logits), _opt_ptr(digits), _opt_ptr(conf), _stream_ptr())
         else:
-            rc = self._lib.sv_cnn3_forward_f32(self._h, _ptr(x), B, _ptr(logits), _ptr(feats) if want_features else None, dg, cf, _stream_ptr())
+            rc = self._lib.sv_cnn3_forward_f32(self._h, _ptr(x), B, _ptr(logits), _opt_ptr(feats), _opt_ptr(digits), _opt_ptr(conf), _stream_ptr())
         self._check(rc, "sv_cnn3_forward")
         out = (logits, digits, conf) if want_digits else (logits,)
         if want_features:
@@ -613,8 +635,8 @@ class Context:
         return out if len(out) > 1 else logits
 
     # ---- whole path ---------------------------------------------------------------------------
-    def frames_to_digits(self, frames, minv_dev, out=None, keep_cells=False, glue=0):
-        """frames u8 [n,H,W,3], minv_dev f64 [n,3,3] on device -> dict(logits [n,81,10], digits [n,81], conf [n,81])."""
+    def _frames_to_digits(self, entry, frames, minv_dev, out, keep_cells, glue):
+        """frames_to_digits through the library's `entry`: sv_frames_to_digits or sv_frames_to_digits_v3."""
         frames, pitch, fstride = _frame_layout(frames, self.device)
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
         minv_dev = self._minv(minv_dev, n)
@@ -624,28 +646,17 @@ class Context:
                    "conf": torch.empty((n, 81), dtype=torch.float32, device=self.device)}
             if keep_cells:
                 out["cells"] = torch.empty((n, 81, 28, 28), dtype=torch.uint8, device=self.device)
-        cells = out.get("cells")
-        self._check(self._lib.sv_frames_to_digits(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(minv_dev), int(glue),
-                                                        _ptr(cells) if cells is not None else None, _ptr(out["logits"]), _ptr(out["digits"]),
-                                                        _ptr(out["conf"]), _stream_ptr()), "sv_frames_to_digits")
+        self._check(getattr(self._lib, entry)(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(minv_dev), int(glue), _opt_ptr(out.get("cells")),
+                                              _ptr(out["logits"]), _ptr(out["digits"]), _ptr(out["conf"]), _stream_ptr()), entry)
         return out
+
+    def frames_to_digits(self, frames, minv_dev, out=None, keep_cells=False, glue=0):
+        """frames u8 [n,H,W,3], minv_dev f64 [n,3,3] on device -> dict(logits [n,81,10], digits [n,81], conf [n,81])."""
+        return self._frames_to_digits("sv_frames_to_digits", frames, minv_dev, out, keep_cells, glue)
 
     def frames_to_digits_v3(self, frames, minv_dev, out=None, keep_cells=False, glue=0):
         """frames_to_digits with the DigitCNNv3 forward (load_state_dict_v3): same arguments, same dict."""
-        frames, pitch, fstride = _frame_layout(frames, self.device)
-        n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
-        minv_dev = self._minv(minv_dev, n)
-        if out is None:
-            out = {"logits": torch.empty((n, 81, 10), dtype=torch.float32, device=self.device),
-                   "digits": torch.empty((n, 81), dtype=torch.uint8, device=self.device),
-                   "conf": torch.empty((n, 81), dtype=torch.float32, device=self.device)}
-            if keep_cells:
-                out["cells"] = torch.empty((n, 81, 28, 28), dtype=torch.uint8, device=self.device)
-        cells = out.get("cells")
-        self._check(self._lib.sv_frames_to_digits_v3(self._h, _ptr(frames), n, H, W, pitch, fstride, _ptr(minv_dev), int(glue),
-                                                           _ptr(cells) if cells is not None else None, _ptr(out["logits"]), _ptr(out["digits"]),
-                                                           _ptr(out["conf"]), _stream_ptr()), "sv_frames_to_digits_v3")
-        return out
+        return self._frames_to_digits("sv_frames_to_digits_v3", frames, minv_dev, out, keep_cells, glue)
 
     # ---- quality gate (cv/grid_quality.py) ------------------------------------------------------
     def frame_quality_stats(self, frames, out=None):
@@ -653,23 +664,12 @@ class Context:
         hist int32 [n,256]) on device: the integer sums of cv2.Laplacian(gray, CV_64F) and its square, and calcHist of gray
         (sv_frame_quality_stats_u8).  out: optional tuple of three such tensors to write into."""
         _dev_tensor(frames, "frames", torch.uint8, self.device, ndim=(3, 4))
-        if frames.dim() == 4:
-            frames, pitch, fstride = _frame_layout(frames, self.device)
-            ch = 3
-        else:
-            n, H, W = frames.shape
-            st = frames.stride()
-            if not (st[2] == 1 and st[1] >= W and (n == 1 or st[0] >= st[1] * (H - 1) + W)):
-                frames = frames.contiguous()
-                st = frames.stride()
-            pitch, fstride, ch = st[1], (st[0] if n > 1 else st[1] * H), 1
+        ch = 3 if frames.dim() == 4 else 1
+        frames, pitch, fstride = _batch_layout(frames, self.device, "frames", ch)
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
-        if out is None:
-            out = (torch.empty((n,), dtype=torch.int64, device=self.device), torch.empty((n,), dtype=torch.int64, device=self.device),
-                   torch.empty((n, 256), dtype=torch.int32, device=self.device))
-        else:
-            out = (self._out(out[0], (n,), torch.int64, "lap_sum"), self._out(out[1], (n,), torch.int64, "lap_sqsum"),
-                   self._out(out[2], (n, 256), torch.int32, "hist"))
+        out = out or (None, None, None)
+        out = (self._out(out[0], (n,), torch.int64, "lap_sum"), self._out(out[1], (n,), torch.int64, "lap_sqsum"),
+               self._out(out[2], (n, 256), torch.int32, "hist"))
         self._check(self._lib.sv_frame_quality_stats_u8(self._h, _ptr(frames), n, H, W, pitch, fstride, ch, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
                                                         _stream_ptr()), "sv_frame_quality_stats_u8")
         return out
@@ -679,20 +679,14 @@ class Context:
         corners_to_minv_batch(corners, 450) on device -> counts int32 [n,20] on device: the warped pixels > 0 of compute_completeness's
         bands, band 2i = grid row line i, 2i+1 = grid column line i (sv_grid_line_coverage_u8 / _bits)."""
         x = _dev_tensor(binary_or_bits, "binary_or_bits", (torch.uint8, torch.int32), self.device, ndim=3)
-        n = x.shape[0]
+        n, H, W = x.shape
         minv_dev = self._minv(minv_dev, n)
-        out = torch.empty((n, 20), dtype=torch.int32, device=self.device) if out is None else self._out(out, (n, 20), torch.int32, "out")
+        out = self._out(out, (n, 20), torch.int32, "out")
         if x.dtype == torch.uint8:
-            H, W = x.shape[1], x.shape[2]
-            st = x.stride()
-            if not (st[2] == 1 and st[1] >= W and (n == 1 or st[0] >= st[1] * (H - 1) + W)):
-                x = x.contiguous()
-                st = x.stride()
-            rc = self._lib.sv_grid_line_coverage_u8(self._h, _ptr(x), n, H, W, st[1], (st[0] if n > 1 else st[1] * H), _ptr(minv_dev), _ptr(out),
-                                                    _stream_ptr())
+            x, pitch, fstride = _plane_layout(x, self.device, "binary_or_bits")
+            rc = self._lib.sv_grid_line_coverage_u8(self._h, _ptr(x), n, H, W, pitch, fstride, _ptr(minv_dev), _ptr(out), _stream_ptr())
         else:
-            x = x.contiguous()
-            rc = self._lib.sv_grid_line_coverage_bits(self._h, _ptr(x), n, x.shape[1], x.shape[2] * 32, _ptr(minv_dev), _ptr(out), _stream_ptr())
+            rc = self._lib.sv_grid_line_coverage_bits(self._h, _ptr(x.contiguous()), n, H, W * 32, _ptr(minv_dev), _ptr(out), _stream_ptr())
         self._check(rc, "sv_grid_line_coverage")
         return out
 
@@ -701,73 +695,54 @@ class Context:
     MORPH_DILATE, MORPH_ERODE, MORPH_CLOSE, MORPH_OPEN = 0, 1, 2, 3
     SHAPE_RECT, SHAPE_ELLIPSE = 0, 1
 
-    def _planes_call(self, fn, what, x, *args, name="gray"):
-        """fn(ctx, x, n, H, W, pitch, stride, *args, stream) with x laid out by _plane_layout."""
+    def _planes_call(self, entry, x, *args, second=None, image=True, counts=False, name="gray"):
+        """The library's entry(ctx, x, n, H, W, pitch, stride, [second,] *args, [image,] [counts,] stream) with x laid out by _plane_layout and
+        the outputs allocated here: image u8 [n,H,W], counts int32 [n].  second: (tensor, name) of a second image that the kernels read
+        densely: u8, same [n,H,W] as x.  Returns the output, or the tuple of both."""
         x, pitch, fstride = _plane_layout(x, self.device, name)
         n, H, W = x.shape
-        self._check(fn(self._h, _ptr(x), n, H, W, pitch, fstride, *args, _stream_ptr()), what)
-
-    def _dense_like(self, x, name):
-        """A second image argument the kernels read densely: u8, same [n,H,W] as the first."""
-        return _dev_tensor(x[1], name, torch.uint8, self.device, shape=tuple(x[0].shape)).contiguous()
+        if second is not None:
+            args = (_ptr(_dev_tensor(second[0], second[1], torch.uint8, self.device, shape=(n, H, W)).contiguous()),) + args
+        outs = ([torch.empty((n, H, W), dtype=torch.uint8, device=self.device)] if image else []) + \
+               ([torch.empty((n,), dtype=torch.int32, device=self.device)] if counts else [])
+        self._check(getattr(self._lib, entry)(self._h, _ptr(x), n, H, W, pitch, fstride, *args, *[_ptr(t) for t in outs], _stream_ptr()), entry)
+        return outs[0] if len(outs) == 1 else tuple(outs)
 
     def morphology(self, gray, op, shape, ksize):
         """cv2.dilate / erode / morphologyEx(CLOSE | OPEN) with getStructuringElement(shape, (ksize, ksize)) (sv_morphology_u8)."""
-        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
-        self._planes_call(self._lib.sv_morphology_u8, "sv_morphology_u8", gray, int(op), int(shape), int(ksize), _ptr(out))
-        return out
+        return self._planes_call("sv_morphology_u8", gray, int(op), int(shape), int(ksize))
 
     def box_mean(self, gray, ksize):
         """cv2.blur(gray, (ksize, ksize)) on u8 (sv_box_mean_u8)."""
-        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
-        self._planes_call(self._lib.sv_box_mean_u8, "sv_box_mean_u8", gray, int(ksize), _ptr(out))
-        return out
+        return self._planes_call("sv_box_mean_u8", gray, int(ksize))
 
     def gaussian_blur21(self, gray):
         """cv2.GaussianBlur(gray, (21, 21), 0) on u8 (sv_gaussian_blur21_u8)."""
-        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
-        self._planes_call(self._lib.sv_gaussian_blur21_u8, "sv_gaussian_blur21_u8", gray, _ptr(out))
-        return out
+        return self._planes_call("sv_gaussian_blur21_u8", gray)
 
     def divide_normalize(self, gray, background):
         """(gray / max(background, 1) * 255) in float32, clipped and truncated to u8 (sv_divide_normalize_u8)."""
-        background = self._dense_like((gray, background), "background")
-        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
-        self._planes_call(self._lib.sv_divide_normalize_u8, "sv_divide_normalize_u8", gray, _ptr(background), _ptr(out))
-        return out
+        return self._planes_call("sv_divide_normalize_u8", gray, second=(background, "background"))
 
     def clahe(self, gray, clip_limit=2.0, tiles=(8, 8)):
         """cv2.createCLAHE(clip_limit, tiles).apply(gray), tiles = (tiles_x, tiles_y), any image size (sv_clahe_u8)."""
-        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
-        self._planes_call(self._lib.sv_clahe_u8, "sv_clahe_u8", gray, float(clip_limit), int(tiles[0]), int(tiles[1]), _ptr(out))
-        return out
+        return self._planes_call("sv_clahe_u8", gray, float(clip_limit), int(tiles[0]), int(tiles[1]))
 
     def threshold_sauvola(self, gray, window=25, k=0.2):
         """Sauvola's threshold from exact integer window sums (sv_threshold_sauvola_u8) -> u8 {0,255}."""
-        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
-        self._planes_call(self._lib.sv_threshold_sauvola_u8, "sv_threshold_sauvola_u8", gray, int(window), float(k), _ptr(out))
-        return out
+        return self._planes_call("sv_threshold_sauvola_u8", gray, int(window), float(k))
 
     def threshold_count(self, gray, thresh, inv=False):
         """gray > thresh ? 255 : 0 (inv: ? 0 : 255) -> (mask u8 [n,H,W], count int32 [n] of the pixels set), sv_threshold_count_u8."""
-        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
-        counts = torch.empty((gray.shape[0],), dtype=torch.int32, device=self.device)
-        self._planes_call(self._lib.sv_threshold_count_u8, "sv_threshold_count_u8", gray, int(thresh), int(bool(inv)), _ptr(out), _ptr(counts))
-        return out, counts
+        return self._planes_call("sv_threshold_count_u8", gray, int(thresh), int(bool(inv)), counts=True)
 
     def shadow_mask(self, gray, local_mean, delta=-30):
         """int(gray) - int(local_mean) < delta ? 255 : 0 -> (mask u8 [n,H,W], count int32 [n]), sv_shadow_mask_u8."""
-        local_mean = self._dense_like((gray, local_mean), "local_mean")
-        out = torch.empty(tuple(gray.shape), dtype=torch.uint8, device=self.device)
-        counts = torch.empty((gray.shape[0],), dtype=torch.int32, device=self.device)
-        self._planes_call(self._lib.sv_shadow_mask_u8, "sv_shadow_mask_u8", gray, _ptr(local_mean), int(delta), _ptr(out), _ptr(counts))
-        return out, counts
+        return self._planes_call("sv_shadow_mask_u8", gray, int(delta), second=(local_mean, "local_mean"), counts=True)
 
     def count_nonzero(self, img):
         """Pixels != 0 per frame -> int32 [n] (sv_count_nonzero_u8)."""
-        counts = torch.empty((img.shape[0],), dtype=torch.int32, device=self.device)
-        self._planes_call(self._lib.sv_count_nonzero_u8, "sv_count_nonzero_u8", img, _ptr(counts), name="img")
-        return counts
+        return self._planes_call("sv_count_nonzero_u8", img, image=False, counts=True, name="img")
 
 
 _default = {}

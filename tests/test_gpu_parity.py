@@ -304,6 +304,21 @@ def test_error_behaviour_on_gpu(ctx):
     fresh.close()
 
 
+def test_frame_batches_end_at_the_grid_limit(ctx):
+    """Every frame-batch entry takes at most 65535 frames (the launch grid's z limit) and says so as a bad shape, sv_gray_u8 included;
+    65535 one-pixel frames still run.  The buffers are full size, so nothing depends on the check for its bounds."""
+    from sudoku_vision_amd._native import NativeError
+    rs = np.random.RandomState(3)
+    px = rs.randint(0, 256, (65536, 1, 1, 3)).astype(np.uint8)
+    frames = torch.from_numpy(px).cuda()
+    for call in (ctx.gray, ctx.preprocess):
+        with pytest.raises(NativeError, match="SV_ERR_BAD_ARG.*bad shape"):
+            call(frames)
+    got = ctx.gray(frames[:65535]).cpu().numpy()
+    want = np.stack([o.gray(px[i]) for i in range(0, 65535, 257)])
+    assert (got[::257] == want).all()
+
+
 def test_tiny_and_odd_images(ctx):
     """Smallest shapes the reference's functions accept: every border path at once."""
     rs = np.random.RandomState(31)

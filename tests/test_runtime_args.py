@@ -1,6 +1,10 @@
 """CPU: the argument checks of runtime.Context.  The library sees only raw pointers, so every tensor argument is checked in Python
 (runtime._dev_tensor) before any library call, and views are passed with their real row stride or made contiguous
-(runtime._image_layout, runtime._frame_layout).  No GPU: tensors stay on the CPU and the expected device is cuda:0."""
+(runtime._image_layout, runtime._frame_layout).  No GPU: tensors stay on the CPU and the expected device is cuda:0.
+Also the host-side helpers the drop-ins share: the array conversion (runtime._to_dev / _back) and the state-dict blob (runtime._state_blob)."""
+import types
+
+import numpy as np
 import pytest
 import torch
 
@@ -67,6 +71,32 @@ def test_frame_layout_checks_device_dtype_and_shape():
     assert (pitch, stride) == (18, 72) and v.data_ptr() == f.data_ptr()
 
 
+def test_plane_and_frame_layout_are_one_rule():
+    """Padded rows and frame gaps pass through with their strides; one frame has stride pitch * H; anything else is copied."""
+    g = torch.arange(3 * 6 * 10, dtype=torch.int32).to(torch.uint8).reshape(3, 6, 10)
+    v, pitch, stride = rt._plane_layout(g[:, 1:5, 2:9], CPU)             # cropped rows and columns: read in place
+    assert (pitch, stride) == (10, 60) and v.data_ptr() == g[:, 1:5, 2:9].data_ptr()
+    v, pitch, stride = rt._plane_layout(g[::2], CPU)                     # every other frame: a gap
+    assert (pitch, stride) == (10, 120) and v.data_ptr() == g.data_ptr()
+    v, pitch, stride = rt._plane_layout(g[1:2, :, :7], CPU)              # one frame
+    assert (pitch, stride) == (10, 60)
+    v, pitch, stride = rt._plane_layout(g[:, :, ::2], CPU)               # every other column: copied
+    assert v.is_contiguous() and (pitch, stride) == (5, 30) and torch.equal(v, g[:, :, ::2])
+    v, pitch, stride = rt._plane_layout(g.permute(0, 2, 1), CPU)            # transposed: copied
+    assert v.is_contiguous() and (pitch, stride) == (6, 60)
+    f = torch.zeros((2, 4, 6, 3), dtype=torch.uint8)
+    v, pitch, stride = rt._frame_layout(f[:, :, ::2], CPU)                  # every other pixel: copied
+    assert v.is_contiguous() and (pitch, stride) == (9, 36)
+    v, pitch, stride = rt._frame_layout(torch.zeros((2, 4, 6, 4), dtype=torch.uint8)[..., :3], CPU)   # BGRA's first three: copied
+    assert v.is_contiguous() and (pitch, stride) == (18, 72)
+    with pytest.raises(TypeError, match="cuda:0"):
+        rt._plane_layout(g, CUDA0)
+    with pytest.raises(ValueError):
+        rt._plane_layout(g[0], CPU)
+    with pytest.raises(TypeError):
+        rt._plane_layout(g.float(), CPU)
+
+
 class _NoLibrary:
     """Stands in for the native library: any call is a failure (the checks must come first)."""
 
@@ -99,6 +129,11 @@ def test_every_method_rejects_host_tensors_before_the_library(ctx):
         lambda: ctx.cnn_forward(cells), lambda: ctx.cnn_forward(torch.zeros((5, 1, 28, 28))), lambda: ctx.softmax_topk(torch.zeros((5, 10))),
         lambda: ctx.frames_to_digits(frames, minv), lambda: ctx.frame_quality_stats(frames), lambda: ctx.frame_quality_stats(gray),
         lambda: ctx.grid_line_coverage(gray, minv), lambda: ctx.grid_line_coverage(torch.zeros((2, 20, 1), dtype=torch.int32), minv),
+        lambda: ctx.cnn3_forward(cells), lambda: ctx.cnn3_forward(torch.zeros((5, 1, 28, 28))), lambda: ctx.frames_to_digits_v3(frames, minv),
+        lambda: ctx.preprocess_mm(frames), lambda: ctx.morphology(gray, ctx.MORPH_CLOSE, ctx.SHAPE_RECT, 3), lambda: ctx.box_mean(gray, 5),
+        lambda: ctx.gaussian_blur21(gray), lambda: ctx.divide_normalize(gray, gray), lambda: ctx.clahe(gray),
+        lambda: ctx.threshold_sauvola(gray), lambda: ctx.threshold_count(gray, 128), lambda: ctx.shadow_mask(gray, gray),
+        lambda: ctx.count_nonzero(gray), lambda: ctx.copy_to_pinned(gray, torch.zeros_like(gray)),
     ]
     for i, call in enumerate(calls):
         with pytest.raises(TypeError, match="cuda:0"):
@@ -112,6 +147,28 @@ def test_minv_on_the_host_is_rejected(ctx, monkeypatch):
         ctx.warp_cells(_u8(2, 20, 24, 3), torch.eye(3, dtype=torch.float64)[None].repeat(2, 1, 1))
     with pytest.raises(TypeError, match="minv_dev"):
         ctx.frames_to_digits(_u8(2, 20, 24, 3), torch.eye(3, dtype=torch.float64)[None].repeat(2, 1, 1))
+
+
+def test_both_images_of_a_two_image_method_are_checked(ctx, monkeypatch):
+    """divide_normalize and shadow_mask read a second image.  With both on the host the first argument is the one reported; with the first
+    passing a stubbed layout check (which records that it was reached) the second is."""
+    host = _u8(2, 20, 24)
+    with pytest.raises(TypeError, match="gray must be on cuda:0"):
+        ctx.divide_normalize(host, host)
+    with pytest.raises(TypeError, match="gray must be on cuda:0"):
+        ctx.shadow_mask(host, host)
+    reached = []
+
+    def first_passes(x, device, name="gray"):
+        reached.append(name)
+        return x, 24, 480
+
+    monkeypatch.setattr(rt, "_plane_layout", first_passes)
+    with pytest.raises(TypeError, match="background must be on cuda:0"):
+        ctx.divide_normalize(host, host)
+    with pytest.raises(TypeError, match="local_mean must be on cuda:0"):
+        ctx.shadow_mask(host, host)
+    assert reached == ["gray", "gray"]
 
 
 def test_cell_shapes_are_checked_first(ctx, monkeypatch):
@@ -137,3 +194,85 @@ def test_cell_shapes_are_checked_first(ctx, monkeypatch):
         ctx.warp_perspective(_u8(20, 24, 3), torch.eye(3, dtype=torch.float32), 64)
     with pytest.raises(TypeError):
         ctx.resize_linear(torch.zeros((20, 24), dtype=torch.int16), (28, 28))
+
+
+# ---- the drop-ins' array conversion ------------------------------------------------------------------------------------
+@pytest.fixture
+def cpu_ctx():
+    """Stands in for a Context in _to_dev, which reads its device only: uploads stay on the CPU."""
+    return types.SimpleNamespace(device=CPU)
+
+
+def test_to_dev_takes_numpy_uint8_and_gives_numpy_back(cpu_ctx):
+    a = np.arange(24, dtype=np.uint8).reshape(4, 6)
+    t, was_tensor = rt._to_dev(a, cpu_ctx)
+    assert isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.device == CPU and was_tensor is False
+    assert tuple(t.shape) == (4, 6) and (t.numpy() == a).all()
+    back = rt._back(t, was_tensor)
+    assert isinstance(back, np.ndarray) and back.dtype == np.uint8 and (back == a).all()
+    assert rt._back(t, True) is t                                      # a tensor argument gets the tensor itself back
+    t, _ = rt._to_dev(a[:, ::2], cpu_ctx)                              # a view: its values, dense
+    assert (t.numpy() == a[:, ::2]).all()
+
+
+def test_to_dev_aliases_a_contiguous_numpy_input(cpu_ctx):
+    a = np.zeros((4, 6), np.uint8)
+    t, _ = rt._to_dev(a, cpu_ctx)
+    a[2, 3] = 77
+    assert int(t[2, 3]) == 77 and t.data_ptr() == a.ctypes.data
+
+
+@pytest.mark.parametrize("bad", [np.zeros((4, 6), np.float32), np.zeros((4, 6), np.int8), np.zeros((4, 6), np.uint16), [[0.5, 1.5]]])
+def test_to_dev_rejects_arrays_that_are_not_uint8(cpu_ctx, bad):
+    with pytest.raises(TypeError, match="uint8"):
+        rt._to_dev(bad, cpu_ctx)
+
+
+def test_to_dev_rejects_cpu_and_float_tensors(cpu_ctx):
+    with pytest.raises(TypeError, match="CUDA"):
+        rt._to_dev(torch.zeros((4, 6), dtype=torch.uint8), cpu_ctx)    # a CPU tensor, even where the context's device is the CPU
+    with pytest.raises(TypeError, match="uint8"):
+        rt._to_dev(torch.zeros((4, 6)), cpu_ctx)
+    with pytest.raises(TypeError):
+        rt._to_dev(torch.zeros((4, 6), dtype=torch.uint8), types.SimpleNamespace(device=CUDA0))
+
+
+# ---- state_dict -> blob ------------------------------------------------------------------------------------------------
+def test_state_blob_of_the_v1_model_is_the_tensors_in_layout_order():
+    import cnn_oracle
+    sd = cnn_oracle.random_state_dict(1234)
+    blob = rt._state_blob(sd, rt._V1_LAYOUT, "DigitCNN")
+    assert blob.dtype == np.float32 and blob.shape == (421642,)
+    assert [k for k, _ in rt._V1_LAYOUT] == ["conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias"]
+    at = 0
+    for k, shape in rt._V1_LAYOUT:
+        v = np.asarray(sd[k].detach().cpu().numpy() if isinstance(sd[k], torch.Tensor) else sd[k], np.float32)
+        assert tuple(v.shape) == shape
+        assert (blob[at:at + v.size] == v.reshape(-1)).all(), k
+        at += v.size
+    assert at == 421642
+    as_arrays = {k: np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, np.float64) for k, v in sd.items()}
+    assert (rt._state_blob(as_arrays, rt._V1_LAYOUT, "DigitCNN") == blob).all()      # arrays of another dtype: converted to f32
+
+
+def test_state_blob_names_the_key_of_a_wrong_shape():
+    import cnn_oracle
+    sd = dict(cnn_oracle.random_state_dict(1))
+    sd["fc1.bias"] = torch.zeros(127)
+    with pytest.raises(ValueError, match="fc1.bias"):
+        rt._state_blob(sd, rt._V1_LAYOUT, "DigitCNN")
+    sd["fc1.bias"] = torch.zeros(128, 1)
+    with pytest.raises(ValueError, match="fc1.bias"):
+        rt._state_blob(sd, rt._V1_LAYOUT, "DigitCNN")
+
+
+@pytest.mark.parametrize("use_se", [True, False])
+def test_state_blob_misses_a_v3_key(use_se):
+    layout = rt.v3_layout(use_se)
+    sd = {k: np.zeros(shape, np.float32) for k, shape in layout}
+    assert rt._state_blob(sd, layout, "DigitCNNv3").size == sum(int(np.prod(shape)) for _, shape in layout)
+    for gone in ("temperature", "layer2.shortcut.1.running_var", "fc.bias"):
+        with pytest.raises(KeyError, match=gone.replace(".", r"\.")):
+            rt._state_blob({k: v for k, v in sd.items() if k != gone}, layout, "DigitCNNv3")
+    with pytest.raises(KeyError):
+        rt._state_blob({}, rt._V1_LAYOUT, "DigitCNN")
