@@ -361,6 +361,38 @@ int sv_frames_to_digits_v3(sv_ctx *ctx, const uint8_t *frames /*dev*/, int n, in
 int sv_softmax_topk_f32(sv_ctx *ctx, const float *logits /*dev, B*10*/, long B, int k,
                         uint8_t *index /*dev, B*k*/, float *prob /*dev, B*k*/, void *stream);
 
+/* The validation and correction stage of pipeline/run_v2.py:344-371 for n frames in one launch: validate_predictions
+ * (pipeline/validator.py:69-159) on the 81 cells of each frame and, where they break the sudoku rules, ConflictResolver.resolve
+ * (pipeline/conflict_resolver.py:58-286): a beam search over the cells' alternatives for the cheapest <= max_corrections corrections.
+ * Exact: every output equals the reference's; the f64 score equals it to the bit whenever no confidence of a filled cell or of a
+ * qualifying alternative is below 2^-18 (then the sum of 81 of them is exact in a double in any order; softmax top-1 values and
+ * alternatives that passed min_alt_conf = 0.1 always are), and is otherwise within rounding of it.
+ * index, prob: the output of sv_softmax_topk_f32 over n*81 cells; per cell digit = index[.,0] (0 = empty), confidence = prob[.,0],
+ * alternatives = slots 1..k-1.  Classes are 0..9 (any other value is read as an empty cell / no alternative), probabilities finite
+ * and >= 0.  run_v2 passes beam_width 5, max_corrections 3, and min_alt_conf is ConflictResolver's default 0.1 (:65).
+ * acceptance_rule != 0 applies pipeline/run_v2.py:365 on the device: a repair that neither succeeded nor left fewer conflicts than
+ * the input had is dropped, and digits, conf, index_out, prob_out, num_conflicts_after, conflict_count, n_corrections, corr_cells and
+ * corr_conf then describe the input (no corrections); success, paths_explored and score stay what the search reported.
+ * Outputs, each may be NULL; index_out / prob_out may be index / prob themselves:
+ *   digits, conf [n*81]              the resulting cells: corrected when success, else the best attempt, or the input when no
+ *                                    alternative qualified (ResolutionResult.cells); callers apply run_v2.py:365 to accept them
+ *   index_out, prob_out [n*81*k]     the same cells with their alternatives as _apply_correction (:225-244) leaves them: the old digit
+ *                                    first, then the others; a slot the correction emptied holds index 255, prob 0
+ *   success [n]                      ResolutionResult.success
+ *   num_conflicts_before/_after [n]  ValidationResult.num_conflicts of the input and of the resulting cells
+ *   conflict_count [n*81]            how many conflicts of the resulting cells name each cell (0-3); != 0: cells_in_conflict
+ *   n_corrections [n], corr_cells [n*3*3] = (cell, old digit, new digit), corr_conf [n*3*2] = (old confidence, alternative's
+ *                                    confidence): corrections_made in order; unused entries are 0
+ *   paths_explored [n], score [n]    as the reference reports them (score 0 unless a correction made the frame valid)
+ * One wave per frame; a frame's result does not depend on the rest of the batch.  1 <= k <= 4, 1 <= beam_width <= 6,
+ * 0 <= max_corrections <= 3, otherwise SV_ERR_UNSUPPORTED; n == 0 is SV_OK. */
+int sv_resolve_conflicts(sv_ctx *ctx, const uint8_t *index /*dev, n*81*k*/, const float *prob /*dev, n*81*k*/, long n, int k,
+                         int beam_width, int max_corrections, double min_alt_conf, int acceptance_rule, uint8_t *digits /*dev*/, float *conf /*dev*/,
+                         uint8_t *index_out /*dev*/, float *prob_out /*dev*/, uint8_t *success /*dev*/,
+                         int32_t *num_conflicts_before /*dev*/, int32_t *num_conflicts_after /*dev*/, uint8_t *conflict_count /*dev*/,
+                         uint8_t *n_corrections /*dev*/, uint8_t *corr_cells /*dev*/, float *corr_conf /*dev*/,
+                         int32_t *paths_explored /*dev*/, double *score /*dev*/, void *stream);
+
 /* ---- N4: JPEG front end -- what cv2.imread does before the path starts (pipeline/run.py:250, pipeline/run_v2.py:267,
  * tests/test_integration.py:126).  Baseline / extended-sequential Huffman JPEG, 8-bit, gray or YCbCr 4:4:4 / 4:2:2 / 4:2:0,
  * restart intervals, EXIF orientation applied as imread applies it.  The serial Huffman bit stream is decoded on the host

@@ -574,6 +574,24 @@ extern "C" int sv_softmax_topk_f32(sv_ctx *ctx, const float *logits, long B, int
     return svk_softmax_topk(logits, B, k, index, prob, S(stream));
 }
 
+extern "C" int sv_resolve_conflicts(sv_ctx *ctx, const uint8_t *index, const float *prob, long n, int k, int beam_width, int max_corrections,
+                                    double min_alt_conf, int acceptance_rule, uint8_t *digits, float *conf, uint8_t *index_out, float *prob_out, uint8_t *success,
+                                    int32_t *num_conflicts_before, int32_t *num_conflicts_after, uint8_t *conflict_count, uint8_t *n_corrections,
+                                    uint8_t *corr_cells, float *corr_conf, int32_t *paths_explored, double *score, void *stream)
+{
+    REQUIRE(ctx, "NULL argument");
+    REQUIRE(n >= 0 && n < (1l << 31), "n out of range");
+    if (!(k >= 1 && k <= 4 && beam_width >= 1 && beam_width <= 6 && max_corrections >= 0 && max_corrections <= 3))
+        return sv_fail(SV_ERR_UNSUPPORTED, "%s: need 1 <= k <= 4, 1 <= beam_width <= 6, 0 <= max_corrections <= 3 (one wave searches one frame)", __func__);
+    if (n == 0) return SV_OK;
+    REQUIRE(index && prob, "NULL argument");
+    REQUIRE((((uintptr_t)prob | (uintptr_t)conf | (uintptr_t)prob_out | (uintptr_t)num_conflicts_before | (uintptr_t)num_conflicts_after |
+              (uintptr_t)corr_conf | (uintptr_t)paths_explored) & 3) == 0 && ((uintptr_t)score & 7) == 0, "misaligned argument");
+    return svk_resolve_conflicts(index, prob, n, k, beam_width, max_corrections, min_alt_conf, acceptance_rule != 0, digits, conf, index_out, prob_out, success,
+                                 num_conflicts_before, num_conflicts_after, conflict_count, n_corrections, corr_cells, corr_conf, paths_explored,
+                                 score, S(stream));
+}
+
 extern "C" int sv_frame_quality_stats_u8(sv_ctx *ctx, const uint8_t *img, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int channels,
                                          int64_t *lap_sum, int64_t *lap_sqsum, uint32_t *hist, void *stream)
 {

@@ -181,5 +181,10 @@ long svk_v3_blob_floats(bool use_se);
 size_t svk_v3_scratch_bytes(long cells);
 int svk_cnn3_forward(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *logits, float *features, u8 *digits, float *conf, hipStream_t s);
 
+// k9_resolve.hip
+int svk_resolve_conflicts(const u8 *index, const float *prob, long n, int k, int beam_width, int max_corrections, double min_alt_conf, int accept, u8 *digits,
+                          float *conf, u8 *index_out, float *prob_out, u8 *success, int *before, int *after, u8 *conflict_count, u8 *ncorr,
+                          u8 *corr_cells, float *corr_conf, int *explored, double *score, hipStream_t s);
+
 // host helpers
 void sv_gaussian_taps_f32(int n, float *out);

@@ -65,7 +65,7 @@ def gpu_local_cpus(device):
 
 class FramePipeline:
     def __init__(self, ctx: Context, H: int, W: int, chunk: int = 32, host_threads=None, min_area_ratio=0.1, glue=0, despeckle=True, sparse=True, depth=5, cpu_affinity="auto", bits_direct=True,
-                 quality=False):
+                 quality=False, resolve=False):
         self.ctx, self.H, self.W, self.chunk = ctx, H, W, chunk
         # chunks in flight.  A chunk's chain is K1 -> D2H -> search -> K2/K3, and chunk i's K1 is only issued once chunk i-depth+1's search has
         # returned: with too few in flight the period is (K1 + D2H + search) / (depth - 1), not the slowest stage
@@ -118,6 +118,9 @@ class FramePipeline:
         self.quality = bool(quality)
         if self.quality:
             self.q_bin = [None] * depth           # shaped on first use like K1's output (bit or byte image)
+        # resolve=True: run() also returns run_v2's validation and correction stage (pipeline/run_v2.py:344-371): top-3 and the beam
+        # search (csrc/k9_resolve.hip) on s_cls after K3, with run_v2's acceptance rule (:365) applied on the device
+        self.resolve = bool(resolve)
         ctx.reserve(chunk * 81)
 
     def _search(self, slot, m, ev):
@@ -149,12 +152,17 @@ class FramePipeline:
               else f"K1 -> {'despeckle (exact speck filter) -> ' if self.despeckle else ''}")
         return (f"{k1}{d2h} -> C++ contour corner search on "
                 f"{self.host_threads} host threads -> K2 -> K3, {self.chunk}-frame chunks, {self.depth} in flight"
-                + (f", host threads on the GPU's NUMA node ({len(self.cpus)} CPUs)" if self.cpus else ""))
+                + (f", host threads on the GPU's NUMA node ({len(self.cpus)} CPUs)" if self.cpus else "")
+                + (", then top-3 -> K9 (validation + beam-search conflict repair) per chunk" if self.resolve else ""))
 
     def run(self, frames, out=None, repeat=1, total=None):
         """frames u8 [n,H,W,3] on the context's device -> dict(digits u8[n,81], logits f32[n,81,10], conf f32[n,81],
         corners int32[n,4,2] (host), found bool[n] (host)); with quality=True also quality f32[n,6] (host: overall, sharpness, contrast,
-        completeness, geometry, size -- cv/grid_quality.py's scores of each frame, NaN in the corner-dependent columns where found is False).  repeat > 1 streams the pool that many times through the
+        completeness, geometry, size -- cv/grid_quality.py's scores of each frame, NaN in the corner-dependent columns where found is False); with
+        resolve=True also resolved_digits u8[n,81] (the digits after run_v2's conflict repair where run_v2 would take them, else the most
+        probable class of `logits`), resolve_success bool[n] (the frame is valid: it was, or the repair made it so), num_conflicts i32[n]
+        (conflicts left in resolved_digits) and n_corrections u8[n] (corrections taken), all on the device; all zero / False for a
+        frame whose grid was not found.  repeat > 1 streams the pool that many times through the
         pipeline without draining it in between (steady-state throughput measurement); total = k streams exactly k frames,
         cycling the pool (the k-th frame is pool frame k mod n: BASELINE configs[3]'s shard of 100,000 frames); both need chunk | n."""
         n = frames.shape[0]
@@ -184,6 +192,10 @@ class FramePipeline:
             q_s2 = torch.empty((n,), dtype=torch.int64, device=dev)
             q_hist = torch.empty((n, 256), dtype=torch.int32, device=dev)
             q_cnt = torch.zeros((n, 20), dtype=torch.int32, device=dev)
+        if self.resolve:
+            resolve_ok = torch.empty((n,), dtype=torch.uint8, device=dev)
+            out.update(resolved_digits=torch.empty((n, 81), dtype=torch.uint8, device=dev), resolve_success=resolve_ok.view(torch.bool),
+                       num_conflicts=torch.empty((n,), dtype=torch.int32, device=dev), n_corrections=torch.empty((n,), dtype=torch.uint8, device=dev))
         if total is None:
             starts = [(s0, min(self.chunk, n - s0)) for _ in range(repeat) for s0 in range(0, n, self.chunk)]
         else:
@@ -201,8 +213,20 @@ class FramePipeline:
                 self.ctx.frames_to_digits(frames[s:s + m], self.minv_dev[slot][:m], out=sub, glue=self.glue)
                 if self.quality:
                     self.ctx.grid_line_coverage(self.q_bin[slot][:m], self.minv_dev[slot][:m], out=q_cnt[s:s + m])
+                if self.resolve:
+                    # two launches per chunk: top-3, then K9 with run_v2's acceptance rule (pipeline/run_v2.py:365) applied in the kernel,
+                    # writing straight into run()'s outputs
+                    idx, prob = self.ctx.softmax_topk(sub["logits"], 3)
+                    self.ctx.resolve_conflicts(idx.view(m, 81, 3), prob.view(m, 81, 3), acceptance_rule=True,
+                                               out={"digits": out["resolved_digits"][s:s + m], "success": resolve_ok[s:s + m],
+                                                    "num_conflicts_after": out["num_conflicts"][s:s + m], "n_corrections": out["n_corrections"][s:s + m]})
                 if not found.all():
-                    out["digits"][s:s + m][torch.from_numpy(~found).to(dev)] = 0
+                    lost = torch.from_numpy(~found).to(dev)
+                    out["digits"][s:s + m][lost] = 0
+                    if self.resolve:              # no grid, no cells: nothing was validated
+                        for key in ("resolved_digits", "num_conflicts", "n_corrections"):
+                            out[key][s:s + m][lost] = 0
+                        resolve_ok[s:s + m][lost] = 0
                 ev = torch.cuda.Event(blocking=True)      # the waiting thread sleeps instead of spinning: the box's CPU quota is for the search
                 ev.record(self.s_cls)
                 free_ev[slot] = ev
@@ -256,7 +280,7 @@ class FramePipeline:
         return out
 
 
-def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1"):
+def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1", resolve=False):
     """One BGR image (numpy uint8 [H,W,3], or a CUDA uint8 tensor of that shape) -> dict(grid 9x9 list, digits, confidences, corners) or None when no
     grid is found -- the call order of pipeline/run.py:261-312, preprocess_cell (:73-95) included by default.
     top_k > 1 adds run_v2's per-cell `alternatives` (pipeline/run_v2.py:165-178): 81 lists of (digit, prob), best excluded.
@@ -267,7 +291,11 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     `preprocess_method`, `has_shadow`, `has_glare`.  It runs on the default context of the current device.
     model="v3": the model run_v2 loads (pipeline/run_v2.py:95-128), DigitCNNv3; model_state_dict is then its state_dict and the same
     call order runs with the v3 forward.  `confidence` is softmax(logits / temperature) at the digit; the top_k alternatives come from
-    softmax(logits), without the temperature, as at run_v2.py:166-180."""
+    softmax(logits), without the temperature, as at run_v2.py:166-180.
+    resolve=True (implies top_k=3 unless more are asked for; at most 4): run_v2's validation and correction stage (pipeline/run_v2.py:344-371)
+    on the device: `validation` (is_valid, num_conflicts, cells_in_conflict of the cells run_v2 goes on with), `corrections` (the
+    (row, col, old digit, new digit, old confidence, new confidence) taken: those of a repair that succeeded or left fewer conflicts,
+    :365), `resolved_grid` and `paths_explored`.  `grid` and `digits` stay the uncorrected recognition."""
     from .runtime import default_context
     if preprocess not in ("v1", "v2"):
         raise ValueError(f"preprocess must be 'v1' or 'v2', got {preprocess!r}")
@@ -296,8 +324,12 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     digits = out["digits"][0].cpu().numpy()
     res = {"grid": [[int(digits[r * 9 + c]) for c in range(9)] for r in range(9)], "digits": digits,
            "confidence": out["conf"][0].cpu().numpy(), "logits": out["logits"][0].cpu().numpy(), "corners": corners}
+    if resolve:
+        top_k = max(top_k, 3)
     if top_k > 1:
         idx, prob = ctx.softmax_topk(out["logits"][0], top_k)
+        if resolve:
+            res.update(_validate_and_resolve(ctx, idx[None], prob[None]))
         idx, prob = idx.cpu().numpy(), prob.cpu().numpy()
         res["alternatives"] = [[(int(idx[i, j]), float(prob[i, j])) for j in range(1, top_k)] for i in range(81)]
     if quality:
@@ -307,6 +339,19 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     if pre is not None:
         res["preprocess_method"], res["has_shadow"], res["has_glare"] = pre.method_used, pre.has_shadow, pre.has_glare
     return res
+
+
+def _validate_and_resolve(ctx, idx, prob):
+    """pipeline/run_v2.py:347-371 on one frame's top-k (device tensors [1,81,k]): validate; if invalid, search; take the search's cells
+    if it succeeded or left fewer conflicts -- one launch, with the acceptance rule applied in the kernel."""
+    state = {k: v[0].cpu().numpy() for k, v in ctx.resolve_conflicts(idx, prob, acceptance_rule=True).items()}
+    corrections = [(int(x) // 9, int(x) % 9, int(old), int(new), float(c0), float(c1))
+                   for (x, old, new), (c0, c1) in zip(state["corr_cells"][:int(state["n_corrections"])], state["corr_conf"])]
+    digits, count = state["digits"], state["conflict_count"]
+    return {"validation": {"is_valid": int(state["num_conflicts_after"]) == 0, "num_conflicts": int(state["num_conflicts_after"]),
+                           "cells_in_conflict": [(x // 9, x % 9) for x in range(81) if count[x]]},
+            "corrections": corrections, "resolved_grid": [[int(digits[r * 9 + c]) for c in range(9)] for r in range(9)],
+            "paths_explored": int(state["paths_explored"])}
 
 
 def run_solver(grid):

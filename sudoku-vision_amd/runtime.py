@@ -690,6 +690,39 @@ class Context:
         self._check(rc, "sv_grid_line_coverage")
         return out
 
+    # ---- validation and correction (resolve/*.py, csrc/k9_resolve.hip) -------------------------------
+    _RESOLVE_OUT = (("digits", (81,), torch.uint8), ("conf", (81,), torch.float32), ("index", None, torch.uint8), ("prob", None, torch.float32),
+                    ("success", (), torch.uint8), ("num_conflicts_before", (), torch.int32), ("num_conflicts_after", (), torch.int32),
+                    ("conflict_count", (81,), torch.uint8), ("n_corrections", (), torch.uint8), ("corr_cells", (3, 3), torch.uint8),
+                    ("corr_conf", (3, 2), torch.float32), ("paths_explored", (), torch.int32), ("score", (), torch.float64))
+
+    def resolve_conflicts(self, index, prob, beam_width=5, max_corrections=3, min_alternative_confidence=0.1, acceptance_rule=False, out=None):
+        """run_v2's validate_predictions + resolve_conflicts (pipeline/run_v2.py:344-371) for n frames in one launch
+        (sv_resolve_conflicts): index u8 [n,81,k], prob f32 [n,81,k] as softmax_topk returns them for n*81 cells -> dict of device
+        tensors: digits u8 [n,81], conf f32 [n,81], index u8 [n,81,k], prob f32 [n,81,k] (the resulting cells and their alternatives),
+        success u8 [n], num_conflicts_before / num_conflicts_after i32 [n], conflict_count u8 [n,81], n_corrections u8 [n],
+        corr_cells u8 [n,3,3] (cell, old digit, new digit), corr_conf f32 [n,3,2] (old, new confidence), paths_explored i32 [n],
+        score f64 [n].  run_v2 takes the resulting cells when success or num_conflicts_after < num_conflicts_before (:365);
+        acceptance_rule=True applies that on the device: a repair run_v2 would not take is dropped and the cell outputs, the conflict
+        outputs after and the corrections describe the input.  out: a dict of some of those names -> contiguous tensors to write into;
+        only they are computed and returned (None: all of them, newly allocated)."""
+        index = _dev_tensor(index, "index", torch.uint8, self.device, shape=(None, 81, None)).contiguous()
+        n, _, k = index.shape
+        prob = _dev_tensor(prob, "prob", torch.float32, self.device, shape=(n, 81, k)).contiguous()
+        shapes = {name: ((n,) + ((81, k) if shape is None else shape), dtype) for name, shape, dtype in self._RESOLVE_OUT}
+        if out is None:
+            out = {name: torch.empty(shape, dtype=dtype, device=self.device) for name, (shape, dtype) in shapes.items()}
+        else:
+            unknown = set(out) - set(shapes)
+            if unknown:
+                raise KeyError(f"not outputs of resolve_conflicts: {sorted(unknown)}")
+            for name, t in out.items():
+                self._out(t, *shapes[name], name)
+        self._check(self._lib.sv_resolve_conflicts(self._h, _ptr(index), _ptr(prob), n, k, int(beam_width), int(max_corrections),
+                                                   float(min_alternative_confidence), int(bool(acceptance_rule)),
+                                                   *[_opt_ptr(out.get(name)) for name, _, _ in self._RESOLVE_OUT], _stream_ptr()), "sv_resolve_conflicts")
+        return out
+
     # ---- run_v2's preprocessing (cv/preprocess_v2.py, csrc/k7_preprocess_v2.hip) -------------------
     # Every method takes gray u8 [n,H,W] on device (rows may be padded, frames may have gaps) and returns new dense tensors.
     MORPH_DILATE, MORPH_ERODE, MORPH_CLOSE, MORPH_OPEN = 0, 1, 2, 3
