@@ -393,6 +393,29 @@ int sv_resolve_conflicts(sv_ctx *ctx, const uint8_t *index /*dev, n*81*k*/, cons
                          uint8_t *n_corrections /*dev*/, uint8_t *corr_cells /*dev*/, float *corr_conf /*dev*/,
                          int32_t *paths_explored /*dev*/, double *score /*dev*/, void *stream);
 
+/* The last stage of pipeline/run_v2.py before the solver (:373-391), resolve_with_constraints(recognized_grid, confidences), for n
+ * frames in one launch: ConstraintResolver.__init__ + propagate (pipeline/constraint_resolver.py:48-267): naked and hidden singles
+ * until nothing moves, a contradiction, or max_iterations passes.  Every output equals the reference's, on contradictory grids too,
+ * where the result depends on the order in which CPython's list(set(...)) hands back the hidden singles of a pass (:200): the
+ * kernel replays that set (CPython 3.8+: the tuple hash of (row, col, digit) and Objects/setobject.c's table).
+ * digits: 0 = empty, 1..9; conf: the cells' confidences, or NULL for the reference's default 1.0 everywhere.
+ * Outputs, each may be NULL; grid may be digits itself:
+ *   grid [n*81]               PropagationResult.grid
+ *   candidates [n*81]         Cell.candidates as a mask, bit d (1..9) set = d still possible; a placed cell holds its digit alone, a
+ *                             cell that came filled holds its digit unless a peer showed the same one (then nothing)
+ *   is_valid [n]              0 when a contradiction was found (run_v2 then reports the frame `invalid`)
+ *   iterations [n]            passes run, the one that found no progress included
+ *   contradiction_cell [n]    9 * row + col, 255 = none
+ *   n_resolved [n], resolved [n*81*2] = (cell, digit): cells_resolved in order; unused entries are 255
+ *   is_fixed [n*81]           Cell.is_fixed: digit > 0 and (double)conf > 0.9
+ * A frame holding a byte above 9 is no grid: is_valid 0, iterations 0, contradiction_cell 255, grid = digits, candidates 0,
+ * n_resolved 0; nothing is indexed with such a byte.  One wave per frame; a frame's result does not depend on the rest of the batch.
+ * 1 <= max_iterations <= 100 (the reference's default), otherwise SV_ERR_UNSUPPORTED; n == 0 is SV_OK. */
+int sv_propagate_constraints(sv_ctx *ctx, const uint8_t *digits /*dev, n*81*/, const float *conf /*dev, n*81, or NULL*/, long n,
+                             int max_iterations, uint8_t *grid /*dev*/, uint16_t *candidates /*dev*/, uint8_t *is_valid /*dev*/,
+                             int32_t *iterations /*dev*/, uint8_t *contradiction_cell /*dev*/, uint8_t *n_resolved /*dev*/,
+                             uint8_t *resolved /*dev*/, uint8_t *is_fixed /*dev*/, void *stream);
+
 /* ---- N4: JPEG front end -- what cv2.imread does before the path starts (pipeline/run.py:250, pipeline/run_v2.py:267,
  * tests/test_integration.py:126).  Baseline / extended-sequential Huffman JPEG, 8-bit, gray or YCbCr 4:4:4 / 4:2:2 / 4:2:0,
  * restart intervals, EXIF orientation applied as imread applies it.  The serial Huffman bit stream is decoded on the host

@@ -67,6 +67,7 @@ SIGNATURES = {
     "sv_jpeg_reconstruct_sparse_bgr_u8": [_p, _p, _p, _p, _p, _p, _p, _pd, _p],
     "sv_softmax_topk_f32": [_p, _p, _l, _i, _p, _p, _p],
     "sv_resolve_conflicts": [_p, _p, _p, _l, _i, _i, _i, _d, _i] + [_p] * 14,
+    "sv_propagate_constraints": [_p, _p, _p, _l, _i] + [_p] * 9,
     "sv_cnn_forward_f32": [_p, _p, _l, _p, _p, _p, _p],
     "sv_cnn_forward_cells_u8": [_p, _p, _l, _i, _p, _p, _p, _p],
     "sv_frames_to_digits": [_p, _p, _i, _i, _i, _pd, _pd, _p, _i, _p, _p, _p, _p, _p],

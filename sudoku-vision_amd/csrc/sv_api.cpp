@@ -592,6 +592,21 @@ extern "C" int sv_resolve_conflicts(sv_ctx *ctx, const uint8_t *index, const flo
                                  score, S(stream));
 }
 
+extern "C" int sv_propagate_constraints(sv_ctx *ctx, const uint8_t *digits, const float *conf, long n, int max_iterations, uint8_t *grid, uint16_t *candidates,
+                                        uint8_t *is_valid, int32_t *iterations, uint8_t *contradiction_cell, uint8_t *n_resolved, uint8_t *resolved,
+                                        uint8_t *is_fixed, void *stream)
+{
+    REQUIRE(ctx, "NULL argument");
+    REQUIRE(n >= 0 && n < (1l << 31), "n out of range");
+    if (!(max_iterations >= 1 && max_iterations <= 100))
+        return sv_fail(SV_ERR_UNSUPPORTED, "%s: need 1 <= max_iterations <= 100", __func__);
+    if (n == 0) return SV_OK;
+    REQUIRE(digits, "NULL argument");
+    REQUIRE((((uintptr_t)conf | (uintptr_t)iterations) & 3) == 0 && ((uintptr_t)candidates & 1) == 0, "misaligned argument");
+    return svk_propagate_constraints(digits, conf, n, max_iterations, grid, candidates, is_valid, iterations, contradiction_cell, n_resolved, resolved, is_fixed,
+                                     S(stream));
+}
+
 extern "C" int sv_frame_quality_stats_u8(sv_ctx *ctx, const uint8_t *img, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int channels,
                                          int64_t *lap_sum, int64_t *lap_sqsum, uint32_t *hist, void *stream)
 {

@@ -186,5 +186,9 @@ int svk_resolve_conflicts(const u8 *index, const float *prob, long n, int k, int
                           float *conf, u8 *index_out, float *prob_out, u8 *success, int *before, int *after, u8 *conflict_count, u8 *ncorr,
                           u8 *corr_cells, float *corr_conf, int *explored, double *score, hipStream_t s);
 
+// k10_propagate.hip
+int svk_propagate_constraints(const u8 *digits, const float *conf, long n, int max_iterations, u8 *grid, uint16_t *candidates, u8 *is_valid, int *iterations,
+                              u8 *contradiction_cell, u8 *n_resolved, u8 *resolved, u8 *is_fixed, hipStream_t s);
+
 // host helpers
 void sv_gaussian_taps_f32(int n, float *out);

@@ -65,7 +65,7 @@ def gpu_local_cpus(device):
 
 class FramePipeline:
     def __init__(self, ctx: Context, H: int, W: int, chunk: int = 32, host_threads=None, min_area_ratio=0.1, glue=0, despeckle=True, sparse=True, depth=5, cpu_affinity="auto", bits_direct=True,
-                 quality=False, resolve=False):
+                 quality=False, resolve=False, propagate=False):
         self.ctx, self.H, self.W, self.chunk = ctx, H, W, chunk
         # chunks in flight.  A chunk's chain is K1 -> D2H -> search -> K2/K3, and chunk i's K1 is only issued once chunk i-depth+1's search has
         # returned: with too few in flight the period is (K1 + D2H + search) / (depth - 1), not the slowest stage
@@ -121,6 +121,9 @@ class FramePipeline:
         # resolve=True: run() also returns run_v2's validation and correction stage (pipeline/run_v2.py:344-371): top-3 and the beam
         # search (csrc/k9_resolve.hip) on s_cls after K3, with run_v2's acceptance rule (:365) applied on the device
         self.resolve = bool(resolve)
+        # propagate=True: run() also returns run_v2's constraint propagation (pipeline/run_v2.py:373-391, csrc/k10_propagate.hip), one more
+        # launch per chunk on s_cls: on the repaired digits when resolve=True, else on the recognised ones
+        self.propagate = bool(propagate)
         ctx.reserve(chunk * 81)
 
     def _search(self, slot, m, ev):
@@ -153,7 +156,8 @@ class FramePipeline:
         return (f"{k1}{d2h} -> C++ contour corner search on "
                 f"{self.host_threads} host threads -> K2 -> K3, {self.chunk}-frame chunks, {self.depth} in flight"
                 + (f", host threads on the GPU's NUMA node ({len(self.cpus)} CPUs)" if self.cpus else "")
-                + (", then top-3 -> K9 (validation + beam-search conflict repair) per chunk" if self.resolve else ""))
+                + (", then top-3 -> K9 (validation + beam-search conflict repair) per chunk" if self.resolve else "")
+                + (", then K10 (constraint propagation) per chunk" if self.propagate else ""))
 
     def run(self, frames, out=None, repeat=1, total=None):
         """frames u8 [n,H,W,3] on the context's device -> dict(digits u8[n,81], logits f32[n,81,10], conf f32[n,81],
@@ -162,7 +166,10 @@ class FramePipeline:
         resolve=True also resolved_digits u8[n,81] (the digits after run_v2's conflict repair where run_v2 would take them, else the most
         probable class of `logits`), resolve_success bool[n] (the frame is valid: it was, or the repair made it so), num_conflicts i32[n]
         (conflicts left in resolved_digits) and n_corrections u8[n] (corrections taken), all on the device; all zero / False for a
-        frame whose grid was not found.  repeat > 1 streams the pool that many times through the
+        frame whose grid was not found; with propagate=True also propagated_digits u8[n,81] (the grid after run_v2's constraint propagation
+        of resolved_digits, or of digits without resolve=True), propagate_valid bool[n] (False: run_v2 reports the frame `invalid`),
+        contradiction_cell u8[n] (9 * row + col, 255 = none) and n_propagated u8[n] (cells the propagation filled), on the device; zeros,
+        False and 255 for a frame whose grid was not found.  repeat > 1 streams the pool that many times through the
         pipeline without draining it in between (steady-state throughput measurement); total = k streams exactly k frames,
         cycling the pool (the k-th frame is pool frame k mod n: BASELINE configs[3]'s shard of 100,000 frames); both need chunk | n."""
         n = frames.shape[0]
@@ -196,6 +203,10 @@ class FramePipeline:
             resolve_ok = torch.empty((n,), dtype=torch.uint8, device=dev)
             out.update(resolved_digits=torch.empty((n, 81), dtype=torch.uint8, device=dev), resolve_success=resolve_ok.view(torch.bool),
                        num_conflicts=torch.empty((n,), dtype=torch.int32, device=dev), n_corrections=torch.empty((n,), dtype=torch.uint8, device=dev))
+        if self.propagate:
+            propagate_ok = torch.empty((n,), dtype=torch.uint8, device=dev)
+            out.update(propagated_digits=torch.empty((n, 81), dtype=torch.uint8, device=dev), propagate_valid=propagate_ok.view(torch.bool),
+                       contradiction_cell=torch.empty((n,), dtype=torch.uint8, device=dev), n_propagated=torch.empty((n,), dtype=torch.uint8, device=dev))
         if total is None:
             starts = [(s0, min(self.chunk, n - s0)) for _ in range(repeat) for s0 in range(0, n, self.chunk)]
         else:
@@ -220,9 +231,18 @@ class FramePipeline:
                     self.ctx.resolve_conflicts(idx.view(m, 81, 3), prob.view(m, 81, 3), acceptance_rule=True,
                                                out={"digits": out["resolved_digits"][s:s + m], "success": resolve_ok[s:s + m],
                                                     "num_conflicts_after": out["num_conflicts"][s:s + m], "n_corrections": out["n_corrections"][s:s + m]})
+                if self.propagate:
+                    self.ctx.propagate_constraints(out["resolved_digits" if self.resolve else "digits"][s:s + m],
+                                                   out={"grid": out["propagated_digits"][s:s + m], "is_valid": propagate_ok[s:s + m],
+                                                        "contradiction_cell": out["contradiction_cell"][s:s + m], "n_resolved": out["n_propagated"][s:s + m]})
                 if not found.all():
                     lost = torch.from_numpy(~found).to(dev)
                     out["digits"][s:s + m][lost] = 0
+                    if self.propagate:            # no grid, nothing to propagate
+                        out["propagated_digits"][s:s + m][lost] = 0
+                        out["n_propagated"][s:s + m][lost] = 0
+                        out["contradiction_cell"][s:s + m][lost] = 255
+                        propagate_ok[s:s + m][lost] = 0
                     if self.resolve:              # no grid, no cells: nothing was validated
                         for key in ("resolved_digits", "num_conflicts", "n_corrections"):
                             out[key][s:s + m][lost] = 0
@@ -280,7 +300,7 @@ class FramePipeline:
         return out
 
 
-def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1", resolve=False):
+def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1", resolve=False, propagate=False):
     """One BGR image (numpy uint8 [H,W,3], or a CUDA uint8 tensor of that shape) -> dict(grid 9x9 list, digits, confidences, corners) or None when no
     grid is found -- the call order of pipeline/run.py:261-312, preprocess_cell (:73-95) included by default.
     top_k > 1 adds run_v2's per-cell `alternatives` (pipeline/run_v2.py:165-178): 81 lists of (digit, prob), best excluded.
@@ -295,7 +315,10 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     resolve=True (implies top_k=3 unless more are asked for; at most 4): run_v2's validation and correction stage (pipeline/run_v2.py:344-371)
     on the device: `validation` (is_valid, num_conflicts, cells_in_conflict of the cells run_v2 goes on with), `corrections` (the
     (row, col, old digit, new digit, old confidence, new confidence) taken: those of a repair that succeeded or left fewer conflicts,
-    :365), `resolved_grid` and `paths_explored`.  `grid` and `digits` stay the uncorrected recognition."""
+    :365), `resolved_grid` and `paths_explored`.  `grid` and `digits` stay the uncorrected recognition.
+    propagate=True: run_v2's constraint propagation (pipeline/run_v2.py:373-391) on the device, of `resolved_grid` when resolve=True and of
+    `grid` otherwise, with the cells' confidences: `propagation` (is_valid, iterations, contradiction_cell as (row, col) or None,
+    cells_resolved as (row, col, digit) in the reference's order) and `propagated_grid` (what run_v2 hands to the solver)."""
     from .runtime import default_context
     if preprocess not in ("v1", "v2"):
         raise ValueError(f"preprocess must be 'v1' or 'v2', got {preprocess!r}")
@@ -330,8 +353,17 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
         idx, prob = ctx.softmax_topk(out["logits"][0], top_k)
         if resolve:
             res.update(_validate_and_resolve(ctx, idx[None], prob[None]))
+            resolved = res.pop("_cells")
         idx, prob = idx.cpu().numpy(), prob.cpu().numpy()
         res["alternatives"] = [[(int(idx[i, j]), float(prob[i, j])) for j in range(1, top_k)] for i in range(81)]
+    if propagate:
+        cells, conf = resolved if resolve else (out["digits"], out["conf"])
+        state = {k: v[0].cpu().numpy() for k, v in ctx.propagate_constraints(cells, conf).items()}
+        bad, g = int(state["contradiction_cell"]), state["grid"]
+        res["propagation"] = {"is_valid": bool(state["is_valid"]), "iterations": int(state["iterations"]),
+                              "contradiction_cell": None if bad == 255 else (bad // 9, bad % 9),
+                              "cells_resolved": [(int(x) // 9, int(x) % 9, int(v)) for x, v in state["resolved"][:int(state["n_resolved"])]]}
+        res["propagated_grid"] = [[int(g[r * 9 + c]) for c in range(9)] for r in range(9)]
     if quality:
         from .cv import grid_quality
         q = grid_quality.assess_grid_quality(frames[0], binary_dev, corners, ctx=ctx)
@@ -344,14 +376,15 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
 def _validate_and_resolve(ctx, idx, prob):
     """pipeline/run_v2.py:347-371 on one frame's top-k (device tensors [1,81,k]): validate; if invalid, search; take the search's cells
     if it succeeded or left fewer conflicts -- one launch, with the acceptance rule applied in the kernel."""
-    state = {k: v[0].cpu().numpy() for k, v in ctx.resolve_conflicts(idx, prob, acceptance_rule=True).items()}
+    dev = ctx.resolve_conflicts(idx, prob, acceptance_rule=True)
+    state = {k: v[0].cpu().numpy() for k, v in dev.items()}
     corrections = [(int(x) // 9, int(x) % 9, int(old), int(new), float(c0), float(c1))
                    for (x, old, new), (c0, c1) in zip(state["corr_cells"][:int(state["n_corrections"])], state["corr_conf"])]
     digits, count = state["digits"], state["conflict_count"]
     return {"validation": {"is_valid": int(state["num_conflicts_after"]) == 0, "num_conflicts": int(state["num_conflicts_after"]),
                            "cells_in_conflict": [(x // 9, x % 9) for x in range(81) if count[x]]},
             "corrections": corrections, "resolved_grid": [[int(digits[r * 9 + c]) for c in range(9)] for r in range(9)],
-            "paths_explored": int(state["paths_explored"])}
+            "paths_explored": int(state["paths_explored"]), "_cells": (dev["digits"], dev["conf"])}
 
 
 def run_solver(grid):

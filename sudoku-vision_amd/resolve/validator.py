@@ -1,6 +1,6 @@
 """Drop-in for the reference's pipeline/validator.py: the names, fields, argument names and defaults that pipeline/run_v2.py:42 imports,
 with the validation itself on the MI355X (sv_resolve_conflicts, csrc/k9_resolve.hip).  Put this directory ahead of the reference's
-pipeline/ on sys.path; constraint_resolver is then still found in the reference's own directory.
+pipeline/ on sys.path; constraint_resolver is then this directory's too (csrc/k10_propagate.hip).
 
 validate_predictions asks the device for the number of conflicts and for how many conflicts name each cell, and lists the Conflict
 objects (which are text) on the host from the same digits; the two are checked against each other.

@@ -723,6 +723,36 @@ class Context:
                                                    *[_opt_ptr(out.get(name)) for name, _, _ in self._RESOLVE_OUT], _stream_ptr()), "sv_resolve_conflicts")
         return out
 
+    # name, per-frame shape, dtype: the order of sv_propagate_constraints' output arguments
+    _PROPAGATE_OUT = (("grid", (81,), torch.uint8), ("candidates", (81,), torch.int16), ("is_valid", (), torch.uint8), ("iterations", (), torch.int32),
+                      ("contradiction_cell", (), torch.uint8), ("n_resolved", (), torch.uint8), ("resolved", (81, 2), torch.uint8),
+                      ("is_fixed", (81,), torch.uint8))
+
+    def propagate_constraints(self, digits, conf=None, max_iterations=100, out=None):
+        """run_v2's resolve_with_constraints (pipeline/run_v2.py:373-391, pipeline/constraint_resolver.py:48-267) for n frames in one
+        launch (sv_propagate_constraints): digits u8 [n,81] (0 = empty), conf f32 [n,81] or None (1.0 everywhere) -> dict of device
+        tensors: grid u8 [n,81], candidates int16 [n,81] (bit d set = d still possible), is_valid u8 [n], iterations i32 [n],
+        contradiction_cell u8 [n] (9 * row + col, 255 = none), n_resolved u8 [n], resolved u8 [n,81,2] ((cell, digit) in the reference's
+        order, unused entries 255), is_fixed u8 [n,81].  out: a dict of some of those names -> contiguous tensors to write into; only
+        they are computed and returned (None: all of them, newly allocated)."""
+        digits = _dev_tensor(digits, "digits", torch.uint8, self.device, shape=(None, 81)).contiguous()
+        n = digits.shape[0]
+        if conf is not None:
+            conf = _dev_tensor(conf, "conf", torch.float32, self.device, shape=(n, 81)).contiguous()
+        shapes = {name: ((n,) + shape, dtype) for name, shape, dtype in self._PROPAGATE_OUT}
+        if out is None:
+            out = {name: torch.empty(shape, dtype=dtype, device=self.device) for name, (shape, dtype) in shapes.items()}
+        else:
+            unknown = set(out) - set(shapes)
+            if unknown:
+                raise KeyError(f"not outputs of propagate_constraints: {sorted(unknown)}")
+            for name, t in out.items():
+                self._out(t, *shapes[name], name)
+        self._check(self._lib.sv_propagate_constraints(self._h, _ptr(digits), _opt_ptr(conf), n, int(max_iterations),
+                                                       *[_opt_ptr(out.get(name)) for name, _, _ in self._PROPAGATE_OUT], _stream_ptr()),
+                    "sv_propagate_constraints")
+        return out
+
     # ---- run_v2's preprocessing (cv/preprocess_v2.py, csrc/k7_preprocess_v2.hip) -------------------
     # Every method takes gray u8 [n,H,W] on device (rows may be padded, frames may have gaps) and returns new dense tensors.
     MORPH_DILATE, MORPH_ERODE, MORPH_CLOSE, MORPH_OPEN = 0, 1, 2, 3
