@@ -168,6 +168,26 @@ int sv_despeckle_bits(sv_ctx *ctx, uint32_t *bits /*dev, n*H*W/32*/, int n, int 
 int sv_despeckle_u8(sv_ctx *ctx, const uint8_t *binary /*dev, n*H*W*/, int n, int H, int W,
                     uint8_t *out /*dev, n*H*W*/, uint32_t *packed /*dev, n*H*W/32, or NULL*/, void *stream);
 
+/* K11, a second accelerator for the host corner search, behind sv_despeckle_*; opt-in, not a reference stage.  An exact connected-
+ * component filter (csrc/k11_components.hip): with min_area = min_area_ratio * ((double)H * (double)W), every 8-connected component of
+ * foreground (pixel != 0) whose pixel bounding box x0..x1, y0..y1 (inclusive) has (double)(x1 - x0) * (double)(y1 - y0) < min_area is
+ * erased, and every other pixel is unchanged.  That is the comparison by which find_grid_contour skips a contour, and a contour's area
+ * never exceeds the product, so
+ *     sv_find_grid_corners_*(filtered with ratio r, searched with r') == sv_find_grid_corners_*(binary, r')   for every r' >= r
+ * (argument at the top of the kernel file).  There is no iteration cap and no input that is left as it is; a 1-pixel-high or -wide
+ * component always goes when min_area > 0; min_area_ratio == 0 erases nothing.  Results do not depend on the order the kernels' atomics
+ * land in.  Batched over n frames, stream-ordered, no host synchronisation; n == 0 is a no-op.
+ * Shapes: any H, W >= 1 with H * W <= 4e9 for the byte form (out may equal binary; packed, optional, needs W % 32 == 0 and receives
+ * the result as 1 bit per pixel as well); W % 32 == 0 for the bit form (in place), else SV_ERR_UNSUPPORTED.
+ * NULL pointers, negative sizes, a negative or NaN ratio: SV_ERR_BAD_ARG.
+ * Scratch in the context, grow-only (nothing is allocated by a call at a shape no larger than an earlier one): 8.25 bytes per pixel of
+ * a frame padded to W % 32 == 0 (one word per possible run start for the union-find parent and three box limits, a word per 32 pixels
+ * for the run numbering, the byte form's bit image), for at most as many frames of a batch as fit in 1 GiB (one frame at least); a
+ * longer batch is worked off in groups on the stream. */
+int sv_component_filter_bits(sv_ctx *ctx, uint32_t *bits /*dev, n*H*W/32, in place*/, int n, int H, int W, double min_area_ratio, void *stream);
+int sv_component_filter_u8(sv_ctx *ctx, const uint8_t *binary /*dev, n*H*W*/, int n, int H, int W, double min_area_ratio,
+                           uint8_t *out /*dev, n*H*W, may equal binary*/, uint32_t *packed /*dev, n*H*W/32, or NULL*/, void *stream);
+
 /* Sparse form of sv_despeckle_u8's packed output for the D2H copy (a despeckled frame is mostly zero words: the hand-over to
  * the host search shrinks 3-4x).  Record of one frame, little endian:
  *   u32 n_values, u32 cap_values, u64 mask[H * gpr], u32 value[cap_values]        gpr = ceil(W/32/64)

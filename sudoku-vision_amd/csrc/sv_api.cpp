@@ -59,6 +59,7 @@ extern "C" int sv_ctx_destroy(sv_ctx *ctx)
     if (ctx->cells2) (void)hipFree(ctx->cells2);
     if (ctx->jpeg_planes) (void)hipFree(ctx->jpeg_planes);
     if (ctx->pp2) (void)hipFree(ctx->pp2);
+    if (ctx->cc) (void)hipFree(ctx->cc);
     if (ctx->k1_list) (void)hipFree(ctx->k1_list);
     if (ctx->range_flag) (void)hipFree(ctx->range_flag);
     for (auto &t : ctx->timeline) { (void)hipEventDestroy(t.t0); (void)hipEventDestroy(t.t1); }
@@ -431,6 +432,36 @@ extern "C" int sv_despeckle_u8(sv_ctx *ctx, const uint8_t *binary, int n, int H,
     REQUIRE(n > 0 && H > 0 && W > 0, "bad shape");
     REQUIRE(!packed || W % 32 == 0, "packed output needs W % 32 == 0");
     return svk_despeckle(binary, n, H, W, out, packed, S(stream));
+}
+
+// K11 (k11_components.hip).  The argument checks come before anything touches the context or the device.
+static int component_filter_args(const void *ctx, const void *a, const void *b, int n, int H, int W, double min_area_ratio)
+{
+    REQUIRE(ctx && a && b, "NULL argument");
+    REQUIRE(n >= 0 && H > 0 && W > 0, "bad shape");
+    REQUIRE(min_area_ratio >= 0.0, "min_area_ratio must be a number >= 0");       // (false for NaN)
+    return SV_OK;
+}
+
+extern "C" int sv_component_filter_bits(sv_ctx *ctx, uint32_t *bits, int n, int H, int W, double min_area_ratio, void *stream)
+{
+    int rc = component_filter_args(ctx, bits, bits, n, H, W, min_area_ratio);
+    if (rc) return rc;
+    if (W % 32) return sv_fail(SV_ERR_UNSUPPORTED, "sv_component_filter_bits: W must be a multiple of 32");
+    if ((double)H * (double)W > 4e9) return sv_fail(SV_ERR_UNSUPPORTED, "sv_component_filter_bits: frames above 4e9 pixels are not supported");
+    if (n == 0 || min_area_ratio == 0.0) return SV_OK;
+    return svk_component_filter_bits(ctx, bits, n, H, W, min_area_ratio * ((double)H * (double)W), S(stream));
+}
+
+extern "C" int sv_component_filter_u8(sv_ctx *ctx, const uint8_t *binary, int n, int H, int W, double min_area_ratio, uint8_t *out, uint32_t *packed,
+                                      void *stream)
+{
+    int rc = component_filter_args(ctx, binary, out, n, H, W, min_area_ratio);
+    if (rc) return rc;
+    REQUIRE(!packed || W % 32 == 0, "packed output needs W % 32 == 0");
+    if ((double)H * (double)W > 4e9) return sv_fail(SV_ERR_UNSUPPORTED, "sv_component_filter_u8: frames above 4e9 pixels are not supported");
+    if (n == 0) return SV_OK;
+    return svk_component_filter(ctx, binary, n, H, W, min_area_ratio * ((double)H * (double)W), out, packed, S(stream));
 }
 
 extern "C" long sv_sparse_bits_record_bytes(int H, int W, long cap_values)

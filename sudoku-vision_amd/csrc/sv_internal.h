@@ -71,6 +71,8 @@ struct sv_ctx {
     size_t cap_jpeg = 0;
     u8 *pp2 = nullptr;          // k7_preprocess_v2.hip: element rows + doubling planes + the close/open intermediate, or CLAHE's tile histograms + LUTs
     size_t cap_pp2 = 0;
+    u8 *cc = nullptr;           // k11_components.hip: run numbering, union-find parents and bounding boxes (layout at the top of that file)
+    size_t cap_cc = 0;
     void *k1_list = nullptr;    // k1_threshold_mm.hip: optional diagnostic counter (pixels decided by the exact evaluation), sv_preprocess_stats
     int precision = 0;          // SV_PREC_F32 / SV_PREC_BF16 (sv_ctx_set_precision)
     int cnn_kernels = 0;        // SV_CNN_AUTO / _F16PAIR / _F32MFMA (sv_ctx_set_cnn_kernels)
@@ -189,6 +191,10 @@ int svk_resolve_conflicts(const u8 *index, const float *prob, long n, int k, int
 // k10_propagate.hip
 int svk_propagate_constraints(const u8 *digits, const float *conf, long n, int max_iterations, u8 *grid, uint16_t *candidates, u8 *is_valid, int *iterations,
                               u8 *contradiction_cell, u8 *n_resolved, u8 *resolved, u8 *is_fixed, hipStream_t s);
+
+// k11_components.hip (min_area: the floor itself, min_area_ratio * H * W of the true frame size)
+int svk_component_filter_bits(sv_ctx *ctx, uint32_t *bits, int n, int H, int W, double min_area, hipStream_t s);
+int svk_component_filter(sv_ctx *ctx, const u8 *binary, int n, int H, int W, double min_area, u8 *out, uint32_t *packed, hipStream_t s);
 
 // host helpers
 void sv_gaussian_taps_f32(int n, float *out);

@@ -300,7 +300,35 @@ class FramePipeline:
         return out
 
 
-def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1", resolve=False, propagate=False):
+def _corners_behind_filters(ctx, frames, binary_dev=None, min_area_ratio=0.1):
+    """The corner search of one frame behind the exact filters K4 (csrc/k4_despeckle.hip) and K11 (csrc/k11_components.hip): same corners
+    as host.find_grid_corners of the unfiltered binary, with one or two borders left for the host to follow instead of thousands.
+    frames u8 [1,H,W,3]; binary_dev: the binary to search (u8 [H,W] on the device) when it is not K1's.  Where W % 32 == 0 the binary
+    crosses to the host as H*W/8 bytes and the bit scanner reads it; otherwise as bytes.  K4 runs only where its precondition holds."""
+    H, W = frames.shape[1], frames.shape[2]
+    k4 = min_area_ratio * H * W > 61 * 61
+    if W % 32 == 0 and H >= 16:
+        if binary_dev is None:
+            bits = ctx.preprocess_bits(frames)
+            if k4:
+                ctx.despeckle_bits(bits)
+        else:
+            bits = torch.empty((1, H, W // 32), dtype=torch.int32, device=ctx.device)
+            if k4:
+                ctx.despeckle(binary_dev[None], packed=bits)
+            else:
+                ctx.component_filter(binary_dev[None], 0.0, packed=bits)           # ratio 0 erases nothing: a plain pack
+        ctx.component_filter_bits(bits, min_area_ratio)
+        corners, found = host.find_grid_corners_bits_batch(bits.cpu().numpy(), H, W, min_area_ratio, threads=1)
+        return corners[0] if found[0] else None
+    b = (ctx.preprocess(frames) if binary_dev is None else binary_dev[None].contiguous())
+    if k4:
+        b = ctx.despeckle(b)
+    b = ctx.component_filter(b, min_area_ratio, out=b if k4 or binary_dev is None else None)
+    return host.find_grid_corners(b[0].cpu().numpy(), min_area_ratio)
+
+
+def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1", resolve=False, propagate=False, component_filter=False):
     """One BGR image (numpy uint8 [H,W,3], or a CUDA uint8 tensor of that shape) -> dict(grid 9x9 list, digits, confidences, corners) or None when no
     grid is found -- the call order of pipeline/run.py:261-312, preprocess_cell (:73-95) included by default.
     top_k > 1 adds run_v2's per-cell `alternatives` (pipeline/run_v2.py:165-178): 81 lists of (digit, prob), best excluded.
@@ -318,7 +346,9 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     :365), `resolved_grid` and `paths_explored`.  `grid` and `digits` stay the uncorrected recognition.
     propagate=True: run_v2's constraint propagation (pipeline/run_v2.py:373-391) on the device, of `resolved_grid` when resolve=True and of
     `grid` otherwise, with the cells' confidences: `propagation` (is_valid, iterations, contradiction_cell as (row, col) or None,
-    cells_resolved as (row, col, digit) in the reference's order) and `propagated_grid` (what run_v2 hands to the solver)."""
+    cells_resolved as (row, col, digit) in the reference's order) and `propagated_grid` (what run_v2 hands to the solver).
+    component_filter=True (opt-in; for photos, where the host corner search is what takes the time): the binary goes to the host behind
+    the exact filters K4 and K11 (_corners_behind_filters), as a bit image where W % 32 == 0.  Same result, keys and values."""
     from .runtime import default_context
     if preprocess not in ("v1", "v2"):
         raise ValueError(f"preprocess must be 'v1' or 'v2', got {preprocess!r}")
@@ -337,9 +367,12 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
         pre = preprocess_v2.preprocess_multi_strategy(frames[0])
         binary_dev = pre.binary
     else:
-        binary_dev = ctx.preprocess(frames)[0]
-    binary = binary_dev.cpu().numpy()
-    corners = host.find_grid_corners(binary)
+        binary_dev = None if component_filter else ctx.preprocess(frames)[0]
+    if component_filter:
+        corners = _corners_behind_filters(ctx, frames, binary_dev)
+    else:
+        binary = binary_dev.cpu().numpy()
+        corners = host.find_grid_corners(binary)
     if corners is None:
         return None
     minv = ctx.minv_to_device(Context.corners_to_minv(corners[None].astype(np.float32)))
@@ -366,6 +399,8 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
         res["propagated_grid"] = [[int(g[r * 9 + c]) for c in range(9)] for r in range(9)]
     if quality:
         from .cv import grid_quality
+        if binary_dev is None:                                # component_filter=True never made the byte image
+            binary_dev = ctx.preprocess(frames)[0]
         q = grid_quality.assess_grid_quality(frames[0], binary_dev, corners, ctx=ctx)
         res["quality"], res["quality_feedback"] = q, grid_quality.get_user_feedback(q)
     if pre is not None:
@@ -450,10 +485,11 @@ def check_constraints(grid):
     return out
 
 
-def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confidence=0.7):
+def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confidence=0.7, component_filter=False):
     """run_pipeline(image_path) of pipeline/run.py:244-355 on the MI355X path: JPEG -> frame in HBM (imgcodecs) -> K1 -> host
     corner search -> K2 (warped 450x450 grid kept, as the reference keeps it) -> preprocess_cell + DigitCNN (K3) -> constraint
-    check -> in-process solver.  Same PipelineResult fields, same error strings, same partial results on failure."""
+    check -> in-process solver.  Same PipelineResult fields, same error strings, same partial results on failure.
+    component_filter=True: the corner search reads the binary behind the exact filters K4 and K11 (recognize_image); same result."""
     from . import imgcodecs
     from .runtime import default_context
     res = PipelineResult(success=False)
@@ -469,12 +505,15 @@ def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confide
 
     t_cv = time.time()
     try:
-        binary = ctx.preprocess(frame[None])[0].cpu().numpy()
+        if component_filter:
+            filtered = _corners_behind_filters(ctx, frame[None])
+        else:
+            binary = ctx.preprocess(frame[None])[0].cpu().numpy()
     except Exception as e:                                   # noqa: BLE001 -- the reference reports, it does not raise
         res.error = f"Preprocessing failed: {e}"
         return res
     try:
-        corners = host.find_grid_corners(binary)
+        corners = filtered if component_filter else host.find_grid_corners(binary)
         if corners is None:
             res.error = "Grid detection failed: no quadrilateral found"
             return res

@@ -357,6 +357,37 @@ class Context:
                                                     _stream_ptr()), "sv_despeckle_u8")
         return out if packed is None else packed
 
+    def component_filter_bits(self, bits, min_area_ratio=0.1):
+        """component_filter on a bit image int32 [n,H,W//32], in place."""
+        self._out(_dev_tensor(bits, "bits", torch.int32, self.device, ndim=3), bits.shape, torch.int32, "bits")
+        n, H, wpr = bits.shape
+        if not float(min_area_ratio) >= 0:
+            raise ValueError(f"min_area_ratio must be >= 0, got {min_area_ratio}")
+        if n == 0:                                                 # an empty tensor has no pointer to pass
+            return bits
+        self._check(self._lib.sv_component_filter_bits(self._h, _ptr(bits), n, H, wpr * 32, float(min_area_ratio), _stream_ptr()), "sv_component_filter_bits")
+        return bits
+
+    def component_filter(self, binary, min_area_ratio=0.1, out=None, packed=None):
+        """binary u8 [n,H,W] (foreground = non-zero) -> the same with every 8-connected component erased whose bounding box has
+        (x1 - x0) * (y1 - y0) < min_area_ratio * H * W: exactly those, whatever their shape (sv_component_filter_u8 in the header).
+        host.find_grid_corners of the result equals that of `binary` for every search ratio >= min_area_ratio.  out may be binary;
+        packed: optional int32 [n,H,W//32] tensor that also receives the result as 1 bit per pixel (W % 32 == 0)."""
+        binary = _dev_tensor(binary, "binary", torch.uint8, self.device, ndim=3).contiguous()
+        n, H, W = binary.shape
+        if not float(min_area_ratio) >= 0:
+            raise ValueError(f"min_area_ratio must be >= 0, got {min_area_ratio}")
+        out = self._out(out, (n, H, W), torch.uint8, "out")
+        if packed is not None:
+            if W % 32:
+                raise ValueError("packed needs W % 32 == 0")
+            self._out(packed, (n, H, W // 32), torch.int32, "packed")
+        if n == 0:
+            return out
+        self._check(self._lib.sv_component_filter_u8(self._h, _ptr(binary), n, H, W, float(min_area_ratio), _ptr(out), _opt_ptr(packed),
+                                                     _stream_ptr()), "sv_component_filter_u8")
+        return out
+
     def pack_sparse_bits(self, bits, records):
         """bits int32 [n,H,W//32] (despeckle's packed output) -> records uint8 [n,stride] (device): per frame the row masks of its
         non-zero words and those words (sv_pack_sparse_bits; layout in include/sudoku_vision_hip.h).  A third to a quarter of the
