@@ -375,6 +375,54 @@ int sv_frames_to_digits_v3(sv_ctx *ctx, const uint8_t *frames /*dev*/, int n, in
                            uint8_t *cells /*dev n*81*784 or NULL*/, float *logits /*dev, n*81*10*/,
                            uint8_t *digits /*dev, n*81*/, float *conf /*dev n*81 or NULL*/, void *stream);
 
+/* ---- K12: DigitCNNv3Light and EmptyClassifier forwards (ml/model_v3.py:232-320) -------------------------------------------------- */
+
+/* Floats in the weight blobs of sv_load_weights_v3_light_f32 and sv_load_weights_empty_f32. */
+#define SV_CNN3_LIGHT_PARAMS 53699
+#define SV_CNN3_LIGHT_FEATURES 96
+#define SV_EMPTY_PARAMS 55041
+
+/* blob: the state_dict of DigitCNNv3Light (ml/model_v3.py:245-270) flattened in key order, the int64 num_batches_tracked entries skipped:
+ * temperature[1] features.0.weight[24,1,3,3] features.1.{weight,bias,running_mean,running_var}[24] features.4.weight[48,24,3,3]
+ * features.5.{...}[48] features.8.weight[96,48,3,3] features.9.{...}[96] fc.weight[10,96] fc.bias[10].  n_floats must be
+ * SV_CNN3_LIGHT_PARAMS, else SV_ERR_BAD_ARG.  Every BatchNorm is folded into its convolution here, in double, with eps = 1e-5.
+ * Synchronous.  The model has a weight slot of its own: a context may hold the DigitCNN, DigitCNNv3, DigitCNNv3Light and EmptyClassifier
+ * weights at once, and loading one leaves the others as they are.  The Light and Empty forwards need no scratch of their own. */
+int sv_load_weights_v3_light_f32(sv_ctx *ctx, const float *blob /*host*/, long n_floats);
+
+/* DigitCNNv3Light.forward, ml/model_v3.py:272-276 (eval mode), in true f32 on v_mfma_f32_16x16x4_f32, one launch, activations in LDS:
+ * x f32 [B,1,28,28] -> logits f32 [B,10].  features: the 96 pooled values the fc layer reads (:274).  digits: argmax of the logits.
+ * conf: softmax(logits / temperature) at that digit, get_confidence (:278-282).  Each may be NULL.  A cell's results do not depend on
+ * the rest of the batch, and a cell holding NaN/Inf does not disturb the others (its own logits are unspecified).  B = 0 is SV_OK.
+ * SV_ERR_NO_WEIGHTS before sv_load_weights_v3_light_f32; SV_ERR_UNSUPPORTED on a context set to SV_PREC_BF16.
+ * After sv_ctx_reserve no Light or Empty entry allocates, so they can be captured in a hipGraph. */
+int sv_cnn3_light_forward_f32(sv_ctx *ctx, const float *x /*dev, B*784*/, long B, float *logits /*dev, B*10*/,
+                              float *features /*dev, B*96, or NULL*/, uint8_t *digits /*dev, B, or NULL*/, float *conf /*dev, B, or NULL*/,
+                              void *stream);
+
+/* The same on 8-bit cells with the glue fused in, as sv_cnn3_forward_cells_u8. */
+int sv_cnn3_light_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells /*dev, B*784*/, long B, int glue, float *logits /*dev, B*10*/,
+                                   uint8_t *digits /*dev or NULL*/, float *conf /*dev or NULL*/, void *stream);
+
+/* sv_frames_to_digits with the Light model: K2, then sv_cnn3_light_forward_cells_u8. */
+int sv_frames_to_digits_v3_light(sv_ctx *ctx, const uint8_t *frames /*dev*/, int n, int H, int W,
+                                 ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv /*dev, n*9*/, int glue,
+                                 uint8_t *cells /*dev n*81*784 or NULL*/, float *logits /*dev, n*81*10*/,
+                                 uint8_t *digits /*dev, n*81*/, float *conf /*dev n*81 or NULL*/, void *stream);
+
+/* blob: the state_dict of EmptyClassifier (ml/model_v3.py:292-311) flattened in key order: features.0.weight[16,1,3,3] features.0.bias[16]
+ * features.3.weight[32,16,3,3] features.3.bias[32] classifier.1.weight[32,1568] classifier.1.bias[32] classifier.4.weight[1,32]
+ * classifier.4.bias[1].  n_floats must be SV_EMPTY_PARAMS, else SV_ERR_BAD_ARG.  Synchronous; a weight slot of its own. */
+int sv_load_weights_empty_f32(sv_ctx *ctx, const float *blob /*host*/, long n_floats);
+
+/* EmptyClassifier.forward, ml/model_v3.py:313-315 (eval mode), true f32, one launch: x f32 [B,1,28,28] -> logit f32 [B,1].  The sigmoid
+ * and threshold of is_empty (:317-320) are the caller's.  Batch independence, NaN isolation, B = 0 and the error codes as
+ * sv_cnn3_light_forward_f32, with sv_load_weights_empty_f32 as the load. */
+int sv_empty_forward_f32(sv_ctx *ctx, const float *x /*dev, B*784*/, long B, float *logit /*dev, B*/, void *stream);
+
+/* The same on 8-bit cells with the glue fused in. */
+int sv_empty_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells /*dev, B*784*/, long B, int glue, float *logit /*dev, B*/, void *stream);
+
 /* F.softmax(output, dim=1) then probs.topk(top_k), pipeline/run_v2.py:165-178 (predict_cells_with_alternatives):
  * per cell the k most probable classes, most probable first (index[.,0] = the predicted digit, prob[.,0] = its
  * confidence, the rest = run_v2's `alternatives`).  Equal probabilities: lower class index first.  1 <= k <= 10. */

@@ -77,6 +77,13 @@ SIGNATURES = {
     "sv_cnn3_forward_f32": [_p, _p, _l, _p, _p, _p, _p, _p],
     "sv_cnn3_forward_cells_u8": [_p, _p, _l, _i, _p, _p, _p, _p],
     "sv_frames_to_digits_v3": [_p, _p, _i, _i, _i, _pd, _pd, _p, _i, _p, _p, _p, _p, _p],
+    "sv_load_weights_v3_light_f32": [_p, _p, _l],
+    "sv_cnn3_light_forward_f32": [_p, _p, _l, _p, _p, _p, _p, _p],
+    "sv_cnn3_light_forward_cells_u8": [_p, _p, _l, _i, _p, _p, _p, _p],
+    "sv_frames_to_digits_v3_light": [_p, _p, _i, _i, _i, _pd, _pd, _p, _i, _p, _p, _p, _p, _p],
+    "sv_load_weights_empty_f32": [_p, _p, _l],
+    "sv_empty_forward_f32": [_p, _p, _l, _p, _p],
+    "sv_empty_forward_cells_u8": [_p, _p, _l, _i, _p, _p],
     "sv_frame_quality_stats_u8": [_p, _p, _i, _i, _i, _pd, _pd, _i, _p, _p, _p, _p],
     "sv_grid_line_coverage_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p, _p],
     "sv_grid_line_coverage_bits": [_p, _p, _i, _i, _i, _p, _p, _p],

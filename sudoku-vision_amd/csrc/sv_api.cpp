@@ -40,7 +40,7 @@ extern "C" int sv_ctx_create(int device, sv_ctx **out)
     return SV_OK;
 }
 
-template <class W>   // sv_weights or sv_weights3
+template <class W>   // sv_weights, sv_weights3 or sv_weights_light
 static void free_weights(W &w)
 {
     for (void *p : w.allocs) (void)hipFree(p);
@@ -53,6 +53,8 @@ extern "C" int sv_ctx_destroy(sv_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     free_weights(ctx->w);
     free_weights(ctx->w3);
+    free_weights(ctx->wl);
+    free_weights(ctx->we);
     if (ctx->v3_act) (void)hipFree(ctx->v3_act);
     if (ctx->features) (void)hipFree(ctx->features);
     if (ctx->cells) (void)hipFree(ctx->cells);
@@ -199,6 +201,30 @@ extern "C" int sv_load_weights_v3_f32(sv_ctx *ctx, const float *blob, long n_flo
     int rc = svk_pack_weights_v3(ctx->w3, blob, use_se != 0);
     if (rc) { free_weights(ctx->w3); return rc; }
     return ctx->cap_cells > 0 ? sv_ensure_scratch_v3(ctx, ctx->cap_cells) : SV_OK;
+}
+
+// the Light and Empty loads: `n_floats` against the model's count, then `pack` into the model's own slot
+static int load_light_slot(const char *fn, sv_ctx *ctx, sv_weights_light sv_ctx::*slot, const float *blob, long n_floats, long want, int (*pack)(sv_weights_light &, const float *))
+{
+    if (!ctx || !blob) return sv_fail(SV_ERR_BAD_ARG, "%s: NULL argument", fn);
+    sv_weights_light &w = ctx->*slot;
+    if (n_floats != want) return sv_fail(SV_ERR_BAD_ARG, "%s: %ld floats, the model has %ld", fn, n_floats, want);
+    SV_HIP(hipSetDevice(ctx->device));
+    SV_HIP(hipDeviceSynchronize());                  // a forward still running on the old images
+    free_weights(w);
+    int rc = pack(w, blob);
+    if (rc) free_weights(w);
+    return rc;
+}
+
+extern "C" int sv_load_weights_v3_light_f32(sv_ctx *ctx, const float *blob, long n_floats)
+{
+    return load_light_slot("sv_load_weights_v3_light_f32", ctx, &sv_ctx::wl, blob, n_floats, SV_CNN3_LIGHT_PARAMS, svk_pack_weights_light);
+}
+
+extern "C" int sv_load_weights_empty_f32(sv_ctx *ctx, const float *blob, long n_floats)
+{
+    return load_light_slot("sv_load_weights_empty_f32", ctx, &sv_ctx::we, blob, n_floats, SV_EMPTY_PARAMS, svk_pack_weights_empty);
 }
 
 // ---- host math ------------------------------------------------------------------------------------
@@ -577,6 +603,58 @@ extern "C" int sv_cnn3_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells, long 
     return cnn3_common(ctx, cells, true, glue, B, logits, nullptr, digits, conf, stream);
 }
 
+// what the Light and Empty forwards check and prepare, reported under `fn`: 1 = nothing to do (B == 0), 0 = go on with x (the cells
+// after preprocess_cell where that glue was asked for), else the error
+static int light_prepare(const char *fn, sv_ctx *ctx, const void *&x, bool u8in, int glue, long B, const void *out, const sv_weights_light *w, const char *loader, void *stream)
+{
+    if (ctx && B == 0) return w->loaded ? 1 : sv_fail(SV_ERR_NO_WEIGHTS, "%s: call %s first", fn, loader);
+    int rc = cnn_args_ok(fn, ctx, x, B, (const float *)out, ctx && w->loaded, loader);
+    if (rc) return rc;
+    if (B > 0x7fffffffL) return sv_fail(SV_ERR_BAD_ARG, "%s: B = %ld", fn, B);
+    if (ctx->precision != SV_PREC_F32) return sv_fail(SV_ERR_UNSUPPORTED, "%s: this forward has f32 arithmetic only (context is set to SV_PREC_BF16)", fn);
+    if ((rc = glue_ok(fn, glue))) return rc;
+    if (u8in && glue == SV_GLUE_RUNPY) {             // preprocess_cell as its own pass; its {0,255} output then takes the plain glue
+        if ((rc = sv_ensure_scratch(ctx, B))) return rc;
+        if ((rc = svk_preprocess_cells((const uint8_t *)x, B, ctx->cells2, S(stream)))) return rc;
+        x = ctx->cells2;
+    }
+    return SV_OK;
+}
+
+static int cnn3_light_common(sv_ctx *ctx, const void *x, bool u8in, int glue, long B, float *logits, float *features, uint8_t *digits, float *conf, void *stream)
+{
+    const int rc = light_prepare("sv_cnn3_light_forward", ctx, x, u8in, glue, B, logits, ctx ? &ctx->wl : nullptr, "sv_load_weights_v3_light_f32", stream);
+    if (rc) return rc == 1 ? SV_OK : rc;
+    return svk_cnn3_light_forward(ctx, x, u8in, B, logits, features, digits, conf, S(stream));
+}
+
+extern "C" int sv_cnn3_light_forward_f32(sv_ctx *ctx, const float *x, long B, float *logits, float *features, uint8_t *digits, float *conf, void *stream)
+{
+    return cnn3_light_common(ctx, x, false, SV_GLUE_NORMALIZE, B, logits, features, digits, conf, stream);
+}
+
+extern "C" int sv_cnn3_light_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells, long B, int glue, float *logits, uint8_t *digits, float *conf, void *stream)
+{
+    return cnn3_light_common(ctx, cells, true, glue, B, logits, nullptr, digits, conf, stream);
+}
+
+static int empty_common(sv_ctx *ctx, const void *x, bool u8in, int glue, long B, float *logit, void *stream)
+{
+    const int rc = light_prepare("sv_empty_forward", ctx, x, u8in, glue, B, logit, ctx ? &ctx->we : nullptr, "sv_load_weights_empty_f32", stream);
+    if (rc) return rc == 1 ? SV_OK : rc;
+    return svk_empty_forward(ctx, x, u8in, B, logit, S(stream));
+}
+
+extern "C" int sv_empty_forward_f32(sv_ctx *ctx, const float *x, long B, float *logit, void *stream)
+{
+    return empty_common(ctx, x, false, SV_GLUE_NORMALIZE, B, logit, stream);
+}
+
+extern "C" int sv_empty_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells, long B, int glue, float *logit, void *stream)
+{
+    return empty_common(ctx, cells, true, glue, B, logit, stream);
+}
+
 extern "C" int sv_resize_linear_u8(sv_ctx *ctx, const uint8_t *src, int sh, int sw, ptrdiff_t pitch, uint8_t *dst, int dh, int dw, void *stream)
 {
     REQUIRE(ctx && src && dst, "NULL argument");
@@ -784,27 +862,34 @@ extern "C" int sv_jpeg_reconstruct_sparse_bgr_u8(sv_ctx *ctx, const sv_jpeg_info
     return svk_jpeg_reconstruct(ctx, info, nullptr, masks, offsets, values, quant, bgr, pitch, S(stream));
 }
 
-// K2 into the caller's cells (or the context's), then the forward `v3` selects
-static int frames_to_digits(const char *fn, bool v3, sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv,
+// K2 into the caller's cells (or the context's), then the forward `model` selects: 0 DigitCNN, 1 DigitCNNv3, 2 DigitCNNv3Light
+static int frames_to_digits(const char *fn, int model, sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv,
                             int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)
 {
     REQUIRE_AS(fn, ctx && frames && minv && logits && digits, "NULL argument");
     REQUIRE_AS(fn, frames_ok(n, H, W, pitch), "bad shape");
-    if (!(v3 ? ctx->w3.loaded : ctx->w.loaded)) return sv_fail(SV_ERR_NO_WEIGHTS, "%s: call %s first", fn, v3 ? "sv_load_weights_v3_f32" : "sv_load_weights_f32");
+    static const char *const loader[3] = {"sv_load_weights_f32", "sv_load_weights_v3_f32", "sv_load_weights_v3_light_f32"};
+    if (!(model == 2 ? ctx->wl.loaded : model == 1 ? ctx->w3.loaded : ctx->w.loaded)) return sv_fail(SV_ERR_NO_WEIGHTS, "%s: call %s first", fn, loader[model]);
     const long B = (long)n * SV_CELLS;
     int rc = sv_ensure_scratch(ctx, B);
     if (rc) return rc;
     uint8_t *c = cells ? cells : ctx->cells;
     if ((rc = svk_warp_cells(ctx, frames, n, H, W, pitch, frame_stride, minv, c, S(stream)))) return rc;
-    return v3 ? cnn3_common(ctx, c, true, glue, B, logits, nullptr, digits, conf, stream) : cnn_common(ctx, c, true, glue, B, logits, digits, conf, stream);
+    if (model == 2) return cnn3_light_common(ctx, c, true, glue, B, logits, nullptr, digits, conf, stream);
+    return model == 1 ? cnn3_common(ctx, c, true, glue, B, logits, nullptr, digits, conf, stream) : cnn_common(ctx, c, true, glue, B, logits, digits, conf, stream);
 }
 
 extern "C" int sv_frames_to_digits(sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv, int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)
 {
-    return frames_to_digits("sv_frames_to_digits", false, ctx, frames, n, H, W, pitch, frame_stride, minv, glue, cells, logits, digits, conf, stream);
+    return frames_to_digits("sv_frames_to_digits", 0, ctx, frames, n, H, W, pitch, frame_stride, minv, glue, cells, logits, digits, conf, stream);
 }
 
 extern "C" int sv_frames_to_digits_v3(sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv, int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)
 {
-    return frames_to_digits("sv_frames_to_digits_v3", true, ctx, frames, n, H, W, pitch, frame_stride, minv, glue, cells, logits, digits, conf, stream);
+    return frames_to_digits("sv_frames_to_digits_v3", 1, ctx, frames, n, H, W, pitch, frame_stride, minv, glue, cells, logits, digits, conf, stream);
+}
+
+extern "C" int sv_frames_to_digits_v3_light(sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv, int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)
+{
+    return frames_to_digits("sv_frames_to_digits_v3_light", 2, ctx, frames, n, H, W, pitch, frame_stride, minv, glue, cells, logits, digits, conf, stream);
 }

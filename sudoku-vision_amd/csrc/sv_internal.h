@@ -55,11 +55,22 @@ struct sv_weights3 {
     std::vector<void *> allocs;
 };
 
+// Packed DigitCNNv3Light or EmptyClassifier weights (k12_cnn_v3_light.hip: svk_pack_weights_light / _empty have the layouts)
+struct sv_weights_light {
+    sv_conv3 conv[3];                                    // Light: 1->24, 24->48, 48->96 (BatchNorm folded); Empty: 1->16, 16->32 (own bias)
+    float *fc1_w = nullptr, *fc1_b = nullptr;            // Light: fc [10][128] (zero-padded from 96), [10]; Empty: classifier.1 [8][49][32][4], [32]
+    float *fc2_w = nullptr, *fc2_b = nullptr;            // Empty: classifier.4 [32], [1]
+    float temperature = 1.f;
+    bool loaded = false;
+    std::vector<void *> allocs;
+};
+
 struct sv_ctx {
     int device = 0;
     int num_cus = 256;
     sv_weights w;
     sv_weights3 w3;
+    sv_weights_light wl, we;    // DigitCNNv3Light, EmptyClassifier
     float *v3_act = nullptr;    // k8_cnn_v3.hip: three activation buffers of [cap_v3][32*784] floats
     long cap_v3 = 0;            // cells, at most SV_V3_SUBBATCH
     // grow-only scratch
@@ -182,6 +193,12 @@ int svk_pack_weights_v3(sv_weights3 &w, const float *blob, bool use_se);
 long svk_v3_blob_floats(bool use_se);
 size_t svk_v3_scratch_bytes(long cells);
 int svk_cnn3_forward(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *logits, float *features, u8 *digits, float *conf, hipStream_t s);
+
+// k12_cnn_v3_light.hip
+int svk_pack_weights_light(sv_weights_light &w, const float *blob);
+int svk_pack_weights_empty(sv_weights_light &w, const float *blob);
+int svk_cnn3_light_forward(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *logits, float *features, u8 *digits, float *conf, hipStream_t s);
+int svk_empty_forward(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *logit, hipStream_t s);
 
 // k9_resolve.hip
 int svk_resolve_conflicts(const u8 *index, const float *prob, long n, int k, int beam_width, int max_corrections, double min_alt_conf, int accept, u8 *digits,

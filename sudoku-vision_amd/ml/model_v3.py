@@ -1,14 +1,16 @@
 """MI355X drop-in for the reference's ml/model_v3.py: `DigitCNNv3` keeps the state_dict keys, constructor and call protocol that
 pipeline/run_v2.py:95-128 relies on; forward() runs the hand-written HIP kernels of csrc/k8_cnn_v3.hip (true f32 on the matrix pipe,
-BatchNorm folded into the convolutions when the weights are packed).  Inference only, GPU only.
+BatchNorm folded into the convolutions when the weights are packed).  `DigitCNNv3Light` and `EmptyClassifier` do the same through
+csrc/k12_cnn_v3_light.hip, one launch per forward.  Inference only, GPU only.  `calibrate_temperature` is plain torch on the logits.
 
 The submodules below exist to hold parameters and buffers under the reference's names, so that a reference checkpoint loads with
-strict=True; none of them is ever called.  Not provided: DigitCNNv3Light, EmptyClassifier, calibrate_temperature (run_v2 uses none)."""
+strict=True; none of them is ever called.  Not provided: MC dropout (forward_with_uncertainty needs train-mode dropout)."""
 import os
 import sys
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from _bootstrap import package  # noqa: E402
@@ -86,6 +88,95 @@ class DigitCNNv3(nn.Module):
     def set_temperature(self, temperature: float):
         with torch.no_grad():
             self.temperature.fill_(temperature)         # in place on the parameter itself, so that its version (the re-pack key) moves
+
+
+def _state_key(module):
+    # parameters AND BatchNorm buffers: running statistics are folded into the packed weights
+    return (id(module), tuple((v.data_ptr(), v._version) for v in module.state_dict(keep_vars=True).values()))
+
+
+class DigitCNNv3Light(nn.Module):
+    """The lighter digit classifier of the reference's ml/model_v3.py:232-282: three conv + BatchNorm + ReLU stages (24, 48, 96 channels,
+    the first two max-pooled), global average pool, fc; `temperature` calibrates get_confidence."""
+
+    def __init__(self, num_classes: int = 10, dropout: float = 0.5):
+        super().__init__()
+        if num_classes != 10:
+            raise NotImplementedError("the HIP forward is specialised for the reference's 10 classes")
+        self.features = nn.Sequential(*_conv_bn(1, 24, 3, 1), nn.ReLU(inplace=True), nn.MaxPool2d(2, 2),
+                                      *_conv_bn(24, 48, 3, 1), nn.ReLU(inplace=True), nn.MaxPool2d(2, 2),
+                                      *_conv_bn(48, 96, 3, 1), nn.ReLU(inplace=True))
+        self.gap = nn.AdaptiveAvgPool2d(1)
+        self.dropout = nn.Dropout(dropout)          # identity in eval mode, the only mode there is here
+        self.fc = nn.Linear(96, num_classes)
+        self.temperature = nn.Parameter(torch.ones(1), requires_grad=False)
+
+    def _context(self, x):
+        ctx = _rt._model_context(x, self.training, "DigitCNNv3Light", "dropout is identity and BatchNorm uses its running statistics")
+        key = _state_key(self)
+        if ctx._weights_light_key != key:
+            ctx.load_state_dict_v3_light(self.state_dict(), key=key)
+        return ctx
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self._context(x).cnn3_light_forward(x.to(torch.float32).contiguous())
+
+    def get_confidence(self, x: torch.Tensor):
+        """(predicted class, softmax(logits / temperature) at it) -- reference ml/model_v3.py:278-282."""
+        _, digits, conf = self._context(x).cnn3_light_forward(x.to(torch.float32).contiguous(), want_digits=True)
+        return digits.to(torch.int64), conf
+
+    def set_temperature(self, temperature: float):
+        with torch.no_grad():
+            self.temperature.fill_(temperature)         # in place on the parameter itself, so that its version (the re-pack key) moves
+
+
+class EmptyClassifier(nn.Module):
+    """The empty-cell classifier of the reference's ml/model_v3.py:285-320: two conv + ReLU + maxpool stages (16, 32 channels, with bias),
+    Linear(1568, 32) + ReLU, Linear(32, 1); forward returns the logit, is_empty thresholds its sigmoid."""
+
+    def __init__(self):
+        super().__init__()
+        self.features = nn.Sequential(nn.Conv2d(1, 16, kernel_size=3, padding=1), nn.ReLU(inplace=True), nn.MaxPool2d(2, 2),
+                                      nn.Conv2d(16, 32, kernel_size=3, padding=1), nn.ReLU(inplace=True), nn.MaxPool2d(2, 2))
+        self.classifier = nn.Sequential(nn.Flatten(), nn.Linear(32 * 7 * 7, 32), nn.ReLU(inplace=True), nn.Dropout(0.3), nn.Linear(32, 1))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        ctx = _rt._model_context(x, self.training, "EmptyClassifier", "dropout is identity")
+        key = _state_key(self)
+        if ctx._weights_empty_key != key:
+            ctx.load_state_dict_empty(self.state_dict(), key=key)
+        return ctx.empty_forward(x.to(torch.float32).contiguous())
+
+    def is_empty(self, x: torch.Tensor, threshold: float = 0.5) -> torch.Tensor:
+        """Boolean [batch, 1]: the cells judged empty (reference ml/model_v3.py:317-320)."""
+        return torch.sigmoid(self.forward(x)) < threshold
+
+
+def calibrate_temperature(model: nn.Module, val_loader, device, lr: float = 0.01, max_iter: int = 50) -> float:
+    """The temperature that minimises the negative log-likelihood of softmax(logits / T) on a validation set (reference
+    ml/model_v3.py:328-371): the model's logits over val_loader's (data, target) batches are gathered once, then one LBFGS step of up to
+    max_iter iterations runs on cross_entropy(logits / T, labels) from T = 1.5.  Calls nothing of the model but eval() and forward."""
+    model.eval()
+    gathered, targets = [], []
+    with torch.no_grad():
+        for data, target in val_loader:
+            gathered.append(model(data.to(device)))
+            targets.append(target.to(device))
+    logits, labels = torch.cat(gathered), torch.cat(targets)
+    t = nn.Parameter(torch.full((1,), 1.5, device=device))
+    opt = torch.optim.LBFGS([t], lr=lr, max_iter=max_iter)
+
+    def closure():
+        opt.zero_grad()
+        loss = F.cross_entropy(logits / t, labels)
+        loss.backward()
+        return loss
+
+    opt.step(closure)
+    value = t.item()
+    print(f"Calibrated temperature: {value:.4f}")
+    return value
 
 
 def count_parameters(model: nn.Module) -> int:

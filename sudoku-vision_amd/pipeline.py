@@ -340,6 +340,7 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     model="v3": the model run_v2 loads (pipeline/run_v2.py:95-128), DigitCNNv3; model_state_dict is then its state_dict and the same
     call order runs with the v3 forward.  `confidence` is softmax(logits / temperature) at the digit; the top_k alternatives come from
     softmax(logits), without the temperature, as at run_v2.py:166-180.
+    model="v3_light": the same with DigitCNNv3Light (ml/model_v3.py:232-282), the reference's lighter model; model_state_dict is its state_dict.
     resolve=True (implies top_k=3 unless more are asked for; at most 4): run_v2's validation and correction stage (pipeline/run_v2.py:344-371)
     on the device: `validation` (is_valid, num_conflicts, cells_in_conflict of the cells run_v2 goes on with), `corrections` (the
     (row, col, old digit, new digit, old confidence, new confidence) taken: those of a repair that succeeded or left fewer conflicts,
@@ -352,11 +353,13 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     from .runtime import default_context
     if preprocess not in ("v1", "v2"):
         raise ValueError(f"preprocess must be 'v1' or 'v2', got {preprocess!r}")
-    if model not in ("v1", "v3"):
-        raise ValueError(f"model must be 'v1' or 'v3', got {model!r}")
+    if model not in ("v1", "v3", "v3_light"):
+        raise ValueError(f"model must be 'v1', 'v3' or 'v3_light', got {model!r}")
     ctx = ctx or default_context()
+    load, forward = {"v1": (ctx.load_state_dict, ctx.frames_to_digits), "v3": (ctx.load_state_dict_v3, ctx.frames_to_digits_v3),
+                     "v3_light": (ctx.load_state_dict_v3_light, ctx.frames_to_digits_v3_light)}[model]
     if model_state_dict is not None:
-        (ctx.load_state_dict_v3 if model == "v3" else ctx.load_state_dict)(model_state_dict)
+        load(model_state_dict)
     if isinstance(image, torch.Tensor):             # already in HBM (imgcodecs.imread(..., device=True))
         frames = image.contiguous()[None]
     else:
@@ -376,7 +379,7 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     if corners is None:
         return None
     minv = ctx.minv_to_device(Context.corners_to_minv(corners[None].astype(np.float32)))
-    out = (ctx.frames_to_digits_v3 if model == "v3" else ctx.frames_to_digits)(frames, minv, glue=glue)
+    out = forward(frames, minv, glue=glue)
     digits = out["digits"][0].cpu().numpy()
     res = {"grid": [[int(digits[r * 9 + c]) for c in range(9)] for r in range(9)], "digits": digits,
            "confidence": out["conf"][0].cpu().numpy(), "logits": out["logits"][0].cpu().numpy(), "corners": corners}

@@ -36,9 +36,30 @@ def v3_layout(use_se=True):
     return out + [("fc.weight", (10, 128)), ("fc.bias", (10,))]
 
 
-def _state_blob(sd, layout, model):
+def light_layout():
+    """(key, shape) of every float entry of a DigitCNNv3Light state_dict (ml/model_v3.py), in key order: the blob
+    sv_load_weights_v3_light_f32 takes.  The int64 num_batches_tracked entries are not part of it."""
+    out = [("temperature", (1,))]
+    for i, (cin, c) in zip((0, 4, 8), ((1, 24), (24, 48), (48, 96))):
+        out += [(f"features.{i}.weight", (c, cin, 3, 3))] + [(f"features.{i + 1}.{n}", (c,)) for n in ("weight", "bias", "running_mean", "running_var")]
+    return out + [("fc.weight", (10, 96)), ("fc.bias", (10,))]
+
+
+def empty_layout():
+    """(key, shape) of an EmptyClassifier state_dict (ml/model_v3.py), in key order: the blob sv_load_weights_empty_f32 takes."""
+    return [("features.0.weight", (16, 1, 3, 3)), ("features.0.bias", (16,)), ("features.3.weight", (32, 16, 3, 3)), ("features.3.bias", (32,)),
+            ("classifier.1.weight", (32, 1568)), ("classifier.1.bias", (32,)), ("classifier.4.weight", (1, 32)), ("classifier.4.bias", (1,))]
+
+
+def _state_blob(sd, layout, model, strict=False):
     """sd: a state_dict of `model` -- tensors or arrays, any device -> its `layout` entries ((key, shape) pairs) as one float32 host
-    array in that order.  KeyError for a missing key, ValueError for a wrong shape; entries outside the layout are not looked at."""
+    array in that order.  KeyError for a missing key, ValueError for a wrong shape; entries outside the layout are not looked at, or with
+    `strict` are a ValueError unless they are num_batches_tracked counters."""
+    if strict:
+        known = dict(layout)
+        extra = [k for k in sd if not k.endswith("num_batches_tracked") and k not in known]
+        if extra:
+            raise ValueError(f"not {model} keys: {extra[:4]}")
     parts = []
     for k, shape in layout:
         if k not in sd:
@@ -165,6 +186,8 @@ class Context:
         self._check(self._lib.sv_ctx_create(self.device.index, C.byref(self._h)), "sv_ctx_create")
         self._weights_key = None
         self._weights_v3_key = None
+        self._weights_light_key = None
+        self._weights_empty_key = None
 
     def _check(self, rc, what):
         _native.check(rc, what, self._lib)
@@ -211,13 +234,22 @@ class Context:
             use_se = has_se
         elif bool(use_se) != has_se:
             raise ValueError(f"use_se={use_se} but the state_dict {'has' if has_se else 'has no'} se.excite weights")
-        layout = v3_layout(bool(use_se))
-        extra = [k for k in sd if not k.endswith("num_batches_tracked") and k not in dict(layout)]
-        if extra:
-            raise ValueError(f"not DigitCNNv3 keys: {extra[:4]}")
-        blob = _state_blob(sd, layout, "DigitCNNv3")
+        blob = _state_blob(sd, v3_layout(bool(use_se)), "DigitCNNv3", strict=True)
         self._check(self._lib.sv_load_weights_v3_f32(self._h, blob.ctypes.data_as(C.c_void_p), blob.size, int(bool(use_se))), "sv_load_weights_v3_f32")
         self._weights_v3_key = key
+
+    def load_state_dict_v3_light(self, sd, key=None):
+        """sd: DigitCNNv3Light state_dict (ml/model_v3.py) -- tensors or arrays, any device; num_batches_tracked entries are ignored.
+        A weight slot of its own: the other models' weights stay as they are."""
+        blob = _state_blob(sd, light_layout(), "DigitCNNv3Light", strict=True)
+        self._check(self._lib.sv_load_weights_v3_light_f32(self._h, blob.ctypes.data_as(C.c_void_p), blob.size), "sv_load_weights_v3_light_f32")
+        self._weights_light_key = key
+
+    def load_state_dict_empty(self, sd, key=None):
+        """sd: EmptyClassifier state_dict (ml/model_v3.py) -- tensors or arrays, any device.  A weight slot of its own."""
+        blob = _state_blob(sd, empty_layout(), "EmptyClassifier", strict=True)
+        self._check(self._lib.sv_load_weights_empty_f32(self._h, blob.ctypes.data_as(C.c_void_p), blob.size), "sv_load_weights_empty_f32")
+        self._weights_empty_key = key
 
     PREC_F32, PREC_BF16 = 0, 1
 
@@ -646,28 +678,50 @@ class Context:
         self._check(rc, "sv_cnn_forward")
         return (logits, digits, conf) if want_digits else logits
 
-    def cnn3_forward(self, x, want_digits=False, want_features=False, glue=0):
-        """DigitCNNv3.forward (ml/model_v3.py): x f32 [B,1,28,28], or u8 [B,28,28] cells with the run_v2.py glue fused in (as cnn_forward)
-        -> logits [B,10]; with want_digits (logits, digits, conf), conf = softmax(logits / temperature)[digit]; with want_features the
-        128 pooled features [B,128] come last (f32 input only)."""
+    def _cnn3_forward(self, entry, nfeat, x, want_digits, want_features, glue):
+        """cnn3_forward through the library's `entry`_f32 / `entry`_cells_u8, for a model with `nfeat` pooled features."""
         x, logits, digits, conf = self._cnn_args(x, want_digits)
         B = x.shape[0]
         if want_features and x.dtype == torch.uint8:
-            raise ValueError("want_features needs f32 input (sv_cnn3_forward_f32)")
-        feats = torch.empty((B, 128), dtype=torch.float32, device=self.device) if want_features else None
+            raise ValueError(f"want_features needs f32 input ({entry}_f32)")
+        feats = torch.empty((B, nfeat), dtype=torch.float32, device=self.device) if want_features else None
         if x.dtype == torch.uint8:
-            rc = self._lib.sv_cnn3_forward_cells_u8(self._h, _ptr(x), B, int(glue), _ptr(logits), _opt_ptr(digits), _opt_ptr(conf), _stream_ptr())
+            rc = getattr(self._lib, entry + "_cells_u8")(self._h, _ptr(x), B, int(glue), _ptr(logits), _opt_ptr(digits), _opt_ptr(conf), _stream_ptr())
         else:
-            rc = self._lib.sv_cnn3_forward_f32(self._h, _ptr(x), B, _ptr(logits), _opt_ptr(feats), _opt_ptr(digits), _opt_ptr(conf), _stream_ptr())
-        self._check(rc, "sv_cnn3_forward")
+            rc = getattr(self._lib, entry + "_f32")(self._h, _ptr(x), B, _ptr(logits), _opt_ptr(feats), _opt_ptr(digits), _opt_ptr(conf), _stream_ptr())
+        self._check(rc, entry)
         out = (logits, digits, conf) if want_digits else (logits,)
         if want_features:
             out += (feats,)
         return out if len(out) > 1 else logits
 
+    def cnn3_forward(self, x, want_digits=False, want_features=False, glue=0):
+        """DigitCNNv3.forward (ml/model_v3.py): x f32 [B,1,28,28], or u8 [B,28,28] cells with the run_v2.py glue fused in (as cnn_forward)
+        -> logits [B,10]; with want_digits (logits, digits, conf), conf = softmax(logits / temperature)[digit]; with want_features the
+        128 pooled features [B,128] come last (f32 input only)."""
+        return self._cnn3_forward("sv_cnn3_forward", 128, x, want_digits, want_features, glue)
+
+    def cnn3_light_forward(self, x, want_digits=False, want_features=False, glue=0):
+        """DigitCNNv3Light.forward (ml/model_v3.py), after load_state_dict_v3_light: the arguments and results of cnn3_forward, with 96
+        pooled features [B,96]."""
+        return self._cnn3_forward("sv_cnn3_light_forward", 96, x, want_digits, want_features, glue)
+
+    def empty_forward(self, x, glue=0):
+        """EmptyClassifier.forward (ml/model_v3.py), after load_state_dict_empty: x as cnn3_forward takes it -> logit f32 [B,1]; a cell is
+        empty where sigmoid(logit) is below the caller's threshold."""
+        x, _, _, _ = self._cnn_args(x, False)
+        B = x.shape[0]
+        logit = torch.empty((B, 1), dtype=torch.float32, device=self.device)
+        if x.dtype == torch.uint8:
+            rc = self._lib.sv_empty_forward_cells_u8(self._h, _ptr(x), B, int(glue), _ptr(logit), _stream_ptr())
+        else:
+            rc = self._lib.sv_empty_forward_f32(self._h, _ptr(x), B, _ptr(logit), _stream_ptr())
+        self._check(rc, "sv_empty_forward")
+        return logit
+
     # ---- whole path ---------------------------------------------------------------------------
     def _frames_to_digits(self, entry, frames, minv_dev, out, keep_cells, glue):
-        """frames_to_digits through the library's `entry`: sv_frames_to_digits or sv_frames_to_digits_v3."""
+        """frames_to_digits through the library's `entry`: sv_frames_to_digits, sv_frames_to_digits_v3 or sv_frames_to_digits_v3_light."""
         frames, pitch, fstride = _frame_layout(frames, self.device)
         n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
         minv_dev = self._minv(minv_dev, n)
@@ -688,6 +742,10 @@ class Context:
     def frames_to_digits_v3(self, frames, minv_dev, out=None, keep_cells=False, glue=0):
         """frames_to_digits with the DigitCNNv3 forward (load_state_dict_v3): same arguments, same dict."""
         return self._frames_to_digits("sv_frames_to_digits_v3", frames, minv_dev, out, keep_cells, glue)
+
+    def frames_to_digits_v3_light(self, frames, minv_dev, out=None, keep_cells=False, glue=0):
+        """frames_to_digits with the DigitCNNv3Light forward (load_state_dict_v3_light): same arguments, same dict."""
+        return self._frames_to_digits("sv_frames_to_digits_v3_light", frames, minv_dev, out, keep_cells, glue)
 
     # ---- quality gate (cv/grid_quality.py) ------------------------------------------------------
     def frame_quality_stats(self, frames, out=None):
