@@ -2,20 +2,19 @@
 //
 // One launch per forward.  One 256-thread workgroup carries one cell from its input to its logits; every activation stays in LDS
 // (the largest, 24 x 14 x 14, is 26 KB with its zero border), weights are read from L2 as MFMA B-operand images.  All matrix work is
-// v_mfma_f32_16x16x4_f32, A from one ds_read_b32 per lane as in k_conv3 (k8_cnn_v3.hip), B one coalesced global dword per lane.
+// v_mfma_f32_16x16x4_f32; the conv core (LDS planes, K loop, weight image) is sv_conv_f32.h's, the scheme of k8_cnn_v3.hip.
 //
 //   conv_in : the first convolution of either model (1 input channel, 28x28).  With one channel the K of the implicit GEMM is the tap:
-//        K = 4 taps per instruction, 3 instructions per tile (taps 9..11 carry zero weights).  k_conv3's scheme (K = 4 input channels of one
-//        tap) would spend 9 instructions on three zero planes.
-//   conv_lds : the other convolutions, K = 4 input channels of one tap, input channel groups outer, taps inner, as k_conv3.
+//        K = 4 taps per instruction, 3 instructions per tile (taps 9..11 carry zero weights).  The shared scheme (K = 4 input channels of
+//        one tap) would spend 9 instructions on three zero planes.
+//   conv_lds : the other convolutions, on the shared K loop, LDS to LDS.
 //   Max pooling is an epilogue: in a pooled layer the 16 rows of an M tile are four 2x2 windows, row 4 w + r = pixel r of window w.  The
 //        MFMA result then has the four pixels of one window in the four accumulator registers of one lane, and the pool is three fmaxf
 //        in registers.  relu(max(x) + b) = max(relu(x + b)): + b and relu are monotone and round monotonically, so the bias and ReLU are
-//        applied once, after the max.  Input planes of pooled layers are padded to 8 mod 32 floats, which puts the 2x2 windows of lanes
-//        0..31 on 32 different banks; the others to 16 mod 32 as k_conv3.
+//        applied once, after the max.  Input planes of pooled layers are padded to 8 mod 32 floats (sv_conv_plane), the others to 16.
 //   N = 24 (Light's first layer) is two 16-channel tiles whose last 8 columns have zero weights and are not stored.
 //   Light: conv_in(24) -> pool -> conv_lds(24 -> 48) -> pool -> conv_lds(48 -> 96) -> mean over the 49 positions in order 0..48 ->
-//        fc through sv_fc2_logit (features and fc.weight zero-padded from 96 to its 128: fmaf(0, 0, s) = s) -> argmax / softmax as k_head3.
+//        sv_head_tail (features and fc.weight zero-padded from 96 to sv_fc2_logit's 128: fmaf(0, 0, s) = s).
 //   Empty: conv_in(16) -> pool -> conv_lds(16 -> 32) -> pool -> flatten [c][y][x] -> Linear(1568 -> 32): thread (j = tid & 31, s = tid >> 5)
 //        sums segment s (196 terms, in order) of output j with fmaf, eight segments are added in order 0..7, + bias, ReLU ->
 //        Linear(32 -> 1) by one thread.
@@ -23,31 +22,14 @@
 #include <cmath>
 #include <vector>
 
-#include "sv_device.h"
+#include "sv_conv_f32.h"
 #include "sv_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int plane16(int hin) { return (((hin + 2) * (hin + 2) - 16 + 31) / 32) * 32 + 16; }   // zero-bordered plane, 16 mod 32 floats
-constexpr int plane8(int hin) { return (((hin + 2) * (hin + 2) - 8 + 31) / 32) * 32 + 8; }      // 8 mod 32: input of a pooled layer
-
-constexpr int IN_PLANE = 912;            // 30 x 30 zero-bordered input
-constexpr int P14 = plane8(14);          // 264: 16 x 16 zero-bordered plane, read by a pooled layer
-constexpr int P7 = plane16(7);           // 112: 9 x 9 zero-bordered plane, read by an unpooled layer
-
-// x (this cell's 784 values) -> the zero-bordered 30 x 30 plane sin.  sin's border was zeroed by the caller.
-template <bool U8IN>
-__device__ __forceinline__ void load_input(const void *x, long cell, float *sin, int tid)
-{
-    for (int i = tid; i < 784; i += 256) {
-        float v;
-        if (U8IN) v = sv_glue_norm(((const u8 *)x)[cell * 784 + i]);
-        else v = ((const float *)x)[cell * 784 + i];
-        sin[(i / 28 + 1) * 30 + i % 28 + 1] = v;
-    }
-}
+constexpr int IN_PLANE = sv_conv_plane(28, 16);   // 912: 30 x 30 zero-bordered input
+constexpr int P14 = sv_conv_plane(14, 8);         // 264: 16 x 16 zero-bordered plane, read by a pooled layer
+constexpr int P7 = sv_conv_plane(7, 16);          // 112: 9 x 9 zero-bordered plane, read by an unpooled layer
 
 // First layer: sin (30 x 30) -> conv3x3 to 16 NT channels + bias + ReLU + maxpool 2x2 -> sout [COUT][P14] (16 x 16 zero-bordered planes).
 // wp: [NT][3 kk][64 lane]: lane l holds w'[oc = 16 nt + (l & 15)][tap = 4 kk + (l >> 4)], zero where tap > 8 or oc >= COUT.  bias [16 NT].
@@ -82,7 +64,7 @@ __device__ __forceinline__ void conv_in(const float *sin, const float *__restric
 }
 
 // sin [CIN][IPLANE] zero-bordered (HIN+2)^2 planes -> conv3x3 to 16 NT channels + bias + ReLU (+ maxpool 2x2 when POOL) -> sout: channel oc at
-// oc * OPLANE, output pixel (y, x) at (y + OB) * OPW + x + OB.  wp: k_conv3's image [NT][CIN/4][9][64 lane].  MB M-tiles share each B value.
+// oc * OPLANE, output pixel (y, x) at (y + OB) * OPW + x + OB.  wp: sv_pack_conv_image's [NT][CIN/4][9][64 lane].  MB M-tiles share each B value.
 template <int CIN, int NT, int HIN, int IPLANE, int MB, bool POOL, int OPLANE, int OPW, int OB>
 __device__ __forceinline__ void conv_lds(const float *sin, const float *__restrict__ wp, const float *__restrict__ bias, float *sout, int wave, int lane)
 {
@@ -109,25 +91,7 @@ __device__ __forceinline__ void conv_lds(const float *sin, const float *__restri
         f32x4 acc[MB];
 #pragma unroll
         for (int i = 0; i < MB; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const float *wb = wp + nt * (G4 * 9 * 64) + lane;
-        float bcur[9], bnext[9];
-#pragma unroll
-        for (int t = 0; t < 9; t++) bcur[t] = wb[t * 64];
-        for (int g = 0; g < G4; g++) {
-            const int gn = g + 1 < G4 ? g + 1 : g;
-#pragma unroll
-            for (int t = 0; t < 9; t++) bnext[t] = wb[(gn * 9 + t) * 64];
-#pragma unroll
-            for (int t = 0; t < 9; t++) {
-#pragma unroll
-                for (int i = 0; i < MB; i++) {
-                    const float a = sin[base[i] + g * 4 * IPLANE + (t / 3) * PW + t % 3];
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bcur[t], acc[i], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < 9; t++) bcur[t] = bnext[t];
-        }
+        sv_conv_kloop<G4, 3, PW, IPLANE, MB>(sin, base, wp + nt * (G4 * 9 * 64) + lane, acc);
         const int oc = nt * 16 + m;
         const float bv = bias[oc];
         float *o = sout + oc * OPLANE + OB * OPW + OB;
@@ -159,7 +123,7 @@ __global__ __launch_bounds__(256) void k_light(const void *__restrict__ x, const
     constexpr int A1 = 24 * P14, A2 = 48 * P7, A3 = 96 * 49;
     static_assert(A3 <= A1, "conv3's output takes conv1's place");
     __shared__ float sm[IN_PLANE + A1 + A2];
-    __shared__ float f[128], lg[10];
+    __shared__ float f[128];
     float *sin = sm, *act1 = sm + IN_PLANE, *act2 = act1 + A1, *act3 = act1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long cell = blockIdx.x;
@@ -167,7 +131,7 @@ __global__ __launch_bounds__(256) void k_light(const void *__restrict__ x, const
     for (int i = tid; i < IN_PLANE + A1 + A2; i += 256) sm[i] = 0.f;
     if (tid < 128) f[tid] = 0.f;
     __syncthreads();
-    load_input<U8IN>(x, cell, sin, tid);
+    sv_conv_load_input<U8IN, 1, 28, IN_PLANE>(x, cell, sin, tid);
     __syncthreads();
     conv_in<2, 24>(sin, w1, b1, act1, wave, lane);
     __syncthreads();
@@ -183,24 +147,7 @@ __global__ __launch_bounds__(256) void k_light(const void *__restrict__ x, const
         f[tid] = s;
         if (features) features[cell * 96 + tid] = s;
     }
-    __syncthreads();
-    if (tid < 10) {
-        lg[tid] = sv_fc2_logit(f, (const float(*)[128])fcw, fcb, tid);
-        logits[cell * 10 + tid] = lg[tid];
-    }
-    __syncthreads();
-    if (tid == 0 && (digits || conf)) {
-        int arg = 0;
-        for (int j = 1; j < 10; j++)
-            if (lg[j] > lg[arg]) arg = j;
-        if (digits) digits[cell] = (u8)arg;
-        if (conf) {
-            const float best = lg[arg] / temperature;
-            float den = 0.f;
-            for (int j = 0; j < 10; j++) den += expf(lg[j] / temperature - best);
-            conf[cell] = 1.0f / den;
-        }
-    }
+    sv_head_tail(f, fcw, fcb, temperature, cell, logits, digits, conf);
 }
 
 // x: B cells -> logit [B].  f1w: [8 s][49 i4][32 j][4 e] = classifier.1.weight[j][196 s + 4 i4 + e]
@@ -219,7 +166,7 @@ __global__ __launch_bounds__(256) void k_empty(const void *__restrict__ x, const
 
     for (int i = tid; i < IN_PLANE + A1; i += 256) sm[i] = 0.f;
     __syncthreads();
-    load_input<U8IN>(x, cell, sin, tid);
+    sv_conv_load_input<U8IN, 1, 28, IN_PLANE>(x, cell, sin, tid);
     __syncthreads();
     conv_in<1, 16>(sin, w1, b1, act1, wave, lane);
     __syncthreads();
@@ -253,46 +200,35 @@ __global__ __launch_bounds__(256) void k_empty(const void *__restrict__ x, const
     }
 }
 
-int upload12(sv_weights_light &w, float **dst, const std::vector<float> &src)
-{
-    SV_HIP(hipMalloc((void **)dst, src.size() * sizeof(float)));
-    w.allocs.push_back(*dst);
-    SV_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(float), hipMemcpyHostToDevice));
-    return SV_OK;
-}
-
-// One convolution of the blob at p: weight [cout][cin][3][3], then either its BatchNorm (gamma, beta, running mean, running var: folded in
-// float64 and rounded once, w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps), eps = 1e-5) or its own bias [cout].
-// cin == 1: conv_in's image [cout16/16][3 kk][64 lane]; else conv_lds's [cout/16][cin/4][9][64 lane].  Bias padded to a multiple of 16.
+// One convolution of the blob at p: weight [cout][cin][3][3], then either its BatchNorm (gamma, beta, running mean, running var: folded by
+// sv_fold_bn) or its own bias [cout].  cin == 1: conv_in's tap-K image [cout16/16][3 kk][64 lane]; else sv_pack_conv_image's.  Bias padded to
+// a multiple of 16.
 int pack_conv12(sv_weights_light &w, sv_conv3 &dst, const float *&p, int cout, int cin, bool has_bn)
 {
-    const int cout16 = (cout + 15) / 16 * 16, g4 = cin / 4;
+    const int cout16 = (cout + 15) / 16 * 16;
     const float *cw = p;
     p += (size_t)cout * cin * 9;
-    std::vector<double> k(cout, 1.0);
+    std::vector<double> k(cout);
     std::vector<float> b(cout16, 0.f);
     if (has_bn) {
-        const float *gamma = p, *beta = gamma + cout, *mean = beta + cout, *var = mean + cout;
-        p = var + cout;
-        for (int oc = 0; oc < cout; oc++) {
-            k[oc] = (double)gamma[oc] / std::sqrt((double)var[oc] + 1e-5);
-            b[oc] = (float)((double)beta[oc] - (double)mean[oc] * k[oc]);
-        }
+        sv_fold_bn(p, p + cout, p + 2 * cout, p + 3 * cout, cout, k.data(), b.data());
+        p += 4 * cout;
     } else {
         for (int oc = 0; oc < cout; oc++) b[oc] = p[oc];
         p += cout;
     }
-    std::vector<float> img(cin == 1 ? (size_t)cout16 / 16 * 3 * 64 : (size_t)cout16 * cin * 9, 0.f);
-    for (int oc = 0; oc < cout; oc++)
-        for (int ic = 0; ic < cin; ic++)
-            for (int t = 0; t < 9; t++) {
-                const float v = has_bn ? (float)((double)cw[((size_t)oc * cin + ic) * 9 + t] * k[oc]) : cw[((size_t)oc * cin + ic) * 9 + t];
-                if (cin == 1) img[((size_t)(oc / 16) * 3 + t / 4) * 64 + (t & 3) * 16 + (oc & 15)] = v;
-                else img[(((size_t)(oc / 16) * g4 + ic / 4) * 9 + t) * 64 + (ic & 3) * 16 + (oc & 15)] = v;
-            }
+    std::vector<float> img;
+    if (cin == 1) {
+        img.assign((size_t)cout16 / 16 * 3 * 64, 0.f);
+        for (int oc = 0; oc < cout; oc++)
+            for (int t = 0; t < 9; t++)
+                img[((size_t)(oc / 16) * 3 + t / 4) * 64 + (t & 3) * 16 + (oc & 15)] = has_bn ? (float)((double)cw[oc * 9 + t] * k[oc]) : cw[oc * 9 + t];
+    } else {
+        img = sv_pack_conv_image(cw, has_bn ? k.data() : nullptr, cout, cin, 9);
+    }
     int rc;
-    if ((rc = upload12(w, &dst.w, img))) return rc;
-    return upload12(w, &dst.b, b);
+    if ((rc = sv_upload(w, &dst.w, img.data(), img.size()))) return rc;
+    return sv_upload(w, &dst.b, b.data(), b.size());
 }
 
 }  // namespace
@@ -310,8 +246,8 @@ int svk_pack_weights_light(sv_weights_light &w, const float *blob)
     for (int j = 0; j < 10; j++)
         for (int n = 0; n < 96; n++) fcw[j * 128 + n] = p[j * 96 + n];
     p += 960;
-    if ((rc = upload12(w, &w.fc1_w, fcw))) return rc;
-    if ((rc = upload12(w, &w.fc1_b, std::vector<float>(p, p + 10)))) return rc;
+    if ((rc = sv_upload(w, &w.fc1_w, fcw.data(), fcw.size()))) return rc;
+    if ((rc = sv_upload(w, &w.fc1_b, p, 10))) return rc;
     p += 10;
     if (p - blob != SV_CNN3_LIGHT_PARAMS) return sv_fail(SV_ERR_BAD_ARG, "svk_pack_weights_light: walked %ld floats", (long)(p - blob));
     w.loaded = true;
@@ -329,12 +265,12 @@ int svk_pack_weights_empty(sv_weights_light &w, const float *blob)
     for (int j = 0; j < 32; j++)
         for (int n = 0; n < 1568; n++) f1[(((size_t)(n / 196) * 49 + (n % 196) / 4) * 32 + j) * 4 + n % 4] = p[(size_t)j * 1568 + n];
     p += 32 * 1568;
-    if ((rc = upload12(w, &w.fc1_w, f1))) return rc;
-    if ((rc = upload12(w, &w.fc1_b, std::vector<float>(p, p + 32)))) return rc;
+    if ((rc = sv_upload(w, &w.fc1_w, f1.data(), f1.size()))) return rc;
+    if ((rc = sv_upload(w, &w.fc1_b, p, 32))) return rc;
     p += 32;
-    if ((rc = upload12(w, &w.fc2_w, std::vector<float>(p, p + 32)))) return rc;
+    if ((rc = sv_upload(w, &w.fc2_w, p, 32))) return rc;
     p += 32;
-    if ((rc = upload12(w, &w.fc2_b, std::vector<float>(p, p + 1)))) return rc;
+    if ((rc = sv_upload(w, &w.fc2_b, p, 1))) return rc;
     p += 1;
     if (p - blob != SV_EMPTY_PARAMS) return sv_fail(SV_ERR_BAD_ARG, "svk_pack_weights_empty: walked %ld floats", (long)(p - blob));
     w.loaded = true;
@@ -345,14 +281,10 @@ int svk_pack_weights_empty(sv_weights_light &w, const float *blob)
 int svk_cnn3_light_forward(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *logits, float *features, u8 *digits, float *conf, hipStream_t s)
 {
     const sv_weights_light &w = ctx->wl;
-    if (x_is_u8)
-        hipLaunchKernelGGL(k_light<true>, dim3((unsigned)B), dim3(256), 0, s, x, (const float *)w.conv[0].w, (const float *)w.conv[0].b, (const float *)w.conv[1].w,
-                           (const float *)w.conv[1].b, (const float *)w.conv[2].w, (const float *)w.conv[2].b, (const float *)w.fc1_w, (const float *)w.fc1_b,
-                           w.temperature, features, logits, digits, conf);
-    else
-        hipLaunchKernelGGL(k_light<false>, dim3((unsigned)B), dim3(256), 0, s, x, (const float *)w.conv[0].w, (const float *)w.conv[0].b, (const float *)w.conv[1].w,
-                           (const float *)w.conv[1].b, (const float *)w.conv[2].w, (const float *)w.conv[2].b, (const float *)w.fc1_w, (const float *)w.fc1_b,
-                           w.temperature, features, logits, digits, conf);
+    auto k = x_is_u8 ? k_light<true> : k_light<false>;
+    hipLaunchKernelGGL(k, dim3((unsigned)B), dim3(256), 0, s, x, (const float *)w.conv[0].w, (const float *)w.conv[0].b, (const float *)w.conv[1].w,
+                       (const float *)w.conv[1].b, (const float *)w.conv[2].w, (const float *)w.conv[2].b, (const float *)w.fc1_w, (const float *)w.fc1_b,
+                       w.temperature, features, logits, digits, conf);
     SV_LAUNCH_CHECK("k_light");
     return SV_OK;
 }
@@ -360,12 +292,9 @@ int svk_cnn3_light_forward(sv_ctx *ctx, const void *x, bool x_is_u8, long B, flo
 int svk_empty_forward(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *logit, hipStream_t s)
 {
     const sv_weights_light &w = ctx->we;
-    if (x_is_u8)
-        hipLaunchKernelGGL(k_empty<true>, dim3((unsigned)B), dim3(256), 0, s, x, (const float *)w.conv[0].w, (const float *)w.conv[0].b, (const float *)w.conv[1].w,
-                           (const float *)w.conv[1].b, (const float *)w.fc1_w, (const float *)w.fc1_b, (const float *)w.fc2_w, (const float *)w.fc2_b, logit);
-    else
-        hipLaunchKernelGGL(k_empty<false>, dim3((unsigned)B), dim3(256), 0, s, x, (const float *)w.conv[0].w, (const float *)w.conv[0].b, (const float *)w.conv[1].w,
-                           (const float *)w.conv[1].b, (const float *)w.fc1_w, (const float *)w.fc1_b, (const float *)w.fc2_w, (const float *)w.fc2_b, logit);
+    auto k = x_is_u8 ? k_empty<true> : k_empty<false>;
+    hipLaunchKernelGGL(k, dim3((unsigned)B), dim3(256), 0, s, x, (const float *)w.conv[0].w, (const float *)w.conv[0].b, (const float *)w.conv[1].w,
+                       (const float *)w.conv[1].b, (const float *)w.fc1_w, (const float *)w.fc1_b, (const float *)w.fc2_w, (const float *)w.fc2_b, logit);
     SV_LAUNCH_CHECK("k_empty");
     return SV_OK;
 }

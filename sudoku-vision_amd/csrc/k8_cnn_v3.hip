@@ -1,19 +1,15 @@
 // K8 -- DigitCNNv3.forward (ml/model_v3.py:163-184, eval mode) on MI355X, true f32 throughout.
 //
-//   k_conv3 : every convolution of the network (stem, the ten 3x3 convs of the five ResidualBlocks, the two 1x1 stride-2 shortcuts) as an
-//        implicit GEMM on v_mfma_f32_16x16x4_f32, BatchNorm folded into weights and bias (svk_pack_weights_v3 below).  One 256-thread
-//        workgroup per (cell, group of NTW 16-channel output tiles).  The workgroup copies the cell's whole input, zero-bordered, into LDS
-//        as [ic][PLANE] (PLANE = 16 mod 32 floats, so the four ic rows a ds_read_b32 touches fall on different banks).  Then
-//        M = 16 consecutive output pixels (row-major over the output plane), N = 16 output channels, K = 4 input channels of one tap per
-//        instruction: A is one ds_read_b32 per lane (pixel lane&15, channel lane>>4), B one coalesced global dword per lane from the
-//        packed image, loaded one 4-channel group ahead.  A wave keeps MB M-tiles of one N-tile in MB independent accumulators, so each
-//        B value feeds MB MFMAs.  The K order of every output (ic groups outer, taps inner) does not depend on the batch.
+//   k_conv3 : every convolution of the network (stem, the ten 3x3 convs of the five ResidualBlocks, the two 1x1 stride-2 shortcuts) on the
+//        f32 MFMA conv scheme of sv_conv_f32.h (input planes in LDS, K loop, weight image), BatchNorm folded into weights and bias
+//        (svk_pack_weights_v3 below).  The K loop is that header's sv_conv_kloop written out in place (see there and below).  One
+//        256-thread workgroup per (cell, group of NTW 16-channel output tiles) copies the cell's whole input into LDS; an M tile is 16
+//        consecutive output pixels, row-major over the output plane, at the layer's stride.
 //        Epilogue: + folded bias, optional ReLU, store [cell][oc][pixel].  The stem has CIN padded to 4 with three zero planes.
 //   k_se_residual : the rest of a ResidualBlock (model_v3.py:33-37, :74-76) in one small kernel, one workgroup per cell: per-channel mean of
 //        conv2's output (lane-strided sums + a fixed xor tree), Linear -> ReLU -> Linear -> sigmoid, then out = ReLU(t * s + shortcut).
 //        Without SE the scale is skipped.
-//   k_head3 : global average pool -> features[128] -> fc (sv_fc2_logit, the fc2 epilogue of the v1 heads) -> argmax and
-//        softmax(logits / temperature)[argmax] (model_v3.py:216-225).
+//   k_head3 : global average pool -> features[128] -> sv_head_tail (fc, argmax, temperature softmax; sv_conv_f32.h).
 //
 // Activations live in context scratch (sv_ctx::v3_act): three buffers of 32*784 floats per cell, rotated through the blocks, for at most
 // SV_V3_SUBBATCH cells: larger batches run as consecutive sub-batches on the same stream.  A cell is always computed by the same
@@ -22,17 +18,12 @@
 #include <cstring>
 #include <vector>
 
-#include "sv_device.h"
+#include "sv_conv_f32.h"
 #include "sv_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
 constexpr int ACT = 32 * 784;            // floats per cell of one activation buffer (the largest tensor: 32 x 28 x 28)
-
-// LDS row of one input channel: the zero-bordered (HIN+2)^2 plane rounded up to 16 mod 32 floats
-constexpr int plane_of(int hin) { return (((hin + 2) * (hin + 2) - 16 + 31) / 32) * 32 + 16; }
 
 // in: [cell][CIN_LOAD][HIN*HIN] (f32, or u8 cells taking the normalise glue), channels CIN_LOAD..CIN-1 are zero.
 // wp: [COUT/16][CIN/4][KS*KS][64 lane]: lane l holds w'[oc = 16 nt + (l & 15)][ic = 4 g + (l >> 4)][tap].  out: [cell][COUT][HOUT*HOUT].
@@ -40,8 +31,8 @@ template <int CIN, int CIN_LOAD, int COUT, int HIN, int STRIDE, int KS, int MB, 
 __global__ __launch_bounds__(256) void k_conv3(const void *__restrict__ in, const float *__restrict__ wp, const float *__restrict__ bias,
                                                float *__restrict__ out)
 {
-    constexpr int PW = HIN + 2, PLANE = plane_of(HIN), HOUT = HIN / STRIDE, HW = HOUT * HOUT, TILES = (HW + 15) / 16;
-    constexpr int GROUPS = (TILES + MB - 1) / MB, TAPS = KS * KS, G4 = CIN / 4, NIN = CIN_LOAD * HIN * HIN;
+    constexpr int PW = HIN + 2, PLANE = sv_conv_plane(HIN, 16), HOUT = HIN / STRIDE, HW = HOUT * HOUT, TILES = (HW + 15) / 16;
+    constexpr int GROUPS = (TILES + MB - 1) / MB, TAPS = KS * KS, G4 = CIN / 4;
     static_assert(CIN % 4 == 0 && COUT % (16 * NTW) == 0 && CIN * PLANE * 4 <= 160 * 1024, "tiling");
     __shared__ float sm[CIN * PLANE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = lane & 15, kq = lane >> 4;
@@ -49,13 +40,7 @@ __global__ __launch_bounds__(256) void k_conv3(const void *__restrict__ in, cons
 
     for (int i = tid; i < CIN * PLANE; i += 256) sm[i] = 0.f;
     __syncthreads();
-    for (int i = tid; i < NIN; i += 256) {
-        const int c = i / (HIN * HIN), p = i % (HIN * HIN);
-        float v;
-        if (U8IN) v = sv_glue_norm(((const u8 *)in)[cell * NIN + i]);
-        else v = ((const float *)in)[cell * NIN + i];
-        sm[c * PLANE + (p / HIN + 1) * PW + p % HIN + 1] = v;
-    }
+    sv_conv_load_input<U8IN, CIN_LOAD, HIN, PLANE>(in, cell, sm, tid);
     __syncthreads();
 
     for (int item = wave; item < GROUPS * NTW; item += 4) {
@@ -70,6 +55,8 @@ __global__ __launch_bounds__(256) void k_conv3(const void *__restrict__ in, cons
         f32x4 acc[MB];
 #pragma unroll
         for (int i = 0; i < MB; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // sv_conv_kloop's sequence, written out: through the function the compiler no longer folds sm's address into the tap offsets and
+        // the forward measures 1.5 % slower (profiles/r13_conv_f32_shared_time.txt).  A change to either copy goes into both.
         const float *wb = wp + (long)nt * G4 * TAPS * 64 + lane;
         float bcur[TAPS], bnext[TAPS];
 #pragma unroll
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(256) void k_se_residual(const float *__restrict__ t
 __global__ __launch_bounds__(128) void k_head3(const float *__restrict__ x, const float *__restrict__ fcw, const float *__restrict__ fcb, float temperature,
                                                float *__restrict__ features, float *__restrict__ logits, u8 *__restrict__ digits, float *__restrict__ conf)
 {
-    __shared__ float f[128], lg[10];
+    __shared__ float f[128];
     const int tid = threadIdx.x;
     const long cell = blockIdx.x;
     const float *xp = x + cell * 6272 + tid * 49;
@@ -164,24 +151,7 @@ __global__ __launch_bounds__(128) void k_head3(const float *__restrict__ x, cons
     s = s / 49.f;
     f[tid] = s;
     if (features) features[cell * 128 + tid] = s;
-    __syncthreads();
-    if (tid < 10) {
-        lg[tid] = sv_fc2_logit(f, (const float(*)[128])fcw, fcb, tid);
-        logits[cell * 10 + tid] = lg[tid];
-    }
-    __syncthreads();
-    if (tid == 0 && (digits || conf)) {
-        int arg = 0;
-        for (int j = 1; j < 10; j++)
-            if (lg[j] > lg[arg]) arg = j;
-        if (digits) digits[cell] = (u8)arg;
-        if (conf) {
-            const float best = lg[arg] / temperature;
-            float den = 0.f;
-            for (int j = 0; j < 10; j++) den += expf(lg[j] / temperature - best);
-            conf[cell] = 1.0f / den;
-        }
-    }
+    sv_head_tail(f, fcw, fcb, temperature, cell, logits, digits, conf);
 }
 
 template <int CIN, int CIN_LOAD, int COUT, int HIN, int STRIDE, int KS, int MB, int NTW, bool RELU, bool U8IN>
@@ -200,35 +170,20 @@ int se_residual(const float *t, const float *sc, const sv_weights3 &w, int layer
     return SV_OK;
 }
 
-template <class T>
-int upload3(sv_weights3 &w, T **dst, const T *src, size_t n)
-{
-    SV_HIP(hipMalloc((void **)dst, n * sizeof(T)));
-    w.allocs.push_back(*dst);
-    SV_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return SV_OK;
-}
-
-// conv weight [cout][cin][ks][ks] + its BatchNorm (gamma, beta, running mean, running var) -> k_conv3's B image and bias, folded in
-// float64 and rounded once: w' = w * gamma / sqrt(var + eps), b' = beta - mean * gamma / sqrt(var + eps), eps = 1e-5 (nn.BatchNorm2d)
+// conv weight [cout][cin][ks][ks] + its BatchNorm (gamma, beta, running mean, running var) at p -> k_conv3's B image and folded bias
+// (sv_fold_bn, sv_pack_conv_image).  cout is a multiple of 16 here; the stem's cin = 1 is padded to 4.
 int pack_conv3(sv_weights3 &w, sv_conv3 &dst, const float *&p, int cout, int cin, int ks)
 {
-    const int taps = ks * ks, cin_pad = (cin + 3) / 4 * 4, g4 = cin_pad / 4;
+    const int taps = ks * ks;
     const float *cw = p, *gamma = cw + (size_t)cout * cin * taps, *beta = gamma + cout, *mean = beta + cout, *var = mean + cout;
     p = var + cout;
-    std::vector<float> img((size_t)cout * cin_pad * taps, 0.f), b(cout);
-    for (int oc = 0; oc < cout; oc++) {
-        const double k = (double)gamma[oc] / std::sqrt((double)var[oc] + 1e-5);
-        b[oc] = (float)((double)beta[oc] - (double)mean[oc] * k);
-        for (int ic = 0; ic < cin; ic++)
-            for (int t = 0; t < taps; t++) {
-                const int lane = (ic & 3) * 16 + (oc & 15);
-                img[(((size_t)(oc / 16) * g4 + ic / 4) * taps + t) * 64 + lane] = (float)((double)cw[((size_t)oc * cin + ic) * taps + t] * k);
-            }
-    }
+    std::vector<double> k(cout);
+    std::vector<float> b(cout);
+    sv_fold_bn(gamma, beta, mean, var, cout, k.data(), b.data());
+    const std::vector<float> img = sv_pack_conv_image(cw, k.data(), cout, cin, taps);
     int rc;
-    if ((rc = upload3(w, &dst.w, img.data(), img.size()))) return rc;
-    return upload3(w, &dst.b, b.data(), b.size());
+    if ((rc = sv_upload(w, &dst.w, img.data(), img.size()))) return rc;
+    return sv_upload(w, &dst.b, b.data(), b.size());
 }
 
 }  // namespace
@@ -249,16 +204,16 @@ int svk_pack_weights_v3(sv_weights3 &w, const float *blob, bool use_se)
         if ((rc = pack_conv3(w, w.conv1[l], p, c, CIN[l], 3))) return rc;
         if ((rc = pack_conv3(w, w.conv2[l], p, c, c, 3))) return rc;
         if (use_se) {
-            if ((rc = upload3(w, &w.se1[l], p, (size_t)c * c / 4))) return rc;
+            if ((rc = sv_upload(w, &w.se1[l], p, (size_t)c * c / 4))) return rc;
             p += c * c / 4;
-            if ((rc = upload3(w, &w.se2[l], p, (size_t)c * c / 4))) return rc;
+            if ((rc = sv_upload(w, &w.se2[l], p, (size_t)c * c / 4))) return rc;
             p += c * c / 4;
         }
         if (CIN[l] != c && (rc = pack_conv3(w, w.shortcut[l], p, c, CIN[l], 1))) return rc;
     }
-    if ((rc = upload3(w, &w.fc_w, p, 1280))) return rc;
+    if ((rc = sv_upload(w, &w.fc_w, p, 1280))) return rc;
     p += 1280;
-    if ((rc = upload3(w, &w.fc_b, p, 10))) return rc;
+    if ((rc = sv_upload(w, &w.fc_b, p, 10))) return rc;
     p += 10;
     if (p - blob != svk_v3_blob_floats(use_se)) return sv_fail(SV_ERR_BAD_ARG, "svk_pack_weights_v3: walked %ld floats", (long)(p - blob));
     w.loaded = true;
@@ -278,12 +233,12 @@ int svk_cnn3_forward(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *lo
     const long cap = ctx->cap_v3;
     float *P = ctx->v3_act, *Q = P + cap * ACT, *R = Q + cap * ACT;
     float *P2 = P + cap * (ACT / 2), *Q2 = Q + cap * (ACT / 2);      // second halves: the stride-2 blocks hold two tensors in one buffer
+    const auto stem = x_is_u8 ? conv3<4, 1, 32, 28, 1, 3, 7, 1, true, true> : conv3<4, 1, 32, 28, 1, 3, 7, 1, true, false>;
+    const size_t cell_bytes = 784 * (x_is_u8 ? sizeof(u8) : sizeof(float));
     int rc;
     for (long b0 = 0; b0 < B; b0 += SV_V3_SUBBATCH) {
         const long n = B - b0 < SV_V3_SUBBATCH ? B - b0 : SV_V3_SUBBATCH;
-        if (x_is_u8) rc = conv3<4, 1, 32, 28, 1, 3, 7, 1, true, true>((const u8 *)x + b0 * 784, w.stem, P, n, s);
-        else rc = conv3<4, 1, 32, 28, 1, 3, 7, 1, true, false>((const float *)x + b0 * 784, w.stem, P, n, s);
-        if (rc) return rc;
+        if ((rc = stem((const char *)x + b0 * cell_bytes, w.stem, P, n, s))) return rc;
         // layer1: 32 -> 32, 28x28
         if ((rc = conv3<32, 32, 32, 28, 1, 3, 7, 1, true, false>(P, w.conv1[0], Q, n, s))) return rc;
         if ((rc = conv3<32, 32, 32, 28, 1, 3, 7, 1, false, false>(Q, w.conv2[0], R, n, s))) return rc;

@@ -142,18 +142,42 @@ __device__ __forceinline__ float sv_fc2_logit(const float *h, const float (*w2s)
     return s;
 }
 
+// index of the first maximum of the 10 logits lg; best = that maximum
+__device__ __forceinline__ int sv_argmax10(const float *lg, float &best)
+{
+    best = lg[0];
+    int arg = 0;
+    for (int j = 1; j < 10; j++)
+        if (lg[j] > best) { best = lg[j]; arg = j; }
+    return arg;
+}
+
 // digit (first maximum of the 10 logits lg) and confidence (its softmax probability, 1 / sum exp(lg - best)) of cell `cell`
 __device__ __forceinline__ void sv_digit_conf(const float *lg, long cell, u8 *digits, float *conf)
 {
     if (!digits && !conf) return;
-    float best = lg[0];
-    int arg = 0;
-    for (int j = 1; j < 10; j++)
-        if (lg[j] > best) { best = lg[j]; arg = j; }
+    float best;
+    const int arg = sv_argmax10(lg, best);
     if (digits) digits[cell] = (u8)arg;
     if (conf) {
         float den = 0.f;
         for (int j = 0; j < 10; j++) den += expf(lg[j] - best);
+        conf[cell] = 1.0f / den;
+    }
+}
+
+// the same with a temperature (ml/model_v3.py:216-225): the digit is the argmax of lg, the confidence softmax(lg / temperature) at it,
+// every logit divided before the subtraction
+__device__ __forceinline__ void sv_digit_conf_t(const float *lg, float temperature, long cell, u8 *digits, float *conf)
+{
+    if (!digits && !conf) return;
+    float best;
+    const int arg = sv_argmax10(lg, best);
+    if (digits) digits[cell] = (u8)arg;
+    if (conf) {
+        best = best / temperature;
+        float den = 0.f;
+        for (int j = 0; j < 10; j++) den += expf(lg[j] / temperature - best);
         conf[cell] = 1.0f / den;
     }
 }

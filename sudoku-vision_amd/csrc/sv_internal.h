@@ -122,9 +122,9 @@ int sv_fail(int code, const char *fmt, ...);
 
 int sv_ensure_scratch(sv_ctx *ctx, long cells);
 
-// n elements of src -> a new device buffer *dst, recorded in w.allocs
-template <class T>
-int sv_upload(sv_weights &w, T **dst, const T *src, size_t n)
+// n elements of src -> a new device buffer *dst, recorded in w.allocs (w: any of the weight structs above)
+template <class W, class T>
+int sv_upload(W &w, T **dst, const T *src, size_t n)
 {
     SV_HIP(hipMalloc((void **)dst, n * sizeof(T)));
     w.allocs.push_back(*dst);
