@@ -10,6 +10,11 @@
 //   k_jpeg_colour  one thread per OUTPUT pixel (so stores stay coalesced under every orientation): luma sample, the two
 //                  interpolated chroma samples in closed form (no intermediate full-resolution chroma planes), colour
 //                  conversion, 3-byte store.
+//
+// Stated limit: idct8 computes in 32-bit int where libjpeg's C code uses long and libjpeg-turbo's SIMD code 16-bit intermediates; the
+// three agree while the dequantised coefficients and the first pass's outputs fit 16 bits, which holds for anything an encoder writes
+// for 8-bit samples.  Far beyond that they differ and signed overflow here is undefined: such files are outside what this kernel
+// promises, and the tests (tests/test_jpeg_crafted.py asserts the bound on its own files) do not feed them.
 #include "sv_internal.h"
 
 namespace {

@@ -17,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import sv_oracle as o  # noqa: E402
+from jpeg_craft import _ZZ, _BitWriter, _huff_codes  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 # data/test_images/sample_{1..5}.jpg of the reference, committed byte for byte as data fixtures
@@ -134,10 +135,6 @@ def _same_info(a, b):
     return all(getattr(a, f) == getattr(b, f) for f, _ in type(b)._fields_)
 
 
-_ZZ = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-       35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63]
-
-
 def _densify(info, masks, offs, vals):
     """The compact transport form back to dense natural-order blocks (what the GPU kernel does by popcount rank)."""
     out = np.zeros(info.coef_count, np.int16)
@@ -228,37 +225,6 @@ def _parse_tables(data):
             sel = {seg[1 + 2 * i]: (seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15) for i in range(ns)}
             return dqt, dht, sof, sel, app
         pos += 2 + L
-
-
-def _huff_codes(counts, symbols):
-    codes, code, k = {}, 0, 0
-    for ln in range(1, 17):
-        for _ in range(counts[ln - 1]):
-            codes[symbols[k]] = (code, ln)
-            code += 1
-            k += 1
-        code <<= 1
-    return codes
-
-
-class _BitWriter:
-    def __init__(self):
-        self.out, self.acc, self.n = bytearray(), 0, 0
-
-    def put(self, value, length):
-        self.acc = (self.acc << length) | (value & ((1 << length) - 1))
-        self.n += length
-        while self.n >= 8:
-            b = (self.acc >> (self.n - 8)) & 0xFF
-            self.out.append(b)
-            if b == 0xFF:
-                self.out.append(0)
-            self.n -= 8
-
-    def flush(self):
-        if self.n:
-            self.put((1 << (8 - self.n)) - 1, 8 - self.n)
-        return bytes(self.out)
 
 
 def _encode_noninterleaved(data):
