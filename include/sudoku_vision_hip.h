@@ -529,6 +529,20 @@ int sv_jpeg_reconstruct_sparse_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, con
                                       const uint32_t *offsets /*dev*/, const int16_t *values /*dev*/,
                                       const uint16_t *quant /*dev, 192*/, uint8_t *bgr /*dev*/, ptrdiff_t pitch, void *stream);
 
+/* Reduced-size decode: libjpeg's scale_denom, what cv2.imread(path, cv2.IMREAD_REDUCED_COLOR_2 / _4 / _8) asks for.  The entropy
+ * stage is the one above (every coefficient is still decoded); the device half runs libjpeg's 4x4 / 2x2 / 1x1 inverse DCTs
+ * (jidctred.c), decodes 4:2:0 chroma at twice the luma block size instead of up-sampling it (jdmaster.c), and never produces
+ * the full-size image.  Bit-identical to libjpeg-turbo at the same scale.  scale_denom is 1, 2, 4 or 8 (1: the entries above,
+ * unchanged); anything else is SV_ERR_BAD_ARG.  The frame is ceil(out_height / d) x ceil(out_width / d) x 3: */
+int sv_jpeg_scaled_size(const sv_jpeg_info *info, int scale_denom, int *out_width, int *out_height);
+int sv_jpeg_reconstruct_scaled_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *coef /*dev*/,
+                                      const uint16_t *quant /*dev, 192*/, uint8_t *bgr /*dev*/, ptrdiff_t pitch, void *stream,
+                                      int scale_denom);
+int sv_jpeg_reconstruct_sparse_scaled_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, const uint64_t *masks /*dev*/,
+                                             const uint32_t *offsets /*dev*/, const int16_t *values /*dev*/,
+                                             const uint16_t *quant /*dev, 192*/, uint8_t *bgr /*dev*/, ptrdiff_t pitch,
+                                             void *stream, int scale_denom);
+
 /* ---- quality gate: the per-pixel statistics of cv/grid_quality.py (pipeline/run_v2.py:299-311) ------------------------- */
 
 /* The integer sums behind compute_sharpness (cv/grid_quality.py:48-62) and compute_contrast (:65-87) for n frames:

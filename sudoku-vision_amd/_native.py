@@ -67,6 +67,9 @@ SIGNATURES = {
     "sv_jpeg_entropy_decode_batch": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p],
     "sv_jpeg_reconstruct_bgr_u8": [_p, _p, _p, _p, _p, _pd, _p],
     "sv_jpeg_reconstruct_sparse_bgr_u8": [_p, _p, _p, _p, _p, _p, _p, _pd, _p],
+    "sv_jpeg_scaled_size": [_p, _i, _p, _p],
+    "sv_jpeg_reconstruct_scaled_bgr_u8": [_p, _p, _p, _p, _p, _pd, _p, _i],
+    "sv_jpeg_reconstruct_sparse_scaled_bgr_u8": [_p, _p, _p, _p, _p, _p, _p, _pd, _p, _i],
     "sv_softmax_topk_f32": [_p, _p, _l, _i, _p, _p, _p],
     "sv_resolve_conflicts": [_p, _p, _p, _l, _i, _i, _i, _d, _i] + [_p] * 14,
     "sv_propagate_constraints": [_p, _p, _p, _l, _i] + [_p] * 9,

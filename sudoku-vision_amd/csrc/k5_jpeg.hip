@@ -11,7 +11,20 @@
 //                  interpolated chroma samples in closed form (no intermediate full-resolution chroma planes), colour
 //                  conversion, 3-byte store.
 //
-// Stated limit: idct8 computes in 32-bit int where libjpeg's C code uses long and libjpeg-turbo's SIMD code 16-bit intermediates; the
+//
+// Reduced-size decode (libjpeg's scale_denom 2, 4, 8; cv2.IMREAD_REDUCED_COLOR_*): the image is never reconstructed at full size.  Luma
+// blocks come out at S = 8 / d samples per side, through jidctred.c's 4x4 / 2x2 / 1x1 transforms; 4:2:0 chroma is decoded at 2S instead of
+// being up-sampled (jdmaster.c), so only 4:2:2 keeps an up-sampling step (h2v1; replication at d = 8, where jdsample.c has no fancy filter).
+// One launch per block size present (at most two); every thread of the reduced kernels stores whole 32-bit words:
+//   k_jpeg_idct4        S = 4: four threads per block, 64 blocks per workgroup.  A thread dequantises block rows t and t + 4 into LDS,
+//                       transforms columns t and t + 4, then row t, and stores its 4 samples.  Row and column 4 are never touched.
+//   k_jpeg_idct_small   S = 2 or 1: one thread per 4 / S horizontally adjacent blocks, in registers.  S = 2 reads rows and columns
+//                       0, 1, 3, 5, 7; S = 1 reads the DC term alone (compact form: mask, offset and at most one value per block).
+//   k_jpeg_idct         S = 8 (4:2:0 chroma at d = 2): the full-size kernel on a geometry whose luma has no blocks.
+//   k_jpeg_colour_reduced  the colour kernel on planes with their own pitches and a same-size or h2v1 chroma relation.
+// They move the coefficients of the full-size decode for 1 / d^2 of its samples: bound by the coefficient read.
+//
+// Stated limit: idct8 (and idct4, idct2 alike) computes in 32-bit int where libjpeg's C code uses long and libjpeg-turbo's SIMD code 16-bit intermediates; the
 // three agree while the dequantised coefficients and the first pass's outputs fit 16 bits, which holds for anything an encoder writes
 // for 8-bit samples.  Far beyond that they differ and signed overflow here is undefined: such files are outside what this kernel
 // promises, and the tests (tests/test_jpeg_crafted.py asserts the bound on its own files) do not feed them.
@@ -150,36 +163,249 @@ __device__ __forceinline__ int chroma_sample(const u8 *__restrict__ p, long pw, 
 
 __device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 
+// source position (x, y) in the stored W x H image of output pixel (ox, oy) under the EXIF orientation
+__device__ __forceinline__ void source_xy(int orientation, int W, int H, int ox, int oy, int &x, int &y)
+{
+    switch (orientation) {
+    case 2: x = W - 1 - ox; y = oy; break;
+    case 3: x = W - 1 - ox; y = H - 1 - oy; break;
+    case 4: x = ox; y = H - 1 - oy; break;
+    case 5: x = oy; y = ox; break;
+    case 6: x = oy; y = H - 1 - ox; break;
+    case 7: x = W - 1 - oy; y = H - 1 - ox; break;
+    case 8: x = W - 1 - oy; y = ox; break;
+    default: x = ox; y = oy;
+    }
+}
+
+// jdcolor.c: FIX(1.40200), FIX(1.77200), FIX(0.34414), FIX(0.71414); cb, cr centred on 0
+__device__ __forceinline__ void store_ycc_as_bgr(u8 *px, int Y, int cb, int cr)
+{
+    px[0] = (u8)clamp255(Y + ((116130 * cb + 32768) >> 16));
+    px[1] = (u8)clamp255(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+    px[2] = (u8)clamp255(Y + ((91881 * cr + 32768) >> 16));
+}
+
 __global__ __launch_bounds__(256) void k_jpeg_colour(const u8 *__restrict__ planes, JpegGeom g, u8 *__restrict__ bgr, long pitch)
 {
     const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
     if (ox >= g.OW) return;
-    int x, y;                                                   // source position of this output pixel
-    switch (g.orientation) {
-    case 2: x = g.W - 1 - ox; y = oy; break;
-    case 3: x = g.W - 1 - ox; y = g.H - 1 - oy; break;
-    case 4: x = ox; y = g.H - 1 - oy; break;
-    case 5: x = oy; y = ox; break;
-    case 6: x = oy; y = g.H - 1 - ox; break;
-    case 7: x = g.W - 1 - oy; y = g.H - 1 - ox; break;
-    case 8: x = g.W - 1 - oy; y = ox; break;
-    default: x = ox; y = oy;
-    }
+    int x, y;
+    source_xy(g.orientation, g.W, g.H, ox, oy, x, y);
     const int Y = planes[g.plane_off[0] + (long)y * g.bw[0] * 8 + x];
-    int r = Y, gr = Y, b = Y;
+    u8 *px = bgr + (long)oy * pitch + 3L * ox;
     if (g.ncomp == 3) {
         const int dw = (g.W + g.hmax - 1) / g.hmax, dh = (g.H + g.vmax - 1) / g.vmax;
         const int cb = chroma_sample(planes + g.plane_off[1], (long)g.bw[1] * 8, dw, dh, g.hmax, g.vmax, x, y) - 128;
         const int cr = chroma_sample(planes + g.plane_off[2], (long)g.bw[2] * 8, dw, dh, g.hmax, g.vmax, x, y) - 128;
-        r = clamp255(Y + ((91881 * cr + 32768) >> 16));         // jdcolor.c: FIX(1.40200), FIX(1.77200), FIX(0.34414), FIX(0.71414)
-        b = clamp255(Y + ((116130 * cb + 32768) >> 16));
-        gr = clamp255(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+        store_ycc_as_bgr(px, Y, cb, cr);
+    } else {
+        px[0] = px[1] = px[2] = (u8)Y;
     }
+}
+
+// ---- reduced-size decode ----------------------------------------------------------------------------------------------------------
+struct JpegRGeom {                     // one launch of a reduced IDCT kernel: the components whose blocks come out at the kernel's S
+    int bw[3], bh[3];                  // block grid; bh 0 for a component that is not this launch's
+    int ipr[3];                        // work items per block row: blocks (S = 4) or groups of 4 / S blocks (S = 2, 1)
+    int pitch[3];                      // plane row pitch in bytes, a multiple of 4
+    long coef_off[3], plane_off[3];
+    long item_start[4];                // prefix sums of work items per component
+};
+
+struct JpegCGeom {                     // k_jpeg_colour_reduced
+    int ncomp, W, H, OW, OH, orientation;
+    int hup;                           // 1: chroma planes have the output's size; 2: half its width (4:2:2), h2v1 up-sampling
+    int dw;                            // chroma plane width for the h2v1 filter; 0 selects plain replication
+    int pitch[3];
+    long plane_off[3];
+};
+
+// the two 1-D transforms of jidctred.c (CONST_BITS 13); the caller applies the pass-specific descale.  Position 4 is not read.
+__device__ __forceinline__ void idct4(const int (&in)[8], int (&out)[4])
+{
+    const int tmp0 = in[0] * 16384;
+    const int tmp2 = in[2] * 15137 + in[6] * (-6270);
+    const int tmp10 = tmp0 + tmp2, tmp12 = tmp0 - tmp2;
+    const int a = in[7] * (-1730) + in[5] * 11893 + in[3] * (-17799) + in[1] * 8697;
+    const int b = in[7] * (-4176) + in[5] * (-4926) + in[3] * 7373 + in[1] * 20995;
+    out[0] = tmp10 + b; out[3] = tmp10 - b;
+    out[1] = tmp12 + a; out[2] = tmp12 - a;
+}
+
+__device__ __forceinline__ void idct2(int i0, int i1, int i3, int i5, int i7, int &o0, int &o1)
+{
+    const int tmp10 = i0 * 32768;
+    const int tmp0 = i7 * (-5906) + i5 * 6967 + i3 * (-10426) + i1 * 29692;
+    o0 = tmp10 + tmp0; o1 = tmp10 - tmp0;
+}
+
+// One block row, dequantised.  Dense: blk points at the block's 64 values.  SPARSE: (mask, vals) as in k_jpeg_idct; only the columns of
+// COLS are looked up, the others come back 0.  q: the component's quantiser steps.
+template <bool SPARSE, unsigned COLS>
+__device__ __forceinline__ void deq_row(const short *__restrict__ blk, unsigned long long mask, const short *__restrict__ vals,
+                                        const unsigned short *__restrict__ q, int row, int (&out)[8])
+{
+    const int4 qr = *(const int4 *)(q + row * 8);
+    const int qw[4] = {qr.x, qr.y, qr.z, qr.w};
+    if (SPARSE) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            out[i] = 0;
+            if (!((COLS >> i) & 1)) continue;
+            const int z = kZigzagOf[row * 8 + i];
+            const int qv = (i & 1) ? (int)((unsigned)qw[i >> 1] >> 16) : (int)(qw[i >> 1] & 0xffff);
+            if ((mask >> z) & 1) out[i] = vals[__popcll(mask & ((1ull << z) - 1))] * qv;
+        }
+    } else {
+        const int4 raw = *(const int4 *)(blk + row * 8);
+        const int cw[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            out[2 * i] = (int)(short)(cw[i] & 0xffff) * (int)(qw[i] & 0xffff);
+            out[2 * i + 1] = (cw[i] >> 16) * (int)((unsigned)qw[i] >> 16);
+        }
+    }
+}
+
+__device__ __forceinline__ int component_of(const JpegRGeom &g, long item)
+{
+    return item >= g.item_start[2] ? 2 : item >= g.item_start[1] ? 1 : 0;
+}
+
+template <bool SPARSE>
+__global__ __launch_bounds__(256) void k_jpeg_idct4(const short *__restrict__ coef, const unsigned long long *__restrict__ masks,
+                                                     const unsigned *__restrict__ offsets, const short *__restrict__ values,
+                                                     const unsigned short *__restrict__ quant, JpegRGeom g, u8 *__restrict__ planes)
+{
+    __shared__ int ws[64][73];                                  // [block][row * 9 + column]; 73: neighbouring blocks start 9 banks apart
+    const int tid = threadIdx.x, b = tid >> 2, t = tid & 3;
+    const long item = (long)blockIdx.x * 64 + b;
+    const bool live = item < g.item_start[3];
+    const int c = live ? component_of(g, item) : 0;
+    const long lb = item - g.item_start[c];                     // block index within the component
+    if (live) {
+        const long gb = g.coef_off[c] / 64 + lb;                // block index over all components
+        const short *blk = SPARSE ? nullptr : coef + gb * 64;
+        const unsigned long long mask = SPARSE ? masks[gb] : 0;
+        const short *vals = SPARSE ? values + offsets[gb] : nullptr;
+#pragma unroll
+        for (int h = 0; h < 2; h++) {                           // rows t and t + 4, never row 4
+            const int row = t + 4 * h;
+            if (row == 4) continue;
+            int d[8];
+            deq_row<SPARSE, 0xEFu>(blk, mask, vals, quant + c * 64, row, d);
+#pragma unroll
+            for (int i = 0; i < 8; i++) ws[b][row * 9 + i] = d[i];
+        }
+    }
+    __syncthreads();
+    int v[8], o[4];
+    v[4] = 0;
+    if (live) {                                                 // pass 1: columns t and t + 4, never column 4; in place (a column has one owner)
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int col = t + 4 * h;
+            if (col == 4) continue;
+#pragma unroll
+            for (int i = 0; i < 8; i++) if (i != 4) v[i] = ws[b][i * 9 + col];
+            idct4(v, o);
+#pragma unroll
+            for (int i = 0; i < 4; i++) ws[b][i * 9 + col] = descale(o[i], 12);
+        }
+    }
+    __syncthreads();
+    if (live) {                                                 // pass 2: row t
+#pragma unroll
+        for (int i = 0; i < 8; i++) if (i != 4) v[i] = ws[b][t * 9 + i];
+        idct4(v, o);
+        unsigned w = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) w |= range_limit(descale(o[i], 19)) << (8 * i);
+        const int bx = (int)(lb % g.bw[c]), by = (int)(lb / g.bw[c]);
+        *(unsigned *)(planes + g.plane_off[c] + ((long)by * 4 + t) * g.pitch[c] + bx * 4) = w;
+    }
+}
+
+template <int S, bool SPARSE>
+__global__ __launch_bounds__(256) void k_jpeg_idct_small(const short *__restrict__ coef, const unsigned long long *__restrict__ masks,
+                                                          const unsigned *__restrict__ offsets, const short *__restrict__ values,
+                                                          const unsigned short *__restrict__ quant, JpegRGeom g, u8 *__restrict__ planes)
+{
+    static_assert(S == 1 || S == 2, "block sizes 1 and 2");
+    constexpr int G = 4 / S;                                    // blocks per thread: S rows of G * S = 4 samples
+    const long item = (long)blockIdx.x * 256 + threadIdx.x;
+    if (item >= g.item_start[3]) return;
+    const int c = component_of(g, item);
+    const long li = item - g.item_start[c];
+    const int by = (int)(li / g.ipr[c]), k = (int)(li % g.ipr[c]);
+    const unsigned short *q = quant + c * 64;
+    unsigned word[S];
+#pragma unroll
+    for (int i = 0; i < S; i++) word[i] = 0;
+#pragma unroll
+    for (int j = 0; j < G; j++) {
+        const int bx = k * G + j;
+        if (bx >= g.bw[c]) break;                               // the pitch is padded to the word: the rest of it stays 0
+        const long gb = g.coef_off[c] / 64 + (long)by * g.bw[c] + bx;
+        const short *blk = SPARSE ? nullptr : coef + gb * 64;
+        const unsigned long long mask = SPARSE ? masks[gb] : 0;
+        const short *vals = SPARSE ? values + offsets[gb] : nullptr;
+        if (S == 1) {                                           // zigzag position 0 is the DC term: the block's first value when present
+            const int dc = SPARSE ? ((mask & 1) ? (int)vals[0] : 0) : (int)blk[0];
+            word[0] |= range_limit(descale(dc * (int)q[0], 3)) << (8 * j);
+        } else {
+            int d[5][8], w0[8], w1[8];
+#pragma unroll
+            for (int r = 0; r < 5; r++) deq_row<SPARSE, 0xABu>(blk, mask, vals, q, r < 2 ? r : 2 * r - 1, d[r]);    // rows 0, 1, 3, 5, 7
+#pragma unroll
+            for (int col = 0; col < 8; col++) {
+                if (!((0xABu >> col) & 1)) continue;
+                int o0, o1;
+                idct2(d[0][col], d[1][col], d[2][col], d[3][col], d[4][col], o0, o1);
+                w0[col] = descale(o0, 13); w1[col] = descale(o1, 13);
+            }
+            int o0, o1;
+            idct2(w0[0], w0[1], w0[3], w0[5], w0[7], o0, o1);
+            word[0] |= (range_limit(descale(o0, 20)) | range_limit(descale(o1, 20)) << 8) << (16 * j);
+            idct2(w1[0], w1[1], w1[3], w1[5], w1[7], o0, o1);
+            word[S - 1] |= (range_limit(descale(o0, 20)) | range_limit(descale(o1, 20)) << 8) << (16 * j);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < S; i++) *(unsigned *)(planes + g.plane_off[c] + ((long)by * S + i) * g.pitch[c] + 4 * k) = word[i];
+}
+
+__global__ __launch_bounds__(256) void k_jpeg_colour_reduced(const u8 *__restrict__ planes, JpegCGeom g, u8 *__restrict__ bgr, long pitch)
+{
+    const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
+    if (ox >= g.OW) return;
+    int x, y;
+    source_xy(g.orientation, g.W, g.H, ox, oy, x, y);
+    const int Y = planes[g.plane_off[0] + (long)y * g.pitch[0] + x];
     u8 *px = bgr + (long)oy * pitch + 3L * ox;
-    px[0] = (u8)b; px[1] = (u8)gr; px[2] = (u8)r;
+    if (g.ncomp == 3) {
+        const int cb = chroma_sample(planes + g.plane_off[1], g.pitch[1], g.dw, g.H, g.hup, 1, x, y) - 128;
+        const int cr = chroma_sample(planes + g.plane_off[2], g.pitch[2], g.dw, g.H, g.hup, 1, x, y) - 128;
+        store_ycc_as_bgr(px, Y, cb, cr);
+    } else {
+        px[0] = px[1] = px[2] = (u8)Y;
+    }
 }
 
 }  // namespace
+
+// the component planes between the IDCT and the colour kernel grow on demand
+static int reserve_planes(sv_ctx *ctx, size_t bytes)
+{
+    if (bytes <= ctx->cap_jpeg) return SV_OK;
+    SV_HIP(hipSetDevice(ctx->device));
+    if (ctx->jpeg_planes) SV_HIP(hipFree(ctx->jpeg_planes));
+    ctx->jpeg_planes = nullptr; ctx->cap_jpeg = 0;
+    SV_HIP(hipMalloc((void **)&ctx->jpeg_planes, bytes));
+    ctx->cap_jpeg = bytes;
+    return SV_OK;
+}
 
 int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
                          const uint16_t *quant, u8 *bgr, ptrdiff_t pitch, hipStream_t s)
@@ -200,13 +426,8 @@ int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *c
     g.blk_start[3] = blocks;
     if (g.ncomp == 1) g.blk_start[1] = g.blk_start[2] = blocks;   // the component pick in the kernel compares against these
     if (coff != info->coef_count) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_reconstruct_bgr_u8: coef_count %ld does not match the geometry (%ld)", info->coef_count, coff);
-    if ((size_t)poff > ctx->cap_jpeg) {
-        SV_HIP(hipSetDevice(ctx->device));
-        if (ctx->jpeg_planes) SV_HIP(hipFree(ctx->jpeg_planes));
-        ctx->jpeg_planes = nullptr; ctx->cap_jpeg = 0;
-        SV_HIP(hipMalloc((void **)&ctx->jpeg_planes, (size_t)poff));
-        ctx->cap_jpeg = (size_t)poff;
-    }
+    const int rc = reserve_planes(ctx, (size_t)poff);
+    if (rc) return rc;
     if (coef)
         hipLaunchKernelGGL(k_jpeg_idct<false>, dim3((unsigned)((blocks + 31) / 32)), dim3(256), 0, s, (const short *)coef, nullptr, nullptr, nullptr, quant, g, ctx->jpeg_planes);
     else
@@ -215,5 +436,84 @@ int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *c
     SV_LAUNCH_CHECK("k_jpeg_idct");
     hipLaunchKernelGGL(k_jpeg_colour, dim3((unsigned)((g.OW + 255) / 256), (unsigned)g.OH), dim3(256), 0, s, ctx->jpeg_planes, g, bgr, (long)pitch);
     SV_LAUNCH_CHECK("k_jpeg_colour");
+    return SV_OK;
+}
+
+// scale_denom 2, 4 or 8 (1 is svk_jpeg_reconstruct).  bgr: ceil(out_height / d) x ceil(out_width / d) x 3.
+int svk_jpeg_reconstruct_scaled(sv_ctx *ctx, const sv_jpeg_info *info, int denom, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets,
+                                const int16_t *values, const uint16_t *quant, u8 *bgr, ptrdiff_t pitch, hipStream_t s)
+{
+    const int ncomp = info->components, hmax = info->h_samp, vmax = info->v_samp, S = 8 / denom;
+    const int mcu_cols = (info->width + 8 * hmax - 1) / (8 * hmax), mcu_rows = (info->height + 8 * vmax - 1) / (8 * vmax);
+    int sc[3], bw[3], bh[3], ppitch[3];
+    long coef_off[3], plane_off[3], coff = 0, poff = 0;
+    for (int c = 0; c < 3; c++) {
+        const int h = c == 0 ? hmax : 1, v = c == 0 ? vmax : 1;
+        sc[c] = S;                                              // jdmaster.c: decode a subsampled component larger instead of up-sampling it
+        while (sc[c] < 8 && (hmax * S) % (h * sc[c] * 2) == 0 && (vmax * S) % (v * sc[c] * 2) == 0) sc[c] *= 2;
+        bw[c] = c < ncomp ? mcu_cols * h : 0;
+        bh[c] = c < ncomp ? mcu_rows * v : 0;
+        ppitch[c] = (bw[c] * sc[c] + 3) & ~3;
+        coef_off[c] = coff; plane_off[c] = poff;
+        coff += (long)bw[c] * bh[c] * 64;
+        poff += (long)ppitch[c] * bh[c] * sc[c];
+    }
+    if (coff != info->coef_count) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_reconstruct_scaled_bgr_u8: coef_count %ld does not match the geometry (%ld)", info->coef_count, coff);
+    const int rc = reserve_planes(ctx, (size_t)poff);
+    if (rc) return rc;
+    const unsigned long long *m = (const unsigned long long *)masks;
+    const short *cf = (const short *)coef, *vl = (const short *)values;
+    for (int first = 0; first < ncomp; first++) {               // one launch per block size: luma's, then chroma's where it differs
+        const int z = sc[first];
+        if (first == 2 || (first == 1 && z == sc[0])) continue;
+        if (z == 8) {                                           // the full-size kernel; its component pick skips components without blocks
+            JpegGeom g = {};
+            g.ncomp = 3;
+            long blocks = 0;
+            for (int c = 0; c < 3; c++) {
+                g.bw[c] = bw[c]; g.bh[c] = bh[c]; g.coef_off[c] = coef_off[c]; g.plane_off[c] = plane_off[c]; g.blk_start[c] = blocks;
+                if (c < ncomp && sc[c] == 8) blocks += (long)bw[c] * bh[c];
+            }
+            g.blk_start[3] = blocks;
+            const dim3 grid((unsigned)((blocks + 31) / 32));
+            if (coef) hipLaunchKernelGGL(k_jpeg_idct<false>, grid, dim3(256), 0, s, cf, nullptr, nullptr, nullptr, quant, g, ctx->jpeg_planes);
+            else hipLaunchKernelGGL(k_jpeg_idct<true>, grid, dim3(256), 0, s, nullptr, m, offsets, vl, quant, g, ctx->jpeg_planes);
+            SV_LAUNCH_CHECK("k_jpeg_idct");
+            continue;
+        }
+        JpegRGeom g = {};
+        const int group = z == 4 ? 1 : 4 / z;
+        long items = 0;
+        for (int c = 0; c < 3; c++) {
+            const bool mine = c < ncomp && sc[c] == z;
+            g.bw[c] = bw[c]; g.bh[c] = mine ? bh[c] : 0;
+            g.ipr[c] = (bw[c] + group - 1) / group;
+            g.pitch[c] = ppitch[c]; g.coef_off[c] = coef_off[c]; g.plane_off[c] = plane_off[c]; g.item_start[c] = items;
+            items += (long)g.ipr[c] * g.bh[c];
+        }
+        g.item_start[3] = items;
+        const dim3 grid((unsigned)((items + (z == 4 ? 63 : 255)) / (z == 4 ? 64 : 256)));
+        if (z == 4) {
+            if (coef) hipLaunchKernelGGL(k_jpeg_idct4<false>, grid, dim3(256), 0, s, cf, nullptr, nullptr, nullptr, quant, g, ctx->jpeg_planes);
+            else hipLaunchKernelGGL(k_jpeg_idct4<true>, grid, dim3(256), 0, s, nullptr, m, offsets, vl, quant, g, ctx->jpeg_planes);
+        } else if (z == 2) {
+            if (coef) hipLaunchKernelGGL((k_jpeg_idct_small<2, false>), grid, dim3(256), 0, s, cf, nullptr, nullptr, nullptr, quant, g, ctx->jpeg_planes);
+            else hipLaunchKernelGGL((k_jpeg_idct_small<2, true>), grid, dim3(256), 0, s, nullptr, m, offsets, vl, quant, g, ctx->jpeg_planes);
+        } else {
+            if (coef) hipLaunchKernelGGL((k_jpeg_idct_small<1, false>), grid, dim3(256), 0, s, cf, nullptr, nullptr, nullptr, quant, g, ctx->jpeg_planes);
+            else hipLaunchKernelGGL((k_jpeg_idct_small<1, true>), grid, dim3(256), 0, s, nullptr, m, offsets, vl, quant, g, ctx->jpeg_planes);
+        }
+        SV_LAUNCH_CHECK("k_jpeg_idct (reduced)");
+    }
+    JpegCGeom cg = {};
+    cg.ncomp = ncomp; cg.orientation = info->orientation;
+    cg.W = (info->width + denom - 1) / denom; cg.H = (info->height + denom - 1) / denom;
+    cg.OW = info->orientation >= 5 ? cg.H : cg.W; cg.OH = info->orientation >= 5 ? cg.W : cg.H;
+    cg.hup = ncomp == 3 ? hmax * S / sc[1] : 1;                 // 2 only for 4:2:2; the vertical relation is 1 for every sampling the front end takes
+    const int cw = (info->width * sc[1] + hmax * 8 - 1) / (hmax * 8);
+    cg.dw = S > 1 ? cw : 0;                                     // jdsample.c: no fancy up-sampling when blocks are 1x1
+    for (int c = 0; c < 3; c++) { cg.pitch[c] = ppitch[c]; cg.plane_off[c] = plane_off[c]; }
+    hipLaunchKernelGGL(k_jpeg_colour_reduced, dim3((unsigned)((cg.OW + 255) / 256), (unsigned)cg.OH), dim3(256), 0, s, ctx->jpeg_planes, cg, bgr, (long)pitch);
+    SV_LAUNCH_CHECK("k_jpeg_colour_reduced");
     return SV_OK;
 }

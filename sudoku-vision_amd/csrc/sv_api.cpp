@@ -830,7 +830,7 @@ extern "C" int sv_count_nonzero_u8(sv_ctx *ctx, const uint8_t *src, int n, int H
     return svk_count_nonzero(src, n, H, W, pitch, img_stride, counts, S(stream));
 }
 
-static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *fn)
+static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *fn, int denom = 1)
 {
     const char *what = nullptr;
     const bool swap = info->orientation >= 5;
@@ -839,7 +839,7 @@ static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *f
     else if (!((info->h_samp == 1 && info->v_samp == 1) || (info->h_samp == 2 && (info->v_samp == 1 || info->v_samp == 2)))) what = "sampling must be 1x1, 2x1 or 2x2";
     else if (!(info->orientation >= 1 && info->orientation <= 8)) what = "orientation must be 1..8";
     else if (!(info->out_width == (swap ? info->height : info->width) && info->out_height == (swap ? info->width : info->height))) what = "out_width/out_height do not match the orientation";
-    else if (pitch < 3 * (ptrdiff_t)info->out_width) what = "pitch smaller than a row";
+    else if (pitch < 3 * (ptrdiff_t)((info->out_width + denom - 1) / denom)) what = "pitch smaller than a row";
     return what ? sv_fail(SV_ERR_BAD_ARG, "%s: %s", fn, what) : SV_OK;
 }
 
@@ -860,6 +860,41 @@ extern "C" int sv_jpeg_reconstruct_sparse_bgr_u8(sv_ctx *ctx, const sv_jpeg_info
     if (rc) return rc;
     REQUIRE(((uintptr_t)masks & 7) == 0 && ((uintptr_t)offsets & 3) == 0 && ((uintptr_t)values & 1) == 0 && ((uintptr_t)quant & 15) == 0, "misaligned argument");
     return svk_jpeg_reconstruct(ctx, info, nullptr, masks, offsets, values, quant, bgr, pitch, S(stream));
+}
+
+static bool jpeg_scale_ok(int d) { return d == 1 || d == 2 || d == 4 || d == 8; }
+
+extern "C" int sv_jpeg_scaled_size(const sv_jpeg_info *info, int scale_denom, int *out_width, int *out_height)
+{
+    REQUIRE(jpeg_scale_ok(scale_denom), "scale_denom must be 1, 2, 4 or 8");
+    REQUIRE(info && out_width && out_height, "NULL argument");
+    *out_width = (info->out_width + scale_denom - 1) / scale_denom;
+    *out_height = (info->out_height + scale_denom - 1) / scale_denom;
+    return SV_OK;
+}
+
+extern "C" int sv_jpeg_reconstruct_scaled_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *coef, const uint16_t *quant, uint8_t *bgr, ptrdiff_t pitch, void *stream,
+                                                 int scale_denom)
+{
+    REQUIRE(jpeg_scale_ok(scale_denom), "scale_denom must be 1, 2, 4 or 8");
+    if (scale_denom == 1) return sv_jpeg_reconstruct_bgr_u8(ctx, info, coef, quant, bgr, pitch, stream);
+    REQUIRE(ctx && info && coef && quant && bgr, "NULL argument");
+    const int rc = jpeg_info_ok(info, pitch, __func__, scale_denom);
+    if (rc) return rc;
+    REQUIRE(((uintptr_t)coef & 15) == 0 && ((uintptr_t)quant & 15) == 0, "coef and quant must be 16-byte aligned");
+    return svk_jpeg_reconstruct_scaled(ctx, info, scale_denom, coef, nullptr, nullptr, nullptr, quant, bgr, pitch, S(stream));
+}
+
+extern "C" int sv_jpeg_reconstruct_sparse_scaled_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
+                                                        const uint16_t *quant, uint8_t *bgr, ptrdiff_t pitch, void *stream, int scale_denom)
+{
+    REQUIRE(jpeg_scale_ok(scale_denom), "scale_denom must be 1, 2, 4 or 8");
+    if (scale_denom == 1) return sv_jpeg_reconstruct_sparse_bgr_u8(ctx, info, masks, offsets, values, quant, bgr, pitch, stream);
+    REQUIRE(ctx && info && masks && offsets && values && quant && bgr, "NULL argument");
+    const int rc = jpeg_info_ok(info, pitch, __func__, scale_denom);
+    if (rc) return rc;
+    REQUIRE(((uintptr_t)masks & 7) == 0 && ((uintptr_t)offsets & 3) == 0 && ((uintptr_t)values & 1) == 0 && ((uintptr_t)quant & 15) == 0, "misaligned argument");
+    return svk_jpeg_reconstruct_scaled(ctx, info, scale_denom, nullptr, masks, offsets, values, quant, bgr, pitch, S(stream));
 }
 
 // K2 into the caller's cells (or the context's), then the forward `model` selects: 0 DigitCNN, 1 DigitCNNv3, 2 DigitCNNv3Light

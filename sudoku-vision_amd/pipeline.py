@@ -488,11 +488,12 @@ def check_constraints(grid):
     return out
 
 
-def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confidence=0.7, component_filter=False):
+def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confidence=0.7, component_filter=False, reduce=1):
     """run_pipeline(image_path) of pipeline/run.py:244-355 on the MI355X path: JPEG -> frame in HBM (imgcodecs) -> K1 -> host
     corner search -> K2 (warped 450x450 grid kept, as the reference keeps it) -> preprocess_cell + DigitCNN (K3) -> constraint
     check -> in-process solver.  Same PipelineResult fields, same error strings, same partial results on failure.
-    component_filter=True: the corner search reads the binary behind the exact filters K4 and K11 (recognize_image); same result."""
+    component_filter=True: the corner search reads the binary behind the exact filters K4 and K11 (recognize_image); same result.
+    reduce = 2, 4 or 8: the JPEG is decoded at 1/reduce of its size (cv2.IMREAD_REDUCED_COLOR_*) and everything downstream runs on that frame."""
     from . import imgcodecs
     from .runtime import default_context
     res = PipelineResult(success=False)
@@ -500,7 +501,7 @@ def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confide
     ctx = ctx or default_context()
     if state_dict is not None:
         ctx.load_state_dict(state_dict)
-    frame = imgcodecs.imread(image_path, device=True, ctx=ctx)
+    frame = imgcodecs.imread(image_path, device=True, ctx=ctx, reduce=reduce)
     if frame is None:
         res.error = f"Failed to load image: {image_path}"
         return res

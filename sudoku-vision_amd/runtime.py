@@ -555,18 +555,38 @@ class Context:
         cap = int(info.sparse_capacity)
         return (base, base + 8 * nb, base + 12 * nb, cap), base + (12 * nb + 2 * cap + 63) // 64 * 64
 
-    def _jpeg_reconstruct(self, info, db, lay, qoff, out, dense, stream):
+    def _jpeg_reconstruct(self, info, db, lay, qoff, out, dense, stream, reduce=1):
         """Coefficients staged at device address db as _jpeg_layout `lay`, quantisation tables at db + qoff -> BGR in `out`, on `stream`."""
         p = [C.c_void_p(db + lay[2])] if dense else [C.c_void_p(db + o) for o in lay[:3]]
-        fn = self._lib.sv_jpeg_reconstruct_bgr_u8 if dense else self._lib.sv_jpeg_reconstruct_sparse_bgr_u8
-        self._check(fn(self._h, C.byref(info), *p, C.c_void_p(db + qoff), _ptr(out), out.stride(0), stream), "sv_jpeg_reconstruct")
+        args = (self._h, C.byref(info), *p, C.c_void_p(db + qoff), _ptr(out), out.stride(0), stream)
+        if reduce == 1:
+            fn = self._lib.sv_jpeg_reconstruct_bgr_u8 if dense else self._lib.sv_jpeg_reconstruct_sparse_bgr_u8
+            self._check(fn(*args), "sv_jpeg_reconstruct")
+        else:
+            fn = self._lib.sv_jpeg_reconstruct_scaled_bgr_u8 if dense else self._lib.sv_jpeg_reconstruct_sparse_scaled_bgr_u8
+            self._check(fn(*args, reduce), "sv_jpeg_reconstruct_scaled")
 
-    def imdecode_batch(self, datas, threads=16, dense=False):
+    @staticmethod
+    def jpeg_reduce_arg(reduce):
+        """reduce= of the imdecode family: libjpeg's scale_denom, 1, 2, 4 or 8"""
+        if not isinstance(reduce, (int, np.integer)) or reduce not in (1, 2, 4, 8):
+            raise ValueError(f"reduce must be 1, 2, 4 or 8, not {reduce!r}")
+        return int(reduce)
+
+    def _jpeg_out_shape(self, info, reduce):
+        """(rows, columns) of the decoded frame: ceil(out_height / reduce), ceil(out_width / reduce)"""
+        w, h = C.c_int(), C.c_int()
+        self._check(self._lib.sv_jpeg_scaled_size(C.byref(info), reduce, C.byref(w), C.byref(h)), "sv_jpeg_scaled_size")
+        return h.value, w.value
+
+    def imdecode_batch(self, datas, threads=16, dense=False, reduce=1):
         """A batch of JPEG files -> uint8 CUDA tensor [n,H,W,3] when all share a shape, else a list of [H,W,3] tensors.
+        reduce = 2, 4 or 8 (one value for the batch): libjpeg's reduced-size decode, frames of ceil(H / reduce) x ceil(W / reduce).
         Images are Huffman-decoded on `threads` host threads (sv_jpeg_entropy_decode_batch) into pinned memory in the compact
         mask + values form (dense=True: plain int16 blocks), cross PCIe one image per copy, and are reconstructed on the GPU
         back to back.  Returns after the last launch; the next call's host decoding overlaps this call's copies and kernels."""
         from . import host
+        reduce = self.jpeg_reduce_arg(reduce)
         n = len(datas)
         datas = [bytes(d) for d in datas]
         infos = [host.jpeg_parse(d) for d in datas]
@@ -591,29 +611,32 @@ class Context:
                     (C.c_long * n)(*[l[3] for l in lay]), used)
         self._check(self._lib.sv_jpeg_entropy_decode_batch(bufs, sizes, n, *args, C.c_void_p(pb + qoff), int(threads), status),
                       "sv_jpeg_entropy_decode_batch")
-        same = all((i.out_height, i.out_width) == (infos[0].out_height, infos[0].out_width) for i in infos)
+        shapes = [self._jpeg_out_shape(i, reduce) for i in infos]
+        same = all(sh == shapes[0] for sh in shapes)
         if same:
-            out = torch.empty((n, infos[0].out_height, infos[0].out_width, 3), dtype=torch.uint8, device=self.device)
+            out = torch.empty((n, *shapes[0], 3), dtype=torch.uint8, device=self.device)
             outs = [out[i] for i in range(n)]
         else:
-            outs = [torch.empty((i.out_height, i.out_width, 3), dtype=torch.uint8, device=self.device) for i in infos]
+            outs = [torch.empty((*sh, 3), dtype=torch.uint8, device=self.device) for sh in shapes]
         dev[qoff:qoff + 384 * n].copy_(pin[qoff:qoff + 384 * n], non_blocking=True)
         sent, stream = 0, _stream_ptr()
         for i, (info, l) in enumerate(zip(infos, lay)):
             end = l[2] + 2 * (int(info.coef_count) if dense else used[i])
             dev[base[i]:end].copy_(pin[base[i]:end], non_blocking=True)
-            self._jpeg_reconstruct(info, db, l, qoff + 384 * i, outs[i], dense, stream)
+            self._jpeg_reconstruct(info, db, l, qoff + 384 * i, outs[i], dense, stream, reduce)
             sent += end - base[i]
         ev.record(torch.cuda.current_stream(self.device))
         self._jpeg_last_bytes = sent / max(n, 1)
         return out if same else outs
 
-    def imdecode(self, data: bytes, threads=1, out=None, dense=False):
+    def imdecode(self, data: bytes, threads=1, out=None, dense=False, reduce=1):
         """cv2.imdecode / cv2.imread of a baseline JPEG -> BGR uint8 CUDA tensor [H,W,3] (EXIF orientation applied).
         Huffman decoding on the host (csrc/host_jpeg.cpp; `threads` work on restart intervals when the file has them) into
-        pinned staging memory, everything after it on the GPU."""
+        pinned staging memory, everything after it on the GPU.  reduce = 2, 4 or 8: cv2.IMREAD_REDUCED_COLOR_*, the frame is
+        ceil(H / reduce) x ceil(W / reduce) and is never reconstructed at full size."""
+        reduce = self.jpeg_reduce_arg(reduce)
         if out is None and threads <= 1:
-            return self.imdecode_batch([data], 1, dense=dense)[0]
+            return self.imdecode_batch([data], 1, dense=dense, reduce=reduce)[0]
         from . import host
         data = bytes(data)
         info = host.jpeg_parse(data)
@@ -630,9 +653,12 @@ class Context:
             end = lay[2] + 2 * used.value
         dev[:end].copy_(pin[:end], non_blocking=True)
         dev[qoff:qoff + 384].copy_(pin[qoff:qoff + 384], non_blocking=True)
+        shape = self._jpeg_out_shape(info, reduce)
         if out is None:
-            out = torch.empty((info.out_height, info.out_width, 3), dtype=torch.uint8, device=self.device)
-        self._jpeg_reconstruct(info, db, lay, qoff, out, dense, _stream_ptr())
+            out = torch.empty((*shape, 3), dtype=torch.uint8, device=self.device)
+        elif tuple(out.shape) != (*shape, 3):
+            raise ValueError(f"out must be [{shape[0]}, {shape[1]}, 3], not {list(out.shape)}")
+        self._jpeg_reconstruct(info, db, lay, qoff, out, dense, _stream_ptr(), reduce)
         ev.record(torch.cuda.current_stream(self.device))
         return out
 
