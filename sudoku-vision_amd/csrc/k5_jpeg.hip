@@ -1,28 +1,25 @@
 // Device half of the JPEG front end (scope row N4; cv2.imread at pipeline/run.py:250): Huffman-decoded coefficient
 // blocks -> BGR frame in HBM.  Integer arithmetic throughout, bit-exact with libjpeg's defaults (the decoder behind
 // cv2.imread and Pillow): JDCT_ISLOW inverse DCT, "fancy" (triangle-filter) chroma up-sampling, 16-bit fixed-point
-// YCbCr -> RGB, EXIF orientation.
+// YCbCr -> RGB, EXIF orientation; at full size and at libjpeg's scale_denom 2, 4, 8 (cv2.IMREAD_REDUCED_COLOR_*).
 //
-//   k_jpeg_idct    one thread per block row/column, 8 threads per 8x8 block, 32 blocks per workgroup.  Coefficients come in as
-//                  one 16-byte load per thread (a block row), are dequantised into LDS, transformed in place column-wise then
-//                  row-wise (LDS rows padded to 9 words: both passes conflict-free), and leave as one 8-byte store per thread
-//                  into the component plane.  HBM-bound: 2 B in + 1 B out per sample.
-//   k_jpeg_colour  one thread per OUTPUT pixel (so stores stay coalesced under every orientation): luma sample, the two
-//                  interpolated chroma samples in closed form (no intermediate full-resolution chroma planes), colour
-//                  conversion, 3-byte store.
-//
-//
-// Reduced-size decode (libjpeg's scale_denom 2, 4, 8; cv2.IMREAD_REDUCED_COLOR_*): the image is never reconstructed at full size.  Luma
-// blocks come out at S = 8 / d samples per side, through jidctred.c's 4x4 / 2x2 / 1x1 transforms; 4:2:0 chroma is decoded at 2S instead of
-// being up-sampled (jdmaster.c), so only 4:2:2 keeps an up-sampling step (h2v1; replication at d = 8, where jdsample.c has no fancy filter).
-// One launch per block size present (at most two); every thread of the reduced kernels stores whole 32-bit words:
+// One rule covers every scale (jdmaster.c; jpeg_plan below): at scale 1 / d luma blocks come out at S = 8 / d samples per side, and a
+// subsampled component is decoded at a larger block size, up to 8, in place of being up-sampled.  So 4:2:0 chroma is up-sampled at full size
+// only (at d > 1 it is decoded at 2S), 4:2:2 chroma keeps its h2v1 step at every d (replication at d = 8, where jdsample.c has no fancy
+// filter), and full size is the case where every block size is 8.  The reduced transforms are jidctred.c's 4x4 / 2x2 / 1x1; the image is never
+// reconstructed at a larger size than asked for.  One IDCT launch per block size present (at most two), then the colour kernel.  Component
+// planes have their own row pitch, a multiple of 4 bytes, and every IDCT thread stores whole 32-bit words:
+//   k_jpeg_idct         S = 8: one thread per block row/column, 8 threads per block, 32 blocks per workgroup.  Coefficients come in as one
+//                       16-byte load per thread (a block row), are dequantised into LDS, transformed in place column-wise then row-wise
+//                       (LDS rows padded to 9 words: both passes conflict-free), and leave as one 8-byte store per thread.
 //   k_jpeg_idct4        S = 4: four threads per block, 64 blocks per workgroup.  A thread dequantises block rows t and t + 4 into LDS,
 //                       transforms columns t and t + 4, then row t, and stores its 4 samples.  Row and column 4 are never touched.
 //   k_jpeg_idct_small   S = 2 or 1: one thread per 4 / S horizontally adjacent blocks, in registers.  S = 2 reads rows and columns
 //                       0, 1, 3, 5, 7; S = 1 reads the DC term alone (compact form: mask, offset and at most one value per block).
-//   k_jpeg_idct         S = 8 (4:2:0 chroma at d = 2): the full-size kernel on a geometry whose luma has no blocks.
-//   k_jpeg_colour_reduced  the colour kernel on planes with their own pitches and a same-size or h2v1 chroma relation.
-// They move the coefficients of the full-size decode for 1 / d^2 of its samples: bound by the coefficient read.
+//   k_jpeg_colour       one thread per OUTPUT pixel (so stores stay coalesced under every orientation): luma sample, the two chroma samples
+//                       (same-size plane, or interpolated in closed form: no intermediate full-resolution chroma planes), colour
+//                       conversion, 3-byte store.
+// The IDCT kernels are HBM-bound, by the coefficient read: 2 B in per full-size sample at every scale, + 1 / d^2 B out.
 //
 // Stated limit: idct8 (and idct4, idct2 alike) computes in 32-bit int where libjpeg's C code uses long and libjpeg-turbo's SIMD code 16-bit intermediates; the
 // three agree while the dequantised coefficients and the first pass's outputs fit 16 bits, which holds for anything an encoder writes
@@ -32,11 +29,20 @@
 
 namespace {
 
-struct JpegGeom {
-    int ncomp, W, H, OW, OH, hmax, vmax, orientation;
-    int bw[3], bh[3];
+struct JpegIdctGeom {                  // one launch of an IDCT kernel: the components whose blocks come out at the kernel's S
+    int bw[3], bh[3];                  // block grid; bh 0 for a component that is not this launch's
+    int ipr[3];                        // work items per block row: blocks (S = 8, 4) or groups of 4 / S blocks (S = 2, 1)
+    int pitch[3];                      // plane row pitch in bytes, a multiple of 4
     long coef_off[3], plane_off[3];
-    long blk_start[4];                 // prefix sums of blocks per component
+    long item_start[4];                // prefix sums of work items per component
+};
+
+struct JpegColourGeom {                // k_jpeg_colour; W, H: the decoded image as stored, OW, OH: after the EXIF orientation
+    int ncomp, W, H, OW, OH, orientation;
+    int hup, vup;                      // what is left to up-sample: 1, 1 chroma planes of the image's size; 2, 1 h2v1; 2, 2 h2v2
+    int dw, dh;                        // chroma plane size for the fancy filters; dw 0 selects plain replication
+    int pitch[3];
+    long plane_off[3];
 };
 
 __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
@@ -74,44 +80,79 @@ __device__ __forceinline__ void idct8(const int (&in)[8], int (&out)[8])
 __constant__ unsigned char kZigzagOf[64] = {0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53,
                                             10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
 
-// SPARSE: the block arrives as (mask over zigzag positions, offset of its first value) + the packed value stream; a thread
-// picks its row's eight coefficients by rank: value index = offset + popcount(mask below the position's zigzag bit).
+// the two 1-D transforms of jidctred.c (CONST_BITS 13); the caller applies the pass-specific descale.  Position 4 is not read.
+__device__ __forceinline__ void idct4(const int (&in)[8], int (&out)[4])
+{
+    const int tmp0 = in[0] * 16384;
+    const int tmp2 = in[2] * 15137 + in[6] * (-6270);
+    const int tmp10 = tmp0 + tmp2, tmp12 = tmp0 - tmp2;
+    const int a = in[7] * (-1730) + in[5] * 11893 + in[3] * (-17799) + in[1] * 8697;
+    const int b = in[7] * (-4176) + in[5] * (-4926) + in[3] * 7373 + in[1] * 20995;
+    out[0] = tmp10 + b; out[3] = tmp10 - b;
+    out[1] = tmp12 + a; out[2] = tmp12 - a;
+}
+
+__device__ __forceinline__ void idct2(int i0, int i1, int i3, int i5, int i7, int &o0, int &o1)
+{
+    const int tmp10 = i0 * 32768;
+    const int tmp0 = i7 * (-5906) + i5 * 6967 + i3 * (-10426) + i1 * 29692;
+    o0 = tmp10 + tmp0; o1 = tmp10 - tmp0;
+}
+
+// One block row, dequantised.  Dense: blk points at the block's 64 values.  SPARSE: the block arrives as (mask over zigzag positions, offset
+// of its first value) + the packed value stream, and a coefficient is picked by rank: vals[popcount(mask below the position's zigzag bit)];
+// only the columns of COLS are looked up, the others come back 0.  q: the component's quantiser steps.
+template <bool SPARSE, unsigned COLS>
+__device__ __forceinline__ void deq_row(const short *__restrict__ blk, unsigned long long mask, const short *__restrict__ vals,
+                                        const unsigned short *__restrict__ q, int row, int (&out)[8])
+{
+    const int4 qr = *(const int4 *)(q + row * 8);
+    const int qw[4] = {qr.x, qr.y, qr.z, qr.w};
+    if (SPARSE) {
+        // the conditional load goes into a scalar, not into out[i]: the compiler keeps out[] as one 8-wide value and would carry copies
+        // of all of it through every branch (40 more VGPRs)
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            int val = 0;
+            if ((COLS >> i) & 1) {
+                const int z = kZigzagOf[row * 8 + i];
+                if ((mask >> z) & 1) val = vals[__popcll(mask & ((1ull << z) - 1))];
+            }
+            out[i] = val * ((i & 1) ? (int)((unsigned)qw[i >> 1] >> 16) : (int)(qw[i >> 1] & 0xffff));
+        }
+    } else {
+        const int4 raw = *(const int4 *)(blk + row * 8);
+        const int cw[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            out[2 * i] = (int)(short)(cw[i] & 0xffff) * (int)(qw[i] & 0xffff);
+            out[2 * i + 1] = (cw[i] >> 16) * (int)((unsigned)qw[i] >> 16);
+        }
+    }
+}
+
+__device__ __forceinline__ int component_of(const JpegIdctGeom &g, long item)
+{
+    return item >= g.item_start[2] ? 2 : item >= g.item_start[1] ? 1 : 0;
+}
+
 template <bool SPARSE>
 __global__ __launch_bounds__(256) void k_jpeg_idct(const short *__restrict__ coef, const unsigned long long *__restrict__ masks,
                                                     const unsigned *__restrict__ offsets, const short *__restrict__ values,
-                                                    const unsigned short *__restrict__ quant, JpegGeom g, u8 *__restrict__ planes)
+                                                    const unsigned short *__restrict__ quant, JpegIdctGeom g, u8 *__restrict__ planes)
 {
     __shared__ int ws[32][8][9];
     const int tid = threadIdx.x, b = tid >> 3, r = tid & 7;
-    const long blk = (long)blockIdx.x * 32 + b;
-    const bool live = blk < g.blk_start[g.ncomp];
-    int c = 0;
-    if (live) { if (blk >= g.blk_start[1]) c = 1; if (blk >= g.blk_start[2]) c = 2; }
-    const long lb = blk - g.blk_start[c];                       // block index within the component
+    const long item = (long)blockIdx.x * 32 + b;
+    const bool live = item < g.item_start[3];
+    const int c = live ? component_of(g, item) : 0;
+    const long lb = item - g.item_start[c];                     // block index within the component
     if (live) {
-        const int4 qr = *(const int4 *)(quant + c * 64 + r * 8);
-        const int qw[4] = {qr.x, qr.y, qr.z, qr.w};
-        if (SPARSE) {
-            const long gb = g.coef_off[c] / 64 + lb;            // block index over all components
-            const unsigned long long mask = masks[gb];
-            const short *v = values + offsets[gb];
+        const long gb = g.coef_off[c] / 64 + lb;                // block index over all components
+        int d[8];
+        deq_row<SPARSE, 0xFFu>(SPARSE ? nullptr : coef + gb * 64, SPARSE ? masks[gb] : 0, SPARSE ? values + offsets[gb] : nullptr, quant + c * 64, r, d);
 #pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const int z = kZigzagOf[r * 8 + i];
-                const int q = (i & 1) ? (int)((unsigned)qw[i >> 1] >> 16) : (int)(qw[i >> 1] & 0xffff);
-                int val = 0;
-                if ((mask >> z) & 1) val = v[__popcll(mask & ((1ull << z) - 1))];
-                ws[b][r][i] = val * q;
-            }
-        } else {
-            const int4 raw = *(const int4 *)(coef + g.coef_off[c] + lb * 64 + r * 8);
-            const int cw[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                ws[b][r][2 * i] = (int)(short)(cw[i] & 0xffff) * (int)(qw[i] & 0xffff);
-                ws[b][r][2 * i + 1] = (cw[i] >> 16) * (int)((unsigned)qw[i] >> 16);
-            }
-        }
+        for (int i = 0; i < 8; i++) ws[b][r][i] = d[i];
     }
     __syncthreads();
     int v[8], o[8];
@@ -134,149 +175,14 @@ __global__ __launch_bounds__(256) void k_jpeg_idct(const short *__restrict__ coe
             hi |= range_limit(descale(o[4 + i], 18)) << (8 * i);
         }
         const int bx = (int)(lb % g.bw[c]), by = (int)(lb / g.bw[c]);
-        const long pw = (long)g.bw[c] * 8;
-        *(uint2 *)(planes + g.plane_off[c] + ((long)by * 8 + r) * pw + bx * 8) = make_uint2(lo, hi);
+        *(uint2 *)(planes + g.plane_off[c] + ((long)by * 8 + r) * g.pitch[c] + bx * 8) = make_uint2(lo, hi);
     }
-}
-
-__device__ __forceinline__ int chroma_sample(const u8 *__restrict__ p, long pw, int dw, int dh, int hmax, int vmax, int x, int y)
-{
-    if (hmax == 1) return p[(long)y * pw + x];
-    const int cx = x >> 1;
-    if (vmax == 1) {                                            // h2v1
-        const u8 *row = p + (long)y * pw;
-        if (dw <= 2) return row[cx];
-        const int cur = row[cx];
-        if (x & 1) return cx == dw - 1 ? cur : (3 * cur + row[cx + 1] + 2) >> 2;
-        return cx == 0 ? cur : (3 * cur + row[cx - 1] + 1) >> 2;
-    }
-    const int cy = y >> 1;                                      // h2v2
-    const u8 *near = p + (long)cy * pw;
-    if (dw <= 2) return near[cx];
-    int fy = (y & 1) ? cy + 1 : cy - 1;
-    fy = fy < 0 ? 0 : fy > dh - 1 ? dh - 1 : fy;
-    const u8 *far = p + (long)fy * pw;
-    const int cur = 3 * near[cx] + far[cx];
-    if (x & 1) return cx == dw - 1 ? (4 * cur + 7) >> 4 : (3 * cur + 3 * near[cx + 1] + far[cx + 1] + 7) >> 4;
-    return cx == 0 ? (4 * cur + 8) >> 4 : (3 * cur + 3 * near[cx - 1] + far[cx - 1] + 8) >> 4;
-}
-
-__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
-
-// source position (x, y) in the stored W x H image of output pixel (ox, oy) under the EXIF orientation
-__device__ __forceinline__ void source_xy(int orientation, int W, int H, int ox, int oy, int &x, int &y)
-{
-    switch (orientation) {
-    case 2: x = W - 1 - ox; y = oy; break;
-    case 3: x = W - 1 - ox; y = H - 1 - oy; break;
-    case 4: x = ox; y = H - 1 - oy; break;
-    case 5: x = oy; y = ox; break;
-    case 6: x = oy; y = H - 1 - ox; break;
-    case 7: x = W - 1 - oy; y = H - 1 - ox; break;
-    case 8: x = W - 1 - oy; y = ox; break;
-    default: x = ox; y = oy;
-    }
-}
-
-// jdcolor.c: FIX(1.40200), FIX(1.77200), FIX(0.34414), FIX(0.71414); cb, cr centred on 0
-__device__ __forceinline__ void store_ycc_as_bgr(u8 *px, int Y, int cb, int cr)
-{
-    px[0] = (u8)clamp255(Y + ((116130 * cb + 32768) >> 16));
-    px[1] = (u8)clamp255(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
-    px[2] = (u8)clamp255(Y + ((91881 * cr + 32768) >> 16));
-}
-
-__global__ __launch_bounds__(256) void k_jpeg_colour(const u8 *__restrict__ planes, JpegGeom g, u8 *__restrict__ bgr, long pitch)
-{
-    const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
-    if (ox >= g.OW) return;
-    int x, y;
-    source_xy(g.orientation, g.W, g.H, ox, oy, x, y);
-    const int Y = planes[g.plane_off[0] + (long)y * g.bw[0] * 8 + x];
-    u8 *px = bgr + (long)oy * pitch + 3L * ox;
-    if (g.ncomp == 3) {
-        const int dw = (g.W + g.hmax - 1) / g.hmax, dh = (g.H + g.vmax - 1) / g.vmax;
-        const int cb = chroma_sample(planes + g.plane_off[1], (long)g.bw[1] * 8, dw, dh, g.hmax, g.vmax, x, y) - 128;
-        const int cr = chroma_sample(planes + g.plane_off[2], (long)g.bw[2] * 8, dw, dh, g.hmax, g.vmax, x, y) - 128;
-        store_ycc_as_bgr(px, Y, cb, cr);
-    } else {
-        px[0] = px[1] = px[2] = (u8)Y;
-    }
-}
-
-// ---- reduced-size decode ----------------------------------------------------------------------------------------------------------
-struct JpegRGeom {                     // one launch of a reduced IDCT kernel: the components whose blocks come out at the kernel's S
-    int bw[3], bh[3];                  // block grid; bh 0 for a component that is not this launch's
-    int ipr[3];                        // work items per block row: blocks (S = 4) or groups of 4 / S blocks (S = 2, 1)
-    int pitch[3];                      // plane row pitch in bytes, a multiple of 4
-    long coef_off[3], plane_off[3];
-    long item_start[4];                // prefix sums of work items per component
-};
-
-struct JpegCGeom {                     // k_jpeg_colour_reduced
-    int ncomp, W, H, OW, OH, orientation;
-    int hup;                           // 1: chroma planes have the output's size; 2: half its width (4:2:2), h2v1 up-sampling
-    int dw;                            // chroma plane width for the h2v1 filter; 0 selects plain replication
-    int pitch[3];
-    long plane_off[3];
-};
-
-// the two 1-D transforms of jidctred.c (CONST_BITS 13); the caller applies the pass-specific descale.  Position 4 is not read.
-__device__ __forceinline__ void idct4(const int (&in)[8], int (&out)[4])
-{
-    const int tmp0 = in[0] * 16384;
-    const int tmp2 = in[2] * 15137 + in[6] * (-6270);
-    const int tmp10 = tmp0 + tmp2, tmp12 = tmp0 - tmp2;
-    const int a = in[7] * (-1730) + in[5] * 11893 + in[3] * (-17799) + in[1] * 8697;
-    const int b = in[7] * (-4176) + in[5] * (-4926) + in[3] * 7373 + in[1] * 20995;
-    out[0] = tmp10 + b; out[3] = tmp10 - b;
-    out[1] = tmp12 + a; out[2] = tmp12 - a;
-}
-
-__device__ __forceinline__ void idct2(int i0, int i1, int i3, int i5, int i7, int &o0, int &o1)
-{
-    const int tmp10 = i0 * 32768;
-    const int tmp0 = i7 * (-5906) + i5 * 6967 + i3 * (-10426) + i1 * 29692;
-    o0 = tmp10 + tmp0; o1 = tmp10 - tmp0;
-}
-
-// One block row, dequantised.  Dense: blk points at the block's 64 values.  SPARSE: (mask, vals) as in k_jpeg_idct; only the columns of
-// COLS are looked up, the others come back 0.  q: the component's quantiser steps.
-template <bool SPARSE, unsigned COLS>
-__device__ __forceinline__ void deq_row(const short *__restrict__ blk, unsigned long long mask, const short *__restrict__ vals,
-                                        const unsigned short *__restrict__ q, int row, int (&out)[8])
-{
-    const int4 qr = *(const int4 *)(q + row * 8);
-    const int qw[4] = {qr.x, qr.y, qr.z, qr.w};
-    if (SPARSE) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            out[i] = 0;
-            if (!((COLS >> i) & 1)) continue;
-            const int z = kZigzagOf[row * 8 + i];
-            const int qv = (i & 1) ? (int)((unsigned)qw[i >> 1] >> 16) : (int)(qw[i >> 1] & 0xffff);
-            if ((mask >> z) & 1) out[i] = vals[__popcll(mask & ((1ull << z) - 1))] * qv;
-        }
-    } else {
-        const int4 raw = *(const int4 *)(blk + row * 8);
-        const int cw[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            out[2 * i] = (int)(short)(cw[i] & 0xffff) * (int)(qw[i] & 0xffff);
-            out[2 * i + 1] = (cw[i] >> 16) * (int)((unsigned)qw[i] >> 16);
-        }
-    }
-}
-
-__device__ __forceinline__ int component_of(const JpegRGeom &g, long item)
-{
-    return item >= g.item_start[2] ? 2 : item >= g.item_start[1] ? 1 : 0;
 }
 
 template <bool SPARSE>
 __global__ __launch_bounds__(256) void k_jpeg_idct4(const short *__restrict__ coef, const unsigned long long *__restrict__ masks,
                                                      const unsigned *__restrict__ offsets, const short *__restrict__ values,
-                                                     const unsigned short *__restrict__ quant, JpegRGeom g, u8 *__restrict__ planes)
+                                                     const unsigned short *__restrict__ quant, JpegIdctGeom g, u8 *__restrict__ planes)
 {
     __shared__ int ws[64][73];                                  // [block][row * 9 + column]; 73: neighbouring blocks start 9 banks apart
     const int tid = threadIdx.x, b = tid >> 2, t = tid & 3;
@@ -330,7 +236,7 @@ __global__ __launch_bounds__(256) void k_jpeg_idct4(const short *__restrict__ co
 template <int S, bool SPARSE>
 __global__ __launch_bounds__(256) void k_jpeg_idct_small(const short *__restrict__ coef, const unsigned long long *__restrict__ masks,
                                                           const unsigned *__restrict__ offsets, const short *__restrict__ values,
-                                                          const unsigned short *__restrict__ quant, JpegRGeom g, u8 *__restrict__ planes)
+                                                          const unsigned short *__restrict__ quant, JpegIdctGeom g, u8 *__restrict__ planes)
 {
     static_assert(S == 1 || S == 2, "block sizes 1 and 2");
     constexpr int G = 4 / S;                                    // blocks per thread: S rows of G * S = 4 samples
@@ -376,7 +282,54 @@ __global__ __launch_bounds__(256) void k_jpeg_idct_small(const short *__restrict
     for (int i = 0; i < S; i++) *(unsigned *)(planes + g.plane_off[c] + ((long)by * S + i) * g.pitch[c] + 4 * k) = word[i];
 }
 
-__global__ __launch_bounds__(256) void k_jpeg_colour_reduced(const u8 *__restrict__ planes, JpegCGeom g, u8 *__restrict__ bgr, long pitch)
+__device__ __forceinline__ int chroma_sample(const u8 *__restrict__ p, long pw, int dw, int dh, int hmax, int vmax, int x, int y)
+{
+    if (hmax == 1) return p[(long)y * pw + x];
+    const int cx = x >> 1;
+    if (vmax == 1) {                                            // h2v1
+        const u8 *row = p + (long)y * pw;
+        if (dw <= 2) return row[cx];
+        const int cur = row[cx];
+        if (x & 1) return cx == dw - 1 ? cur : (3 * cur + row[cx + 1] + 2) >> 2;
+        return cx == 0 ? cur : (3 * cur + row[cx - 1] + 1) >> 2;
+    }
+    const int cy = y >> 1;                                      // h2v2
+    const u8 *near = p + (long)cy * pw;
+    if (dw <= 2) return near[cx];
+    int fy = (y & 1) ? cy + 1 : cy - 1;
+    fy = fy < 0 ? 0 : fy > dh - 1 ? dh - 1 : fy;
+    const u8 *far = p + (long)fy * pw;
+    const int cur = 3 * near[cx] + far[cx];
+    if (x & 1) return cx == dw - 1 ? (4 * cur + 7) >> 4 : (3 * cur + 3 * near[cx + 1] + far[cx + 1] + 7) >> 4;
+    return cx == 0 ? (4 * cur + 8) >> 4 : (3 * cur + 3 * near[cx - 1] + far[cx - 1] + 8) >> 4;
+}
+
+__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+
+// source position (x, y) in the stored W x H image of output pixel (ox, oy) under the EXIF orientation
+__device__ __forceinline__ void source_xy(int orientation, int W, int H, int ox, int oy, int &x, int &y)
+{
+    switch (orientation) {
+    case 2: x = W - 1 - ox; y = oy; break;
+    case 3: x = W - 1 - ox; y = H - 1 - oy; break;
+    case 4: x = ox; y = H - 1 - oy; break;
+    case 5: x = oy; y = ox; break;
+    case 6: x = oy; y = H - 1 - ox; break;
+    case 7: x = W - 1 - oy; y = H - 1 - ox; break;
+    case 8: x = W - 1 - oy; y = ox; break;
+    default: x = ox; y = oy;
+    }
+}
+
+// jdcolor.c: FIX(1.40200), FIX(1.77200), FIX(0.34414), FIX(0.71414); cb, cr centred on 0
+__device__ __forceinline__ void store_ycc_as_bgr(u8 *px, int Y, int cb, int cr)
+{
+    px[0] = (u8)clamp255(Y + ((116130 * cb + 32768) >> 16));
+    px[1] = (u8)clamp255(Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+    px[2] = (u8)clamp255(Y + ((91881 * cr + 32768) >> 16));
+}
+
+__global__ __launch_bounds__(256) void k_jpeg_colour(const u8 *__restrict__ planes, JpegColourGeom g, u8 *__restrict__ bgr, long pitch)
 {
     const int ox = blockIdx.x * 256 + threadIdx.x, oy = blockIdx.y;
     if (ox >= g.OW) return;
@@ -385,15 +338,55 @@ __global__ __launch_bounds__(256) void k_jpeg_colour_reduced(const u8 *__restric
     const int Y = planes[g.plane_off[0] + (long)y * g.pitch[0] + x];
     u8 *px = bgr + (long)oy * pitch + 3L * ox;
     if (g.ncomp == 3) {
-        const int cb = chroma_sample(planes + g.plane_off[1], g.pitch[1], g.dw, g.H, g.hup, 1, x, y) - 128;
-        const int cr = chroma_sample(planes + g.plane_off[2], g.pitch[2], g.dw, g.H, g.hup, 1, x, y) - 128;
+        const int cb = chroma_sample(planes + g.plane_off[1], g.pitch[1], g.dw, g.dh, g.hup, g.vup, x, y) - 128;
+        const int cr = chroma_sample(planes + g.plane_off[2], g.pitch[2], g.dw, g.dh, g.hup, g.vup, x, y) - 128;
         store_ycc_as_bgr(px, Y, cb, cr);
     } else {
         px[0] = px[1] = px[2] = (u8)Y;
     }
 }
 
+// the dense or the compact-form instantiation of the IDCT kernel for block size S
+using IdctKernel = void (*)(const short *, const unsigned long long *, const unsigned *, const short *, const unsigned short *, JpegIdctGeom, u8 *);
+
+template <bool SPARSE>
+constexpr IdctKernel idct_kernel(int S)
+{
+    return S == 8 ? k_jpeg_idct<SPARSE> : S == 4 ? k_jpeg_idct4<SPARSE> : S == 2 ? k_jpeg_idct_small<2, SPARSE> : k_jpeg_idct_small<1, SPARSE>;
+}
+
+// How each component is decoded at scale 1 / denom (denom 1, 2, 4 or 8), and where its coefficients and its plane lie
+struct JpegPlan {
+    int sc[3];                         // block size: 8 / denom, doubled while the component is subsampled against it and it is below 8
+    int bw[3], bh[3];                  // block grid (whole MCUs); 0 for a component the image does not have
+    int pitch[3];                      // plane row pitch: bw * sc padded to a multiple of 4
+    long coef_off[3], plane_off[3];
+    long plane_bytes;
+};
+
 }  // namespace
+
+// fn: the entry point that was called, for the error text
+static int jpeg_plan(const sv_jpeg_info *info, int denom, const char *fn, JpegPlan &p)
+{
+    const int hmax = info->h_samp, vmax = info->v_samp, S = 8 / denom;
+    const int mcu_cols = (info->width + 8 * hmax - 1) / (8 * hmax), mcu_rows = (info->height + 8 * vmax - 1) / (8 * vmax);
+    long coff = 0, poff = 0;
+    for (int c = 0; c < 3; c++) {
+        const int h = c == 0 ? hmax : 1, v = c == 0 ? vmax : 1;
+        p.sc[c] = S;                                            // jdmaster.c: decode a subsampled component larger instead of up-sampling it
+        while (p.sc[c] < 8 && (hmax * S) % (h * p.sc[c] * 2) == 0 && (vmax * S) % (v * p.sc[c] * 2) == 0) p.sc[c] *= 2;
+        p.bw[c] = c < info->components ? mcu_cols * h : 0;
+        p.bh[c] = c < info->components ? mcu_rows * v : 0;
+        p.pitch[c] = (p.bw[c] * p.sc[c] + 3) & ~3;
+        p.coef_off[c] = coff; p.plane_off[c] = poff;
+        coff += (long)p.bw[c] * p.bh[c] * 64;
+        poff += (long)p.pitch[c] * p.bh[c] * p.sc[c];
+    }
+    p.plane_bytes = poff;
+    if (coff != info->coef_count) return sv_fail(SV_ERR_BAD_ARG, "%s: coef_count %ld does not match the geometry (%ld)", fn, info->coef_count, coff);
+    return SV_OK;
+}
 
 // the component planes between the IDCT and the colour kernel grow on demand
 static int reserve_planes(sv_ctx *ctx, size_t bytes)
@@ -407,113 +400,41 @@ static int reserve_planes(sv_ctx *ctx, size_t bytes)
     return SV_OK;
 }
 
-int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
-                         const uint16_t *quant, u8 *bgr, ptrdiff_t pitch, hipStream_t s)
-{
-    JpegGeom g;
-    g.ncomp = info->components; g.W = info->width; g.H = info->height; g.OW = info->out_width; g.OH = info->out_height;
-    g.hmax = info->h_samp; g.vmax = info->v_samp; g.orientation = info->orientation;
-    const int mcu_cols = (g.W + 8 * g.hmax - 1) / (8 * g.hmax), mcu_rows = (g.H + 8 * g.vmax - 1) / (8 * g.vmax);
-    long coff = 0, poff = 0, blocks = 0;
-    for (int c = 0; c < 3; c++) {
-        const int h = c == 0 ? g.hmax : 1, v = c == 0 ? g.vmax : 1;
-        g.bw[c] = c < g.ncomp ? mcu_cols * h : 0;
-        g.bh[c] = c < g.ncomp ? mcu_rows * v : 0;
-        g.coef_off[c] = coff; g.plane_off[c] = poff; g.blk_start[c] = blocks;
-        const long nb = (long)g.bw[c] * g.bh[c];
-        coff += nb * 64; poff += nb * 64; blocks += nb;
-    }
-    g.blk_start[3] = blocks;
-    if (g.ncomp == 1) g.blk_start[1] = g.blk_start[2] = blocks;   // the component pick in the kernel compares against these
-    if (coff != info->coef_count) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_reconstruct_bgr_u8: coef_count %ld does not match the geometry (%ld)", info->coef_count, coff);
-    const int rc = reserve_planes(ctx, (size_t)poff);
-    if (rc) return rc;
-    if (coef)
-        hipLaunchKernelGGL(k_jpeg_idct<false>, dim3((unsigned)((blocks + 31) / 32)), dim3(256), 0, s, (const short *)coef, nullptr, nullptr, nullptr, quant, g, ctx->jpeg_planes);
-    else
-        hipLaunchKernelGGL(k_jpeg_idct<true>, dim3((unsigned)((blocks + 31) / 32)), dim3(256), 0, s, nullptr, (const unsigned long long *)masks, offsets, (const short *)values, quant, g,
-                           ctx->jpeg_planes);
-    SV_LAUNCH_CHECK("k_jpeg_idct");
-    hipLaunchKernelGGL(k_jpeg_colour, dim3((unsigned)((g.OW + 255) / 256), (unsigned)g.OH), dim3(256), 0, s, ctx->jpeg_planes, g, bgr, (long)pitch);
-    SV_LAUNCH_CHECK("k_jpeg_colour");
-    return SV_OK;
-}
-
-// scale_denom 2, 4 or 8 (1 is svk_jpeg_reconstruct).  bgr: ceil(out_height / d) x ceil(out_width / d) x 3.
-int svk_jpeg_reconstruct_scaled(sv_ctx *ctx, const sv_jpeg_info *info, int denom, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets,
-                                const int16_t *values, const uint16_t *quant, u8 *bgr, ptrdiff_t pitch, hipStream_t s)
+// bgr: ceil(out_height / denom) x ceil(out_width / denom) x 3
+int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, int denom, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
+                         const uint16_t *quant, u8 *bgr, ptrdiff_t pitch, hipStream_t s, const char *fn)
 {
     const int ncomp = info->components, hmax = info->h_samp, vmax = info->v_samp, S = 8 / denom;
-    const int mcu_cols = (info->width + 8 * hmax - 1) / (8 * hmax), mcu_rows = (info->height + 8 * vmax - 1) / (8 * vmax);
-    int sc[3], bw[3], bh[3], ppitch[3];
-    long coef_off[3], plane_off[3], coff = 0, poff = 0;
-    for (int c = 0; c < 3; c++) {
-        const int h = c == 0 ? hmax : 1, v = c == 0 ? vmax : 1;
-        sc[c] = S;                                              // jdmaster.c: decode a subsampled component larger instead of up-sampling it
-        while (sc[c] < 8 && (hmax * S) % (h * sc[c] * 2) == 0 && (vmax * S) % (v * sc[c] * 2) == 0) sc[c] *= 2;
-        bw[c] = c < ncomp ? mcu_cols * h : 0;
-        bh[c] = c < ncomp ? mcu_rows * v : 0;
-        ppitch[c] = (bw[c] * sc[c] + 3) & ~3;
-        coef_off[c] = coff; plane_off[c] = poff;
-        coff += (long)bw[c] * bh[c] * 64;
-        poff += (long)ppitch[c] * bh[c] * sc[c];
-    }
-    if (coff != info->coef_count) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_reconstruct_scaled_bgr_u8: coef_count %ld does not match the geometry (%ld)", info->coef_count, coff);
-    const int rc = reserve_planes(ctx, (size_t)poff);
-    if (rc) return rc;
-    const unsigned long long *m = (const unsigned long long *)masks;
-    const short *cf = (const short *)coef, *vl = (const short *)values;
+    JpegPlan p;
+    int rc = jpeg_plan(info, denom, fn, p);
+    if (rc || (rc = reserve_planes(ctx, (size_t)p.plane_bytes))) return rc;
     for (int first = 0; first < ncomp; first++) {               // one launch per block size: luma's, then chroma's where it differs
-        const int z = sc[first];
-        if (first == 2 || (first == 1 && z == sc[0])) continue;
-        if (z == 8) {                                           // the full-size kernel; its component pick skips components without blocks
-            JpegGeom g = {};
-            g.ncomp = 3;
-            long blocks = 0;
-            for (int c = 0; c < 3; c++) {
-                g.bw[c] = bw[c]; g.bh[c] = bh[c]; g.coef_off[c] = coef_off[c]; g.plane_off[c] = plane_off[c]; g.blk_start[c] = blocks;
-                if (c < ncomp && sc[c] == 8) blocks += (long)bw[c] * bh[c];
-            }
-            g.blk_start[3] = blocks;
-            const dim3 grid((unsigned)((blocks + 31) / 32));
-            if (coef) hipLaunchKernelGGL(k_jpeg_idct<false>, grid, dim3(256), 0, s, cf, nullptr, nullptr, nullptr, quant, g, ctx->jpeg_planes);
-            else hipLaunchKernelGGL(k_jpeg_idct<true>, grid, dim3(256), 0, s, nullptr, m, offsets, vl, quant, g, ctx->jpeg_planes);
-            SV_LAUNCH_CHECK("k_jpeg_idct");
-            continue;
-        }
-        JpegRGeom g = {};
-        const int group = z == 4 ? 1 : 4 / z;
+        const int z = p.sc[first];
+        if (first == 2 || (first == 1 && z == p.sc[0])) continue;
+        JpegIdctGeom g = {};
+        const int group = z >= 4 ? 1 : 4 / z, per_wg = z == 8 ? 32 : z == 4 ? 64 : 256;
         long items = 0;
         for (int c = 0; c < 3; c++) {
-            const bool mine = c < ncomp && sc[c] == z;
-            g.bw[c] = bw[c]; g.bh[c] = mine ? bh[c] : 0;
-            g.ipr[c] = (bw[c] + group - 1) / group;
-            g.pitch[c] = ppitch[c]; g.coef_off[c] = coef_off[c]; g.plane_off[c] = plane_off[c]; g.item_start[c] = items;
+            g.bw[c] = p.bw[c]; g.bh[c] = p.sc[c] == z ? p.bh[c] : 0;
+            g.ipr[c] = (p.bw[c] + group - 1) / group;
+            g.pitch[c] = p.pitch[c]; g.coef_off[c] = p.coef_off[c]; g.plane_off[c] = p.plane_off[c]; g.item_start[c] = items;
             items += (long)g.ipr[c] * g.bh[c];
         }
         g.item_start[3] = items;
-        const dim3 grid((unsigned)((items + (z == 4 ? 63 : 255)) / (z == 4 ? 64 : 256)));
-        if (z == 4) {
-            if (coef) hipLaunchKernelGGL(k_jpeg_idct4<false>, grid, dim3(256), 0, s, cf, nullptr, nullptr, nullptr, quant, g, ctx->jpeg_planes);
-            else hipLaunchKernelGGL(k_jpeg_idct4<true>, grid, dim3(256), 0, s, nullptr, m, offsets, vl, quant, g, ctx->jpeg_planes);
-        } else if (z == 2) {
-            if (coef) hipLaunchKernelGGL((k_jpeg_idct_small<2, false>), grid, dim3(256), 0, s, cf, nullptr, nullptr, nullptr, quant, g, ctx->jpeg_planes);
-            else hipLaunchKernelGGL((k_jpeg_idct_small<2, true>), grid, dim3(256), 0, s, nullptr, m, offsets, vl, quant, g, ctx->jpeg_planes);
-        } else {
-            if (coef) hipLaunchKernelGGL((k_jpeg_idct_small<1, false>), grid, dim3(256), 0, s, cf, nullptr, nullptr, nullptr, quant, g, ctx->jpeg_planes);
-            else hipLaunchKernelGGL((k_jpeg_idct_small<1, true>), grid, dim3(256), 0, s, nullptr, m, offsets, vl, quant, g, ctx->jpeg_planes);
-        }
-        SV_LAUNCH_CHECK("k_jpeg_idct (reduced)");
+        const IdctKernel k = coef ? idct_kernel<false>(z) : idct_kernel<true>(z);
+        hipLaunchKernelGGL(k, dim3((unsigned)((items + per_wg - 1) / per_wg)), dim3(256), 0, s, (const short *)coef, (const unsigned long long *)masks, offsets,
+                           (const short *)values, quant, g, ctx->jpeg_planes);
+        SV_LAUNCH_CHECK("k_jpeg_idct");
     }
-    JpegCGeom cg = {};
+    JpegColourGeom cg = {};
     cg.ncomp = ncomp; cg.orientation = info->orientation;
     cg.W = (info->width + denom - 1) / denom; cg.H = (info->height + denom - 1) / denom;
     cg.OW = info->orientation >= 5 ? cg.H : cg.W; cg.OH = info->orientation >= 5 ? cg.W : cg.H;
-    cg.hup = ncomp == 3 ? hmax * S / sc[1] : 1;                 // 2 only for 4:2:2; the vertical relation is 1 for every sampling the front end takes
-    const int cw = (info->width * sc[1] + hmax * 8 - 1) / (hmax * 8);
-    cg.dw = S > 1 ? cw : 0;                                     // jdsample.c: no fancy up-sampling when blocks are 1x1
-    for (int c = 0; c < 3; c++) { cg.pitch[c] = ppitch[c]; cg.plane_off[c] = plane_off[c]; }
-    hipLaunchKernelGGL(k_jpeg_colour_reduced, dim3((unsigned)((cg.OW + 255) / 256), (unsigned)cg.OH), dim3(256), 0, s, ctx->jpeg_planes, cg, bgr, (long)pitch);
-    SV_LAUNCH_CHECK("k_jpeg_colour_reduced");
+    cg.hup = hmax * S / p.sc[1]; cg.vup = vmax * S / p.sc[1];   // full size: hmax, vmax; reduced: 2, 1 for 4:2:2 and 1, 1 otherwise
+    cg.dw = S > 1 ? (info->width * p.sc[1] + hmax * 8 - 1) / (hmax * 8) : 0;    // jdsample.c: no fancy up-sampling when blocks are 1x1
+    cg.dh = (info->height * p.sc[1] + vmax * 8 - 1) / (vmax * 8);
+    for (int c = 0; c < 3; c++) { cg.pitch[c] = p.pitch[c]; cg.plane_off[c] = p.plane_off[c]; }
+    hipLaunchKernelGGL(k_jpeg_colour, dim3((unsigned)((cg.OW + 255) / 256), (unsigned)cg.OH), dim3(256), 0, s, ctx->jpeg_planes, cg, bgr, (long)pitch);
+    SV_LAUNCH_CHECK("k_jpeg_colour");
     return SV_OK;
 }

@@ -830,7 +830,7 @@ extern "C" int sv_count_nonzero_u8(sv_ctx *ctx, const uint8_t *src, int n, int H
     return svk_count_nonzero(src, n, H, W, pitch, img_stride, counts, S(stream));
 }
 
-static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *fn, int denom = 1)
+static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *fn, int denom)
 {
     const char *what = nullptr;
     const bool swap = info->orientation >= 5;
@@ -841,25 +841,6 @@ static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *f
     else if (!(info->out_width == (swap ? info->height : info->width) && info->out_height == (swap ? info->width : info->height))) what = "out_width/out_height do not match the orientation";
     else if (pitch < 3 * (ptrdiff_t)((info->out_width + denom - 1) / denom)) what = "pitch smaller than a row";
     return what ? sv_fail(SV_ERR_BAD_ARG, "%s: %s", fn, what) : SV_OK;
-}
-
-extern "C" int sv_jpeg_reconstruct_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *coef, const uint16_t *quant, uint8_t *bgr, ptrdiff_t pitch, void *stream)
-{
-    REQUIRE(ctx && info && coef && quant && bgr, "NULL argument");
-    const int rc = jpeg_info_ok(info, pitch, "sv_jpeg_reconstruct_bgr_u8");
-    if (rc) return rc;
-    REQUIRE(((uintptr_t)coef & 15) == 0 && ((uintptr_t)quant & 15) == 0, "coef and quant must be 16-byte aligned");
-    return svk_jpeg_reconstruct(ctx, info, coef, nullptr, nullptr, nullptr, quant, bgr, pitch, S(stream));
-}
-
-extern "C" int sv_jpeg_reconstruct_sparse_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
-                                                 const uint16_t *quant, uint8_t *bgr, ptrdiff_t pitch, void *stream)
-{
-    REQUIRE(ctx && info && masks && offsets && values && quant && bgr, "NULL argument");
-    const int rc = jpeg_info_ok(info, pitch, "sv_jpeg_reconstruct_sparse_bgr_u8");
-    if (rc) return rc;
-    REQUIRE(((uintptr_t)masks & 7) == 0 && ((uintptr_t)offsets & 3) == 0 && ((uintptr_t)values & 1) == 0 && ((uintptr_t)quant & 15) == 0, "misaligned argument");
-    return svk_jpeg_reconstruct(ctx, info, nullptr, masks, offsets, values, quant, bgr, pitch, S(stream));
 }
 
 static bool jpeg_scale_ok(int d) { return d == 1 || d == 2 || d == 4 || d == 8; }
@@ -873,28 +854,44 @@ extern "C" int sv_jpeg_scaled_size(const sv_jpeg_info *info, int scale_denom, in
     return SV_OK;
 }
 
+// The four reconstruct entries.  dense: coef, else masks, offsets and values.  Only a scaled entry can come with a bad scale_denom; at
+// scale_denom 1 a scaled entry is the unscaled one, and reports its errors under that name.
+static int jpeg_reconstruct(bool dense, sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
+                            const uint16_t *quant, uint8_t *bgr, ptrdiff_t pitch, void *stream, int scale_denom)
+{
+    static const char *const entry[2][2] = {{"sv_jpeg_reconstruct_sparse_bgr_u8", "sv_jpeg_reconstruct_sparse_scaled_bgr_u8"},
+                                            {"sv_jpeg_reconstruct_bgr_u8", "sv_jpeg_reconstruct_scaled_bgr_u8"}};
+    REQUIRE_AS(entry[dense][1], jpeg_scale_ok(scale_denom), "scale_denom must be 1, 2, 4 or 8");
+    const char *fn = entry[dense][scale_denom != 1];
+    REQUIRE_AS(fn, ctx && info && (dense ? coef != nullptr : masks && offsets && values) && quant && bgr, "NULL argument");
+    const int rc = jpeg_info_ok(info, pitch, fn, scale_denom);
+    if (rc) return rc;
+    if (dense) REQUIRE_AS(fn, ((uintptr_t)coef & 15) == 0 && ((uintptr_t)quant & 15) == 0, "coef and quant must be 16-byte aligned");
+    else REQUIRE_AS(fn, ((uintptr_t)masks & 7) == 0 && ((uintptr_t)offsets & 3) == 0 && ((uintptr_t)values & 1) == 0 && ((uintptr_t)quant & 15) == 0, "misaligned argument");
+    return svk_jpeg_reconstruct(ctx, info, scale_denom, coef, masks, offsets, values, quant, bgr, pitch, S(stream), fn);
+}
+
+extern "C" int sv_jpeg_reconstruct_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *coef, const uint16_t *quant, uint8_t *bgr, ptrdiff_t pitch, void *stream)
+{
+    return jpeg_reconstruct(true, ctx, info, coef, nullptr, nullptr, nullptr, quant, bgr, pitch, stream, 1);
+}
+
+extern "C" int sv_jpeg_reconstruct_sparse_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
+                                                 const uint16_t *quant, uint8_t *bgr, ptrdiff_t pitch, void *stream)
+{
+    return jpeg_reconstruct(false, ctx, info, nullptr, masks, offsets, values, quant, bgr, pitch, stream, 1);
+}
+
 extern "C" int sv_jpeg_reconstruct_scaled_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *coef, const uint16_t *quant, uint8_t *bgr, ptrdiff_t pitch, void *stream,
                                                  int scale_denom)
 {
-    REQUIRE(jpeg_scale_ok(scale_denom), "scale_denom must be 1, 2, 4 or 8");
-    if (scale_denom == 1) return sv_jpeg_reconstruct_bgr_u8(ctx, info, coef, quant, bgr, pitch, stream);
-    REQUIRE(ctx && info && coef && quant && bgr, "NULL argument");
-    const int rc = jpeg_info_ok(info, pitch, __func__, scale_denom);
-    if (rc) return rc;
-    REQUIRE(((uintptr_t)coef & 15) == 0 && ((uintptr_t)quant & 15) == 0, "coef and quant must be 16-byte aligned");
-    return svk_jpeg_reconstruct_scaled(ctx, info, scale_denom, coef, nullptr, nullptr, nullptr, quant, bgr, pitch, S(stream));
+    return jpeg_reconstruct(true, ctx, info, coef, nullptr, nullptr, nullptr, quant, bgr, pitch, stream, scale_denom);
 }
 
 extern "C" int sv_jpeg_reconstruct_sparse_scaled_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *info, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
                                                         const uint16_t *quant, uint8_t *bgr, ptrdiff_t pitch, void *stream, int scale_denom)
 {
-    REQUIRE(jpeg_scale_ok(scale_denom), "scale_denom must be 1, 2, 4 or 8");
-    if (scale_denom == 1) return sv_jpeg_reconstruct_sparse_bgr_u8(ctx, info, masks, offsets, values, quant, bgr, pitch, stream);
-    REQUIRE(ctx && info && masks && offsets && values && quant && bgr, "NULL argument");
-    const int rc = jpeg_info_ok(info, pitch, __func__, scale_denom);
-    if (rc) return rc;
-    REQUIRE(((uintptr_t)masks & 7) == 0 && ((uintptr_t)offsets & 3) == 0 && ((uintptr_t)values & 1) == 0 && ((uintptr_t)quant & 15) == 0, "misaligned argument");
-    return svk_jpeg_reconstruct_scaled(ctx, info, scale_denom, nullptr, masks, offsets, values, quant, bgr, pitch, S(stream));
+    return jpeg_reconstruct(false, ctx, info, nullptr, masks, offsets, values, quant, bgr, pitch, stream, scale_denom);
 }
 
 // K2 into the caller's cells (or the context's), then the forward `model` selects: 0 DigitCNN, 1 DigitCNNv3, 2 DigitCNNv3Light

@@ -170,10 +170,9 @@ int svk_cnn_forward_bf16(sv_ctx *ctx, const u8 *cells, long B, float *logits, u8
 int svk_cnn_forward_h2(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *logits, u8 *digits, float *conf, const int *run_if_clear, hipStream_t s);
 int svk_cell_ink_ratio(const u8 *cells, long B, int npx, float *ratio, int *otsu, hipStream_t s);
 int svk_preprocess_cells(const u8 *cells, long B, u8 *out, hipStream_t s);
-int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
-                         const uint16_t *quant, u8 *bgr, ptrdiff_t pitch, hipStream_t s);   // dense when coef != nullptr, else sparse
-int svk_jpeg_reconstruct_scaled(sv_ctx *ctx, const sv_jpeg_info *info, int denom, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets,
-                                const int16_t *values, const uint16_t *quant, u8 *bgr, ptrdiff_t pitch, hipStream_t s);   // denom 2, 4 or 8
+// denom: libjpeg's scale_denom, 1, 2, 4 or 8; dense when coef != nullptr, else sparse; fn: the entry point that was called, for error texts
+int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, int denom, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
+                         const uint16_t *quant, u8 *bgr, ptrdiff_t pitch, hipStream_t s, const char *fn);
 int svk_softmax_topk(const float *logits, long B, int k, u8 *index, float *prob, hipStream_t s);
 int svk_frame_quality_stats(const u8 *img, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int C, long long *lap_sum, long long *lap_sqsum,
                             uint32_t *hist, hipStream_t s);

@@ -1,7 +1,8 @@
-"""GPU (-m gpu): reduced-size JPEG decode (reduce = 2, 4, 8; csrc/k5_jpeg.hip: k_jpeg_idct4, k_jpeg_idct_small<2>, <1>, the full
-k_jpeg_idct on 4:2:0 chroma at reduce = 2, k_jpeg_colour_reduced) against Pillow's libjpeg-turbo decode at the same scale
+"""GPU (-m gpu): reduced-size JPEG decode (reduce = 2, 4, 8; csrc/k5_jpeg.hip: k_jpeg_idct4, k_jpeg_idct_small<2>, <1>, k_jpeg_idct on
+4:2:0 chroma at reduce = 2, and k_jpeg_colour, the colour kernel of every scale) against Pillow's libjpeg-turbo decode at the same scale
 (tests/test_jpeg_reduced_ref.py::pil_reduced_bgr, which asserts that Pillow did reduce by d).  Exact equality, through the compact and
 the dense transport.  tests/test_jpeg_reduced_ref.py checks the same files against the numpy restatement on the CPU."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -11,7 +12,7 @@ import torch
 import cnn_oracle
 import sv_oracle as o
 import test_jpeg_crafted as T
-from test_jpeg_reduced_ref import DENOMS, crafted_files, pil_reduced_bgr, synth_file
+from test_jpeg_reduced_ref import DENOMS, SCALES, crafted_files, orientation_cases, pil_reduced_bgr, synth_file
 
 pytestmark = pytest.mark.gpu
 
@@ -63,6 +64,49 @@ def test_reduced_orientations(ctx, orient):
     data = synth_file(61, 83, 2, orient)
     want = assert_equals_pillow(ctx, data, 2, orient)
     assert want.shape == ((42, 31, 3) if orient >= 5 else (31, 42, 3))
+
+
+@pytest.mark.parametrize("d", SCALES)
+def test_orientations_samplings_scales(ctx, d):
+    """every EXIF orientation x gray, 4:4:4, 4:2:2, 4:2:0 at scale 1 / d, both transports: the cases
+    tests/test_jpeg_reduced_ref.py::test_restatement_orientations_samplings_scales holds the restatement to on the CPU"""
+    for what, data, want in orientation_cases(d):
+        for dense in (False, True):
+            got = ctx.imdecode(data, dense=dense, reduce=d).cpu().numpy()
+            assert got.shape == want.shape, (what, dense, got.shape, want.shape)
+            assert (got == want).all(), (what, dense, int((got != want).sum()))
+
+
+def test_scaled_entries_at_one_are_the_unscaled_entries(ctx):
+    """the C entry points called directly: sv_jpeg_reconstruct[_sparse]_scaled_bgr_u8 at scale_denom = 1 write the bytes
+    sv_jpeg_reconstruct[_sparse]_bgr_u8 write (the oracle's) into a buffer with padded rows, and nothing outside the rows"""
+    from sudoku_vision_amd import _native, host
+    lib = _native.lib()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(ctx.device).cuda_stream)
+    for sub in (2, "gray"):
+        data = synth_file(61, 83, sub)
+        want = o.imdecode(data)
+        H, W = want.shape[:2]
+        assert (H, W) == (61, 83)
+        info, coef, quant = host.jpeg_entropy_decode(data)
+        _, masks, offs, vals, _ = host.jpeg_entropy_decode_sparse(data)
+        dquant, dcoef = torch.from_numpy(quant.view(np.int16)).to(ctx.device), torch.from_numpy(coef).to(ctx.device)
+        dm, do, dv = (torch.from_numpy(a.view(t)).to(ctx.device) for a, t in ((masks, np.int64), (offs, np.int32), (vals, np.int16)))
+        pitch, offset = 3 * W + 37, 1001
+        inside = np.zeros(offset + H * pitch + 333, bool)
+        inside[((offset + pitch * np.arange(H))[:, None] + np.arange(3 * W)).ravel()] = True
+        for name, coefs in (("sv_jpeg_reconstruct%s_bgr_u8", (p(dcoef),)), ("sv_jpeg_reconstruct_sparse%s_bgr_u8", (p(dm), p(do), p(dv)))):
+            hosts = []
+            for scaled in (False, True):
+                buf = torch.full((inside.size,), 0xA5, dtype=torch.uint8, device=ctx.device)
+                args = (ctx._h, C.byref(info), *coefs, p(dquant), C.c_void_p(buf.data_ptr() + offset), pitch, stream)
+                fn = getattr(lib, name % ("_scaled" if scaled else ""))
+                _native.check(fn(*args, 1) if scaled else fn(*args), fn.__name__)
+                hosts.append(buf.cpu().numpy())
+                assert (hosts[-1][inside].reshape(H, W, 3) == want).all(), (sub, name, scaled)
+                assert (hosts[-1][~inside] == 0xA5).all(), (sub, name, scaled)
+            assert (hosts[0] == hosts[1]).all(), (sub, name)
 
 
 def test_reduced_out_with_pitch(ctx):

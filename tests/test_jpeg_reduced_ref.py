@@ -15,12 +15,17 @@ from PIL import Image, ImageOps
 import jpeg_reduced_ref as R
 import sv_oracle as o
 import test_jpeg_crafted as T
-from test_jpeg import GOLDEN, encode, host, synth_image  # noqa: F401  (host: fixture)
+from test_jpeg import GOLDEN, encode, host, pil_bgr, synth_image  # noqa: F401  (host: fixture)
 
 DENOMS = (2, 4, 8)
 SHAPES = [(61, 83), (64, 80), (17, 9), (8, 8)]                                # (H, W)
 SUBS = (0, 1, 2, "gray")
 B_SIZES = [(9, 17), (17, 9), (33, 18), (34, 47)]                             # W x H of T.B_SIZES with both sides >= 8
+# Every orientation x sampling x scale (full size too), which one colour kernel serves on the GPU (tests/test_gpu_jpeg_reduced.py runs
+# these same cases).  (37, 51): partial MCUs; the reduced 4:2:2 chroma is wider than 2 at d = 2 and 4, so the h2v1 filter runs under
+# the transposing orientations, and is replicated at d = 8.  (17, 9): chroma at most 2 wide, replication only.
+ORIENT_SHAPES = [(37, 51), (17, 9)]                                           # (H, W)
+SCALES = (1,) + DENOMS
 
 
 def pil_reduced_bgr(data, d):
@@ -40,6 +45,15 @@ def synth_file(h, w, sub, orient=1, **kw):
     if sub == "gray":
         return encode(synth_image(h, w, h * 131 + w, gray=True), quality=88, **extra, **kw)
     return encode(synth_image(h, w, h * 131 + w), quality=85, subsampling=sub, **extra, **kw)
+
+
+def orientation_cases(d):
+    """(what, data, expected BGR) at scale 1 / d: Pillow at the same scale; at d = 1 the full-size oracle"""
+    for h, w in ORIENT_SHAPES:
+        for sub in SUBS:
+            for orient in range(1, 9):
+                data = synth_file(h, w, sub, orient)
+                yield (h, w, sub, orient), data, pil_reduced_bgr(data, d) if d > 1 else o.imdecode(data)
 
 
 def crafted_files():
@@ -104,6 +118,16 @@ def test_restatement_orientations(orient):
         ow, oh = R.scaled_size(83, 61, d)
         assert want.shape == ((ow, oh, 3) if orient >= 5 else (oh, ow, 3))
         assert_equal(R.decode_file(data, d), want, d)
+
+
+@pytest.mark.parametrize("d", SCALES)
+def test_restatement_orientations_samplings_scales(d):
+    """the expected images the GPU test uses, before a GPU sees them: Pillow's against the restatement; at d = 1 the oracle's against
+    Pillow's full-size decode (the restatement has no h2v2 up-sampling: 4:2:0 at full size is not a reduced decode)"""
+    for what, data, want in orientation_cases(d):
+        ow, oh = R.scaled_size(what[1], what[0], d)
+        assert want.shape == ((ow, oh, 3) if what[3] >= 5 else (oh, ow, 3)), what
+        assert_equal(R.decode_file(data, d) if d > 1 else pil_bgr(data), want, what)
 
 
 def test_scale_one_is_the_full_decode():
