@@ -4,8 +4,9 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsudokuvision_hip.so")
-# test-only superset build (csrc/Makefile, include/sudoku_vision_xcheck.h): independent second implementations for cross-checks.  Loaded by
-# tests/ and tools/ through lib_xcheck(); never by the package itself.
+# test-only superset (csrc/Makefile, include/sudoku_vision_xcheck.h): the product's objects plus independent second implementations
+# (csrc/x_cnn_round1.hip, csrc/k1_threshold_mm.hip) for cross-checks.  Loaded by tests/ and tools/ through lib_xcheck(); never by the
+# package itself.
 XCHECK_LIB_PATH = os.path.join(_HERE, "csrc", "libsudokuvision_xcheck.so")
 ABI_VERSION = 2
 

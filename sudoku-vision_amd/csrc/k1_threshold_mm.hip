@@ -38,6 +38,7 @@
 //   S2 vertical   1-4-6-4-1, >> 8  -> BL  f16 [y][x]     blurred image, REPLICATE border applied in place afterwards
 //   S3 horizontal 11 taps (approx) -> RT  f16 pair [x][y]
 //   S4 vertical   11 taps (approx) -> decision vs BL, ambiguous pixels listed, 64 x 128 result staged in LDS, written as full rows
+#include "../../include/sudoku_vision_xcheck.h"
 #include "sv_device.h"
 #include "sv_internal.h"
 #include <cstdlib>
@@ -366,7 +367,7 @@ __global__ __launch_bounds__(512, 4) void k_preprocess_mm(const u8 *__restrict__
 }  // namespace
 
 // diagnostics: how many pixels of the launches since the counter was last read went to the exact evaluation (synchronises the device)
-int svk_preprocess_mm_stats(sv_ctx *ctx, unsigned *ambiguous, unsigned long *capacity)
+static int svk_preprocess_mm_stats(sv_ctx *ctx, unsigned *ambiguous, unsigned long *capacity)
 {
     *ambiguous = 0; *capacity = 0;
     if (!ctx->k1_list) return SV_OK;
@@ -376,12 +377,12 @@ int svk_preprocess_mm_stats(sv_ctx *ctx, unsigned *ambiguous, unsigned long *cap
     return SV_OK;
 }
 
-bool svk_preprocess_mm_supported(const u8 *bgr, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const void *out, bool bits)
+static bool svk_preprocess_mm_supported(const u8 *bgr, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const void *out, bool bits)
 {
     return H >= 16 && W >= 16 && W % (bits ? 32 : 16) == 0 && pitch % 4 == 0 && img_stride % 4 == 0 && (uintptr_t)bgr % 4 == 0 && (uintptr_t)out % 16 == 0;
 }
 
-int svk_preprocess_mm(sv_ctx *ctx, const u8 *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, u8 *out, bool bits, float *mean_dbg, hipStream_t s)
+static int svk_preprocess_mm(sv_ctx *ctx, const u8 *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, u8 *out, bool bits, float *mean_dbg, hipStream_t s)
 {
     Taps11 t;
     sv_gaussian_taps_f32(11, t.k);
@@ -403,10 +404,27 @@ int svk_preprocess_mm(sv_ctx *ctx, const u8 *bgr, int n, int H, int W, ptrdiff_t
 }
 
 // turn the diagnostic counter on (allocates 16 bytes in the context)
-int svk_preprocess_mm_enable_stats(sv_ctx *ctx)
+static int svk_preprocess_mm_enable_stats(sv_ctx *ctx)
 {
     if (ctx->k1_list) return SV_OK;
     SV_HIP(hipMalloc(&ctx->k1_list, 16));
     SV_HIP(hipMemset(ctx->k1_list, 0, 16));
     return SV_OK;
+}
+
+// ---- the entry points (include/sudoku_vision_xcheck.h) ------------------------------------------------------------------
+extern "C" int sv_preprocess_mm_u8(sv_ctx *ctx, const uint8_t *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint8_t *binary, float *mean, void *stream)
+{
+    REQUIRE(ctx && bgr && binary, "NULL argument");
+    REQUIRE_FRAMES();
+    if (!svk_preprocess_mm_supported(bgr, H, W, pitch, img_stride, binary, false))
+        return sv_fail(SV_ERR_UNSUPPORTED, "sv_preprocess_mm_u8: needs H, W >= 16, W %% 16 == 0, 4-byte aligned frames and a 16-byte aligned output");
+    return svk_preprocess_mm(ctx, bgr, n, H, W, pitch, img_stride, binary, false, mean, (hipStream_t)stream);
+}
+
+extern "C" int sv_preprocess_stats(sv_ctx *ctx, unsigned *ambiguous, unsigned long *capacity)
+{
+    REQUIRE(ctx && ambiguous && capacity, "NULL argument");
+    if (!ctx->k1_list) { *ambiguous = 0; *capacity = 0; return svk_preprocess_mm_enable_stats(ctx); }
+    return svk_preprocess_mm_stats(ctx, ambiguous, capacity);
 }

@@ -365,15 +365,7 @@ extern "C" int sv_corners_to_minv_batch(const float *corners, int n, int out_siz
 }
 
 // ---- argument checks + dispatch ---------------------------------------------------------------------
-#define REQUIRE_AS(fn, cond, what) \
-    do { if (!(cond)) return sv_fail(SV_ERR_BAD_ARG, "%s: %s", fn, what); } while (0)
-#define REQUIRE(cond, what) REQUIRE_AS(__func__, cond, what)
-
 static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
-// one BGR frame batch: n frames of H x W pixels, `pitch` bytes between rows; 65535 = the grid's z limit
-static inline bool frames_ok(int n, int H, int W, ptrdiff_t pitch) { return n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W; }
-#define REQUIRE_FRAMES() REQUIRE(frames_ok(n, H, W, pitch), "bad shape")
 
 extern "C" int sv_gray_u8(sv_ctx *ctx, const uint8_t *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint8_t *gray, void *stream)
 {
@@ -417,25 +409,6 @@ extern "C" int sv_preprocess_warp_cells_u8(sv_ctx *ctx, const uint8_t *bgr, int 
     REQUIRE_FRAMES();
     return svk_preprocess_warp_fused(ctx, bgr, n, H, W, pitch, img_stride, binary, minv, cells, S(stream));
 }
-
-#ifdef SV_XCHECK   // the matrix-pipe formulation of K1: a second implementation, built into the test-only library
-extern "C" int sv_preprocess_mm_u8(sv_ctx *ctx, const uint8_t *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint8_t *binary, float *mean, void *stream)
-{
-    REQUIRE(ctx && bgr && binary, "NULL argument");
-    REQUIRE_FRAMES();
-    if (!svk_preprocess_mm_supported(bgr, H, W, pitch, img_stride, binary, false))
-        return sv_fail(SV_ERR_UNSUPPORTED, "sv_preprocess_mm_u8: needs H, W >= 16, W %% 16 == 0, 4-byte aligned frames and a 16-byte aligned output");
-    return svk_preprocess_mm(ctx, bgr, n, H, W, pitch, img_stride, binary, false, mean, S(stream));
-}
-
-extern "C" int sv_preprocess_stats(sv_ctx *ctx, unsigned *ambiguous, unsigned long *capacity)
-{
-    REQUIRE(ctx && ambiguous && capacity, "NULL argument");
-    if (!ctx->k1_list) { *ambiguous = 0; *capacity = 0; return svk_preprocess_mm_enable_stats(ctx); }
-    return svk_preprocess_mm_stats(ctx, ambiguous, capacity);
-}
-
-#endif  // SV_XCHECK
 
 extern "C" int sv_preprocess_bits_u8(sv_ctx *ctx, const uint8_t *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint32_t *bits, void *stream)
 {

@@ -7,9 +7,6 @@
 #include <vector>
 
 #include "../../include/sudoku_vision_hip.h"
-#ifdef SV_XCHECK
-#include "../../include/sudoku_vision_xcheck.h"
-#endif
 
 typedef uint8_t u8;
 
@@ -18,11 +15,11 @@ struct sv_weights {
     float *conv1_w = nullptr;   // [32][9]
     float *conv1_b = nullptr;   // [32]
     float *conv2_wreg = nullptr;// [2 np][2 t][72 ks][64 lane]  MFMA B-operand register image
-    float *conv2_wino = nullptr;// [4 nt][16 xi][8 ks][64 lane]  Winograd U = G g G^T as MFMA B-operand image
+    float *conv2_wino = nullptr;// [4 nt][16 xi][8 ks][64 lane]  Winograd U = G g G^T as MFMA B-operand image (x_cnn_round1.hip; null in the product)
     float *conv2_b = nullptr;   // [64]
     float *fc1_wreg = nullptr;  // [196 chunk][8 t][64 lane][4 e] MFMA B-operand register image
     float *fc1_b = nullptr;     // [128]
-    unsigned short *conv2_wsplit = nullptr; // [4 nt][16 xi][3 parts][64 lane][8] U split into three bf16 parts (k_conv_features_wsplit)
+    unsigned short *conv2_wsplit = nullptr; // [4 nt][16 xi][3 parts][64 lane][8] U split into three bf16 parts (x_cnn_round1.hip k_conv_features_wsplit; null in the product)
     unsigned short *conv2_bf16 = nullptr; // [9 tap][4 t][64 lane][8] bf16 MFMA B image (bf16 configuration)
     unsigned short *fc1_bf16 = nullptr;   // [98 step][8 t][64 lane][8] bf16
     // k3_cnn_h2.hip: weights x 2^e split into f16 hi + lo (w * 2^e = hi + lo to 22 bits); scale_inv = 2^-e
@@ -88,7 +85,7 @@ struct sv_ctx {
     int precision = 0;          // SV_PREC_F32 / SV_PREC_BF16 (sv_ctx_set_precision)
     int cnn_kernels = 0;        // SV_CNN_AUTO / _F16PAIR / _F32MFMA (sv_ctx_set_cnn_kernels)
     int *range_flag = nullptr;  // [2] device ints: the per-call kernel choice for f32 inputs (k3_cnn.hip k_input_range)
-    bool x_fc_frame = false;    // xcheck builds: k_fc_head_frame for large batches
+    bool x_fc_frame = false;    // x_cnn_round1.hip (svx_ctx_set_fc_frame_kernel): k_fc_head_frame for large batches; never set in the product
     int dev_ablate = 0;         // SV_DEV builds: k3_cnn_h2.hip ablation / stamp bits
     // optional per-kernel timing (sv_timing_begin/sv_timing_end): hipEvents on the launch stream
     bool timing = false;
@@ -120,6 +117,14 @@ int sv_fail(int code, const char *fmt, ...);
         if (e_ != hipSuccess) return sv_fail(SV_ERR_HIP, "launch %s: %s", name, hipGetErrorString(e_)); \
     } while (0)
 
+// argument checks of the entry points: SV_ERR_BAD_ARG with "<entry point>: <what>"
+#define REQUIRE_AS(fn, cond, what) \
+    do { if (!(cond)) return sv_fail(SV_ERR_BAD_ARG, "%s: %s", fn, what); } while (0)
+#define REQUIRE(cond, what) REQUIRE_AS(__func__, cond, what)
+// one BGR frame batch: n frames of H x W pixels, `pitch` bytes between rows; 65535 = the grid's z limit
+static inline bool frames_ok(int n, int H, int W, ptrdiff_t pitch) { return n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= 3 * (ptrdiff_t)W; }
+#define REQUIRE_FRAMES() REQUIRE(frames_ok(n, H, W, pitch), "bad shape")
+
 int sv_ensure_scratch(sv_ctx *ctx, long cells);
 
 // n elements of src -> a new device buffer *dst, recorded in w.allocs (w: any of the weight structs above)
@@ -135,6 +140,18 @@ int sv_upload(W &w, T **dst, const T *src, size_t n)
 // The conv/fc kernel family of an SV_PREC_F32 forward (svk_cnn_forward).  The values are ABI: sv_conv_kernel_info reports them.
 enum sv_cnn_algo { SV_ALGO_F32MFMA = 0, SV_ALGO_X_WINOGRAD = 2, SV_ALGO_X_WSPLIT = 3, SV_ALGO_F16PAIR = 4 };
 
+// The one seam between the product and the cross-check kernels of the test-only libsudokuvision_xcheck.so: x_cnn_round1.hip defines
+// sv_xcheck, the product links x_none.cpp, where it is null (SV_CNN_X_WINOGRAD / _WSPLIT are then unknown selections and x_fc_frame stays
+// false).  Hidden: the tests load both libraries into one process, and each must see its own whichever was loaded first.
+struct sv_xcheck_ops {
+    bool (*select_conv)(int which, sv_cnn_algo *algo);      // a further selection of sv_ctx_set_cnn_kernels (SV_CNN_X_*) -> its kernel family
+    int (*pack_weights)(sv_weights &w, const float *c2w);   // conv2_wino and conv2_wsplit, after svk_pack_weights_f32mfma's own images
+    // the launches alone: svk_cnn_forward keeps the timing scope and the launch check
+    void (*launch_conv)(sv_ctx *ctx, sv_cnn_algo algo, const void *x, bool x_is_u8, long B, hipStream_t s);   // SV_ALGO_X_WINOGRAD / _X_WSPLIT -> ctx->features
+    void (*launch_fc_frame)(sv_ctx *ctx, long B, float *logits, u8 *digits, float *conf, const int *run_if_set, hipStream_t s);   // k_fc_head_frame
+};
+extern __attribute__((visibility("hidden"))) const sv_xcheck_ops *const sv_xcheck;
+
 // kernel launchers (one per .hip file)
 int svk_gray(const u8 *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, u8 *gray, hipStream_t s);
 int svk_blur(const u8 *src, int n, int H, int W, int ksize, u8 *dst, hipStream_t s);
@@ -143,10 +160,6 @@ int svk_adaptive_threshold(const u8 *src, int n, int H, int W, int block, const 
 int svk_preprocess(sv_ctx *ctx, const u8 *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, u8 *binary, hipStream_t s);
 int svk_preprocess_bits(sv_ctx *ctx, const u8 *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, uint32_t *bits, hipStream_t s);
 int svk_despeckle_bits(uint32_t *bits, int n, int H, int W, hipStream_t s);
-int svk_preprocess_mm_stats(sv_ctx *ctx, unsigned *ambiguous, unsigned long *capacity);
-int svk_preprocess_mm_enable_stats(sv_ctx *ctx);
-bool svk_preprocess_mm_supported(const u8 *bgr, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const void *out, bool bits);
-int svk_preprocess_mm(sv_ctx *ctx, const u8 *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, u8 *out, bool bits, float *mean_dbg, hipStream_t s);
 int svk_preprocess_warp_fused(sv_ctx *ctx, const u8 *bgr, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, u8 *binary, const double *minv, u8 *cells,
                               hipStream_t s);
 int svk_warp_perspective(const u8 *img, int H, int W, ptrdiff_t pitch, int channels, const double *minv, int out_size,

@@ -109,7 +109,7 @@ def test_dropin_module_names_resolve():
 
 
 def test_winograd_stream_schedule():
-    """The producer schedule of k_conv_features_wstream (csrc/k3_cnn.hip): checked exhaustively for every run length a
+    """The producer schedule of k_conv_features_wstream (csrc/x_cnn_round1.hip): checked exhaustively for every run length a
     workgroup can get.  Invariants: a tile is transformed only after its cell's conv1; conv1(c) finds its input staged;
     a conv1 plane (double-buffered by cell parity) is never overwritten while tiles of the cell it held are still to be
     transformed in the same step; staging never writes the input buffer conv1 is reading."""

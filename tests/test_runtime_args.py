@@ -196,6 +196,24 @@ def test_cell_shapes_are_checked_first(ctx, monkeypatch):
         ctx.resize_linear(torch.zeros((20, 24), dtype=torch.int16), (28, 28))
 
 
+@pytest.mark.gpu
+def test_cross_check_selections_are_unknown_to_the_product():
+    """SV_CNN_X_WINOGRAD (102) and SV_CNN_X_WSPLIT (103) name kernels of the test-only library: a product context rejects them and keeps
+    its selection, a context of libsudokuvision_xcheck.so takes them.  Needs a context (so a device) but launches nothing."""
+    import sudoku_vision_amd as sva
+    product, xc = sva.Context(), sva.Context(library=sva._native.lib_xcheck())
+    try:
+        for which, algo in ((rt.Context.CNN_X_WINOGRAD, 2), (rt.Context.CNN_X_WSPLIT, 3)):
+            with pytest.raises(sva._native.NativeError, match=rf"SV_ERR_BAD_ARG: sv_ctx_set_cnn_kernels: unknown selection {which}$"):
+                product.set_cnn_kernels(which)
+            assert product.conv_kernel_info()["algo"] in (0, 4)      # still SV_CNN_AUTO: f32-MFMA or f16 pairs
+            xc.set_cnn_kernels(which)
+            assert xc.conv_kernel_info()["algo"] == algo
+    finally:
+        product.close()
+        xc.close()
+
+
 # ---- the drop-ins' array conversion ------------------------------------------------------------------------------------
 @pytest.fixture
 def cpu_ctx():
