@@ -12,15 +12,15 @@
 //        144 VGPRs for the life of the kernel.  The 16x16 accumulator holds the 4 positions of a
 //        pooling window in the 4 registers of one lane, so bias + ReLU + max-pool are 3 v_max and
 //        never leave the lane.  Output: features [cell][window 49][oc 64] f32.
-//   k_fc_head : fc1 (3136->128) on the same MFMA with cells as M (16 cells per wave, weights streamed per wave) + ReLU, fc2 (128->10),
-//        argmax (pipeline/run.py:142) and softmax[argmax] (run.py:141-143).
+//   k_fc_head : fc1 (3136->128) on the same MFMA with cells as M (16 cells per wave, weights streamed per wave); bias + ReLU, fc2 (128->10),
+//        argmax (pipeline/run.py:142) and softmax[argmax] (run.py:141-143) are sv_fc_tail, the tail of every fc head (sv_fc_head.h).
 //   k_softmax_topk, k_preprocess_cells: the run_v2 top-k epilogue and run.py's preprocess_cell (scope rows N3, N1).
 //   (The round-1 kernels the tests compare these with -- k_conv_features_wstream / _wsplit, k_fc_head_frame -- are x_cnn_round1.hip, in the
 //        test-only libsudokuvision_xcheck.so alone; svk_cnn_forward reaches them through sv_xcheck, sv_internal.h.)
 //
 // Weight images are packed on the host by svk_pack_weights_f32mfma (below) into exactly the
 // per-lane register order the kernels load.
-#include "sv_cnn_f32_dev.h"
+#include "sv_fc_head.h"
 #include "sv_internal.h"
 
 namespace {
@@ -280,11 +280,8 @@ __global__ __launch_bounds__(256) void k_fc_head(const float *__restrict__ feat,
     __shared__ float lg[4][16][12];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 15, q = lane >> 4;
-    const long cell0 = (long)blockIdx.x * 64 + wave * 16;
-    long crow = cell0 + r;
-    if (crow >= B) crow = B - 1;
-    const f32x4 *ap = (const f32x4 *)(feat + crow * FEAT + 4 * q);
+    const sv_fc_lane l = sv_fc_wave_tile(lane, wave, B);
+    const f32x4 *ap = (const f32x4 *)(feat + l.crow * FEAT + 4 * l.q);
     const f32x4 *bp = (const f32x4 *)w1reg + lane;
 
     sv_fc2_stage<256>(w2s, w2, tid);
@@ -319,26 +316,7 @@ __global__ __launch_bounds__(256) void k_fc_head(const float *__restrict__ feat,
         for (int t = 0; t < 8; t++) { wb0[t] = nwb0[t]; wb1[t] = nwb1[t]; }
     }
 
-    // acc[t][reg]: cell row 4q+reg, hidden unit 16t + r
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        const float bias = b1[16 * t + r];
-#pragma unroll
-        for (int reg = 0; reg < 4; reg++) hs[wave][4 * q + reg][16 * t + r] = fmaxf(acc[t][reg] + bias, 0.f);
-    }
-    __syncthreads();
-
-    // fc2: lane (cell r, class group q) -> classes q, q+4, q+8
-    for (int jj = 0; jj < 3; jj++) {
-        const int j = q + 4 * jj;
-        if (j < 10) {
-            const float s = sv_fc2_logit(hs[wave][r], w2s, b2, j);
-            lg[wave][r][j] = s;
-            if (cell0 + r < B) logits[(cell0 + r) * 10 + j] = s;
-        }
-    }
-    __syncthreads();
-    if (q == 0 && cell0 + r < B) sv_digit_conf(lg[wave][r], cell0 + r, digits, conf);
+    sv_fc_tail<8>(hs[wave], 0, [=](int t, int reg) { return acc[t][reg]; }, b1, w2s, b2, lg[wave], l.cell0, B, true, logits, digits, conf);
 }
 
 // preprocess_cell (pipeline/run.py:73-95) as a stand-alone call: one wave per cell, u8 in -> u8 {0,255} out

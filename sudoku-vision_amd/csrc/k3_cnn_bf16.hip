@@ -8,28 +8,23 @@
 //        a wave keeps all 9 x 4 B operands (288 x 64 weights) in 144 VGPRs.  36 MFMAs per 16 positions x 64 channels
 //        instead of 288 in f32.  N tiles are interleaved (column c of tile t = channel 4c + t) so that a lane ends up with
 //        4 consecutive channels of one pooled window: one 8-byte store of bf16 features.
-//   k_fc_head_bf16       : fc1 on the same MFMA (K = 3136 = 98 steps), fc2/argmax/softmax epilogue in f32 as in k_fc_head.
+//   k_fc_head_bf16p      : fc1 on the same MFMA with one workgroup per CU, the 0.8 MB weight image streamed once per CU and both operands
+//        global -> LDS by DMA: sv_fc_head_percu (sv_fc_head.h) with the bf16 sizes and MFMA loop of fc_bf16p_fmt.  Serves every batch whose
+//        share per CU fits a 96-cell pass (sv_fc_percu_share).
+//   k_fc_head_bf16       : one 16-cell tile per wave, 64 cells per workgroup, operands straight from global memory (K = 3136 = 98 steps),
+//        for larger batches.  Both end in sv_fc_tail, the f32 fc2/argmax/softmax tail of every fc head.
 #include <cstring>
 
-#include "sv_device.h"
+#include "sv_fc_head.h"
 #include "sv_internal.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
 constexpr int POS_STRIDE = 80;                 // bytes per padded position (64 data + 16)
 constexpr int C1B_CELL = 256 * POS_STRIDE;     // 16x16 padded positions
-constexpr int IN_W = 30, IN_CELL = 900;
-constexpr int FEAT = 3136;
 
-__device__ __forceinline__ float glue_norm(u8 c)
-{
-    const float t = __fdiv_rn((float)(255 - (int)c), 255.0f);
-    return __fdiv_rn(__fsub_rn(t, 0.5f), 0.5f);
-}
 __device__ __forceinline__ unsigned short bf16_bits(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
 
 __global__ __launch_bounds__(256, 2) void k_conv_features_bf16(const u8 *__restrict__ cells, long B, const float *__restrict__ w1,
@@ -175,11 +170,8 @@ __global__ __launch_bounds__(256) void k_fc_head_bf16(const unsigned short *__re
     __shared__ float lg[4][16][12];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 15, q = lane >> 4;
-    const long cell0 = (long)blockIdx.x * 64 + wave * 16;
-    long crow = cell0 + r;
-    if (crow >= B) crow = B - 1;
-    const uint4 *ap = (const uint4 *)(feat + crow * FEAT) + q;      // step s: + 4*s
+    const sv_fc_lane l = sv_fc_wave_tile(lane, wave, B);
+    const uint4 *ap = (const uint4 *)(feat + l.crow * FEAT) + l.q;  // step s: + 4*s
     const uint4 *bp = w1img + lane;                                 // [98][8][64]
 
     sv_fc2_stage<256>(w2s, w2, tid);
@@ -194,131 +186,47 @@ __global__ __launch_bounds__(256) void k_fc_head_bf16(const unsigned short *__re
         for (int t = 0; t < 8; t++)
             acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, bp[(s * 8 + t) * 64]), acc[t], 0, 0, 0);
     }
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        const float bias = b1[16 * t + r];
-#pragma unroll
-        for (int reg = 0; reg < 4; reg++) hs[wave][4 * q + reg][16 * t + r] = fmaxf(acc[t][reg] + bias, 0.f);
-    }
-    __syncthreads();
-    for (int jj = 0; jj < 3; jj++) {
-        const int j = q + 4 * jj;
-        if (j < 10) {
-            const float sacc = sv_fc2_logit(hs[wave][r], w2s, b2, j);
-            lg[wave][r][j] = sacc;
-            if (cell0 + r < B) logits[(cell0 + r) * 10 + j] = sacc;
-        }
-    }
-    __syncthreads();
-    if (q == 0 && cell0 + r < B) sv_digit_conf(lg[wave][r], cell0 + r, digits, conf);
+    sv_fc_tail<8>(hs[wave], 0, [=](int t, int reg) { return acc[t][reg]; }, b1, w2s, b2, lg[wave], l.cell0, B, true, logits, digits, conf);
 }
 
-
-// k_fc_head_bf16p: the per-CU form of the fc head (k_fc_head_h2p in k3_cnn_h2.hip has the reasoning and the measurements): one 768-thread
-// workgroup per CU, 12 waves = 6 M tiles x 2 N halves, the weight image streamed once per CU, both operands global -> LDS by DMA, one counted
-// wait and one raw barrier per 64-k stage.  bf16 sizes: a feature row gives 128 B per stage, a DMA piece is 8 rows x 128 B (one per wave, ring of
-// three 12-KB stages), the weight stage is 16 KB (waves 0-7, two pieces each, ring of two).  Feature image in the LDS: [96 rows][8 units of 16 B],
-// unit u of row r in slot u ^ (r >> 1 & 7): two rows share a 256-B bank row, and with that the 16 lanes of a ds_read_b128 lane group hit 16 slots.
-constexpr int BFP_WAVES = 12, BFP_MT = 6, BFP_CELLS = 16 * BFP_MT, BFP_NSTAGE = 49;
-constexpr int BFP_W_STAGE = 16384, BFP_A_STAGE = BFP_CELLS * 128, BFP_OFF_A = 2 * BFP_W_STAGE, BFP_HS_LD = 129;
-
-__device__ __forceinline__ void bfp_glds(const void *gsrc, unsigned lds_dst)          // 64 lanes x 16 B -> lds_dst + 16 * lane
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-__global__ __launch_bounds__(64 * BFP_WAVES, 1) void k_fc_head_bf16p(const unsigned short *__restrict__ feat, long B, long per, const uint4 *__restrict__ w1img,
-                                                                    const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ b2,
-                                                                    float *__restrict__ logits, u8 *__restrict__ digits, float *__restrict__ conf)
-{
-    // one LDS object: [2 weight stages][3 feature stages] (the hidden activations alias both after the K loop) [w2][logits]
-    constexpr int RINGS = BFP_OFF_A + 3 * BFP_A_STAGE, HS_B = BFP_CELLS * BFP_HS_LD * 4;
-    constexpr int OFF_W2 = RINGS > HS_B ? RINGS : HS_B, OFF_LG = OFF_W2 + 10 * 128 * 4, LDS_B = OFF_LG + BFP_MT * 16 * 12 * 4;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_B];
-    float(*hs)[BFP_HS_LD] = (float(*)[BFP_HS_LD])lds;
-    float(*w2s)[128] = (float(*)[128])(lds + OFF_W2);
-    float(*lg)[16][12] = (float(*)[16][12])(lds + OFF_LG);
-    const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char *)lds;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 15, q = lane >> 4;
-    const int mt = wave % BFP_MT, nh = wave / BFP_MT;
-    const bool loader = wave < 8;
-    sv_fc2_stage<64 * BFP_WAVES>(w2s, w2, tid);
-
-    // this lane's A fragments in a feature stage: row 16 mt + r, step ss = unit 4 ss + q, in slot unit ^ (r >> 1 & 7)
-    unsigned a_off[2];
-#pragma unroll
-    for (int ss = 0; ss < 2; ss++) a_off[ss] = BFP_OFF_A + (16 * mt + r) * 128 + (((unsigned)(4 * ss + q)) ^ ((unsigned)(r >> 1) & 7u)) * 16;
-
-    const long base = (long)blockIdx.x * per, c_end = base + per < B ? base + per : B;          // per <= 96: one pass (svk_cnn_forward_bf16)
-    const long cell0 = base + 16 * mt;
-    const bool tile_live = cell0 < c_end;
-    // this lane's share of the wave's feature piece: row 8 wave + lane / 8 of the pass, slot lane % 8 -> unit slot ^ (row >> 1 & 7)
-    const int rl = 8 * wave + (lane >> 3);
-    long srow = base + rl;
-    if (srow >= c_end) srow = c_end - 1;
-    const unsigned char *asrc = (const unsigned char *)(feat + srow * FEAT) + ((((unsigned)lane & 7u) ^ ((unsigned)(rl >> 1) & 7u)) * 16);
-    const uint4 *wp = w1img + (wave & 7) * 2 * 64 + lane;                                       // this wave's 2 pieces of a weight stage
-    auto issue_w = [&](int st) {
-        if (loader) {
-            const unsigned dst = lds_base + (st & 1) * BFP_W_STAGE + (wave & 7) * 2048;
-            bfp_glds(wp + (long)st * 1024, dst);
-            bfp_glds(wp + (long)st * 1024 + 64, dst + 1024);
-        }
-    };
-    auto issue_a = [&](int st) { bfp_glds(asrc + 128 * st, lds_base + BFP_OFF_A + (st % 3) * BFP_A_STAGE + wave * 1024); };
+// k_fc_head_bf16p: the per-CU form of the fc head, sv_fc_head_percu (sv_fc_head.h has the protocol, the reasoning and the measurements) at bf16
+// sizes: a feature row gives 128 B per stage, a DMA piece is 8 rows x 128 B (one per wave, ring of three 12-KB stages), the weight stage is
+// 16 KB (waves 0-7, two pieces each, ring of two).  Feature image in the LDS: [96 rows][8 units of 16 B], unit u of row r in slot
+// u ^ (r >> 1 & 7): two rows share a 256-B bank row, and with that the 16 lanes of a ds_read_b128 lane group hit 16 slots.
+struct fc_bf16p_fmt {
+    static constexpr int A_ROW_B = 128, A_PIECES = 1, W_STAGE = 16384, ROW_HBM_B = FEAT * 2, NA = 2;
+    static __device__ __forceinline__ unsigned swz(int row) { return (unsigned)(row >> 1) & 7u; }
+    static __device__ __forceinline__ unsigned a_unit(int q, int ss) { return (unsigned)(4 * ss + q); }   // step ss of the stage
     f32x4 acc[4];
+    __device__ __forceinline__ void zero()
+    {
 #pragma unroll
-    for (int t = 0; t < 4; t++) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    issue_w(0);
-    issue_a(0);
-    issue_a(1);
-    for (int st = 0; st < BFP_NSTAGE; st++) {
-        // only this wave's feature piece of stage st + 1 stays in flight: its weight pieces of stage st were issued before it
-        if (st + 1 < BFP_NSTAGE) asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (st + 1 < BFP_NSTAGE) issue_w(st + 1);
-        if (st + 2 < BFP_NSTAGE) issue_a(st + 2);
-        if (tile_live) {
-            const unsigned char *wt = lds + (st & 1) * BFP_W_STAGE + lane * 16, *at = lds + (st % 3) * BFP_A_STAGE;
-            uint4 fa[2], fb[2][4];
-#pragma unroll
-            for (int ss = 0; ss < 2; ss++) fa[ss] = *(const uint4 *)(at + a_off[ss]);
-#pragma unroll
-            for (int ss = 0; ss < 2; ss++)
-#pragma unroll
-                for (int t = 0; t < 4; t++) fb[ss][t] = *(const uint4 *)(wt + (ss * 8 + 4 * nh + t) * 1024);
-#pragma unroll
-            for (int ss = 0; ss < 2; ss++)
-#pragma unroll
-                for (int t = 0; t < 4; t++)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[ss]), __builtin_bit_cast(bf16x8, fb[ss][t]), acc[t], 0, 0, 0);
-        }
+        for (int t = 0; t < 4; t++) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-    __syncthreads();                                                                           // everybody is done reading the rings: hs may overwrite them
+    __device__ __forceinline__ void compute(const unsigned char *wt, const unsigned char *at, const unsigned (&a_off)[NA], int nh)
+    {
+        uint4 fa[2], fb[2][4];
 #pragma unroll
-    for (int t = 0; t < 4; t++) {
-        const float bias = b1[64 * nh + 16 * t + r];
+        for (int ss = 0; ss < 2; ss++) fa[ss] = *(const uint4 *)(at + a_off[ss]);
 #pragma unroll
-        for (int reg = 0; reg < 4; reg++) hs[16 * mt + 4 * q + reg][64 * nh + 16 * t + r] = fmaxf(acc[t][reg] + bias, 0.f);
+        for (int ss = 0; ss < 2; ss++)
+#pragma unroll
+            for (int t = 0; t < 4; t++) fb[ss][t] = *(const uint4 *)(wt + (ss * 8 + 4 * nh + t) * 1024);
+#pragma unroll
+        for (int ss = 0; ss < 2; ss++)
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+                acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fa[ss]), __builtin_bit_cast(bf16x8, fb[ss][t]), acc[t], 0, 0, 0);
     }
-    __syncthreads();
-    if (nh == 0) {
-        for (int jj = 0; jj < 3; jj++) {
-            const int j = q + 4 * jj;
-            if (j < 10) {
-                const float sacc = sv_fc2_logit(hs[16 * mt + r], w2s, b2, j);
-                lg[mt][r][j] = sacc;
-                if (cell0 + r < c_end) logits[(cell0 + r) * 10 + j] = sacc;
-            }
-        }
-    }
-    __syncthreads();
-    if (nh == 0 && q == 0 && cell0 + r < c_end) sv_digit_conf(lg[mt][r], cell0 + r, digits, conf);
+    __device__ __forceinline__ float hidden(int t, int reg) const { return acc[t][reg]; }
+};
+
+__global__ __launch_bounds__(64 * SV_FCP_WAVES, 1) void k_fc_head_bf16p(const unsigned short *__restrict__ feat, long B, long per, const uint4 *__restrict__ w1img,
+                                                                       const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ b2,
+                                                                       float *__restrict__ logits, u8 *__restrict__ digits, float *__restrict__ conf)
+{
+    fc_bf16p_fmt f;
+    sv_fc_head_percu(f, feat, B, per, w1img, b1, w2, b2, logits, digits, conf);
 }
 
 }  // namespace
@@ -362,9 +270,9 @@ int svk_cnn_forward_bf16(sv_ctx *ctx, const u8 *cells, long B, float *logits, u8
     }
     SV_LAUNCH_CHECK("k_conv_features_bf16");
     sv_time_scope ts(ctx, SVK_FC_HEAD, s);
-    const long per = std::max<long>(16, (B + ctx->num_cus - 1) / ctx->num_cus);               // as in svk_cnn_forward_h2
-    if (per <= BFP_CELLS) {
-        hipLaunchKernelGGL(k_fc_head_bf16p, dim3((unsigned)((B + per - 1) / per)), dim3(64 * BFP_WAVES), 0, s, (const unsigned short *)ctx->features, B, per,
+    const long per = sv_fc_percu_share(ctx, B);
+    if (per <= SV_FC_PERCU_CELLS) {
+        hipLaunchKernelGGL(k_fc_head_bf16p, dim3((unsigned)((B + per - 1) / per)), dim3(64 * SV_FCP_WAVES), 0, s, (const unsigned short *)ctx->features, B, per,
                            (const uint4 *)w.fc1_bf16, w.fc1_b, w.fc2_w, w.fc2_b, logits, digits, conf);
         SV_LAUNCH_CHECK("k_fc_head_bf16p");
         return SV_OK;

@@ -22,21 +22,21 @@
 //        The pooled, ReLU'd features leave the kernel already split into f16 pairs, 16 B of hi parts and 16 B of lo parts per
 //        group of 8: what the fc kernels' MFMAs take as they stand.
 //   k_fc_head_h2p : fc1 (3136 -> 128) with cells as M, one workgroup per CU (12 waves = 6 M tiles x 2 N halves), the 1.6 MB weight
-//        image (hi and lo halves) streamed once per CU, weights and features global -> LDS by DMA; fc2 + argmax + softmax[argmax]
-//        epilogue in f32 (pipeline/run.py:139-143).  Serves every batch whose share per CU fits a 96-cell pass.
+//        image (hi and lo halves) streamed once per CU, weights and features global -> LDS by DMA: sv_fc_head_percu (sv_fc_head.h, shared
+//        with the bf16 configuration) with the f16-pair sizes and MFMA pipeline of fc_h2p_fmt.  Serves every batch whose share per CU fits
+//        a 96-cell pass (sv_fc_percu_share).
 //   k_fc_head_h2  : round 2's form (one 16-cell tile per wave, 64 cells per workgroup, the weight image staged once per workgroup
 //        through double-buffered LDS, A fragments straight from global memory) for larger batches.
+//        Both end in sv_fc_tail (sv_fc_head.h): bias, ReLU, fc2 + argmax + softmax[argmax] in f32 (pipeline/run.py:139-143).
 //
 // Range: inputs and activations are carried as f16 pairs, so their magnitudes must stay below 65,504 (and a pair holds 22 significant bits
 // only while its low half is a normal f16, |v| >= 2^-3; below that the absolute error is f16's subnormal step, 2^-24).  svk_pack_weights_h2
 // bounds the activations from the weights, scales conv1's activations and the features by powers of two when their bounds are below 1
 // (folded into b1, b2 and the scale_inv factors), and svk_cnn_forward (k3_cnn.hip) routes anything outside to the f32-MFMA kernels;
 // `run_if_clear` is that decision for f32 inputs, made on the device.  SV_DEV builds (tools/dev) add an ablation switch and s_memtime stamps; the product is compiled without them.
-#include "sv_device.h"
+#include "sv_fc_head.h"
 #include "sv_internal.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 namespace {
@@ -49,25 +49,12 @@ namespace {
 constexpr int POS_STRIDE = 64, ROW_STRIDE = 16 * POS_STRIDE + 32;
 constexpr int PLANE_B = 16 * ROW_STRIDE;
 constexpr int IN_PLANE_B = 32 * 64;             // one f16 plane of a cell's input: 30x30 zero-bordered pixels in 32 rows of 64 B
-constexpr int FEAT = 3136;
-
-__device__ __forceinline__ float glue_norm(u8 c)
-{
-    // x = ((255 - cell)/255 - 0.5)/0.5, one rounding per operation (pipeline/run.py:129-135)
-    const float t = __fdiv_rn((float)(255 - (int)c), 255.0f);
-    return __fdiv_rn(__fsub_rn(t, 0.5f), 0.5f);
-}
 
 // The compiler puts the s_waitcnt for a value loaded before a loop at its first use INSIDE the loop, where it then also waits, every
 // iteration, for whatever the loop itself has in flight (the next cell's input load, the previous tile's feature stores).  Touching the
 // registers in an empty asm statement ahead of the loop makes it wait there, once.
 __device__ __forceinline__ void settle(uint4 &v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 __device__ __forceinline__ void settle(float &v) { asm volatile("" : "+v"(v)); }
-
-__device__ __forceinline__ unsigned pack2h(_Float16 a, _Float16 b)
-{
-    return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
 
 // v -> (hi, lo) with hi + lo = v to 22 bits (the kernels' activations and, on the host, the weights of svk_pack_weights_h2)
 __host__ __device__ __forceinline__ void split_h2(float v, _Float16 &hi, _Float16 &lo)
@@ -400,15 +387,12 @@ __global__ __launch_bounds__(256, 2) void k_fc_head_h2(const float *__restrict__
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 15, q = lane >> 4;
-    const long cell0 = (long)blockIdx.x * 64 + wave * 16;
-    long crow = cell0 + r;
-    if (crow >= B) crow = B - 1;
+    const sv_fc_lane l = sv_fc_wave_tile(lane, wave, B);
     // K is permuted so that a lane's operands of the SPS = 2 steps of a stage are 64 consecutive bytes (k-slot (q, j) of step
     // 2S + ss = feature 64S + 16q + 8ss + j; the weight image is packed to match; k_conv_features_h2 writes the features as f16
     // pairs, group of 8 by group of 8: 16 B of hi parts, 16 B of lo parts): the four q-lanes of a row read 256 contiguous bytes
     // per stage, and what arrives are the MFMA operands themselves
-    const uint4 *ap = (const uint4 *)(feat + crow * FEAT + 16 * q);     // stage S: + 16*S uint4; [2 ss] = hi, [2 ss + 1] = lo
+    const uint4 *ap = (const uint4 *)(feat + l.crow * FEAT + 16 * l.q); // stage S: + 16*S uint4; [2 ss] = hi, [2 ss + 1] = lo
 
     sv_fc2_stage<256>(w2s, w2, tid);
 
@@ -457,186 +441,73 @@ __global__ __launch_bounds__(256, 2) void k_fc_head_h2(const float *__restrict__
         __syncthreads();
     }
 
-    // acc[t][reg]: cell row 4q + reg of this wave's tile, hidden unit 16t + r   (hs aliases the weight stages: all waves are
-    // past the last barrier of the K loop, nobody reads wt any more)
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        const float bias = b1[16 * t + r];
-#pragma unroll
-        for (int reg = 0; reg < 4; reg++) hs[wave][4 * q + reg][16 * t + r] = fmaxf((acc_h[t][reg] + acc_l[t][reg]) * scale_inv + bias, 0.f);
-    }
-    __syncthreads();
-    for (int jj = 0; jj < 3; jj++) {                                  // fc2: lane (cell r, class group q) -> classes q, q+4, q+8
-        const int j = q + 4 * jj;
-        if (j < 10) {
-            const float s = sv_fc2_logit(hs[wave][r], w2s, b2, j);
-            lg[wave][r][j] = s;
-            if (cell0 + r < B) logits[(cell0 + r) * 10 + j] = s;
-        }
-    }
-    __syncthreads();
-    if (q == 0 && cell0 + r < B) sv_digit_conf(lg[wave][r], cell0 + r, digits, conf);
+    // (hs aliases the weight stages: all waves are past the last barrier of the K loop, nobody reads wt any more)
+    sv_fc_tail<8>(hs[wave], 0, [=](int t, int reg) { return (acc_h[t][reg] + acc_l[t][reg]) * scale_inv; }, b1, w2s, b2, lg[wave], l.cell0, B, true, logits, digits,
+                  conf);
 }
 
-
 // ---------------------------------------------------------------------------------------------------------------------
-// k_fc_head_h2p: the same arithmetic for large batches, one 768-thread workgroup per CU that streams the 1.6 MB weight image
-// ONCE for all of its cells (k_fc_head_h2 streams it once per 64 cells: 324 times for 256 frames, 0.52 GB through the L2s).
-// 12 waves = 6 M tiles (96 cells per pass) x 2 N halves; 3 waves per SIMD.
-// What bounds an fc kernel of this shape is not the MFMA pipe (a quarter busy), the LDS or the L2s but the texture addresser:
-// a wave-load of MFMA A fragments straight from the features touches 64 different 16-byte pieces in 32 lines and takes the
-// TA ~55 cycles, and the waves queue up behind it in program order (tools/ubench_fc_read.hip: 62 us for the 260 MB read that
-// way, 40 us with 16 adjacent lanes reading 256 contiguous bytes).  So BOTH operands go global -> LDS directly
-// (global_load_lds_dwordx4, inline asm: hipcc would guard every ds_read after one with vmcnt(0)):
-//   * weights: 32 pieces of 1 KB per 32-KB stage (waves 0-7, four each), ring of two stages, one in flight (L2 hits);
-//   * features: 24 pieces per stage, each 4 rows x 256 B with lane-contiguous sources (two per wave), ring of three 24-KB
-//     stages, two in flight (HBM).  The image is row-major, [96 rows][16 units of 16 B]; unit u of row r sits in slot
-//     u ^ g(r), g(r) = (r & 3) << 2 | (r >> 2) & 3 -- the DMA cannot scatter, so the permutation is on the source address --
-//     which makes the 16 lanes of every ds_read_b128 lane group of an A-fragment fetch hit 16 different bank slots.
-// One counted wait and one raw barrier per stage: at the top of stage s a wave waits until only its two feature pieces of
-// stage s + 1 are in flight (s_waitcnt vmcnt(2): its weight pieces of stage s, issued after the features of s and before
-// those of s + 1, have landed), the barrier makes everybody's pieces visible and frees the slots that stage s - 1 read, and
-// the pieces of weight stage s + 1 and feature stage s + 2 are issued into them.
+// k_fc_head_h2p: the same arithmetic with one 768-thread workgroup per CU, sv_fc_head_percu (sv_fc_head.h has the protocol, the reasoning
+// and the measurements) at the sizes of f16 pairs: a feature row gives 256 B per stage (two steps x 8 hi + 8 lo halves x 4 k-groups), a DMA
+// piece is 4 rows x 256 B (two per wave, ring of three 24-KB stages), the weight stage is 32 KB (waves 0-7, four pieces each, ring of two).
+// Feature image in the LDS: [96 rows][16 units of 16 B], unit u of row r in slot u ^ g(r), g(r) = (r & 3) << 2 | (r >> 2) & 3.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int FCP_WAVES = 12, FCP_MT = 6, FCP_CELLS = 16 * FCP_MT, FCP_NSTAGE = 49;
-constexpr int FCP_W_STAGE = 32768, FCP_A_STAGE = FCP_CELLS * 256, FCP_OFF_A = 2 * FCP_W_STAGE;
-constexpr int FCP_HS_LD = 129;
-
-// one LDS-DMA piece: 64 lanes x 16 B from the lanes' own addresses to lds_dst + 16 * lane (M0 carries the LDS byte address)
-__device__ __forceinline__ void fcp_glds(const void *gsrc, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-__global__ __launch_bounds__(64 * FCP_WAVES, 1) void k_fc_head_h2p(const float *__restrict__ feat, long B, long per, const uint4 *__restrict__ w1img,
-                                                                  const float *__restrict__ b1, float scale_inv, const float *__restrict__ w2,
-                                                                  const float *__restrict__ b2, float *__restrict__ logits, u8 *__restrict__ digits,
-                                                                  float *__restrict__ conf, const int *__restrict__ run_if_clear)
-{
-    if (run_if_clear && *run_if_clear != 0) return;
-    // one LDS object: [2 weight stages (the hidden activations alias them after the K loop)][3 feature stages][w2][logits]
-    constexpr int OFF_W2 = FCP_OFF_A + 3 * FCP_A_STAGE, OFF_LG = OFF_W2 + 10 * 128 * 4, LDS_B = OFF_LG + FCP_MT * 16 * 12 * 4;
-    static_assert(FCP_CELLS * FCP_HS_LD * 4 <= 2 * FCP_W_STAGE, "the hidden activations alias the weight ring");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_B];
-    float(*hs)[FCP_HS_LD] = (float(*)[FCP_HS_LD])lds;                                 // [96][129] floats = 49.5 KB
-    float(*w2s)[128] = (float(*)[128])(lds + OFF_W2);
-    float(*lg)[16][12] = (float(*)[16][12])(lds + OFF_LG);
-    const unsigned lds_base = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char *)lds;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 15, q = lane >> 4;
-    const int mt = wave % FCP_MT, nh = wave / FCP_MT;                                  // M tile, N half (hidden units 64 nh ..)
-    const bool loader = wave < 8;
-    sv_fc2_stage<64 * FCP_WAVES>(w2s, w2, tid);
-
-    // this lane's A fragments in a feature stage: row 16 mt + r; (step ss, part) = unit 4 q + 2 ss + part, in slot unit ^ g(r)
-    const unsigned g_r = ((unsigned)(r & 3) << 2) | (unsigned)(r >> 2);
-    unsigned a_off[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) a_off[c] = FCP_OFF_A + (16 * mt + r) * 256 + (((unsigned)(4 * q + c)) ^ g_r) * 16;
-    // this lane's share of the wave's two feature pieces: row 8 wave + 4 i + lane / 16 of the pass, slot lane % 16 -> unit slot ^ g(row)
-    const int prow = 8 * wave + (lane >> 4), pslot = lane & 15;
-
-    const long base = (long)blockIdx.x * per, c_end = base + per < B ? base + per : B;       // per <= 96: one pass (svk_cnn_forward_h2)
+struct fc_h2p_fmt {
+    static constexpr int A_ROW_B = 256, A_PIECES = 2, W_STAGE = 32768, ROW_HBM_B = FEAT * 4, NA = 4;
+    static __device__ __forceinline__ unsigned swz(int row) { return ((unsigned)(row & 3) << 2) | ((unsigned)(row >> 2) & 3u); }
+    static __device__ __forceinline__ unsigned a_unit(int q, int c) { return (unsigned)(4 * q + c); }   // c = 2 ss + part: step ss of the stage, hi / lo
+    float scale_inv;
+    f32x4 acc_h[4], acc_l[4];
+    __device__ __forceinline__ void zero()
     {
-        const long cell0 = base + 16 * mt;
-        const bool tile_live = cell0 < c_end;                            // (wave-uniform) an M tile with no cell does no arithmetic
-        const unsigned char *asrc[2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int rl = prow + 4 * i;
-            long row = base + rl;
-            if (row >= c_end) row = c_end - 1;                                         // rows past the end: a valid address, results dropped
-            const unsigned gr = ((unsigned)(rl & 3) << 2) | ((unsigned)(rl >> 2) & 3u);
-            asrc[i] = (const unsigned char *)feat + row * (FEAT * 4) + (((unsigned)pslot) ^ gr) * 16;
-        }
-        const uint4 *wp = w1img + (wave & 7) * 4 * 64 + lane;                          // this wave's 4 pieces of a weight stage
-        auto issue_w = [&](int st) {
-            if (loader) {
-                const unsigned dst = lds_base + (st & 1) * FCP_W_STAGE + (wave & 7) * 4096;
-#pragma unroll
-                for (int j = 0; j < 4; j++) fcp_glds(wp + (long)st * 2048 + 64 * j, dst + 1024 * j);
-            }
-        };
-        auto issue_a = [&](int st) {
-            const unsigned dst = lds_base + FCP_OFF_A + (st % 3) * FCP_A_STAGE + 2 * wave * 1024;
-#pragma unroll
-            for (int i = 0; i < 2; i++) fcp_glds(asrc[i] + 256 * st, dst + 1024 * i);
-        };
-        f32x4 acc_h[4], acc_l[4];
 #pragma unroll
         for (int t = 0; t < 4; t++) { acc_h[t] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc_l[t] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        issue_w(0);
-        issue_a(0);
-        issue_a(1);
-
-        // The stage's eight (step, N tile) pairs are a pipeline of their own: the hi/lo B fragments of pairs i + BD, i + BD + 1 are read from
-        // the LDS while the six MFMAs of pairs i, i + 1 issue (two N tiles at a time: no MFMA reads the result of the one before it).
-        auto compute = [&](int st) {
-            constexpr int BD = 4;
-            const unsigned char *wt = lds + (st & 1) * FCP_W_STAGE + lane * 16, *at = lds + (st % 3) * FCP_A_STAGE;
-            uint4 fa[4], fb[8][2];
-#pragma unroll
-            for (int c = 0; c < 4; c++) fa[c] = *(const uint4 *)(at + a_off[c]);
-            auto rd = [&](int i) {
-                const int sstep = i >> 2, t = i & 3;
-                fb[i][0] = *(const uint4 *)(wt + ((sstep * 8 + 4 * nh + t) * 2 + 0) * 1024);
-                fb[i][1] = *(const uint4 *)(wt + ((sstep * 8 + 4 * nh + t) * 2 + 1) * 1024);
-            };
-#pragma unroll
-            for (int i = 0; i < BD; i++) rd(i);
-            __builtin_amdgcn_sched_barrier(0);
-            const h8 ah[2] = {__builtin_bit_cast(h8, fa[0]), __builtin_bit_cast(h8, fa[2])}, al[2] = {__builtin_bit_cast(h8, fa[1]), __builtin_bit_cast(h8, fa[3])};
-#pragma unroll
-            for (int i = 0; i < 8; i += 2) {
-                if (i + BD < 8) { rd(i + BD); rd(i + BD + 1); }
-                __builtin_amdgcn_sched_barrier(0);
-                const int sstep = i >> 2, t = i & 3;
-                const h8 bh0 = __builtin_bit_cast(h8, fb[i][0]), bl0 = __builtin_bit_cast(h8, fb[i][1]);
-                const h8 bh1 = __builtin_bit_cast(h8, fb[i + 1][0]), bl1 = __builtin_bit_cast(h8, fb[i + 1][1]);
-                acc_h[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[sstep], bh0, acc_h[t], 0, 0, 0);
-                acc_h[t + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[sstep], bh1, acc_h[t + 1], 0, 0, 0);
-                acc_l[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[sstep], bl0, acc_l[t], 0, 0, 0);
-                acc_l[t + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[sstep], bl1, acc_l[t + 1], 0, 0, 0);
-                acc_l[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[sstep], bh0, acc_l[t], 0, 0, 0);
-                acc_l[t + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[sstep], bh1, acc_l[t + 1], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        for (int st = 0; st < FCP_NSTAGE; st++) {
-            if (st + 1 < FCP_NSTAGE) asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (st + 1 < FCP_NSTAGE) issue_w(st + 1);
-            if (st + 2 < FCP_NSTAGE) issue_a(st + 2);
-            if (tile_live) compute(st);
-        }
-        __syncthreads();                                                                // everybody is done reading the rings: hs may overwrite them
-
-        // acc[t][reg]: cell row 4q + reg of the wave's M tile, hidden unit 64 nh + 16 t + r
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const float bias = b1[64 * nh + 16 * t + r];
-#pragma unroll
-            for (int reg = 0; reg < 4; reg++)
-                hs[16 * mt + 4 * q + reg][64 * nh + 16 * t + r] = fmaxf((acc_h[t][reg] + acc_l[t][reg]) * scale_inv + bias, 0.f);
-        }
-        __syncthreads();
-        if (nh == 0) {
-            for (int jj = 0; jj < 3; jj++) {                                            // fc2: lane (cell r, class group q) -> classes q, q+4, q+8
-                const int j = q + 4 * jj;
-                if (j < 10) {
-                    const float s = sv_fc2_logit(hs[16 * mt + r], w2s, b2, j);
-                    lg[mt][r][j] = s;
-                    if (cell0 + r < c_end) logits[(cell0 + r) * 10 + j] = s;
-                }
-            }
-        }
-        __syncthreads();
-        if (nh == 0 && q == 0 && cell0 + r < c_end) sv_digit_conf(lg[mt][r], cell0 + r, digits, conf);
     }
+    // The stage's eight (step, N tile) pairs are a pipeline of their own: the hi/lo B fragments of pairs i + BD, i + BD + 1 are read from
+    // the LDS while the six MFMAs of pairs i, i + 1 issue (two N tiles at a time: no MFMA reads the result of the one before it).
+    __device__ __forceinline__ void compute(const unsigned char *wt, const unsigned char *at, const unsigned (&a_off)[NA], int nh)
+    {
+        constexpr int BD = 4;
+        uint4 fa[4], fb[8][2];
+#pragma unroll
+        for (int c = 0; c < 4; c++) fa[c] = *(const uint4 *)(at + a_off[c]);
+        auto rd = [&](int i) {
+            const int sstep = i >> 2, t = i & 3;
+            fb[i][0] = *(const uint4 *)(wt + ((sstep * 8 + 4 * nh + t) * 2 + 0) * 1024);
+            fb[i][1] = *(const uint4 *)(wt + ((sstep * 8 + 4 * nh + t) * 2 + 1) * 1024);
+        };
+#pragma unroll
+        for (int i = 0; i < BD; i++) rd(i);
+        __builtin_amdgcn_sched_barrier(0);
+        const h8 ah[2] = {__builtin_bit_cast(h8, fa[0]), __builtin_bit_cast(h8, fa[2])}, al[2] = {__builtin_bit_cast(h8, fa[1]), __builtin_bit_cast(h8, fa[3])};
+#pragma unroll
+        for (int i = 0; i < 8; i += 2) {
+            if (i + BD < 8) { rd(i + BD); rd(i + BD + 1); }
+            __builtin_amdgcn_sched_barrier(0);
+            const int sstep = i >> 2, t = i & 3;
+            const h8 bh0 = __builtin_bit_cast(h8, fb[i][0]), bl0 = __builtin_bit_cast(h8, fb[i][1]);
+            const h8 bh1 = __builtin_bit_cast(h8, fb[i + 1][0]), bl1 = __builtin_bit_cast(h8, fb[i + 1][1]);
+            acc_h[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[sstep], bh0, acc_h[t], 0, 0, 0);
+            acc_h[t + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[sstep], bh1, acc_h[t + 1], 0, 0, 0);
+            acc_l[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[sstep], bl0, acc_l[t], 0, 0, 0);
+            acc_l[t + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[sstep], bl1, acc_l[t + 1], 0, 0, 0);
+            acc_l[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[sstep], bh0, acc_l[t], 0, 0, 0);
+            acc_l[t + 1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[sstep], bh1, acc_l[t + 1], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    __device__ __forceinline__ float hidden(int t, int reg) const { return (acc_h[t][reg] + acc_l[t][reg]) * scale_inv; }
+};
+
+__global__ __launch_bounds__(64 * SV_FCP_WAVES, 1) void k_fc_head_h2p(const float *__restrict__ feat, long B, long per, const uint4 *__restrict__ w1img,
+                                                                     const float *__restrict__ b1, float scale_inv, const float *__restrict__ w2,
+                                                                     const float *__restrict__ b2, float *__restrict__ logits, u8 *__restrict__ digits,
+                                                                     float *__restrict__ conf, const int *__restrict__ run_if_clear)
+{
+    if (run_if_clear && *run_if_clear != 0) return;
+    fc_h2p_fmt f;
+    f.scale_inv = scale_inv;
+    sv_fc_head_percu(f, feat, B, per, w1img, b1, w2, b2, logits, digits, conf);
 }
 
 }  // namespace
@@ -772,12 +643,11 @@ int svk_cnn_forward_h2(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *
 #undef SV_ABLATE_ARG
     SV_LAUNCH_CHECK("k_conv_features_h2");
     sv_time_scope ts(ctx, SVK_FC_HEAD, s);
-    // One workgroup per CU and one pass over the weight image as long as a CU's share of the cells fits a pass (96): faster than k_fc_head_h2 at
-    // every such size (81 cells: 0.040 against 0.059 ms; 20,736: 0.069 against 0.094; tools/dev/fc_sweep.py).  Beyond that the share would take a
-    // second full pass for a few cells, and two co-resident 64-cell workgroups per CU do better (32,768 cells: 0.115 against 0.136 ms).
-    const long per = std::max<long>(16, (B + ctx->num_cus - 1) / ctx->num_cus);
-    if (per <= FCP_CELLS) {
-        hipLaunchKernelGGL(k_fc_head_h2p, dim3((unsigned)((B + per - 1) / per)), dim3(64 * FCP_WAVES), 0, s, ctx->features, B, per, (const uint4 *)w.fc1_h2, w.fc1_b,
+    // The per-CU head is faster than k_fc_head_h2 at every size it serves (81 cells: 0.040 against 0.059 ms; 20,736: 0.069 against 0.094;
+    // tools/dev/fc_sweep.py); beyond a 96-cell share two co-resident 64-cell workgroups per CU do better (32,768 cells: 0.115 against 0.136 ms).
+    const long per = sv_fc_percu_share(ctx, B);
+    if (per <= SV_FC_PERCU_CELLS) {
+        hipLaunchKernelGGL(k_fc_head_h2p, dim3((unsigned)((B + per - 1) / per)), dim3(64 * SV_FCP_WAVES), 0, s, ctx->features, B, per, (const uint4 *)w.fc1_h2, w.fc1_b,
                            w.fc1_h2_scale_inv, w.fc2_w, w.fc2_b, logits, digits, conf, run_if_clear);
         SV_LAUNCH_CHECK("k_fc_head_h2p");
         return SV_OK;

@@ -179,6 +179,15 @@ int svk_despeckle(const u8 *src, int n, int H, int W, u8 *dst, unsigned *packed,
 int svk_pack_sparse_bits(const uint32_t *bits, int n, int H, int W, u8 *records, long stride, hipStream_t s);
 int svk_copy_to_host(const void *src, void *dst_host, size_t bytes, hipStream_t s);
 int svk_resize_linear(const u8 *src, int sh, int sw, ptrdiff_t pitch, u8 *dst, int dh, int dw, hipStream_t s);
+// Which fc head serves a batch of B cells (svk_cnn_forward_h2, svk_cnn_forward_bf16): a CU's share of the cells, at least one M tile.  While it
+// fits one pass of the per-CU head (sv_fc_head.h: 6 M tiles of 16 cells) that head runs, one workgroup per `share` cells; beyond that the share
+// would take a second full pass over the weight image for a few cells, and the wave-tile head, two co-resident 64-cell workgroups per CU, does better.
+constexpr int SV_FC_PERCU_CELLS = 16 * 6;
+inline long sv_fc_percu_share(const sv_ctx *ctx, long B)
+{
+    const long per = (B + ctx->num_cus - 1) / ctx->num_cus;
+    return per > 16 ? per : 16;
+}
 int svk_cnn_forward_bf16(sv_ctx *ctx, const u8 *cells, long B, float *logits, u8 *digits, float *conf, hipStream_t s);
 int svk_cnn_forward_h2(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *logits, u8 *digits, float *conf, const int *run_if_clear, hipStream_t s);
 int svk_cell_ink_ratio(const u8 *cells, long B, int npx, float *ratio, int *otsu, hipStream_t s);

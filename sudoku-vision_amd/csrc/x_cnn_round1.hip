@@ -5,11 +5,11 @@
 //   k_conv_features_wsplit  : the same stream on bf16 MFMA, every f32 operand split into three bf16 parts   (SV_CNN_X_WSPLIT)
 //   k_fc_head_frame         : fc1 + head with one workgroup per frame   (svx_ctx_set_fc_frame_kernel)
 // and their weight images.  The product reaches them through sv_xcheck (sv_internal.h), defined at the end of this file; what the
-// kernels share with k3_cnn.hip on the device is in sv_cnn_f32_dev.h.
+// kernels share with k3_cnn.hip on the device is in sv_cnn_dev.h.
 #include <cstring>
 
 #include "../../include/sudoku_vision_xcheck.h"
-#include "sv_cnn_f32_dev.h"
+#include "sv_cnn_dev.h"
 #include "sv_internal.h"
 
 namespace {

@@ -484,12 +484,13 @@ def test_bf16_configuration_digit_parity(golden_dir):
         slack = cnn_oracle.BF16_RUNPY_SLACK * np.abs(emu).max() if glue == 1 else 0.0
         assert emu_err <= cnn_oracle.tolerance(emu, noise, cnn_oracle.C_BF16) + slack, (glue, emu_err, noise)
     # the two fc kernels of this configuration against each other: a cell's logits do not depend on the batch it sits in, and both kernels add the
-    # 98 K steps in the same order -- 97 cells per CU runs k_fc_head_bf16, its first 256 frames' worth alone runs k_fc_head_bf16p
+    # 98 K steps in the same order -- 97 cells per CU runs k_fc_head_bf16, its first 256 frames' worth alone runs k_fc_head_bf16p; 96 * 256 + 1
+    # cells run k_fc_head_bf16 again, with a last tile of one cell (its clamp of the rows past the end of the batch)
     big = np.random.RandomState(6).randint(0, 256, (97 * 256, 28, 28)).astype(np.uint8)
     big[::3] = np.clip(big[::3].astype(int) // 4 + 150, 0, 255).astype(np.uint8)
     d = torch.from_numpy(big).cuda()
     l_all, dg_all, _ = c.cnn_forward(d, want_digits=True)
-    for n in (81 * 256, 81 * 256 - 19, 3000, 81):
+    for n in (96 * 256 + 1, 81 * 256, 81 * 256 - 19, 3000, 81):
         l_n, dg_n, _ = c.cnn_forward(d[:n], want_digits=True)
         assert torch.equal(l_n, l_all[:n]) and torch.equal(dg_n, dg_all[:n]), n
         assert (digits.cpu().numpy() == ed.numpy()).mean() > 0.97

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""K3 (conv + fc, HIP-event kernel times) over batch sizes, for choosing where k_fc_head_h2p takes over from k_fc_head_h2.  Argument: the library to time."""
+"""K3 (conv + fc, HIP-event kernel times) over batch sizes, for choosing where the per-CU fc head takes over from the wave-tile head.  Arguments: the library to time; the kernel family, `default` (f16 pairs),
+`bf16` or `f32mfma`."""
 import os
 import sys
 
@@ -15,6 +16,13 @@ from sudoku_vision_amd.synth import random_state_dict  # noqa: E402
 
 ctx = sva.default_context()
 ctx.load_state_dict(random_state_dict(1))
+family = sys.argv[2] if len(sys.argv) > 2 else "default"
+if family == "bf16":
+    ctx.set_precision(ctx.PREC_BF16)
+elif family == "f32mfma":
+    ctx.set_cnn_kernels(ctx.CNN_F32MFMA)
+elif family != "default":
+    sys.exit(f"unknown kernel family {family!r}: default, bf16 or f32mfma")
 x = torch.randint(0, 256, (32768, 28, 28), dtype=torch.uint8, device="cuda")
 ctx.reserve(32768)
 out = []
@@ -28,4 +36,4 @@ for B in (81, 324, 1296, 2592, 5184, 8192, 10368, 13000, 16384, 20736, 32768):
     torch.cuda.synchronize()
     k = ctx.timing_end()
     out.append(f"B={B}: fc {k['k_fc_head'][0] / k['k_fc_head'][1]:.4f} conv {k['k_conv_features'][0] / k['k_conv_features'][1]:.4f}")
-print(" | ".join(out))
+print(f"{family}: " + " | ".join(out))
