@@ -425,7 +425,12 @@ int sv_empty_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells /*dev, B*784*/, 
 
 /* F.softmax(output, dim=1) then probs.topk(top_k), pipeline/run_v2.py:165-178 (predict_cells_with_alternatives):
  * per cell the k most probable classes, most probable first (index[.,0] = the predicted digit, prob[.,0] = its
- * confidence, the rest = run_v2's `alternatives`).  Equal probabilities: lower class index first.  1 <= k <= 10. */
+ * confidence, the rest = run_v2's `alternatives`).  1 <= k <= 10.
+ * Ties: equal probabilities come lower class index first (bit-equal logits always tie; so do the classes of a confident cell whose
+ * exponentials underflow to 0.0).  sv_resolve_conflicts' slot order relies on it.
+ * Rows that are not finite: a NaN or +inf logit, or ten -inf, make the row's denominator NaN; every prob of that row is then NaN and
+ * its k indices are still distinct classes (the finite exponentials by value, the rest by class index); other rows are unaffected.
+ * -inf beside finite logits is an ordinary probability of 0. */
 int sv_softmax_topk_f32(sv_ctx *ctx, const float *logits /*dev, B*10*/, long B, int k,
                         uint8_t *index /*dev, B*k*/, float *prob /*dev, B*k*/, void *stream);
 
@@ -434,7 +439,9 @@ int sv_softmax_topk_f32(sv_ctx *ctx, const float *logits /*dev, B*10*/, long B, 
  * (pipeline/conflict_resolver.py:58-286): a beam search over the cells' alternatives for the cheapest <= max_corrections corrections.
  * Exact: every output equals the reference's; the f64 score equals it to the bit whenever no confidence of a filled cell or of a
  * qualifying alternative is below 2^-18 (then the sum of 81 of them is exact in a double in any order; softmax top-1 values and
- * alternatives that passed min_alt_conf = 0.1 always are), and is otherwise within rounding of it.
+ * alternatives that passed min_alt_conf = 0.1 always are), and is otherwise within rounding of it.  That is the domain in which
+ * "to the bit" is defined: every confidence that can enter a path's sum (top-1 of a filled cell, any qualifying alternative) is 0 or
+ * >= 2^-18.  A min_alt_conf below 2^-18 leaves it; outside it even CPython's own sum() depends on its version (compensated from 3.12).
  * index, prob: the output of sv_softmax_topk_f32 over n*81 cells; per cell digit = index[.,0] (0 = empty), confidence = prob[.,0],
  * alternatives = slots 1..k-1.  Classes are 0..9 (any other value is read as an empty cell / no alternative), probabilities finite
  * and >= 0.  run_v2 passes beam_width 5, max_corrections 3, and min_alt_conf is ConflictResolver's default 0.1 (:65).

@@ -373,7 +373,9 @@ int svk_preprocess_cells(const u8 *cells, long B, u8 *out, hipStream_t s)
     return SV_OK;
 }
 
-// F.softmax + topk (pipeline/run_v2.py:165-178): one thread per cell, 10 logits in registers, k selection passes
+// F.softmax + topk (pipeline/run_v2.py:165-178): one thread per cell, 10 logits in registers, k selection passes.  A pass starts from
+// the lowest untaken class and moves only to a strictly greater one: equal probabilities come lowest class first, and a row whose
+// probabilities do not compare (a NaN or +inf logit, all -inf: den is NaN and so is every prob written) still gets k distinct classes.
 __global__ __launch_bounds__(256) void k_softmax_topk(const float *__restrict__ logits, long B, int k, u8 *__restrict__ index, float *__restrict__ prob)
 {
     const long cell = (long)blockIdx.x * 256 + threadIdx.x;
@@ -388,10 +390,10 @@ __global__ __launch_bounds__(256) void k_softmax_topk(const float *__restrict__ 
     unsigned taken = 0;
     for (int r = 0; r < k; r++) {
         float top = -1.f;
-        int arg = 0;
+        int arg = -1;
 #pragma unroll
         for (int j = 0; j < 10; j++)
-            if (!(taken >> j & 1) && p[j] > top) { top = p[j]; arg = j; }
+            if (!(taken >> j & 1) && (arg < 0 || p[j] > top)) { top = p[j]; arg = j; }
         taken |= 1u << arg;
         index[cell * k + r] = (u8)arg;
         prob[cell * k + r] = top / den;

@@ -817,7 +817,11 @@ class Context:
         tensors: digits u8 [n,81], conf f32 [n,81], index u8 [n,81,k], prob f32 [n,81,k] (the resulting cells and their alternatives),
         success u8 [n], num_conflicts_before / num_conflicts_after i32 [n], conflict_count u8 [n,81], n_corrections u8 [n],
         corr_cells u8 [n,3,3] (cell, old digit, new digit), corr_conf f32 [n,3,2] (old, new confidence), paths_explored i32 [n],
-        score f64 [n].  run_v2 takes the resulting cells when success or num_conflicts_after < num_conflicts_before (:365);
+        score f64 [n].  Every output equals the reference's; the score equals it to the bit inside this domain: every confidence that
+        can enter a path's sum (top-1 of a filled cell, any alternative that passes min_alternative_confidence) is 0 or >= 2^-18, so
+        the sum is exact in a double in any order.  softmax_topk's output at the default 0.1 is inside it; lowering
+        min_alternative_confidence below 2^-18 leaves it (the score is then within rounding of the reference's, whose own sum()
+        depends on the CPython version there).  run_v2 takes the resulting cells when success or num_conflicts_after < num_conflicts_before (:365);
         acceptance_rule=True applies that on the device: a repair run_v2 would not take is dropped and the cell outputs, the conflict
         outputs after and the corrections describe the input.  out: a dict of some of those names -> contiguous tensors to write into;
         only they are computed and returned (None: all of them, newly allocated)."""

@@ -5,7 +5,18 @@ frame and is validated from nothing, which is exactly what the kernel avoids.
 
 A frame is index u8 [81,k] and prob f32 [81,k] (sv_softmax_topk_f32's output): digit = index[.,0], confidence = prob[.,0], the
 alternatives are slots 1..k-1.  Probabilities are held as Python floats (doubles) holding f32 values, as run_v2 holds them.
+
+The score's claim ("exact to the bit") has a domain: every confidence that can enter a path's sum -- top-1 of a filled cell, any
+eligible alternative -- is 0 or at least 2^-18; then the sum of up to 81 of them is exact in a double in any order, so CPython's sum()
+(whose rounding changed in 3.12), math.fsum, a running sum and the kernel's reduction agree.  Softmax top-1 values (>= 0.1) and
+alternatives that passed min_alt >= 2^-18 are inside it; `scored=` hands out the confidences of every scored path so a test can prove it.
+
+`mutant=` (tests only) restates the resolver with one plausible float mistake of a kernel: "f32_sum" keeps the confidence sum in
+np.float32, "f32_score" keeps the sum in double but computes the average and the final expression in np.float32, "f32_threshold"
+tests eligibility as np.float32(p) >= np.float32(min_alt).
 """
+import math
+
 import numpy as np
 
 ROWS = [[9 * r + c for c in range(9)] for r in range(9)]
@@ -57,23 +68,30 @@ def validate(digit):
     return n, count, named
 
 
-def score(frame, num_conflicts):
-    """Lower is better.  Every operation is one IEEE double operation; the sum is exact so its order is free."""
+def score(frame, num_conflicts, mutant=None, scored=None):
+    """Lower is better.  Every operation is one IEEE double operation; the sum is exact (see the module docstring) so its order is
+    free.  scored: a list that receives the confidences summed, in order."""
     filled = [x for x in range(81) if frame.digit[x] > 0]
-    total = 0.0
+    if scored is not None:
+        scored.append([frame.conf[x] for x in filled])
+    total = np.float32(0.0) if mutant == "f32_sum" else 0.0
     for x in filled:
-        total = total + frame.conf[x]
+        total = total + (np.float32(frame.conf[x]) if mutant == "f32_sum" else frame.conf[x])
+    total = float(total)
+    if mutant == "f32_score":
+        avg = np.float32(total) / np.float32(len(filled)) if filled else np.float32(0.0)
+        return float(np.float32(num_conflicts * 100) + (np.float32(1.0) - avg) * np.float32(10.0))
     avg = total / len(filled) if filled else 0.0
     return float(num_conflicts * 100) + (1.0 - avg) * 10.0
 
 
-def candidates(frame, min_alt):
+def candidates(frame, min_alt, mutant=None):
     """-> ([(cell, slot)] of the first 10 corrections to try, how many there were before the cut)."""
     _, count, named = validate(frame.digit)
     keyed = []
     for order, x in enumerate(named):
         for slot, (d, p) in enumerate(frame.alts[x]):
-            if d != frame.digit[x] and p >= min_alt:
+            if d != frame.digit[x] and (np.float32(p) >= np.float32(min_alt) if mutant == "f32_threshold" else p >= min_alt):
                 keyed.append(((-count[x], frame.conf[x], -p, order, slot), x, slot))
     keyed.sort(key=lambda t: t[0])
     return [(x, slot) for _, x, slot in keyed[:10]], len(keyed)
@@ -114,11 +132,13 @@ def smallest_by_score(scores, n):
     return sorted(heap, key=lambda i: scores[i])
 
 
-def resolve_frame(index, prob, beam_width=5, max_corrections=3, min_alt=0.1):
+def resolve_frame(index, prob, beam_width=5, max_corrections=3, min_alt=0.1, mutant=None, scored=None):
     """One frame -> dict of its outputs (the fields of Context.resolve_conflicts) plus `stats` for the golden set's coverage checks:
     (depth that succeeded or 0, beam ran empty, most candidates of a path before the cut, most invalid paths of a depth)."""
     start = Frame.from_arrays(index, prob)
     before, _, _ = validate(start.digit)
+    if scored is not None and before:
+        score(start, before, scored=scored)             # the reference scores the input too (and never reads that score)
     explored, most_cand, most_invalid = 1, 0, 0
     if before == 0:
         return _result(start, [], True, before, explored, 0.0, index.shape[1], (0, 0, 0, 0))
@@ -126,14 +146,14 @@ def resolve_frame(index, prob, beam_width=5, max_corrections=3, min_alt=0.1):
     for depth in range(max_corrections):
         invalid, best = [], None
         for frame, made in beam:
-            cands, total = candidates(frame, min_alt)
+            cands, total = candidates(frame, min_alt, mutant)
             most_cand = max(most_cand, total)
             for x, slot in cands:
                 child = frame.corrected(x, slot)
                 corr = made + [(x, frame.digit[x], child.digit[x], frame.conf[x], child.conf[x])]
                 explored += 1
                 nconf = validate(child.digit)[0]
-                s = score(child, nconf)
+                s = score(child, nconf, mutant, scored)
                 if nconf == 0:
                     if best is None or s < best[0]:
                         best = (s, child, corr, explored)
@@ -171,10 +191,10 @@ FIELDS = ("digits", "conf", "index", "prob", "success", "num_conflicts_before", 
           "corr_cells", "corr_conf", "paths_explored", "score")
 
 
-def resolve(index, prob, beam_width=5, max_corrections=3, min_alt=0.1):
+def resolve(index, prob, beam_width=5, max_corrections=3, min_alt=0.1, mutant=None, scored=None):
     """index u8 [n,81,k], prob f32 [n,81,k] -> dict of stacked arrays, FIELDS plus `stats` [n,4]."""
     index, prob = np.asarray(index, np.uint8), np.asarray(prob, np.float32)
-    per = [resolve_frame(index[i], prob[i], beam_width, max_corrections, min_alt) for i in range(index.shape[0])]
+    per = [resolve_frame(index[i], prob[i], beam_width, max_corrections, min_alt, mutant, scored) for i in range(index.shape[0])]
     return {key: np.stack([r[key] for r in per]) for key in FIELDS + ("stats",)}
 
 
@@ -236,6 +256,125 @@ def frames(seed, n, k=3):
             index[f, x] = [d] + rest[:k - 1]
             prob[f, x] = np.array(p[:k], np.float32) / np.float32(4096)
     return index, prob
+
+
+# ---- real probabilities: the top-k of a float64 softmax over generated logits, rounded to f32 -----------------------------------------
+REAL_SEED, REAL_N = 41, 256
+REAL_VARIANTS = {"real_k2": (42, 32, 2), "real_k4": (43, 32, 4)}          # name -> (seed, n, k)
+DOMAIN_FLOOR = 2.0 ** -18              # see the module docstring
+
+
+def softmax_topk(logits, k):
+    """Float64 softmax of f32 logits [..., 10] rounded to f32, then the k largest by a stable sort (equal probabilities: lowest class
+    first) -> (index u8 [..., k], prob f32 [..., k]).  The denominator is math.fsum, which is correctly rounded whatever the order:
+    cells that hold the same ten logits under different classes get bit-equal probabilities."""
+    z = np.asarray(logits, np.float32).astype(np.float64)
+    e = np.exp(z - z.max(-1, keepdims=True))
+    den = np.array([math.fsum(row) for row in e.reshape(-1, 10)]).reshape(e.shape[:-1] + (1,))
+    p = (e / den).astype(np.float32)
+    order = np.argsort(-p, axis=-1, kind="stable")[..., :k]
+    return order.astype(np.uint8), np.take_along_axis(p, order, -1)
+
+
+def real_logits(seed, n):
+    """Logits f32 [n,81,10] of n frames built as `frames` builds them (solved grid, about 50 blanks, 0-5 misread cells), ten normal
+    draws (sigma 4) per cell, sorted, the largest given to the digit the cell shows and the true digit of a misread cell placed at
+    rank 1, 2 or beyond 4.  Shapes: a misread cell is unsure (draws scaled by 0.08-0.3: alternatives around 0.1-0.3); other cells are
+    confident (gap 20-30 to the runner-up: a tail that is tiny, not zero), near-uniform (scaled by 0.04: top-1 0.11-0.2) or as drawn;
+    one frame in four is unsure everywhere (many eligible alternatives: long candidate lists, full beams), one in twelve confident
+    everywhere (nothing to try).  In the last n // 8 frames every conflicted cell holds a copy of one cell's ten logits, each under
+    its own classes: bit-equal full-mantissa confidences for the tie rules."""
+    rs = np.random.RandomState(seed)
+    out = np.zeros((n, 81, 10), np.float32)
+    for f in range(n):
+        truth = _solved(rs)
+        digit = truth.copy()
+        digit[rs.permutation(81)[:50]] = 0
+        mood = rs.randint(0, 12)                              # 0: confident everywhere, 1-3: unsure everywhere
+        wrong = {}
+        for _ in range(rs.randint(0, 6)):
+            filled = [x for x in range(81) if digit[x] > 0 and x not in wrong]
+            x = filled[rs.randint(0, len(filled))]
+            others = [y for y in _peers(x) if digit[y] > 0 and digit[y] != digit[x] and y not in wrong]
+            if not others:
+                continue
+            wrong[x] = int(digit[x])
+            digit[x] = digit[others[rs.randint(0, len(others))]]
+        conflicted = validate([int(d) for d in digit])[2] if f >= n - n // 8 else []
+        shared = None
+        for x in range(81):
+            d = int(digit[x])
+            v = np.sort(rs.randn(10) * 4.0)[::-1].copy()
+            shape = rs.rand()
+            if mood == 0 or (x not in wrong and mood > 3 and shape < 0.5):
+                v[0] = v[1] + 20.0 + 10.0 * rs.rand()
+            elif x in wrong:
+                v *= (0.08, 0.15, 0.3)[rs.randint(0, 3)]
+            elif mood <= 3:
+                v *= (0.03, 0.06, 0.12)[rs.randint(0, 3)]
+            elif shape < 0.65:
+                v *= 0.04
+            v[0] += 0.05
+            v = v.astype(np.float32)
+            if x in conflicted:
+                shared = v if shared is None else shared
+                v = shared
+            rest = [c for c in rs.permutation(10) if c != d]
+            if x in wrong:
+                rest.remove(wrong[x])
+                rest.insert((0, 1, 3 + rs.randint(0, 5))[rs.randint(0, 3)], wrong[x])
+            out[f, x, [d] + rest] = v
+    return out
+
+
+def real_frames(seed, n, k=3):
+    """`frames` with real probabilities: softmax_topk of real_logits -> (index u8 [n,81,k], prob f32 [n,81,k])."""
+    return softmax_topk(real_logits(seed, n), k)
+
+
+# ---- the eligibility threshold where f32 rounds the wrong way -----------------------------------------------------------------------
+# np.float32(0.1) lies above 0.1, so at the default an f32 comparison and a double one agree on every f32.  These thresholds round
+# DOWN to f32: an alternative of exactly np.float32(m) is below m in doubles (not eligible) and passes an f32 comparison.
+MINALT = tuple(m for m in (0.7, 0.3, 0.45, 0.35) if float(np.float32(m)) < m)
+MINALT_SEED, MINALT_GENERATED, MINALT_CRAFTED = 44, 16, 6
+
+
+def minalt_frames(m, k=3):
+    """The frames run with min_alternative_confidence = m: MINALT_GENERATED real frames, then MINALT_CRAFTED frames whose deciding
+    alternative is exactly np.float32(m), then the same frames with it one ulp above.  A crafted frame is a valid real frame in which
+    a filled cell is given the digit of a confident peer and its true digit as alternative 1 with the deciding probability; every other
+    confidence stays as the softmax made it (the peer's alternatives are far below m: the deciding one is the frame's only candidate).
+    -> (index, prob, rows of the exact frames, rows of the frames one ulp above)"""
+    gi, gp = real_frames(MINALT_SEED, MINALT_GENERATED, k)
+    pool_i, pool_p = real_frames(MINALT_SEED + 1, 16 * MINALT_CRAFTED, k)
+    at = np.float32(m)
+    crafted = []
+    for f in range(pool_i.shape[0]):
+        digit = [int(v) for v in pool_i[f, :, 0]]
+        if validate(digit)[0]:
+            continue
+        pairs = [(x, y) for x in range(81) for y in _peers(x) if digit[x] > 0 and digit[y] > 0 and pool_p[f, y, 1] < 0.01
+                 and pool_p[f, x, 0] != at and all(digit[z] != digit[y] for z in _peers(x) if z != y)]
+        if pairs and len(crafted) < MINALT_CRAFTED:
+            x, y = pairs[len(crafted) % len(pairs)]
+            ci, cp = pool_i[f].copy(), pool_p[f].copy()
+            others = [c for c in range(10) if c not in (digit[x], digit[y])]
+            ci[x, :] = ([digit[y], digit[x]] + others)[:k]
+            cp[x, 1] = at
+            cp[x, 2:] = np.minimum(cp[x, 2:], np.float32(0.01) * pool_p[f, x, 0])
+            crafted.append((ci, cp))
+    assert len(crafted) == MINALT_CRAFTED
+    above = [(ci, cp.copy()) for ci, cp in crafted]
+    for _, cp in above:
+        cp[cp == at] = np.nextafter(at, np.float32(1))
+    index = np.concatenate([gi] + [c[0][None] for c in crafted + above])
+    prob = np.concatenate([gp] + [c[1][None] for c in crafted + above])
+    exact = np.arange(MINALT_GENERATED, MINALT_GENERATED + MINALT_CRAFTED)
+    return index, prob, exact, exact + MINALT_CRAFTED
+
+
+def minalt_name(m):
+    return "real_minalt." + repr(m).replace(".", "p")
 
 
 # ---- crafted frames: the smallest inputs at which each rule can go wrong ---------------------------------------------------------------

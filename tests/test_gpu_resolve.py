@@ -1,6 +1,11 @@
 """GPU: sv_resolve_conflicts (csrc/k9_resolve.hip) through Context.resolve_conflicts == the plain-Python restatement
 (tests/resolve_ref.py) == the reference's own results (tests/golden/resolve_goldens.npz), every output, the f64 score to the bit; then
-the layers above it: the resolve/ drop-in modules, recognize_image(resolve=True) and FramePipeline(resolve=True)."""
+the layers above it: the resolve/ drop-in modules, recognize_image(resolve=True) and FramePipeline(resolve=True).
+
+The generated frames hold integers / 4096, whose sums are exact even in f32; the real-probability sets (resolve_ref.real_frames, the
+thresholds of resolve_ref.MINALT) hold f32-rounded softmax outputs, on which a kernel that summed, averaged or compared in f32 differs
+from the restatement (tests/test_resolve_ref.py shows it on mutants of the restatement); and the chain tests run K9 on what
+k_softmax_topk itself returns.  All inside the domain in which the score is exact: confidences that enter a sum are >= 2^-18."""
 import os
 import sys
 
@@ -113,6 +118,73 @@ def test_other_arguments(ctx, golden, name):
     got = run(ctx, index, prob, beam_width=beam, max_corrections=maxc)
     same(got, rr.resolve(index, prob, beam, maxc), name)
     same(got, from_golden(golden, f"var.{name}"), f"{name} against the reference's results")
+
+
+# ---- real probabilities ---------------------------------------------------------------------------------------------------------------
+REAL_SETS = {"real": (rr.REAL_SEED, rr.REAL_N, 3), **rr.REAL_VARIANTS}
+ALL_REAL = sorted(REAL_SETS) + [rr.minalt_name(m) for m in rr.MINALT]
+_REAL = {}
+
+
+def real_set(name):
+    """-> (index, prob, min_alt, the restatement's results), computed once."""
+    if name not in _REAL:
+        if name in REAL_SETS:
+            (index, prob), m = rr.real_frames(*REAL_SETS[name]), 0.1
+        else:
+            m = next(m for m in rr.MINALT if rr.minalt_name(m) == name)
+            index, prob = rr.minalt_frames(m)[:2]
+        _REAL[name] = (index, prob, m, rr.resolve(index, prob, min_alt=m))
+    return _REAL[name]
+
+
+@pytest.mark.parametrize("name", ALL_REAL)
+def test_real_frames_one_batch(ctx, golden, name):
+    """k = 3, 2 and 4 at the default threshold, and the thresholds that f32 rounds down (an alternative of exactly np.float32(m) is
+    not eligible, one ulp above it is)."""
+    index, prob, m, want = real_set(name)
+    got = run(ctx, index, prob, min_alternative_confidence=m)
+    same(got, want, f"{name}, one launch")
+    same(got, from_golden(golden, name), f"{name} against the reference's results")
+
+
+@pytest.mark.parametrize("batch", [1, 5])
+def test_real_frames_small_batches(ctx, batch):
+    index, prob, _, want = real_set("real")
+    same(run(ctx, index, prob, batch=batch), want, f"real frames in launches of {batch}")
+
+
+def test_real_frames_do_not_depend_on_the_batch(ctx):
+    index, prob, _, want = real_set("real")
+    rows = np.nonzero(want["num_conflicts_before"] > 0)[0]
+    assert 0 < rows.size < index.shape[0]
+    same(run(ctx, index[rows], prob[rows]), want, "real frames, valid frames removed", rows)
+
+
+@pytest.mark.parametrize("name", ["real", rr.minalt_name(rr.MINALT[0])])
+def test_real_frames_acceptance_rule(ctx, name):
+    index, prob, m, want = real_set(name)
+    expect, take = _accepted(want, index, prob)
+    assert (~take).any() and (want["success"] != 0).any() and ((take & (want["success"] == 0)).any() or name != "real")
+    same(run(ctx, index, prob, min_alternative_confidence=m, acceptance_rule=True), expect, f"{name}, acceptance rule")
+
+
+def test_softmax_topk_feeds_resolve(ctx):
+    """The chain as production runs it: k_softmax_topk on real logits, its own index and prob into K9 on the device and, copied to
+    the host, into the restatement.  The GPU's expf may put an alternative on the other side of 0.1 than a CPU softmax would, so both
+    sides take the GPU's top-3; what must hold first is the domain: top-1 of a filled cell >= 2^-18."""
+    n = 64
+    logits = torch.from_numpy(rr.real_logits(rr.REAL_SEED, n)).to(ctx.device)
+    idx, prob = ctx.softmax_topk(logits.reshape(n * 81, 10), 3)
+    idx, prob = idx.view(n, 81, 3), prob.view(n, 81, 3)
+    hi, hp = idx.cpu().numpy(), prob.cpu().numpy()
+    assert np.isfinite(hp).all() and (hp[:, :, 0][hi[:, :, 0] > 0] >= rr.DOMAIN_FLOOR).all()
+    assert (hi == real_set("real")[0][:n]).mean() > 0.99                      # the same frames, up to near-ties
+    want = rr.resolve(hi, hp)
+    stats = want["stats"]
+    assert (want["num_conflicts_before"] == 0).sum() >= 5 and (stats[:, 0] == 1).sum() >= 2 and (stats[:, 0] >= 2).sum() >= 5 and (want["success"] == 0).sum() >= 5
+    got = ctx.resolve_conflicts(idx, prob)
+    same({key: got[key].cpu().numpy() for key in rr.FIELDS}, want, "K9 on k_softmax_topk's output")
 
 
 def test_argument_ranges(ctx):
@@ -379,5 +451,31 @@ def test_frame_pipeline_resolve(ctx, monkeypatch):
     idx, prob = ctx.softmax_topk(crafted.reshape(-1, 10), 3)
     idx, prob = idx.view(n, 81, 3).cpu().numpy(), prob.view(n, 81, 3).cpu().numpy()
     expect, _ = _accepted(rr.resolve(idx, prob), idx, prob)
+    for key, name in (("resolved_digits", "digits"), ("resolve_success", "success"), ("num_conflicts", "num_conflicts_after"), ("n_corrections", "n_corrections")):
+        assert (got[key][found] == expect[name][found]).all(), key
+
+
+def test_frame_pipeline_resolve_real_logits(ctx, monkeypatch):
+    """FramePipeline(resolve=True) with the generator's real logits handed over in place of the CNN's: full-mantissa confidences
+    through softmax_topk, K9 and the acceptance rule, against the restatement on the GPU's own top-3."""
+    from sudoku_vision_amd.pipeline import FramePipeline
+    from sudoku_vision_amd.synth import synth_frames, random_state_dict
+    ctx.load_state_dict(random_state_dict(1234))
+    n, H, W = 24, 270, 480
+    frames, _, _ = synth_frames(n, H, W, seed=17, device="cuda")
+    frames = frames.contiguous()
+    crafted = torch.from_numpy(rr.real_logits(rr.REAL_SEED + 5, n)).to(ctx.device)
+    torch.cuda.synchronize()
+    _inject(monkeypatch, ctx, crafted, frames)
+    on = FramePipeline(ctx, H, W, chunk=8, depth=3, resolve=True).run(frames)
+    found = on["found"]
+    assert found.sum() >= n - 1
+    got = {key: on[key].cpu().numpy() for key in ("digits", "resolved_digits", "resolve_success", "num_conflicts", "n_corrections")}
+    idx, prob = ctx.softmax_topk(crafted.reshape(-1, 10), 3)
+    idx, prob = idx.view(n, 81, 3).cpu().numpy(), prob.view(n, 81, 3).cpu().numpy()
+    assert (prob[:, :, 0][idx[:, :, 0] > 0] >= rr.DOMAIN_FLOOR).all() and (got["digits"][found] == idx[:, :, 0][found]).all()
+    want = rr.resolve(idx, prob)
+    expect, take = _accepted(want, idx, prob)
+    assert (want["num_conflicts_before"] == 0).any() and (want["n_corrections"][take] > 0).any() and (~take).any() and (take & (want["success"] == 0)).any()
     for key, name in (("resolved_digits", "digits"), ("resolve_success", "success"), ("num_conflicts", "num_conflicts_after"), ("n_corrections", "n_corrections")):
         assert (got[key][found] == expect[name][found]).all(), key

@@ -1,8 +1,14 @@
 """CPU: the restatement of run_v2's validation and conflict repair (tests/resolve_ref.py) == what the reference's own code returned
 (tests/golden/resolve_goldens.npz, written by tests/golden/make_resolve_goldens.py), every output, the f64 score to the bit; the
-golden set covers every way the search can end; and the drop-in modules import under the reference's names."""
+golden set covers every way the search can end; and the drop-in modules import under the reference's names.
+
+The same again on real probabilities (resolve_ref.real_frames: f32-rounded float64 softmax outputs with full mantissas, where the
+generated frames above hold integers / 4096 whose sums are exact even in f32), with the domain in which "to the bit" is defined proved
+on the restatement, thresholds that f32 rounds the wrong way, and mutants of the restatement that a float mistake in K9 would equal."""
 import dataclasses
+import hashlib
 import heapq
+import math
 import os
 import subprocess
 import sys
@@ -63,6 +69,140 @@ def test_generator_probabilities(golden):
     assert (prob * 4096 == np.round(prob * 4096)).all() and (prob[:, :, 0] >= 0.1).all()
     alts = set((prob[:, :, 1:] * 4096).astype(int).ravel().tolist())
     assert {409, 410} <= alts and np.float32(410) / np.float32(4096) >= 0.1 > np.float32(409) / np.float32(4096)
+
+
+# ---- real probabilities ---------------------------------------------------------------------------------------------------------------
+REAL_SETS = {"real": (rr.REAL_SEED, rr.REAL_N, 3), **rr.REAL_VARIANTS}
+MUTANTS = ("f32_sum", "f32_score", "f32_threshold")
+_CACHE = {}
+
+
+def real_set(name):
+    """-> (index, prob, min_alt, the restatement's results, the confidences of every path it scored), computed once."""
+    if name not in _CACHE:
+        if name in REAL_SETS:
+            (index, prob), m = rr.real_frames(*REAL_SETS[name]), 0.1
+        else:
+            m = next(m for m in rr.MINALT if rr.minalt_name(m) == name)
+            index, prob = rr.minalt_frames(m)[:2]
+        scored = []
+        _CACHE[name] = (index, prob, m, rr.resolve(index, prob, min_alt=m, scored=scored), scored)
+    return _CACHE[name]
+
+
+ALL_REAL = sorted(REAL_SETS) + [rr.minalt_name(m) for m in rr.MINALT]
+
+
+def changed(a, b, fields=rr.FIELDS):
+    """The frames in which results a and b differ in one of `fields`, bit for bit."""
+    return [f for f in range(a["score"].shape[0]) if any(a[key][f].tobytes() != b[key][f].tobytes() for key in fields)]
+
+
+@pytest.mark.parametrize("name", ALL_REAL)
+def test_real_frames_match_the_reference(golden, name):
+    """Every field, the score as bits.  The inputs are regenerated here; their digest tells a platform whose exp() rounds one of the
+    float64 softmax values the other way from a wrong restatement."""
+    index, prob, _, got, _ = real_set(name)
+    assert hashlib.sha256(index.tobytes() + prob.tobytes()).hexdigest() == str(golden[f"{name}.input_sha256"]), "the generated inputs differ"
+    same(got, golden, name)
+
+
+def test_real_set_is_not_degenerate():
+    """Counted on the restatement's results, which test_real_frames_match_the_reference pins to the reference's."""
+    index, prob, _, got, _ = real_set("real")
+    stats, before, success = got["stats"], got["num_conflicts_before"], got["success"]
+    counts = {"valid on entry": int((before == 0).sum()), "repaired at depth 1": int((stats[:, 0] == 1).sum()),
+              "repaired at depth 2 or 3": int((stats[:, 0] >= 2).sum()), "failed": int((success == 0).sum())}
+    assert all(v >= 25 for v in counts.values()), counts
+    assert (stats[:, 2] > 10).any() and (stats[:, 3] > 5).any(), "no frame with more than 10 candidates / more invalid paths than the beam holds"
+    assert got["score"][success == 0].max() == 0.0 and (got["score"][(success == 1) & (before > 0)] > 0).all()
+    assert {int(got["index"].shape[2])} | {real_set(n)[0].shape[2] for n in rr.REAL_VARIANTS} == {2, 3, 4}
+
+
+def test_real_generator_probabilities():
+    """What the generator promises: full mantissas; confident cells whose tails are tiny, not zero, and below 0.1; near-uniform cells;
+    the intended digit on top; and a block of frames whose conflicted cells share one set of bit-equal confidences."""
+    logits = rr.real_logits(rr.REAL_SEED, rr.REAL_N)
+    index, prob, _, got, _ = real_set("real")
+    assert logits.dtype == np.float32 and (index[:, :, 0] == logits.argmax(-1)).all()
+    part = prob[prob < 1]                                  # a confident cell's top-1 rounds to exactly 1.0
+    assert (part * 4096 != np.round(part * 4096)).mean() > 0.99 and (prob[:, :, 0] < 1).mean() > 0.4 and (np.diff(prob, axis=2) <= 0).all()
+    top2 = np.sort(logits, -1)[:, :, -2:]
+    sure = top2[:, :, 1] - top2[:, :, 0] > 20
+    assert sure.mean() > 0.25 and (prob[sure][:, 1:] > 0).all() and (prob[sure][:, 1:] < 1e-8).all()
+    assert ((prob[:, :, 0] >= 0.11) & (prob[:, :, 0] <= 0.2)).mean() > 0.05 and prob[:, :, 0].min() >= 0.1
+    assert (prob[:, :, 1:] >= 0.1).any() and ((prob[:, :, 1:] < 0.1) & (prob[:, :, 1:] > 0.05)).any()
+    tied = 0
+    for f in range(rr.REAL_N - rr.REAL_N // 8, rr.REAL_N):
+        named = rr.validate([int(v) for v in index[f, :, 0]])[2]
+        assert len({prob[f, x].tobytes() for x in named}) <= 1, f
+        tied += len(named) >= 4 and got["paths_explored"][f] > 1
+    assert tied >= 8
+
+
+@pytest.mark.parametrize("name", ALL_REAL)
+def test_real_frames_are_inside_the_exact_domain(name):
+    """The domain of "the score equals the reference's to the bit": every confidence that enters a path's sum is 0 or >= 2^-18.  Proved
+    on the restatement alone, for every path it scored: a correctly rounded sum (math.fsum) == the left-to-right double sum, so no
+    order of summation and no CPython version's sum() can give another value."""
+    _, prob, m, got, scored = real_set(name)
+    assert m >= rr.DOMAIN_FLOOR and len(scored) >= int(got["paths_explored"].sum() - (got["num_conflicts_before"] == 0).sum())
+    for confs in scored:
+        assert all(c == 0.0 or c >= rr.DOMAIN_FLOOR for c in confs)
+        total = 0.0
+        for c in confs:
+            total = total + c
+        assert math.fsum(confs) == total == math.fsum(reversed(confs))
+
+
+def test_thresholds_that_f32_rounds_down(golden):
+    """min_alternative_confidence = m with np.float32(m) < m: an alternative of exactly np.float32(m) is not eligible (the reference:
+    nothing to try, paths_explored 1) and one ulp above it is (one correction)."""
+    assert len(rr.MINALT) >= 2 and 0.3 not in rr.MINALT and float(np.float32(0.1)) > 0.1
+    for m in rr.MINALT:
+        at = np.float32(m)
+        assert float(at) < m < float(np.nextafter(at, np.float32(1)))
+        _, prob, exact, above = rr.minalt_frames(m)
+        g = {key: golden[f"{rr.minalt_name(m)}.{key}"] for key in ("success", "paths_explored", "n_corrections", "num_conflicts_before")}
+        assert (prob[exact] == at).sum(axis=(1, 2)).tolist() == [1] * len(exact) and not (prob[above] == at).any()
+        assert (prob[above] == np.nextafter(at, np.float32(1))).sum(axis=(1, 2)).tolist() == [1] * len(above)
+        assert (g["num_conflicts_before"][exact] >= 1).all() and (g["num_conflicts_before"][above] >= 1).all()
+        assert (g["success"][exact] == 0).all() and (g["paths_explored"][exact] == 1).all() and (g["n_corrections"][exact] == 0).all()
+        assert (g["success"][above] == 1).all() and (g["paths_explored"][above] == 2).all() and (g["n_corrections"][above] == 1).all()
+
+
+@pytest.fixture(scope="module")
+def old_frames():
+    index, prob = rr.frames(rr.GOLDEN_SEED, rr.GOLDEN_N)
+    return index, prob, rr.resolve(index, prob)
+
+
+def test_mutants_are_caught_by_the_real_frames_only(old_frames):
+    """Each mutant of the restatement (resolve_ref's docstring) is a way K9 could be wrong; the kernel is pinned to the unmutated
+    restatement bit for bit, so a mutant that changes a result here is a kernel mistake the GPU test would see.
+
+    Frames (of the 256 + 32 + 32 real ones) in which a mutant changes a field / a field other than `score`:
+      f32_sum    113 / 3      f32_score  110 / 0
+    f32_threshold changes the 6 frames per threshold whose deciding alternative is exactly np.float32(m), 18 in all, in success, the
+    cells, the corrections and paths_explored; at the default 0.1 it can change nothing (np.float32(0.1) > 0.1).
+
+    On the 512 frames of integers / 4096, f32_sum changes nothing: their sums are exact in f32 (81 * 4096 < 2^24), which is the gap
+    the real frames close, and the assertion keeps an edit of `frames` from closing it silently.  f32_score is NOT invisible there,
+    whatever one might expect: sum / filled is rarely an f32, so the score's bits differ in 142 of those frames (the cells in 1)."""
+    index, prob, want = old_frames
+    assert changed(want, rr.resolve(index, prob, mutant="f32_sum")) == []
+    assert len(changed(want, rr.resolve(index, prob, mutant="f32_score"))) >= 8
+    for mutant in ("f32_sum", "f32_score"):
+        hit = sum(len(changed(real_set(n)[3], rr.resolve(*real_set(n)[:2], mutant=mutant))) for n in sorted(REAL_SETS))
+        assert hit >= 8, (mutant, hit)
+    hit = 0
+    for m in rr.MINALT:
+        index, prob, _, want, _ = real_set(rr.minalt_name(m))
+        exact = rr.minalt_frames(m)[2]
+        assert changed(want, rr.resolve(index, prob, min_alt=m, mutant="f32_threshold")) == exact.tolist()
+        hit += len(exact)
+    assert hit >= 8
+    assert changed(real_set("real_k4")[3], rr.resolve(*real_set("real_k4")[:2], mutant="f32_threshold")) == []
 
 
 def test_next_beam_order_is_heapq_nsmallest():
