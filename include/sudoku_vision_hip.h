@@ -221,6 +221,36 @@ int sv_find_grid_corners_batch_u8(const uint8_t *binary /*host*/, int n, int H, 
                                   ptrdiff_t img_stride, double min_area_ratio, double epsilon_ratio,
                                   int *corners /*host, n*8*/, uint8_t *found /*host, n*/, int threads);
 
+/* detect_grid_contour(binary, min_area_ratio), cv/grid_v2.py:102-128: sv_find_grid_corners_u8's search with run_v2's loop.
+ * Contours by area, largest first (ties in cv2's order); the loop ends at the first contour below min_area_ratio*H*W; a
+ * 4-vertex approximation is taken only if is_valid_quadrilateral (cv/grid_v2.py:64-95) holds for its float32 corners, in
+ * float32 arithmetic: for every vertex, with v1 = p[i] - p[i+1] and v2 = p[i+2] - p[i+1],
+ * acos(clip(dot(v1,v2) / (|v1|*|v2| + 1e-6f), -1, 1)) * (180/pi) lies in [45, 135]; and the longest side is <= 2 * the
+ * shortest.  Otherwise the search goes on with the next contour.  Returns 1 / 0 / a negative sv_status like the v1 entry. */
+int sv_find_grid_corners_v2_u8(const uint8_t *binary /*host*/, int H, int W, ptrdiff_t pitch,
+                               double min_area_ratio, double epsilon_ratio, int *corners /*host, 8*/);
+
+/* The same for n images on `threads` host threads; found[i] = 1/0. */
+int sv_find_grid_corners_v2_batch_u8(const uint8_t *binary /*host*/, int n, int H, int W, ptrdiff_t pitch,
+                                     ptrdiff_t img_stride, double min_area_ratio, double epsilon_ratio,
+                                     int *corners /*host, n*8*/, uint8_t *found /*host, n*/, int threads);
+
+/* detect_lines, cv/grid_v2.py:135-149 = cv2.HoughLinesP(binary, rho, theta, threshold, minLineLength, maxLineGap): the
+ * progressive probabilistic Hough transform (csrc/host_hough.cpp; host code, it is sequential).  rho and theta are rounded
+ * to float as cv2 takes them.  numangle = round(pi/theta), numrho = round(((W+H)*2+1)/rho); trig table float:
+ * cos(n*theta)/rho, sin(n*theta)/rho computed in double, rounded once.  The non-zero points are collected in raster order
+ * and drawn with cv::RNG's generator, state = (uint32)state*4164903690 + (state>>32) from state 2^64-1, idx = low 32 bits %
+ * remaining, the drawn point replaced by the last; a point whose mask is already clear is skipped.  A point votes at every
+ * angle n in bin round(x*cos[n] + y*sin[n]) + (numrho-1)/2 (float products and sum, round half to even); the first
+ * maximum above threshold-1 names the line.  From the point the line is walked both ways in 16-bit fixed point (major
+ * axis +-1, minor axis round(b*65536/|a|) in float, start offset by half a unit) to the image border or until more than
+ * max_line_gap pixels in a row are clear; the last set pixel of each side is an end.  The line is good if |dx| or |dy| of
+ * the ends is >= min_line_length.  A second walk up to the ends clears the mask and, for a good line, takes the cleared
+ * pixels' votes back.  Good lines are written as (x0, y0, x1, y1) in the order they are found.  *count = lines found;
+ * SV_ERR_BUFFER (with *count set) when cap is too small. */
+int sv_hough_lines_p_u8(const uint8_t *binary /*host*/, int H, int W, ptrdiff_t pitch, double rho, double theta, int threshold,
+                        int min_line_length, int max_line_gap, int *lines /*host, cap*4*/, int cap, int *count);
+
 /* sv_find_grid_corners_batch_u8 on bit-packed images (layout of sv_despeckle_u8's `packed`). */
 int sv_find_grid_corners_bits_batch(const uint32_t *bits /*host, n*H*W/32*/, int n, int H, int W,
                                     double min_area_ratio, double epsilon_ratio,
@@ -643,6 +673,43 @@ int sv_shadow_mask_u8(sv_ctx *ctx, const uint8_t *gray /*dev*/, int n, int H, in
 /* counts[f] = pixels != 0 of frame f: what score_binary's np.mean(b) / 255 needs of a {0,255} image, cv/preprocess_v2.py:285-290. */
 int sv_count_nonzero_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
                         uint32_t *counts /*dev, n*/, void *stream);
+
+/* ---- K13: run_v2's grid detection fallbacks, cv/grid_v2.py (pipeline/run_v2.py:287) ------------------------------------
+ * n gray frames of H x W (any `pitch` >= W, `img_stride` bytes between frames).  cv2 is not available to pin these against:
+ * the arithmetic stated here is the contract (tests/grid_v2_ref.py restates it in numpy); parity with OpenCV is unpinned. */
+
+/* detect_corners_harris, cv/grid_v2.py:272-290 = cv2.goodFeaturesToTrack(gray, max_corners, quality_level, min_distance,
+ * blockSize=3, useHarrisDetector=True, k).  All borders BORDER_REFLECT_101; IEEE float32 operations in this order, none fused:
+ *   ks = [f32(s), f32(2s), f32(s)], s = 1/(4*3*255) in double
+ *   Dx: rows p[x+1] - p[x-1], then columns ks[1]*S[y] + ks[0]*(S[y-1] + S[y+1])
+ *   Dy: rows ks[1]*p[x] + ks[0]*(p[x-1] + p[x+1]), then columns S[y+1] - S[y-1]
+ *   a, b, c = the 3x3 sums of Dx*Dx, Dx*Dy, Dy*Dy (float32 products; summed in double, each row left to right, then the
+ *   rows top to bottom; rounded to float32 once; the product images are reflected at the border)
+ *   response = a*c - b*b - (k*(a+c))*(a+c), the subtractions left to right
+ * Selection per frame: max = the largest response; nothing if max <= 0; a response below quality_level*max (product in
+ * double) counts as 0; candidates are the non-zero pixels equal to the maximum of their 3x3 neighbourhood, the outermost
+ * one-pixel frame excluded; ordered by response descending, ties in raster order; a candidate is kept unless a kept corner
+ * lies at squared distance < min_distance^2 (integers); at most max_corners (1..SV_HARRIS_MAX_CORNERS) are kept.
+ * corners[f][i] = (x, y) as float, counts[f] = corners of frame f.  cand_capacity: room for candidates per frame in the
+ * context's scratch; a frame with more fails the call with SV_ERR_BUFFER (the message names the count) -- never a shorter
+ * list.  response: NULL, or where to leave the response images (else they live in the context's scratch).  H, W >= 3.
+ * The call waits for `stream` (the status depends on the candidate counts). */
+#define SV_HARRIS_MAX_CORNERS 4096
+int sv_harris_corners_u8(sv_ctx *ctx, const uint8_t *gray /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
+                         int max_corners, double quality_level, int min_distance, double k, int cand_capacity,
+                         float *corners /*dev, n*max_corners*2*/, int *counts /*dev, n*/, float *response /*dev n*H*W or NULL*/,
+                         void *stream);
+
+/* rotate_image's warp, cv/grid_v2.py:371-394 = cv2.warpAffine(src, M, (dst_w, dst_h), INTER_LINEAR, BORDER_CONSTANT,
+ * border_value) on single-channel u8.  M: per frame the FORWARD 2x3 matrix, inverted in double as cv2 does:
+ * D = M0*M4 - M1*M3; D = D ? 1/D : 0; A11 = M4*D; A22 = M0*D; M1 *= -D; M3 *= -D; b1 = -A11*M2 - M1*M5;
+ * b2 = -M3*M2 - A22*M5.  Destination (x, y) reads the source at X = (sat((M1*y + b1)*1024) + 16 + sat(A11*x*1024)) >> 5,
+ * Y likewise from M3, A22, b2 (sat: round half to even, saturated to int32); cell (X >> 5, Y >> 5) saturated to int16,
+ * fractions (X & 31, Y & 31) / 32; bilinear with cv2's 15-bit weight table (weights sum to 32768), (sum + 16384) >> 15, a tap
+ * outside the source is border_value.  H, W < 32768. */
+int sv_warp_affine_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
+                      const double *M /*dev, n*6*/, int dst_h, int dst_w, int border_value, uint8_t *dst /*dev, n*dst_h*dst_w*/,
+                      void *stream);
 
 /* ---- the whole device-resident path ----------------------------------------------------------- */
 

@@ -100,6 +100,11 @@ SIGNATURES = {
     "sv_threshold_count_u8": [_p, _p, _i, _i, _i, _pd, _pd, _i, _i, _p, _p, _p],
     "sv_shadow_mask_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _i, _p, _p, _p],
     "sv_count_nonzero_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p],
+    "sv_harris_corners_u8": [_p, _p, _i, _i, _i, _pd, _pd, _i, _d, _i, _d, _i, _p, _p, _p, _p],
+    "sv_warp_affine_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _i, _i, _i, _p, _p],
+    "sv_find_grid_corners_v2_u8": [_p, _i, _i, _pd, _d, _d, _p],
+    "sv_find_grid_corners_v2_batch_u8": [_p, _i, _i, _i, _pd, _pd, _d, _d, _p, _p, _i],
+    "sv_hough_lines_p_u8": [_p, _i, _i, _pd, _d, _d, _i, _i, _i, _p, _i, _p],
 }
 _RESTYPES = {"sv_last_error": C.c_char_p, "sv_sparse_bits_record_bytes": C.c_long}
 # what libsudokuvision_xcheck.so exports on top of SIGNATURES (include/sudoku_vision_xcheck.h)

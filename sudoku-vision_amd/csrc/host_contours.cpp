@@ -706,6 +706,66 @@ bool grid_corners_from(Scanner &sc, int H, int W, double min_area_ratio, double 
     return false;
 }
 
+// is_valid_quadrilateral, cv/grid_v2.py:64-95, on float32 corners in numpy's float32 arithmetic: v1 = p[i] - p[i+1],
+// v2 = p[i+2] - p[i+1]; cos = dot / (|v1| * |v2| + 1e-6f); the angle acos(clip(cos)) * (180/pi) must lie in [45, 135]; then the
+// longest side must not exceed twice the shortest.
+bool valid_quad_f32(const float *c)
+{
+    auto norm = [](float x, float y) { return std::sqrt(x * x + y * y); };
+    float lo = 0, hi = 0;
+    for (int i = 0; i < 4; i++) {
+        const float *p1 = c + 2 * i, *p2 = c + 2 * ((i + 1) & 3), *p3 = c + 2 * ((i + 2) & 3);
+        const float v1x = p1[0] - p2[0], v1y = p1[1] - p2[1], v2x = p3[0] - p2[0], v2y = p3[1] - p2[1];
+        float cosv = (v1x * v2x + v1y * v2y) / (norm(v1x, v1y) * norm(v2x, v2y) + 1e-6f);
+        cosv = cosv < -1.f ? -1.f : (cosv > 1.f ? 1.f : cosv);
+        const float angle = std::acos(cosv) * (float)(180.0 / 3.14159265358979323846);
+        if (angle < 45.f || angle > 135.f) return false;
+    }
+    for (int i = 0; i < 4; i++) {
+        const float side = norm(c[2 * ((i + 1) & 3)] - c[2 * i], c[2 * ((i + 1) & 3) + 1] - c[2 * i + 1]);
+        lo = i == 0 || side < lo ? side : lo;
+        hi = i == 0 || side > hi ? side : hi;
+    }
+    return !(hi > 2.f * lo);
+}
+
+// detect_grid_contour, cv/grid_v2.py:102-128: the contours by area, largest first (ties in cv2's order); the first 4-vertex
+// approximation that is a valid quadrilateral wins; the loop ends at the first contour below the area floor.
+template <class Scanner>
+bool grid_corners_v2_from(Scanner &sc, int H, int W, double min_area_ratio, double eps_ratio, int *out8)
+{
+    sc.run();
+    const double min_area = min_area_ratio * ((double)H * (double)W);
+    struct Cand { double area; size_t idx; };
+    std::vector<Cand> cand;
+    for (size_t k = sc.contours.size(); k-- > 0;) {
+        const Contour &c = sc.contours[k];
+        if ((double)(c.x1 - c.x0) * (double)(c.y1 - c.y0) < min_area) continue;  // area <= bounding box: sorted behind the floor anyway
+        const double a = contour_area(sc.points.data() + c.first, c.count);
+        if (a >= min_area) cand.push_back({a, k});
+    }
+    std::stable_sort(cand.begin(), cand.end(), [](const Cand &a, const Cand &b) { return a.area > b.area; });
+    for (const Cand &cd : cand) {
+        const Contour &c = sc.contours[cd.idx];
+        const Pt *p = sc.points.data() + c.first;
+        const double eps = eps_ratio * arc_length(p, c.count, true);
+        const std::vector<Pt> poly = approx_poly(p, (int)c.count, eps, true);
+        if (poly.size() != 4) continue;
+        float q[8];
+        for (int i = 0; i < 4; i++) { q[2 * i] = (float)poly[i].x; q[2 * i + 1] = (float)poly[i].y; }
+        if (!valid_quad_f32(q)) continue;
+        for (int i = 0; i < 4; i++) { out8[2 * i] = poly[i].x; out8[2 * i + 1] = poly[i].y; }
+        return true;
+    }
+    return false;
+}
+
+bool grid_corners_v2(const u8 *bin, int H, int W, ptrdiff_t pitch, double min_area_ratio, double eps_ratio, int *out8)
+{
+    BorderScanner sc(bin, H, W, pitch);
+    return grid_corners_v2_from(sc, H, W, min_area_ratio, eps_ratio, out8);
+}
+
 }  // namespace
 
 // ---- C ABI -------------------------------------------------------------------------------------------
@@ -724,6 +784,24 @@ extern "C" int sv_find_grid_corners_batch_u8(const uint8_t *binary, int n, int H
     if (threads > n) threads = n;
     WorkerPool::instance().parallel_for(n, threads, [&](int i) {
         found[i] = grid_corners(binary + (ptrdiff_t)i * img_stride, H, W, pitch, min_area_ratio, epsilon_ratio, corners + 8 * i) ? 1 : 0;
+    });
+    return SV_OK;
+}
+
+extern "C" int sv_find_grid_corners_v2_u8(const uint8_t *binary, int H, int W, ptrdiff_t pitch, double min_area_ratio, double epsilon_ratio, int *corners)
+{
+    if (!binary || !corners || H <= 0 || W <= 0 || pitch < W) return sv_fail(SV_ERR_BAD_ARG, "sv_find_grid_corners_v2_u8: bad argument");
+    return grid_corners_v2(binary, H, W, pitch, min_area_ratio, epsilon_ratio, corners) ? 1 : 0;
+}
+
+extern "C" int sv_find_grid_corners_v2_batch_u8(const uint8_t *binary, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, double min_area_ratio,
+                                                double epsilon_ratio, int *corners, uint8_t *found, int threads)
+{
+    if (!binary || !corners || !found || n <= 0 || H <= 0 || W <= 0 || pitch < W) return sv_fail(SV_ERR_BAD_ARG, "sv_find_grid_corners_v2_batch_u8: bad argument");
+    if (threads < 1) threads = 1;
+    if (threads > n) threads = n;
+    WorkerPool::instance().parallel_for(n, threads, [&](int i) {
+        found[i] = grid_corners_v2(binary + (ptrdiff_t)i * img_stride, H, W, pitch, min_area_ratio, epsilon_ratio, corners + 8 * i) ? 1 : 0;
     });
     return SV_OK;
 }

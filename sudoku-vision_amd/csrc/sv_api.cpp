@@ -62,6 +62,7 @@ extern "C" int sv_ctx_destroy(sv_ctx *ctx)
     if (ctx->jpeg_planes) (void)hipFree(ctx->jpeg_planes);
     if (ctx->pp2) (void)hipFree(ctx->pp2);
     if (ctx->cc) (void)hipFree(ctx->cc);
+    if (ctx->grid2) (void)hipFree(ctx->grid2);
     if (ctx->k1_list) (void)hipFree(ctx->k1_list);
     if (ctx->range_flag) (void)hipFree(ctx->range_flag);
     for (auto &t : ctx->timeline) { (void)hipEventDestroy(t.t0); (void)hipEventDestroy(t.t1); }
@@ -801,6 +802,32 @@ extern "C" int sv_count_nonzero_u8(sv_ctx *ctx, const uint8_t *src, int n, int H
     REQUIRE_PLANES();
     REQUIRE(((uintptr_t)counts & 3) == 0, "misaligned counts");
     return svk_count_nonzero(src, n, H, W, pitch, img_stride, counts, S(stream));
+}
+
+// ---- K13: cv/grid_v2.py ---------------------------------------------------------------------------------
+extern "C" int sv_harris_corners_u8(sv_ctx *ctx, const uint8_t *gray, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int max_corners,
+                                    double quality_level, int min_distance, double k, int cand_capacity, float *corners, int *counts, float *response, void *stream)
+{
+    REQUIRE(ctx && gray && corners && counts, "NULL argument");
+    REQUIRE_PLANES();
+    REQUIRE(H >= 3 && W >= 3 && W < 65536, "a frame must be at least 3x3");
+    REQUIRE(max_corners >= 1 && max_corners <= SV_HARRIS_MAX_CORNERS, "max_corners must be in 1..SV_HARRIS_MAX_CORNERS");
+    REQUIRE(quality_level >= 0 && quality_level <= 1 && min_distance >= 0 && min_distance < 32768 && k == k, "bad quality_level, min_distance or k");
+    REQUIRE(cand_capacity >= 1 && cand_capacity <= (1 << 24), "cand_capacity must be in 1..2^24");
+    REQUIRE((((uintptr_t)corners | (uintptr_t)counts | (uintptr_t)response) & 3) == 0, "misaligned argument");
+    return svk_harris_corners(ctx, gray, n, H, W, pitch, img_stride, max_corners, quality_level, min_distance, k, cand_capacity, corners, counts, response, S(stream));
+}
+
+extern "C" int sv_warp_affine_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const double *M, int dst_h, int dst_w,
+                                 int border_value, uint8_t *dst, void *stream)
+{
+    REQUIRE(ctx && src && M && dst, "NULL argument");
+    REQUIRE_PLANES();
+    REQUIRE(W < 32768 && H < 32768, "source larger than cv2's 16-bit coordinates");
+    REQUIRE(dst_h > 0 && dst_h < 65536 && dst_w > 0 && dst_w < 65536, "bad destination size");
+    REQUIRE(border_value >= 0 && border_value <= 255, "border_value must be in 0..255");
+    REQUIRE(((uintptr_t)M & 7) == 0, "misaligned matrices");
+    return svk_warp_affine(ctx, src, n, H, W, pitch, img_stride, M, dst_h, dst_w, border_value, dst, S(stream));
 }
 
 static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *fn, int denom)

@@ -81,6 +81,8 @@ struct sv_ctx {
     size_t cap_pp2 = 0;
     u8 *cc = nullptr;           // k11_components.hip: run numbering, union-find parents and bounding boxes (layout at the top of that file)
     size_t cap_cc = 0;
+    u8 *grid2 = nullptr;        // k13_grid_v2.hip: the Harris response, tile and frame maxima, candidate counts and sort keys
+    size_t cap_grid2 = 0;
     void *k1_list = nullptr;    // k1_threshold_mm.hip: optional diagnostic counter (pixels decided by the exact evaluation), sv_preprocess_stats
     int precision = 0;          // SV_PREC_F32 / SV_PREC_BF16 (sv_ctx_set_precision)
     int cnn_kernels = 0;        // SV_CNN_AUTO / _F16PAIR / _F32MFMA (sv_ctx_set_cnn_kernels)
@@ -94,7 +96,7 @@ struct sv_ctx {
     std::vector<hipEvent_t> event_pool;
 };
 
-enum sv_kernel_id { SVK_PREPROCESS = 0, SVK_WARP_CELLS = 1, SVK_CONV_FEATURES = 2, SVK_FC_HEAD = 3, SVK_FUSED12 = 4, SVK_COUNT = 5 };
+enum sv_kernel_id { SVK_PREPROCESS = 0, SVK_WARP_CELLS = 1, SVK_CONV_FEATURES = 2, SVK_FC_HEAD = 3, SVK_FUSED12 = 4, SVK_HARRIS = 5, SVK_WARP_AFFINE = 6, SVK_COUNT = 7 };
 
 // RAII bracket: records an event before and after a launch when ctx->timing is on
 struct sv_time_scope {
@@ -235,6 +237,12 @@ int svk_propagate_constraints(const u8 *digits, const float *conf, long n, int m
 // k11_components.hip (min_area: the floor itself, min_area_ratio * H * W of the true frame size)
 int svk_component_filter_bits(sv_ctx *ctx, uint32_t *bits, int n, int H, int W, double min_area, hipStream_t s);
 int svk_component_filter(sv_ctx *ctx, const u8 *binary, int n, int H, int W, double min_area, u8 *out, uint32_t *packed, hipStream_t s);
+
+// k13_grid_v2.hip
+int svk_harris_corners(sv_ctx *ctx, const u8 *gray, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int max_corners, double quality_level,
+                       int min_distance, double k, int cand_capacity, float *corners, int *counts, float *response, hipStream_t s);
+int svk_warp_affine(sv_ctx *ctx, const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const double *fwd, int dh, int dw, int border, u8 *dst,
+                    hipStream_t s);
 
 // host helpers
 void sv_gaussian_taps_f32(int n, float *out);

@@ -109,6 +109,54 @@ def find_grid_corners_batch(binaries, min_area_ratio=0.1, epsilon_ratio=0.02, th
     return corners, found.astype(bool)
 
 
+def find_grid_corners_v2(binary, min_area_ratio=0.1, epsilon_ratio=0.02):
+    """detect_grid_contour's search (cv/grid_v2.py:102-128): as find_grid_corners, but a 4-gon that is not roughly rectangular
+    (is_valid_quadrilateral) is passed over for the next contour -> int32 (4,2) or None."""
+    b = _bin(binary)
+    H, W = b.shape
+    corners = np.empty((4, 2), np.int32)
+    rc = _native.lib().sv_find_grid_corners_v2_u8(b.ctypes.data_as(C.c_void_p), H, W, W, float(min_area_ratio), float(epsilon_ratio),
+                                                  corners.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        _native.check(rc, "sv_find_grid_corners_v2_u8")
+    return corners if rc == 1 else None
+
+
+def find_grid_corners_v2_batch(binaries, min_area_ratio=0.1, epsilon_ratio=0.02, threads=None):
+    """binaries uint8 [n,H,W] (host) -> (corners int32 [n,4,2], found bool [n]), find_grid_corners_v2 of every image."""
+    b = np.asarray(binaries)
+    if b.dtype != np.uint8 or b.ndim != 3:
+        raise TypeError("expected uint8 [n,H,W]")
+    b = np.ascontiguousarray(b)
+    n, H, W = b.shape
+    corners = np.zeros((n, 4, 2), np.int32)
+    found = np.zeros(n, np.uint8)
+    threads = threads or min(n, os.cpu_count() or 1)
+    _native.check(_native.lib().sv_find_grid_corners_v2_batch_u8(b.ctypes.data_as(C.c_void_p), n, H, W, W, H * W, float(min_area_ratio),
+                                                                 float(epsilon_ratio), corners.ctypes.data_as(C.c_void_p),
+                                                                 found.ctypes.data_as(C.c_void_p), int(threads)), "sv_find_grid_corners_v2_batch_u8")
+    return corners, found.astype(bool)
+
+
+def hough_lines_p(binary, rho=1.0, theta=np.pi / 180, threshold=100, min_line_length=50, max_line_gap=10):
+    """cv2.HoughLinesP(binary, rho, theta, threshold, minLineLength, maxLineGap) -> int32 [N,4] rows (x0, y0, x1, y1) in the order the
+    lines are found (N may be 0)."""
+    b = _bin(binary)
+    H, W = b.shape
+    lib = _native.lib()
+    cap = 256
+    while True:
+        lines = np.empty((cap, 4), np.int32)
+        count = C.c_int()
+        rc = lib.sv_hough_lines_p_u8(b.ctypes.data_as(C.c_void_p), H, W, W, float(rho), float(theta), int(threshold), int(min_line_length),
+                                     int(max_line_gap), lines.ctypes.data_as(C.c_void_p), cap, C.byref(count))
+        if rc == -6:                                          # SV_ERR_BUFFER: count holds the number of lines
+            cap = count.value
+            continue
+        _native.check(rc, "sv_hough_lines_p_u8")
+        return lines[:count.value].copy()
+
+
 def find_grid_corners_bits_batch(bits, H, W, min_area_ratio=0.1, epsilon_ratio=0.02, threads=None):
     """bits int32/uint32 [n,H,W//32] (host; 1 bit per pixel, LSB = leftmost) -> (corners int32 [n,4,2], found bool [n])."""
     b = np.ascontiguousarray(bits)

@@ -328,7 +328,7 @@ def _corners_behind_filters(ctx, frames, binary_dev=None, min_area_ratio=0.1):
     return host.find_grid_corners(b[0].cpu().numpy(), min_area_ratio)
 
 
-def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1", resolve=False, propagate=False, component_filter=False):
+def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1", resolve=False, propagate=False, component_filter=False, grid="v1"):
     """One BGR image (numpy uint8 [H,W,3], or a CUDA uint8 tensor of that shape) -> dict(grid 9x9 list, digits, confidences, corners) or None when no
     grid is found -- the call order of pipeline/run.py:261-312, preprocess_cell (:73-95) included by default.
     top_k > 1 adds run_v2's per-cell `alternatives` (pipeline/run_v2.py:165-178): 81 lists of (digit, prob), best excluded.
@@ -349,8 +349,14 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     `grid` otherwise, with the cells' confidences: `propagation` (is_valid, iterations, contradiction_cell as (row, col) or None,
     cells_resolved as (row, col, digit) in the reference's order) and `propagated_grid` (what run_v2 hands to the solver).
     component_filter=True (opt-in; for photos, where the host corner search is what takes the time): the binary goes to the host behind
-    the exact filters K4 and K11 (_corners_behind_filters), as a bit image where W % 32 == 0.  Same result, keys and values."""
+    the exact filters K4 and K11 (_corners_behind_filters), as a bit image where W % 32 == 0.  Same result, keys and values.
+    grid="v2": the corners come from run_v2's detection (pipeline/run_v2.py:287), cv.grid_v2.detect_grid(binary, gray), which falls back
+    to Hough lines, a de-rotated contour search and Harris corners + RANSAC where the contour search alone finds nothing; the result
+    carries `detection_method`, `detection_confidence` and `rotation_angle`, and `corners` are the ordered float32 corners.
+    component_filter does not apply to it."""
     from .runtime import default_context
+    if grid not in ("v1", "v2"):
+        raise ValueError(f"grid must be 'v1' or 'v2', got {grid!r}")
     if preprocess not in ("v1", "v2"):
         raise ValueError(f"preprocess must be 'v1' or 'v2', got {preprocess!r}")
     if model not in ("v1", "v3", "v3_light"):
@@ -370,8 +376,13 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
         pre = preprocess_v2.preprocess_multi_strategy(frames[0])
         binary_dev = pre.binary
     else:
-        binary_dev = None if component_filter else ctx.preprocess(frames)[0]
-    if component_filter:
+        binary_dev = None if component_filter and grid == "v1" else ctx.preprocess(frames)[0]
+    detection = None
+    if grid == "v2":
+        from .cv import grid_v2
+        detection = grid_v2.detect_grid(binary_dev, ctx.gray(frames)[0])
+        corners = detection.corners
+    elif component_filter:
         corners = _corners_behind_filters(ctx, frames, binary_dev)
     else:
         binary = binary_dev.cpu().numpy()
@@ -408,6 +419,8 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
         res["quality"], res["quality_feedback"] = q, grid_quality.get_user_feedback(q)
     if pre is not None:
         res["preprocess_method"], res["has_shadow"], res["has_glare"] = pre.method_used, pre.has_shadow, pre.has_glare
+    if detection is not None:
+        res["detection_method"], res["detection_confidence"], res["rotation_angle"] = detection.method, detection.confidence, detection.rotation_angle
     return res
 
 
@@ -488,14 +501,18 @@ def check_constraints(grid):
     return out
 
 
-def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confidence=0.7, component_filter=False, reduce=1):
+def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confidence=0.7, component_filter=False, reduce=1, grid="v1"):
     """run_pipeline(image_path) of pipeline/run.py:244-355 on the MI355X path: JPEG -> frame in HBM (imgcodecs) -> K1 -> host
     corner search -> K2 (warped 450x450 grid kept, as the reference keeps it) -> preprocess_cell + DigitCNN (K3) -> constraint
     check -> in-process solver.  Same PipelineResult fields, same error strings, same partial results on failure.
     component_filter=True: the corner search reads the binary behind the exact filters K4 and K11 (recognize_image); same result.
-    reduce = 2, 4 or 8: the JPEG is decoded at 1/reduce of its size (cv2.IMREAD_REDUCED_COLOR_*) and everything downstream runs on that frame."""
+    reduce = 2, 4 or 8: the JPEG is decoded at 1/reduce of its size (cv2.IMREAD_REDUCED_COLOR_*) and everything downstream runs on that frame.
+    grid="v2": the corners come from cv.grid_v2.detect_grid (recognize_image); the result then has the attributes detection_method,
+    detection_confidence and rotation_angle (run_v2's PipelineResult fields)."""
     from . import imgcodecs
     from .runtime import default_context
+    if grid not in ("v1", "v2"):
+        raise ValueError(f"grid must be 'v1' or 'v2', got {grid!r}")
     res = PipelineResult(success=False)
     t_total = time.time()
     ctx = ctx or default_context()
@@ -509,7 +526,7 @@ def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confide
 
     t_cv = time.time()
     try:
-        if component_filter:
+        if component_filter and grid == "v1":
             filtered = _corners_behind_filters(ctx, frame[None])
         else:
             binary = ctx.preprocess(frame[None])[0].cpu().numpy()
@@ -517,7 +534,13 @@ def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confide
         res.error = f"Preprocessing failed: {e}"
         return res
     try:
-        corners = filtered if component_filter else host.find_grid_corners(binary)
+        if grid == "v2":
+            from .cv import grid_v2
+            detection = grid_v2.detect_grid(binary, ctx.gray(frame[None])[0])
+            corners = detection.corners
+            res.detection_method, res.detection_confidence, res.rotation_angle = detection.method, detection.confidence, detection.rotation_angle
+        else:
+            corners = filtered if component_filter else host.find_grid_corners(binary)
         if corners is None:
             res.error = "Grid detection failed: no quadrilateral found"
             return res

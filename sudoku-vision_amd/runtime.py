@@ -269,7 +269,7 @@ class Context:
         self._check(self._lib.sv_ctx_reserve(self._h, int(max_cells)), "sv_ctx_reserve")
 
     # ---- per-kernel timing (hipEvents on the launch stream, inside the library) -------------------
-    KERNELS = ("k_preprocess", "k_warp_cells", "k_conv_features", "k_fc_head", "k_preprocess_warp_fused")
+    KERNELS = ("k_preprocess", "k_warp_cells", "k_conv_features", "k_fc_head", "k_preprocess_warp_fused", "k_harris", "k_warp_affine")
 
     def timing_begin(self):
         self._check(self._lib.sv_timing_begin(self._h), "sv_timing_begin")
@@ -925,6 +925,52 @@ class Context:
     def count_nonzero(self, img):
         """Pixels != 0 per frame -> int32 [n] (sv_count_nonzero_u8)."""
         return self._planes_call("sv_count_nonzero_u8", img, image=False, counts=True, name="img")
+
+
+    # ---- grid detection fallbacks (cv/grid_v2.py, csrc/k13_grid_v2.hip) ------------------------------
+    def harris_corners(self, gray, max_corners=100, quality_level=0.01, min_distance=10, k=0.04, cand_capacity=None, want_response=False):
+        """cv2.goodFeaturesToTrack(gray, max_corners, quality_level, min_distance, blockSize=3, useHarrisDetector=True, k)
+        (sv_harris_corners_u8).  gray u8 [H,W] -> corners float32 [m,2] as (x, y); gray u8 [n,H,W] -> (corners float32
+        [n,max_corners,2], counts int32 [n]).  A numpy array or a CUDA tensor; a tensor gives tensors.  cand_capacity: room for corner
+        candidates per frame; a frame with more raises (SV_ERR_BUFFER), it is never cut short.  None: 2^18, and a frame with more (a noisy
+        10-megapixel photo can have them) is run again with room for every pixel, so the default never raises for that.  want_response: also return the Harris
+        response float32 [H,W] / [n,H,W] as the last element."""
+        d, was_tensor = _to_dev(gray, self)
+        single = d.dim() == 2
+        x, pitch, fstride = _plane_layout(d[None] if single else d, self.device)
+        n, H, W = x.shape
+        corners = torch.empty((n, int(max_corners), 2), dtype=torch.float32, device=self.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=self.device)
+        resp = torch.empty((n, H, W), dtype=torch.float32, device=self.device) if want_response else None
+        for cap in ((int(cand_capacity),) if cand_capacity is not None else (min(1 << 18, H * W), min(1 << 24, H * W))):
+            rc = self._lib.sv_harris_corners_u8(self._h, _ptr(x), n, H, W, pitch, fstride, int(max_corners), float(quality_level), int(min_distance), float(k),
+                                                cap, _ptr(corners), _ptr(counts), _opt_ptr(resp), _stream_ptr())
+            if rc != -6 or cap >= H * W:                      # SV_ERR_BUFFER: more candidates than `cap`
+                break
+        self._check(rc, "sv_harris_corners_u8")
+        out = (corners[0, :int(counts[0].item())],) if single else (corners, counts)
+        if want_response:
+            out += (resp[0] if single else resp,)
+        out = tuple(_back(t, was_tensor) for t in out)
+        return out[0] if len(out) == 1 else out
+
+    def warp_affine(self, img, M, dsize, border_value=0):
+        """cv2.warpAffine(img, M, dsize=(w, h), INTER_LINEAR, BORDER_CONSTANT, border_value) on gray u8 (sv_warp_affine_u8).  img [H,W] with M
+        [2,3], or [n,H,W] with M [n,2,3]: the forward matrices, float64 (numpy or a tensor).  A numpy image or a CUDA tensor; a tensor
+        gives a tensor."""
+        d, was_tensor = _to_dev(img, self)
+        single = d.dim() == 2
+        x, pitch, fstride = _plane_layout(d[None] if single else d, self.device, "img")
+        n, H, W = x.shape
+        m = M if isinstance(M, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(M, np.float64)))
+        m = m.to(device=self.device, dtype=torch.float64).contiguous()
+        if m.numel() != 6 * n:
+            raise ValueError(f"M must hold {n} 2x3 matrices, got shape {list(m.shape)}")
+        dw, dh = int(dsize[0]), int(dsize[1])
+        out = torch.empty((n, dh, dw), dtype=torch.uint8, device=self.device)
+        self._check(self._lib.sv_warp_affine_u8(self._h, _ptr(x), n, H, W, pitch, fstride, _ptr(m), dh, dw, int(border_value), _ptr(out), _stream_ptr()),
+                    "sv_warp_affine_u8")
+        return _back(out[0] if single else out, was_tensor)
 
 
 _default = {}

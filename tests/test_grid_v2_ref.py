@@ -1,0 +1,244 @@
+"""CPU: the host half of the cv/grid_v2.py drop-in against tests/grid_v2_ref.py -- the Hough transform line for line, cv::RNG's
+generator, the v2 contour search, and the module's host heuristics on hand-computed cases."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import grid_v2_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def host():
+    import __graft_entry__ as g
+    import sudoku_vision_amd as sva
+    if not os.path.exists(sva._native.LIB_PATH):
+        g.build()
+    return sva.host
+
+
+def _stroke(img, x0, y0, x1, y1, skip=()):
+    """A one-pixel line from (x0,y0) to (x1,y1); skip: indices along it that stay clear."""
+    n = max(abs(x1 - x0), abs(y1 - y0))
+    for i in range(n + 1):
+        if i not in skip:
+            img[y0 + (y1 - y0) * i // n, x0 + (x1 - x0) * i // n] = 255
+
+
+def _crossing_strokes(gap):
+    """64x64: a horizontal stroke with a gap of exactly max_line_gap clear pixels, a vertical one with max_line_gap + 1."""
+    img = np.zeros((64, 64), np.uint8)
+    _stroke(img, 4, 30, 60, 30, skip=range(20, 20 + gap))
+    _stroke(img, 25, 3, 25, 61, skip=range(35, 35 + gap + 1))
+    return img
+
+
+def _rotated_grid(size=96, lines=9, angle=7.0):
+    img = np.zeros((size, size), np.uint8)
+    c, s = np.cos(np.radians(angle)), np.sin(np.radians(angle))
+    mid, half = size / 2, size * 0.36
+    for k in range(lines):
+        o = -half + 2 * half * k / (lines - 1)
+        for t in np.arange(-half, half + 0.25, 0.25):
+            for u, v in ((t, o), (o, t)):
+                x, y = int(round(mid + u * c - v * s)), int(round(mid + u * s + v * c))
+                img[y, x] = 255
+    return img
+
+
+HOUGH_CASES = {
+    "crossing strokes, gaps of max_line_gap and max_line_gap + 1": (_crossing_strokes(4), dict(threshold=15, min_line_length=10, max_line_gap=4)),
+    "nothing set": (np.zeros((40, 56), np.uint8), dict(threshold=10, min_line_length=5, max_line_gap=2)),
+    "one pixel": (np.pad(np.full((1, 1), 255, np.uint8), ((7, 12), (20, 9))), dict(threshold=1, min_line_length=0, max_line_gap=2)),
+    "9-line grid at 7 degrees": (_rotated_grid(), dict(threshold=30, min_line_length=30, max_line_gap=5)),
+}
+
+
+@pytest.mark.parametrize("case", list(HOUGH_CASES))
+def test_hough_lines_equal_the_restatement(host, case):
+    img, kw = HOUGH_CASES[case]
+    want = R.hough_lines_p(img, **kw)
+    got = host.hough_lines_p(img, **kw)
+    assert got.dtype == np.int32 and got.shape == (len(want), 4)
+    assert [tuple(int(v) for v in l) for l in got] == want
+    if case == "nothing set":
+        assert want == []
+    if case.startswith("crossing"):
+        # the stroke with the tolerated gap is one line end to end; the other breaks at its gap
+        assert (4, 30, 60, 30) in want or (60, 30, 4, 30) in want
+        assert not any({(l[0], l[1]), (l[2], l[3])} == {(25, 3), (25, 61)} for l in want)
+    if case.startswith("9-line"):
+        assert len(want) >= 18
+
+
+def test_hough_padded_rows_and_capacity(host):
+    """pitch > W reads the same image; a capacity below the line count reports SV_ERR_BUFFER with the count."""
+    import ctypes as C
+    import sudoku_vision_amd as sva
+    img, kw = HOUGH_CASES["9-line grid at 7 degrees"]
+    want = R.hough_lines_p(img, **kw)
+    wide = np.full((96, 128), 255, np.uint8)
+    wide[:, :96] = img
+    lib = sva._native.lib()
+    lines, count = np.zeros((len(want), 4), np.int32), C.c_int()
+    args = (float(1), float(np.pi / 180), kw["threshold"], kw["min_line_length"], kw["max_line_gap"])
+    assert lib.sv_hough_lines_p_u8(wide.ctypes.data_as(C.c_void_p), 96, 96, 128, *args, lines.ctypes.data_as(C.c_void_p), len(want), C.byref(count)) == 0
+    assert count.value == len(want) and [tuple(int(v) for v in l) for l in lines] == want
+    assert lib.sv_hough_lines_p_u8(wide.ctypes.data_as(C.c_void_p), 96, 96, 128, *args, lines.ctypes.data_as(C.c_void_p), 3, C.byref(count)) == -6
+    assert count.value == len(want)
+
+
+def test_rng_recurrence(host):
+    """cv::RNG: state = (uint32)state * 4164903690 + (state >> 32) from 2^64 - 1, output the low word -- in Python integers."""
+    state, want = (1 << 64) - 1, []
+    for _ in range(8):
+        state = (state % (1 << 32)) * 4164903690 + state // (1 << 32)
+        assert state < 1 << 64
+        want.append(state % (1 << 32))
+    assert want[0] == (0xffffffff * 4164903690 + 0xffffffff) % (1 << 32)
+    assert R.rng_outputs(8) == want
+    # the library draws the same sequence: with k set pixels in a row and a threshold no vote reaches, the walk never starts, and
+    # the order of the draws is invisible; what is visible is the first point drawn from two far-apart pixels with threshold 1
+    img = np.zeros((8, 40), np.uint8)
+    img[1, 2] = img[6, 37] = 255
+    first = want[0] % 2                                       # index into the raster-ordered points
+    got = host.hough_lines_p(img, threshold=1, min_line_length=0, max_line_gap=0)
+    pts = [(2, 1), (37, 6)]
+    assert tuple(got[0][:2]) == pts[first] and tuple(got[1][:2]) == pts[1 - first]
+    # more of the sequence: 12 isolated pixels, each its own one-point line, come out in the order the generator draws them
+    img = np.zeros((60, 60), np.uint8)
+    left = [(5 + 10 * (i % 5), 5 + 20 * (i // 5)) for i in range(12)]       # raster order, far apart
+    for x, y in left:
+        img[y, x] = 255
+    order = []
+    for k, word in enumerate(R.rng_outputs(12)):
+        idx = word % len(left)
+        order.append(left[idx])
+        left[idx] = left[-1]
+        left.pop()
+    got = host.hough_lines_p(img, threshold=1, min_line_length=0, max_line_gap=0)
+    assert [tuple(int(v) for v in l[:2]) for l in got] == order and len(set(order)) == 12
+
+
+def _frame_rect_and_square():
+    """240x320: the largest 4-gon is a 3:1 rectangle outline (v1 takes it, v2 must not); a smaller square outline above the floor."""
+    img = np.zeros((240, 320), np.uint8)
+    img[10:14, 10:310] = img[106:110, 10:310] = 255          # 300 x 100 rectangle
+    img[10:110, 10:14] = img[10:110, 306:310] = 255
+    img[125:129, 100:200] = img[221:225, 100:200] = 255      # 100 x 100 square: area 10^4 > 0.1 * 76800
+    img[125:225, 100:104] = img[125:225, 196:200] = 255
+    return img
+
+
+def test_v2_search_skips_the_long_rectangle(host):
+    img = _frame_rect_and_square()
+    v1 = host.find_grid_corners(img)
+    v2 = host.find_grid_corners_v2(img)
+    assert v1 is not None and v2 is not None
+    assert sorted(map(tuple, v1.tolist())) == [(10, 10), (10, 109), (309, 10), (309, 109)]
+    assert sorted(map(tuple, v2.tolist())) == [(100, 125), (100, 224), (199, 125), (199, 224)]
+    want = R.detect_grid_contour(img)
+    assert (R.order_points(v2.astype(np.float32)) == want).all()
+    corners, found = host.find_grid_corners_v2_batch(np.stack([img, np.zeros_like(img), img]))
+    assert found.tolist() == [True, False, True] and (corners[0] == v2).all() and (corners[2] == v2).all()
+    only_rect = img.copy()
+    only_rect[120:, :] = 0
+    assert host.find_grid_corners(only_rect) is not None and host.find_grid_corners_v2(only_rect) is None
+
+
+def test_valid_quadrilateral_restatement_and_module_agree():
+    sys.path.insert(0, os.path.join(ROOT, "sudoku-vision_amd", "cv"))
+    try:
+        import grid_v2 as m
+    finally:
+        sys.path.pop(0)
+    rs = np.random.RandomState(5)
+    for _ in range(200):
+        quad = (np.array([[50, 50], [150, 50], [150, 150], [50, 150]]) + rs.randint(-45, 46, (4, 2))).astype(np.float32)
+        assert m.is_valid_quadrilateral(quad) == R.is_valid_quadrilateral(quad)
+    assert m.is_valid_quadrilateral(np.array([[0, 0], [100, 0], [100, 100], [0, 100]], np.float32))
+    assert not m.is_valid_quadrilateral(np.array([[0, 0], [300, 0], [300, 100], [0, 100]], np.float32))      # 3:1
+    assert not m.is_valid_quadrilateral(np.array([[0, 0], [100, 0], [200, 30], [0, 100]], np.float32))       # an angle below 45
+    assert not m.is_valid_quadrilateral(np.zeros((3, 2), np.float32))
+
+
+PUBLIC = ("GridDetectionResult find_contours approximate_polygon order_points is_valid_quadrilateral detect_grid_contour detect_lines "
+          "cluster_lines_by_angle line_intersection find_grid_from_lines detect_grid_lines detect_corners_harris fit_quadrilateral_ransac "
+          "detect_rotation_angle rotate_image detect_grid warp_perspective").split()
+
+
+def test_module_names_resolve_in_a_fresh_interpreter():
+    """run_v2 does sys.path.insert(cv/) and `from grid_v2 import detect_grid, warp_perspective` (pipeline/run_v2.py:38)."""
+    code = ("import sys, inspect; sys.path.insert(0, %r); import grid_v2;"
+            "from grid_v2 import detect_grid, warp_perspective;"
+            "names = %r; missing = [n for n in names if not hasattr(grid_v2, n)]; assert not missing, missing;"
+            "p = inspect.signature(grid_v2.detect_grid).parameters;"
+            "assert list(p) == ['binary', 'gray', 'try_rotation', 'try_multiple_methods'] and p['gray'].default is None;"
+            "p = inspect.signature(grid_v2.detect_lines).parameters;"
+            "assert [p[k].default for k in ('rho', 'threshold', 'min_line_length', 'max_line_gap')] == [1, 100, 50, 10];"
+            "p = inspect.signature(grid_v2.detect_corners_harris).parameters;"
+            "assert [p[k].default for k in ('max_corners', 'quality_level', 'min_distance')] == [100, 0.01, 10];"
+            "p = inspect.signature(grid_v2.fit_quadrilateral_ransac).parameters;"
+            "assert [p[k].default for k in ('n_iterations', 'inlier_threshold')] == [100, 10];"
+            "print('ok')") % (os.path.join(ROOT, "sudoku-vision_amd", "cv"), PUBLIC)
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd="/tmp")
+    assert out.returncode == 0 and "ok" in out.stdout, out.stderr
+
+
+def test_line_heuristics_hand_computed(host):
+    import sudoku_vision_amd.cv.grid_v2 as m
+    seg = lambda *v: np.array([v], np.int32)                  # noqa: E731 -- one cv2 line: shape (1,4)
+    lines = np.array([seg(0, 10, 100, 12), seg(100, 50, 0, 48), seg(20, 0, 22, 100), seg(0, 0, 50, 50), seg(80, 100, 80, 0)])
+    hor, ver = m.cluster_lines_by_angle(lines)
+    # 1.1 deg and 178.9 deg are horizontal; 88.9 deg and -90 -> 90 deg vertical; the diagonal is dropped
+    assert [l.tolist() for l in hor] == [[0, 10, 100, 12], [100, 50, 0, 48]]
+    assert [l.tolist() for l in ver] == [[20, 0, 22, 100], [80, 100, 80, 0]]
+    assert m.cluster_lines_by_angle(np.array([seg(0, 0, 100, 18)]))[0] == []                       # 10.2 deg: outside the tolerance
+    assert m.line_intersection([0, 0, 10, 0], [0, 5, 10, 5]) is None                               # parallel
+    assert m.line_intersection([0, 0, 10, 10], [0, 10, 10, 0]) == (5.0, 5.0)
+    assert m.line_intersection([0, 2, 8, 2], [3, -4, 3, 9]) == (3.0, 2.0)
+    # y = 10, y = 90, x = 20, x = 80, given out of order
+    horizontal = [np.array([0, 90, 100, 90]), np.array([0, 10, 100, 10]), np.array([0, 50, 100, 50])]
+    vertical = [np.array([80, 0, 80, 100]), np.array([20, 0, 20, 100])]
+    got = m.find_grid_from_lines(horizontal, vertical, (100, 100))
+    assert got.dtype == np.float32 and got.tolist() == [[20, 10], [80, 10], [80, 90], [20, 90]]
+    assert (got == R.find_grid_from_lines([tuple(l) for l in horizontal], [tuple(l) for l in vertical], (100, 100))).all()
+    assert m.find_grid_from_lines(horizontal[:1], vertical, (100, 100)) is None                   # fewer than two
+    # x = 151 in a 100-wide image: 51 px outside -> None; x = 150 is still taken
+    assert m.find_grid_from_lines(horizontal, [np.array([20, 0, 20, 100]), np.array([151, 0, 151, 100])], (100, 100)) is None
+    assert m.find_grid_from_lines(horizontal, [np.array([20, 0, 20, 100]), np.array([150, 0, 150, 100])], (100, 100)) is not None
+    # two "horizontal" lines that are the same infinite line as a vertical pair's partner: parallel -> None
+    assert m.find_grid_from_lines([np.array([0, 10, 100, 10]), np.array([0, 90, 100, 90])], [np.array([0, 20, 100, 20]), np.array([0, 30, 100, 30])], (100, 100)) is None
+
+
+def test_detect_lines_shape_and_none(host):
+    import sudoku_vision_amd.cv.grid_v2 as m
+    assert m.detect_lines(np.zeros((40, 56), np.uint8)) is None
+    img, kw = HOUGH_CASES["9-line grid at 7 degrees"]
+    got = m.detect_lines(img, **kw)
+    assert got.dtype == np.int32 and got.ndim == 3 and got.shape[1:] == (1, 4)
+    assert [tuple(int(v) for v in l[0]) for l in got] == R.hough_lines_p(img, **kw)
+    assert abs(m.detect_rotation_angle(img) - 7) < 1.5 and m.detect_rotation_angle(img) == R.detect_rotation_angle(img)
+
+
+def test_ransac_draws_the_reference_sequence(host):
+    """One np.random.choice(len, 4, replace=False) per iteration and before any test: after the call numpy's generator is where 100
+    such draws leave it, and the result equals the restatement's under the same seed."""
+    import sudoku_vision_amd.cv.grid_v2 as m
+    rs = np.random.RandomState(3)
+    pts = np.concatenate([np.array([[40, 30], [200, 34], [204, 190], [38, 186]]), rs.randint(60, 180, (8, 2))]).astype(np.float32)
+    np.random.seed(0)
+    got = m.fit_quadrilateral_ransac(pts, (240, 320))
+    after = np.random.randint(1 << 30)
+    np.random.seed(0)
+    want = R.fit_quadrilateral_ransac(pts, (240, 320))
+    assert got is not None and (got == want).all()
+    np.random.seed(0)
+    for _ in range(100):
+        np.random.choice(len(pts), 4, replace=False)
+    assert np.random.randint(1 << 30) == after
+    assert m.fit_quadrilateral_ransac(pts[:3], (240, 320)) is None
