@@ -271,18 +271,6 @@ __global__ __launch_bounds__(256) void k_cc_mask(const u8 *__restrict__ src, con
     for (int i = 0; i < n; i++) dst[o + i] = (w >> i) & 1 ? src[o + i] : (u8)0;
 }
 
-int ensure_cc(sv_ctx *ctx, size_t bytes)
-{
-    if (bytes <= ctx->cap_cc) return SV_OK;
-    SV_HIP(hipSetDevice(ctx->device));
-    if (ctx->cc) SV_HIP(hipFree(ctx->cc));
-    ctx->cc = nullptr;
-    ctx->cap_cc = 0;
-    SV_HIP(hipMalloc((void **)&ctx->cc, bytes));
-    ctx->cap_cc = bytes;
-    return SV_OK;
-}
-
 inline unsigned blocks(long items, int per) { return (unsigned)((items + per - 1) / per); }
 
 }  // namespace
@@ -313,12 +301,12 @@ static int cc_plan(sv_ctx *ctx, int n, int H, int wpr, bool own_bits, int *group
     g = g < 1 ? 1 : (g > (size_t)n ? (size_t)n : g);
     *group = (int)g;
     *frame_words = fw;
-    return ensure_cc(ctx, g * per_frame);
+    return ctx->cc.grow(ctx, g * per_frame);
 }
 
 static cc_frame cc_layout(sv_ctx *ctx, int group, size_t fw)
 {
-    u32 *p = (u32 *)ctx->cc;
+    u32 *p = ctx->cc.as<u32>();
     const size_t slots = (size_t)group * fw * 16;
     cc_frame fr;
     fr.base = p;

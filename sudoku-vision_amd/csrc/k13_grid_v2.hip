@@ -256,21 +256,6 @@ __global__ __launch_bounds__(256) void k_warp_affine(const u8 *__restrict__ src,
     dst[((ptrdiff_t)frame * dh + y) * dw + x] = (u8)v;
 }
 
-// grow-only scratch of the context for the Harris intermediates
-int scratch(sv_ctx *ctx, size_t bytes, u8 **out)
-{
-    if (bytes > ctx->cap_grid2) {
-        SV_HIP(hipSetDevice(ctx->device));
-        if (ctx->grid2) SV_HIP(hipFree(ctx->grid2));
-        ctx->grid2 = nullptr;
-        ctx->cap_grid2 = 0;
-        SV_HIP(hipMalloc((void **)&ctx->grid2, bytes));
-        ctx->cap_grid2 = bytes;
-    }
-    *out = ctx->grid2;
-    return SV_OK;
-}
-
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
@@ -288,9 +273,9 @@ int svk_harris_corners(sv_ctx *ctx, const u8 *gray, int n, int H, int W, ptrdiff
     const size_t o_cnt = o_fmax + align16((size_t)n * sizeof(float));
     const size_t o_keys = o_cnt + align16((size_t)n * sizeof(uint32_t));
     const size_t total = o_keys + (size_t)n * key_stride * sizeof(unsigned long long);
-    u8 *sc;
-    int rc = scratch(ctx, total, &sc);
+    int rc = ctx->grid2.grow(ctx, total);
     if (rc) return rc;
+    u8 *sc = ctx->grid2.as<u8>();
     float *resp = response ? response : (float *)sc;
     float *tile_max = (float *)(sc + o_tile), *frame_max = (float *)(sc + o_fmax);
     uint32_t *cand_count = (uint32_t *)(sc + o_cnt);

@@ -370,10 +370,10 @@ __global__ __launch_bounds__(512, 4) void k_preprocess_mm(const u8 *__restrict__
 static int svk_preprocess_mm_stats(sv_ctx *ctx, unsigned *ambiguous, unsigned long *capacity)
 {
     *ambiguous = 0; *capacity = 0;
-    if (!ctx->k1_list) return SV_OK;
+    if (!ctx->k1_list.p) return SV_OK;
     SV_HIP(hipDeviceSynchronize());
-    SV_HIP(hipMemcpy(ambiguous, ctx->k1_list, 4, hipMemcpyDeviceToHost));
-    SV_HIP(hipMemset(ctx->k1_list, 0, 4));
+    SV_HIP(hipMemcpy(ambiguous, ctx->k1_list.p, 4, hipMemcpyDeviceToHost));
+    SV_HIP(hipMemset(ctx->k1_list.p, 0, 4));
     return SV_OK;
 }
 
@@ -394,7 +394,7 @@ static int svk_preprocess_mm(sv_ctx *ctx, const u8 *bgr, int n, int H, int W, pt
     if (wgs_per_xcd > per_xcd) wgs_per_xcd = per_xcd;
     if (wgs_per_xcd < 1) wgs_per_xcd = 1;
     const dim3 grid((unsigned)(wgs_per_xcd * 8));
-    unsigned *amb_total = (unsigned *)ctx->k1_list;                    // optional counter (sv_preprocess_stats); null until someone asks
+    unsigned *amb_total = ctx->k1_list.as<unsigned>();                 // optional counter (sv_preprocess_stats); null until someone asks
     if (bits)
         hipLaunchKernelGGL(k_preprocess_mm<true>, grid, dim3(512), 0, s, bgr, H, W, pitch, img_stride, out, t, tiles_x, tiles_y, ntiles, per_xcd, (int)wgs_per_xcd, mean_dbg, amb_total);
     else
@@ -406,9 +406,10 @@ static int svk_preprocess_mm(sv_ctx *ctx, const u8 *bgr, int n, int H, int W, pt
 // turn the diagnostic counter on (allocates 16 bytes in the context)
 static int svk_preprocess_mm_enable_stats(sv_ctx *ctx)
 {
-    if (ctx->k1_list) return SV_OK;
-    SV_HIP(hipMalloc(&ctx->k1_list, 16));
-    SV_HIP(hipMemset(ctx->k1_list, 0, 16));
+    if (ctx->k1_list.p) return SV_OK;
+    const int rc = ctx->k1_list.grow(ctx, 16);
+    if (rc) return rc;
+    SV_HIP(hipMemset(ctx->k1_list.p, 0, 16));
     return SV_OK;
 }
 
@@ -425,6 +426,6 @@ extern "C" int sv_preprocess_mm_u8(sv_ctx *ctx, const uint8_t *bgr, int n, int H
 extern "C" int sv_preprocess_stats(sv_ctx *ctx, unsigned *ambiguous, unsigned long *capacity)
 {
     REQUIRE(ctx && ambiguous && capacity, "NULL argument");
-    if (!ctx->k1_list) { *ambiguous = 0; *capacity = 0; return svk_preprocess_mm_enable_stats(ctx); }
+    if (!ctx->k1_list.p) { *ambiguous = 0; *capacity = 0; return svk_preprocess_mm_enable_stats(ctx); }
     return svk_preprocess_mm_stats(ctx, ambiguous, capacity);
 }

@@ -486,9 +486,9 @@ int svk_cnn_forward(sv_ctx *ctx, const void *x, bool x_is_u8, int glue, long B, 
     if (ctx->precision == SV_PREC_BF16 && !x_is_u8)
         return sv_fail(SV_ERR_UNSUPPORTED, "sv_cnn_forward_f32: the bf16 configuration takes 8-bit cells (sv_cnn_forward_cells_u8 / sv_frames_to_digits)");
     if (x_is_u8 && glue == SV_GLUE_RUNPY) {      // run.py's preprocess_cell as its own pass; its {0,255} output then takes the plain glue
-        int rc = svk_preprocess_cells((const u8 *)x, B, ctx->cells2, s);
+        int rc = svk_preprocess_cells((const u8 *)x, B, ctx->cells2.as<u8>(), s);
         if (rc) return rc;
-        x = ctx->cells2;
+        x = ctx->cells2.p;
     }
     if (ctx->precision == SV_PREC_BF16) return svk_cnn_forward_bf16(ctx, (const u8 *)x, B, logits, digits, conf, s);
     sv_cnn_algo conv_algo = effective_algo(ctx);
@@ -497,13 +497,15 @@ int svk_cnn_forward(sv_ctx *ctx, const void *x, bool x_is_u8, int glue, long B, 
     const int *flag = nullptr;                   // device flag: 0 = the f16-pair kernels run, 1 = the f32-MFMA kernels (both are launched)
     if (conv_algo == SV_ALGO_F16PAIR && !x_is_u8 && ctx->cnn_kernels == SV_CNN_AUTO) {
         // 8-bit cells are in [-1, 1] after the glue (what svk_pack_weights_h2 sized the activations for); f32 input can be anything
-        if (!ctx->range_flag) SV_HIP(hipMalloc((void **)&ctx->range_flag, 2 * sizeof(int)));
-        SV_HIP(hipMemsetAsync(ctx->range_flag, 0, 2 * sizeof(int), s));
+        const int rc = ctx->range_flag.grow(ctx, 2 * sizeof(int));       // (sv_ctx_reserve has done it where a capture follows)
+        if (rc) return rc;
+        int *range_flag = ctx->range_flag.as<int>();
+        SV_HIP(hipMemsetAsync(range_flag, 0, 2 * sizeof(int), s));
         const long n = B * 784;
-        hipLaunchKernelGGL(k_input_range, dim3((unsigned)(n / 4096 + 1 < 1024 ? n / 4096 + 1 : 1024)), dim3(256), 0, s, (const float *)x, n, w.h2_x_lo, w.h2_x_hi, ctx->range_flag);
-        hipLaunchKernelGGL(k_input_range_finish, dim3(1), dim3(1), 0, s, ctx->range_flag);
+        hipLaunchKernelGGL(k_input_range, dim3((unsigned)(n / 4096 + 1 < 1024 ? n / 4096 + 1 : 1024)), dim3(256), 0, s, (const float *)x, n, w.h2_x_lo, w.h2_x_hi, range_flag);
+        hipLaunchKernelGGL(k_input_range_finish, dim3(1), dim3(1), 0, s, range_flag);
         SV_LAUNCH_CHECK("k_input_range");
-        flag = ctx->range_flag;
+        flag = range_flag;
     }
     if (conv_algo == SV_ALGO_F16PAIR) {
         const int rc = svk_cnn_forward_h2(ctx, x, x_is_u8, B, logits, digits, conf, flag, s);
@@ -516,16 +518,16 @@ int svk_cnn_forward(sv_ctx *ctx, const void *x, bool x_is_u8, int glue, long B, 
         const int grid_pc = (int)(npairs < (long)ctx->num_cus ? npairs : (long)ctx->num_cus);
         sv_time_scope ts(ctx, SVK_CONV_FEATURES, s);
         if (x_is_u8)
-            hipLaunchKernelGGL(k_conv_features_pc<true>, dim3(grid_pc), dim3(512), 0, s, x, B, w.conv1_w, w.conv1_b, w.conv2_wreg, w.conv2_b, ctx->features, flag);
+            hipLaunchKernelGGL(k_conv_features_pc<true>, dim3(grid_pc), dim3(512), 0, s, x, B, w.conv1_w, w.conv1_b, w.conv2_wreg, w.conv2_b, ctx->features.as<float>(), flag);
         else
-            hipLaunchKernelGGL(k_conv_features_pc<false>, dim3(grid_pc), dim3(512), 0, s, x, B, w.conv1_w, w.conv1_b, w.conv2_wreg, w.conv2_b, ctx->features, flag);
+            hipLaunchKernelGGL(k_conv_features_pc<false>, dim3(grid_pc), dim3(512), 0, s, x, B, w.conv1_w, w.conv1_b, w.conv2_wreg, w.conv2_b, ctx->features.as<float>(), flag);
     }
     SV_LAUNCH_CHECK("k_conv_features");
     sv_time_scope ts(ctx, SVK_FC_HEAD, s);
     if (sv_xcheck && ctx->x_fc_frame && B >= 81 * 64)       // (svx_ctx_set_fc_frame_kernel) enough frames to give most CUs a workgroup
         sv_xcheck->launch_fc_frame(ctx, B, logits, digits, conf, flag, s);
     else
-        hipLaunchKernelGGL(k_fc_head, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, ctx->features, B, w.fc1_wreg, w.fc1_b, w.fc2_w, w.fc2_b, logits, digits, conf, flag);
+        hipLaunchKernelGGL(k_fc_head, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, ctx->features.as<float>(), B, w.fc1_wreg, w.fc1_b, w.fc2_w, w.fc2_b, logits, digits, conf, flag);
     SV_LAUNCH_CHECK("k_fc_head");
     return SV_OK;
 }

@@ -266,18 +266,18 @@ int svk_cnn_forward_bf16(sv_ctx *ctx, const u8 *cells, long B, float *logits, u8
     {
         sv_time_scope ts(ctx, SVK_CONV_FEATURES, s);
         hipLaunchKernelGGL(k_conv_features_bf16, dim3(grid), dim3(256), 0, s, cells, B, w.conv1_w, w.conv1_b, (const uint4 *)w.conv2_bf16, w.conv2_b,
-                           (unsigned short *)ctx->features);
+                           ctx->features.as<unsigned short>());
     }
     SV_LAUNCH_CHECK("k_conv_features_bf16");
     sv_time_scope ts(ctx, SVK_FC_HEAD, s);
     const long per = sv_fc_percu_share(ctx, B);
     if (per <= SV_FC_PERCU_CELLS) {
-        hipLaunchKernelGGL(k_fc_head_bf16p, dim3((unsigned)((B + per - 1) / per)), dim3(64 * SV_FCP_WAVES), 0, s, (const unsigned short *)ctx->features, B, per,
+        hipLaunchKernelGGL(k_fc_head_bf16p, dim3((unsigned)((B + per - 1) / per)), dim3(64 * SV_FCP_WAVES), 0, s, ctx->features.as<const unsigned short>(), B, per,
                            (const uint4 *)w.fc1_bf16, w.fc1_b, w.fc2_w, w.fc2_b, logits, digits, conf);
         SV_LAUNCH_CHECK("k_fc_head_bf16p");
         return SV_OK;
     }
-    hipLaunchKernelGGL(k_fc_head_bf16, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, (const unsigned short *)ctx->features, B, (const uint4 *)w.fc1_bf16,
+    hipLaunchKernelGGL(k_fc_head_bf16, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, ctx->features.as<const unsigned short>(), B, (const uint4 *)w.fc1_bf16,
                        w.fc1_b, w.fc2_w, w.fc2_b, logits, digits, conf);
     SV_LAUNCH_CHECK("k_fc_head_bf16");
     return SV_OK;

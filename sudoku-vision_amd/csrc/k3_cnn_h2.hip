@@ -635,10 +635,10 @@ int svk_cnn_forward_h2(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *
         sv_time_scope ts(ctx, SVK_CONV_FEATURES, s);
         if (x_is_u8)
             hipLaunchKernelGGL(k_conv_features_h2<true>, dim3(grid), dim3(512), 0, s, x, B, (const uint4 *)w.conv1_h2, w.conv1_b_h2, w.conv1_h2_scale_inv, (const uint4 *)w.conv2_h2, w.conv2_b_h2,
-                               w.conv2_h2_scale_inv, ctx->features, run_if_clear SV_ABLATE_ARG);
+                               w.conv2_h2_scale_inv, ctx->features.as<float>(), run_if_clear SV_ABLATE_ARG);
         else
             hipLaunchKernelGGL(k_conv_features_h2<false>, dim3(grid), dim3(512), 0, s, x, B, (const uint4 *)w.conv1_h2, w.conv1_b_h2, w.conv1_h2_scale_inv, (const uint4 *)w.conv2_h2, w.conv2_b_h2,
-                               w.conv2_h2_scale_inv, ctx->features, run_if_clear SV_ABLATE_ARG);
+                               w.conv2_h2_scale_inv, ctx->features.as<float>(), run_if_clear SV_ABLATE_ARG);
     }
 #undef SV_ABLATE_ARG
     SV_LAUNCH_CHECK("k_conv_features_h2");
@@ -647,12 +647,12 @@ int svk_cnn_forward_h2(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *
     // tools/dev/fc_sweep.py); beyond a 96-cell share two co-resident 64-cell workgroups per CU do better (32,768 cells: 0.115 against 0.136 ms).
     const long per = sv_fc_percu_share(ctx, B);
     if (per <= SV_FC_PERCU_CELLS) {
-        hipLaunchKernelGGL(k_fc_head_h2p, dim3((unsigned)((B + per - 1) / per)), dim3(64 * SV_FCP_WAVES), 0, s, ctx->features, B, per, (const uint4 *)w.fc1_h2, w.fc1_b,
+        hipLaunchKernelGGL(k_fc_head_h2p, dim3((unsigned)((B + per - 1) / per)), dim3(64 * SV_FCP_WAVES), 0, s, ctx->features.as<float>(), B, per, (const uint4 *)w.fc1_h2, w.fc1_b,
                            w.fc1_h2_scale_inv, w.fc2_w, w.fc2_b, logits, digits, conf, run_if_clear);
         SV_LAUNCH_CHECK("k_fc_head_h2p");
         return SV_OK;
     }
-    hipLaunchKernelGGL(k_fc_head_h2, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, ctx->features, B, (const uint4 *)w.fc1_h2, w.fc1_b, w.fc1_h2_scale_inv,
+    hipLaunchKernelGGL(k_fc_head_h2, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, s, ctx->features.as<float>(), B, (const uint4 *)w.fc1_h2, w.fc1_b, w.fc1_h2_scale_inv,
                        w.fc2_w, w.fc2_b, logits, digits, conf, run_if_clear);
     SV_LAUNCH_CHECK("k_fc_head_h2");
     return SV_OK;

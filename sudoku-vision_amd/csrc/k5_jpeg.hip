@@ -388,18 +388,6 @@ static int jpeg_plan(const sv_jpeg_info *info, int denom, const char *fn, JpegPl
     return SV_OK;
 }
 
-// the component planes between the IDCT and the colour kernel grow on demand
-static int reserve_planes(sv_ctx *ctx, size_t bytes)
-{
-    if (bytes <= ctx->cap_jpeg) return SV_OK;
-    SV_HIP(hipSetDevice(ctx->device));
-    if (ctx->jpeg_planes) SV_HIP(hipFree(ctx->jpeg_planes));
-    ctx->jpeg_planes = nullptr; ctx->cap_jpeg = 0;
-    SV_HIP(hipMalloc((void **)&ctx->jpeg_planes, bytes));
-    ctx->cap_jpeg = bytes;
-    return SV_OK;
-}
-
 // bgr: ceil(out_height / denom) x ceil(out_width / denom) x 3
 int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, int denom, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
                          const uint16_t *quant, u8 *bgr, ptrdiff_t pitch, hipStream_t s, const char *fn)
@@ -407,7 +395,8 @@ int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, int denom, const
     const int ncomp = info->components, hmax = info->h_samp, vmax = info->v_samp, S = 8 / denom;
     JpegPlan p;
     int rc = jpeg_plan(info, denom, fn, p);
-    if (rc || (rc = reserve_planes(ctx, (size_t)p.plane_bytes))) return rc;
+    if (rc || (rc = ctx->jpeg_planes.grow(ctx, (size_t)p.plane_bytes))) return rc;   // the component planes between the IDCT and the colour kernel
+    u8 *planes = ctx->jpeg_planes.as<u8>();
     for (int first = 0; first < ncomp; first++) {               // one launch per block size: luma's, then chroma's where it differs
         const int z = p.sc[first];
         if (first == 2 || (first == 1 && z == p.sc[0])) continue;
@@ -423,7 +412,7 @@ int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, int denom, const
         g.item_start[3] = items;
         const IdctKernel k = coef ? idct_kernel<false>(z) : idct_kernel<true>(z);
         hipLaunchKernelGGL(k, dim3((unsigned)((items + per_wg - 1) / per_wg)), dim3(256), 0, s, (const short *)coef, (const unsigned long long *)masks, offsets,
-                           (const short *)values, quant, g, ctx->jpeg_planes);
+                           (const short *)values, quant, g, planes);
         SV_LAUNCH_CHECK("k_jpeg_idct");
     }
     JpegColourGeom cg = {};
@@ -434,7 +423,7 @@ int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, int denom, const
     cg.dw = S > 1 ? (info->width * p.sc[1] + hmax * 8 - 1) / (hmax * 8) : 0;    // jdsample.c: no fancy up-sampling when blocks are 1x1
     cg.dh = (info->height * p.sc[1] + vmax * 8 - 1) / (vmax * 8);
     for (int c = 0; c < 3; c++) { cg.pitch[c] = p.pitch[c]; cg.plane_off[c] = p.plane_off[c]; }
-    hipLaunchKernelGGL(k_jpeg_colour, dim3((unsigned)((cg.OW + 255) / 256), (unsigned)cg.OH), dim3(256), 0, s, ctx->jpeg_planes, cg, bgr, (long)pitch);
+    hipLaunchKernelGGL(k_jpeg_colour, dim3((unsigned)((cg.OW + 255) / 256), (unsigned)cg.OH), dim3(256), 0, s, planes, cg, bgr, (long)pitch);
     SV_LAUNCH_CHECK("k_jpeg_colour");
     return SV_OK;
 }

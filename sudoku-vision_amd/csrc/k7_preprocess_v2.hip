@@ -366,21 +366,6 @@ __global__ __launch_bounds__(256) void k_pointwise(const u8 *__restrict__ src, i
     }
 }
 
-// grow-only scratch of the context for the stages that need intermediates
-int scratch(sv_ctx *ctx, size_t bytes, u8 **out)
-{
-    if (bytes > ctx->cap_pp2) {
-        SV_HIP(hipSetDevice(ctx->device));
-        if (ctx->pp2) SV_HIP(hipFree(ctx->pp2));
-        ctx->pp2 = nullptr;
-        ctx->cap_pp2 = 0;
-        SV_HIP(hipMalloc((void **)&ctx->pp2, bytes));
-        ctx->cap_pp2 = bytes;
-    }
-    *out = ctx->pp2;
-    return SV_OK;
-}
-
 template <bool MAX>
 int morph_once(const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int nlev, u8 *planes, const short2 *rows, int k, u8 *dst,
                hipStream_t s)
@@ -415,9 +400,9 @@ int svk_morphology(sv_ctx *ctx, const u8 *src, int n, int H, int W, ptrdiff_t pi
     while ((2 << nlev) <= std::min(k, W)) nlev++;
     const size_t plane_bytes = (size_t)n * H * W, rows_bytes = ((size_t)k * sizeof(short2) + 255) / 256 * 256;
     const bool two = op == SV_MORPH_CLOSE || op == SV_MORPH_OPEN;
-    u8 *base;
-    int rc = scratch(ctx, rows_bytes + plane_bytes * (nlev + (two ? 1 : 0)), &base);
+    int rc = ctx->pp2.grow(ctx, rows_bytes + plane_bytes * (nlev + (two ? 1 : 0)));
     if (rc) return rc;
+    u8 *base = ctx->pp2.as<u8>();
     short2 *rows = (short2 *)base;
     u8 *planes = base + rows_bytes, *mid = planes + plane_bytes * nlev;
     hipLaunchKernelGGL(k_morph_element, dim3((k + 255) / 256), dim3(256), 0, s, shape, k, rows);
@@ -468,9 +453,9 @@ int svk_clahe(sv_ctx *ctx, const u8 *src, int n, int H, int W, ptrdiff_t pitch, 
     if (clip > 0.0) clip_limit = std::max((int)(clip * area / 256), 1);
     const float lut_scale = 255.0f / (float)area, inv_tw = 1.0f / (float)tw, inv_th = 1.0f / (float)th;
     const size_t hist_bytes = (size_t)n * ntiles * 256 * sizeof(uint32_t);
-    u8 *base;
-    const int rc = scratch(ctx, hist_bytes + (size_t)n * ntiles * 256, &base);
+    const int rc = ctx->pp2.grow(ctx, hist_bytes + (size_t)n * ntiles * 256);
     if (rc) return rc;
+    u8 *base = ctx->pp2.as<u8>();
     uint32_t *hist = (uint32_t *)base;
     u8 *luts = base + hist_bytes;
     SV_HIP(hipMemsetAsync(hist, 0, hist_bytes, s));

@@ -230,8 +230,8 @@ size_t svk_v3_scratch_bytes(long cells)
 int svk_cnn3_forward(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *logits, float *features, u8 *digits, float *conf, hipStream_t s)
 {
     const sv_weights3 &w = ctx->w3;
-    const long cap = ctx->cap_v3;
-    float *P = ctx->v3_act, *Q = P + cap * ACT, *R = Q + cap * ACT;
+    const long cap = ctx->v3_cells;
+    float *P = ctx->v3_act.as<float>(), *Q = P + cap * ACT, *R = Q + cap * ACT;
     float *P2 = P + cap * (ACT / 2), *Q2 = Q + cap * (ACT / 2);      // second halves: the stride-2 blocks hold two tensors in one buffer
     const auto stem = x_is_u8 ? conv3<4, 1, 32, 28, 1, 3, 7, 1, true, true> : conv3<4, 1, 32, 28, 1, 3, 7, 1, true, false>;
     const size_t cell_bytes = 784 * (x_is_u8 ? sizeof(u8) : sizeof(float));

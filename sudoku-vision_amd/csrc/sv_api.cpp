@@ -55,37 +55,35 @@ extern "C" int sv_ctx_destroy(sv_ctx *ctx)
     free_weights(ctx->w3);
     free_weights(ctx->wl);
     free_weights(ctx->we);
-    if (ctx->v3_act) (void)hipFree(ctx->v3_act);
-    if (ctx->features) (void)hipFree(ctx->features);
-    if (ctx->cells) (void)hipFree(ctx->cells);
-    if (ctx->cells2) (void)hipFree(ctx->cells2);
-    if (ctx->jpeg_planes) (void)hipFree(ctx->jpeg_planes);
-    if (ctx->pp2) (void)hipFree(ctx->pp2);
-    if (ctx->cc) (void)hipFree(ctx->cc);
-    if (ctx->grid2) (void)hipFree(ctx->grid2);
-    if (ctx->k1_list) (void)hipFree(ctx->k1_list);
-    if (ctx->range_flag) (void)hipFree(ctx->range_flag);
+    ctx->for_each_scratch([](sv_scratch &b) { b.release(); });
     for (auto &t : ctx->timeline) { (void)hipEventDestroy(t.t0); (void)hipEventDestroy(t.t1); }
     for (auto &e : ctx->event_pool) (void)hipEventDestroy(e);
     delete ctx;
     return SV_OK;
 }
 
+int sv_scratch::grow(sv_ctx *ctx, size_t bytes)
+{
+    if (bytes <= cap) return SV_OK;
+    SV_HIP(hipSetDevice(ctx->device));
+    if (p) SV_HIP(hipFree(p));
+    p = nullptr;
+    cap = 0;
+    SV_HIP(hipMalloc(&p, bytes));
+    cap = bytes;
+    return SV_OK;
+}
+
+// features, cells and cells2 for `cells` cells: three allocations (kernels test their alignment)
 int sv_ensure_scratch(sv_ctx *ctx, long cells)
 {
-    if (cells <= ctx->cap_cells) return SV_OK;
-    SV_HIP(hipSetDevice(ctx->device));
-    if (ctx->features) SV_HIP(hipFree(ctx->features));
-    if (ctx->cells) SV_HIP(hipFree(ctx->cells));
-    if (ctx->cells2) SV_HIP(hipFree(ctx->cells2));
-    ctx->features = nullptr;
-    ctx->cells = nullptr;
-    ctx->cells2 = nullptr;
-    ctx->cap_cells = 0;
-    SV_HIP(hipMalloc((void **)&ctx->features, sizeof(float) * 3136 * (size_t)cells));
-    SV_HIP(hipMalloc((void **)&ctx->cells, (size_t)SV_CELL_PX * (size_t)cells));
-    SV_HIP(hipMalloc((void **)&ctx->cells2, (size_t)SV_CELL_PX * (size_t)cells));
-    ctx->cap_cells = cells;
+    if (cells <= ctx->n_cells) return SV_OK;
+    ctx->n_cells = 0;
+    int rc;
+    if ((rc = ctx->features.grow(ctx, sizeof(float) * 3136 * (size_t)cells))) return rc;
+    if ((rc = ctx->cells.grow(ctx, (size_t)SV_CELL_PX * (size_t)cells))) return rc;
+    if ((rc = ctx->cells2.grow(ctx, (size_t)SV_CELL_PX * (size_t)cells))) return rc;
+    ctx->n_cells = cells;
     return SV_OK;
 }
 
@@ -93,13 +91,11 @@ int sv_ensure_scratch(sv_ctx *ctx, long cells)
 static int sv_ensure_scratch_v3(sv_ctx *ctx, long cells)
 {
     const long want = cells < SV_V3_SUBBATCH ? cells : SV_V3_SUBBATCH;
-    if (want <= ctx->cap_v3) return SV_OK;
-    SV_HIP(hipSetDevice(ctx->device));
-    if (ctx->v3_act) SV_HIP(hipFree(ctx->v3_act));
-    ctx->v3_act = nullptr;
-    ctx->cap_v3 = 0;
-    SV_HIP(hipMalloc((void **)&ctx->v3_act, svk_v3_scratch_bytes(want)));
-    ctx->cap_v3 = want;
+    if (want <= ctx->v3_cells) return SV_OK;
+    ctx->v3_cells = 0;
+    const int rc = ctx->v3_act.grow(ctx, svk_v3_scratch_bytes(want));
+    if (rc) return rc;
+    ctx->v3_cells = want;
     return SV_OK;
 }
 
@@ -114,9 +110,8 @@ extern "C" int sv_ctx_reserve(sv_ctx *ctx, long max_cells)
 {
     if (!ctx || max_cells <= 0) return sv_fail(SV_ERR_BAD_ARG, "sv_ctx_reserve: bad argument");
     SV_HIP(hipSetDevice(ctx->device));
-    if (!ctx->range_flag) SV_HIP(hipMalloc((void **)&ctx->range_flag, 2 * sizeof(int)));     // sv_cnn_forward_f32's per-call range flag: no hipMalloc after reserve
-    int rc = sv_ensure_scratch(ctx, max_cells);
-    if (rc) return rc;
+    int rc = ctx->range_flag.grow(ctx, 2 * sizeof(int));                  // sv_cnn_forward_f32's per-call range flag: no hipMalloc after reserve
+    if (rc || (rc = sv_ensure_scratch(ctx, max_cells))) return rc;
     return ctx->w3.loaded ? sv_ensure_scratch_v3(ctx, max_cells) : SV_OK;    // v1-only contexts do not pay for the v3 activations
 }
 
@@ -201,7 +196,7 @@ extern "C" int sv_load_weights_v3_f32(sv_ctx *ctx, const float *blob, long n_flo
     free_weights(ctx->w3);
     int rc = svk_pack_weights_v3(ctx->w3, blob, use_se != 0);
     if (rc) { free_weights(ctx->w3); return rc; }
-    return ctx->cap_cells > 0 ? sv_ensure_scratch_v3(ctx, ctx->cap_cells) : SV_OK;
+    return ctx->n_cells > 0 ? sv_ensure_scratch_v3(ctx, ctx->n_cells) : SV_OK;
 }
 
 // the Light and Empty loads: `n_floats` against the model's count, then `pack` into the model's own slot
@@ -561,8 +556,8 @@ static int cnn3_common(sv_ctx *ctx, const void *x, bool u8in, int glue, long B, 
     if ((rc = sv_ensure_scratch_v3(ctx, B))) return rc;
     if (u8in && glue == SV_GLUE_RUNPY) {             // preprocess_cell as its own pass; its {0,255} output then takes the plain glue
         if ((rc = sv_ensure_scratch(ctx, B))) return rc;
-        if ((rc = svk_preprocess_cells((const uint8_t *)x, B, ctx->cells2, S(stream)))) return rc;
-        x = ctx->cells2;
+        if ((rc = svk_preprocess_cells((const uint8_t *)x, B, ctx->cells2.as<u8>(), S(stream)))) return rc;
+        x = ctx->cells2.p;
     }
     return svk_cnn3_forward(ctx, x, u8in, B, logits, features, digits, conf, S(stream));
 }
@@ -589,8 +584,8 @@ static int light_prepare(const char *fn, sv_ctx *ctx, const void *&x, bool u8in,
     if ((rc = glue_ok(fn, glue))) return rc;
     if (u8in && glue == SV_GLUE_RUNPY) {             // preprocess_cell as its own pass; its {0,255} output then takes the plain glue
         if ((rc = sv_ensure_scratch(ctx, B))) return rc;
-        if ((rc = svk_preprocess_cells((const uint8_t *)x, B, ctx->cells2, S(stream)))) return rc;
-        x = ctx->cells2;
+        if ((rc = svk_preprocess_cells((const uint8_t *)x, B, ctx->cells2.as<u8>(), S(stream)))) return rc;
+        x = ctx->cells2.p;
     }
     return SV_OK;
 }
@@ -905,7 +900,7 @@ static int frames_to_digits(const char *fn, int model, sv_ctx *ctx, const uint8_
     const long B = (long)n * SV_CELLS;
     int rc = sv_ensure_scratch(ctx, B);
     if (rc) return rc;
-    uint8_t *c = cells ? cells : ctx->cells;
+    uint8_t *c = cells ? cells : ctx->cells.as<u8>();
     if ((rc = svk_warp_cells(ctx, frames, n, H, W, pitch, frame_stride, minv, c, S(stream)))) return rc;
     if (model == 2) return cnn3_light_common(ctx, c, true, glue, B, logits, nullptr, digits, conf, stream);
     return model == 1 ? cnn3_common(ctx, c, true, glue, B, logits, nullptr, digits, conf, stream) : cnn_common(ctx, c, true, glue, B, logits, digits, conf, stream);

@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/sudoku_vision_hip.h"
@@ -62,33 +63,49 @@ struct sv_weights_light {
     std::vector<void *> allocs;
 };
 
+struct sv_ctx;
+
+// One device buffer that a context owns and only ever grows.  The kernels' files say what lives inside each (layout comments there).
+struct sv_scratch {
+    void *p = nullptr;
+    size_t cap = 0;             // bytes
+    // At least `bytes`: nothing to do while they fit (the hot path: one compare), else free and allocate anew -- the contents are not
+    // kept, and hipFree synchronises the device.  A failed allocation leaves p == nullptr, cap == 0.
+    int grow(sv_ctx *ctx, size_t bytes);
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    template <class T> T *as() const { return (T *)p; }
+};
+
 struct sv_ctx {
     int device = 0;
     int num_cus = 256;
     sv_weights w;
     sv_weights3 w3;
     sv_weights_light wl, we;    // DigitCNNv3Light, EmptyClassifier
-    float *v3_act = nullptr;    // k8_cnn_v3.hip: three activation buffers of [cap_v3][32*784] floats
-    long cap_v3 = 0;            // cells, at most SV_V3_SUBBATCH
-    // grow-only scratch
-    float *features = nullptr;  // [cells][49][64] pooled conv2 output
-    u8 *cells = nullptr;        // [cells][784]
-    u8 *cells2 = nullptr;       // [cells][784] preprocess_cell output (SV_GLUE_RUNPY)
-    long cap_cells = 0;
-    u8 *jpeg_planes = nullptr;  // decoded component planes (MCU-padded) between the IDCT and the colour kernel
-    size_t cap_jpeg = 0;
-    u8 *pp2 = nullptr;          // k7_preprocess_v2.hip: element rows + doubling planes + the close/open intermediate, or CLAHE's tile histograms + LUTs
-    size_t cap_pp2 = 0;
-    u8 *cc = nullptr;           // k11_components.hip: run numbering, union-find parents and bounding boxes (layout at the top of that file)
-    size_t cap_cc = 0;
-    u8 *grid2 = nullptr;        // k13_grid_v2.hip: the Harris response, tile and frame maxima, candidate counts and sort keys
-    size_t cap_grid2 = 0;
-    void *k1_list = nullptr;    // k1_threshold_mm.hip: optional diagnostic counter (pixels decided by the exact evaluation), sv_preprocess_stats
+    // grow-only scratch; for_each_scratch below lists every one of them
+    sv_scratch v3_act;          // k8_cnn_v3.hip: three activation buffers of [v3_cells][32*784] floats
+    long v3_cells = 0;          // at most SV_V3_SUBBATCH
+    sv_scratch features;        // float [cells][49][64] pooled conv2 output
+    sv_scratch cells;           // u8 [cells][784]
+    sv_scratch cells2;          // u8 [cells][784] preprocess_cell output (SV_GLUE_RUNPY)
+    long n_cells = 0;           // what features, cells and cells2 hold (sv_ensure_scratch); nonzero only while all three are allocated
+    sv_scratch jpeg_planes;     // decoded component planes (MCU-padded) between the IDCT and the colour kernel
+    sv_scratch pp2;             // k7_preprocess_v2.hip: element rows + doubling planes + the close/open intermediate, or CLAHE's tile histograms + LUTs
+    sv_scratch cc;              // k11_components.hip: run numbering, union-find parents and bounding boxes (layout at the top of that file)
+    sv_scratch grid2;           // k13_grid_v2.hip: the Harris response, tile and frame maxima, candidate counts and sort keys
+    sv_scratch k1_list;         // k1_threshold_mm.hip: optional diagnostic counter (pixels decided by the exact evaluation), sv_preprocess_stats; 16 bytes
+    sv_scratch range_flag;      // int [2]: the per-call kernel choice for f32 inputs (k3_cnn.hip k_input_range)
+    // sv_ctx_destroy frees through this and nothing else: a new buffer goes in here
+    template <class F> void for_each_scratch(F f)
+    {
+        for (sv_scratch *b : {&v3_act, &features, &cells, &cells2, &jpeg_planes, &pp2, &cc, &grid2, &k1_list, &range_flag}) f(*b);
+    }
     int precision = 0;          // SV_PREC_F32 / SV_PREC_BF16 (sv_ctx_set_precision)
     int cnn_kernels = 0;        // SV_CNN_AUTO / _F16PAIR / _F32MFMA (sv_ctx_set_cnn_kernels)
-    int *range_flag = nullptr;  // [2] device ints: the per-call kernel choice for f32 inputs (k3_cnn.hip k_input_range)
     bool x_fc_frame = false;    // x_cnn_round1.hip (svx_ctx_set_fc_frame_kernel): k_fc_head_frame for large batches; never set in the product
-    int dev_ablate = 0;         // SV_DEV builds: k3_cnn_h2.hip ablation / stamp bits
+#ifdef SV_DEV
+    int dev_ablate = 0;         // k3_cnn_h2.hip: the ablation / stamp bits of k_conv_features_h2 (sv_dev_set_h2_ablate, svk_cnn_forward_h2)
+#endif
     // optional per-kernel timing (sv_timing_begin/sv_timing_end): hipEvents on the launch stream
     bool timing = false;
     struct timed { int kernel; hipEvent_t t0, t1; };

@@ -644,21 +644,21 @@ void launch_conv(sv_ctx *ctx, sv_cnn_algo conv_algo, const void *x, bool x_is_u8
     const int grid_s = (int)((B + cpw - 1) / cpw);
     if (conv_algo == SV_ALGO_X_WSPLIT) {
         if (x_is_u8)
-            hipLaunchKernelGGL(k_conv_features_wsplit<true>, dim3(grid_s), dim3(512), 0, s, x, B, cpw, w.conv1_w, w.conv1_b, (const uint4 *)w.conv2_wsplit, w.conv2_b, ctx->features);
+            hipLaunchKernelGGL(k_conv_features_wsplit<true>, dim3(grid_s), dim3(512), 0, s, x, B, cpw, w.conv1_w, w.conv1_b, (const uint4 *)w.conv2_wsplit, w.conv2_b, ctx->features.as<float>());
         else
-            hipLaunchKernelGGL(k_conv_features_wsplit<false>, dim3(grid_s), dim3(512), 0, s, x, B, cpw, w.conv1_w, w.conv1_b, (const uint4 *)w.conv2_wsplit, w.conv2_b, ctx->features);
+            hipLaunchKernelGGL(k_conv_features_wsplit<false>, dim3(grid_s), dim3(512), 0, s, x, B, cpw, w.conv1_w, w.conv1_b, (const uint4 *)w.conv2_wsplit, w.conv2_b, ctx->features.as<float>());
     } else {
         if (x_is_u8)
-            hipLaunchKernelGGL(k_conv_features_wstream<true>, dim3(grid_s), dim3(512), 0, s, x, B, cpw, w.conv1_w, w.conv1_b, w.conv2_wino, w.conv2_b, ctx->features);
+            hipLaunchKernelGGL(k_conv_features_wstream<true>, dim3(grid_s), dim3(512), 0, s, x, B, cpw, w.conv1_w, w.conv1_b, w.conv2_wino, w.conv2_b, ctx->features.as<float>());
         else
-            hipLaunchKernelGGL(k_conv_features_wstream<false>, dim3(grid_s), dim3(512), 0, s, x, B, cpw, w.conv1_w, w.conv1_b, w.conv2_wino, w.conv2_b, ctx->features);
+            hipLaunchKernelGGL(k_conv_features_wstream<false>, dim3(grid_s), dim3(512), 0, s, x, B, cpw, w.conv1_w, w.conv1_b, w.conv2_wino, w.conv2_b, ctx->features.as<float>());
     }
 }
 
 void launch_fc_frame(sv_ctx *ctx, long B, float *logits, u8 *digits, float *conf, const int *run_if_set, hipStream_t s)
 {
     const sv_weights &w = ctx->w;
-    hipLaunchKernelGGL(k_fc_head_frame, dim3((unsigned)((B + 80) / 81)), dim3(512), 0, s, ctx->features, B, w.fc1_wreg, w.fc1_b, w.fc2_w, w.fc2_b, logits, digits, conf, run_if_set);
+    hipLaunchKernelGGL(k_fc_head_frame, dim3((unsigned)((B + 80) / 81)), dim3(512), 0, s, ctx->features.as<float>(), B, w.fc1_wreg, w.fc1_b, w.fc2_w, w.fc2_b, logits, digits, conf, run_if_set);
 }
 
 sv_xcheck_ops ops = {select_conv, pack_weights, launch_conv, launch_fc_frame};   // (not const: a const table would be emitted for the device as well)
