@@ -295,6 +295,35 @@ int sv_approx_poly_dp_i32(const int *xy /*host*/, int n, double epsilon, int clo
  * -1 invalid input (solver/include/sudoku.h:13-16); solution = grid unless solved. */
 int sv_solve_sudoku(const uint8_t *grid /*host, 81*/, uint8_t *solution /*host, 81*/, int *result);
 
+/* ---- K14: the solver for n grids in one launch (pipeline/run_v2.py:393-407, run_solver) ---------------- */
+
+/* Result codes of the batch entries on top of the reference's 1 / 0 / -1 (solver/include/sudoku.h:13-16). */
+#define SV_SOLVE_BUDGET 2           /* max_nodes search nodes were entered and another one was due: the frame is undecided */
+#define SV_SOLVE_SKIPPED 3          /* active[f] == 0: the caller did not want this frame solved */
+#define SV_SOLVE_MAX_NODES 65536    /* the largest budget a launch takes */
+
+/* solver/src/sudoku.c for n grids, one wave per grid: validate_grid (:413-467); init_candidates (:226-247); propagate (:287-401):
+ * naked singles row-major, each placed before the next cell is looked at, then hidden singles by row, by column, by box, digits
+ * ascending, repeated while anything was placed; solve_with_candidates (:6-59): branch on the first cell with the fewest candidates,
+ * digits ascending.  The same decision order as sv_solve_sudoku, so the same grid also where a puzzle has several solutions.
+ * A node is one entry into solve_with_candidates (one call of propagate); the root is node 1.  When a node would be entered
+ * with max_nodes already entered, the frame ends with SV_SOLVE_BUDGET.
+ *   grid [n*81]      0 = empty, 1..9; a byte above 9 or a duplicate in a unit: result -1
+ *   active [n]       or NULL (all): frames with 0 are not solved (SV_SOLVE_SKIPPED)
+ * Outputs, each may be NULL:
+ *   solution [n*81]  = grid unless result is 1; may be grid itself
+ *   result [n]       1, 0, -1, SV_SOLVE_BUDGET, SV_SOLVE_SKIPPED
+ *   nodes [n]        nodes entered; 0 for results -1 and SV_SOLVE_SKIPPED
+ * Asynchronous on `stream`; a frame's result does not depend on the rest of the batch.  1 <= max_nodes <= SV_SOLVE_MAX_NODES,
+ * otherwise SV_ERR_BAD_ARG; n == 0 is SV_OK. */
+int sv_solve_sudoku_batch(sv_ctx *ctx, const uint8_t *grid /*dev, n*81*/, const uint8_t *active /*dev, n, or NULL*/, int n, int max_nodes,
+                          uint8_t *solution /*dev, n*81*/, int8_t *result /*dev, n*/, int32_t *nodes /*dev, n, or NULL*/, void *stream);
+
+/* The same on the host over `threads` threads, all pointers host memory: same codes, same solutions, same node counts.
+ * max_nodes == 0: no budget (then SV_SOLVE_BUDGET never occurs; nodes saturates at INT32_MAX); max_nodes < 0: SV_ERR_BAD_ARG. */
+int sv_solve_sudoku_batch_host(const uint8_t *grid, const uint8_t *active /*or NULL*/, int n, int max_nodes, uint8_t *solution,
+                               int8_t *result, int32_t *nodes /*or NULL*/, int threads);
+
 /* ---- K2: perspective warp + cell extraction (cv/grid.py, cv/extract.py) ------------------------- */
 
 /* Host, fp64.  order_points + inset + cv2.getPerspectiveTransform to (0,0)..(S-1,S-1) + the inverse

@@ -34,6 +34,8 @@ SIGNATURES = {
     "sv_adaptive_threshold_u8": [_p, _p, _i, _i, _i, _i, _d, _i, _p, _p],
     "sv_preprocess_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p],
     "sv_solve_sudoku": [_p, _p, _p],
+    "sv_solve_sudoku_batch": [_p, _p, _p, _i, _i, _p, _p, _p, _p],
+    "sv_solve_sudoku_batch_host": [_p, _p, _i, _i, _p, _p, _p, _i],
     "sv_despeckle_u8": [_p, _p, _i, _i, _i, _p, _p, _p],
     "sv_preprocess_bits_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p],
     "sv_preprocess_warp_cells_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p, _p, _p],

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "host_pool.h"
 #include "sv_internal.h"
 
 namespace {
@@ -67,19 +68,22 @@ inline int hidden_single(State &s, const int *idx, int d)
     return 0;
 }
 
+struct Units {
+    int u[27][9];                                        // rows, then columns, then boxes (boxes row-major)
+    Units()
+    {
+        for (int i = 0; i < 9; i++)
+            for (int k = 0; k < 9; k++) {
+                u[i][k] = i * 9 + k;
+                u[9 + i][k] = k * 9 + i;
+                u[18 + i][k] = (i / 3 * 3 + k / 3) * 9 + i % 3 * 3 + k % 3;
+            }
+    }
+};
+const Units kUnits;
+
 bool propagate(State &s)
 {
-    static int unit[27][9];
-    static bool init = false;
-    if (!init) {
-        for (int u = 0; u < 9; u++)
-            for (int k = 0; k < 9; k++) {
-                unit[u][k] = u * 9 + k;
-                unit[9 + u][k] = k * 9 + u;
-                unit[18 + u][k] = (u / 3 * 3 + k / 3) * 9 + u % 3 * 3 + k % 3;
-            }
-        init = true;
-    }
     for (bool progress = true; progress;) {
         progress = false;
         for (int i = 0; i < 81; i++)
@@ -88,9 +92,9 @@ bool propagate(State &s)
                 if (c == 0) return false;
                 if ((c & (c - 1)) == 0) { place(s, i, __builtin_ctz(c)); progress = true; }
             }
-        for (int u = 0; u < 27; u++)                     // rows, then columns, then boxes (boxes row-major)
+        for (int u = 0; u < 27; u++)
             for (int d = 1; d <= 9; d++) {
-                const int r = hidden_single(s, unit[u], d);
+                const int r = hidden_single(s, kUnits.u[u], d);
                 if (r < 0) return false;
                 progress |= r > 0;
             }
@@ -98,24 +102,53 @@ bool propagate(State &s)
     return true;
 }
 
-bool search(State &s)
+// A node is one entry into search(), that is one call of propagate(); the root is node 1.  max_nodes == 0: no budget.
+struct Budget { long nodes, max_nodes; };
+
+// 1 solved (s holds the solution), 0 no solution below this node, SV_SOLVE_BUDGET a node would have been entered with the budget spent
+int search(State &s, Budget &b)
 {
-    if (!propagate(s)) return false;
+    if (b.max_nodes && b.nodes == b.max_nodes) return SV_SOLVE_BUDGET;
+    b.nodes++;
+    if (!propagate(s)) return 0;
     int best = -1, best_n = 10;
     for (int i = 0; i < 81; i++)
         if (s.g[i] == 0) {
             const int n = __builtin_popcount(s.cand[i]);
             if (n < best_n) { best_n = n; best = i; }
         }
-    if (best < 0) return true;                           // no empty cell left: solved
+    if (best < 0) return 1;                              // no empty cell left: solved
     const unsigned c = s.cand[best];
     for (int d = 1; d <= 9; d++)
         if (c >> d & 1) {
             State t = s;
             place(t, best, d);
-            if (search(t)) { s = t; return true; }
+            const int r = search(t, b);
+            if (r == 1) s = t;
+            if (r) return r;
         }
-    return false;
+    return 0;
+}
+
+// One grid: the result code, the solution (= grid unless solved) and the nodes entered (0 for invalid input).
+int solve_one(const uint8_t *grid, long max_nodes, uint8_t *solution, long *nodes)
+{
+    State s;
+    memcpy(s.g, grid, 81);                               // grid and solution may be one buffer
+    if (solution != grid) memcpy(solution, grid, 81);
+    *nodes = 0;
+    if (!valid(s.g)) return -1;
+    for (int i = 0; i < 81; i++) s.cand[i] = s.g[i] ? 0 : 0x3FE;
+    for (int i = 0; i < 81; i++)
+        if (s.g[i]) {
+            const uint16_t m = (uint16_t)~(1u << s.g[i]);
+            for (int k = 0; k < 20; k++) s.cand[kPeers.p[i][k]] &= m;
+        }
+    Budget b = {0, max_nodes};
+    const int r = search(s, b);
+    *nodes = b.nodes;
+    if (r == 1) memcpy(solution, s.g, 81);
+    return r;
 }
 
 }  // namespace
@@ -125,17 +158,30 @@ bool search(State &s)
 extern "C" int sv_solve_sudoku(const uint8_t *grid, uint8_t *solution, int *result)
 {
     if (!grid || !solution || !result) return sv_fail(SV_ERR_BAD_ARG, "sv_solve_sudoku: NULL argument");
-    memcpy(solution, grid, 81);
-    if (!valid(grid)) { *result = -1; return SV_OK; }
-    State s;
-    memcpy(s.g, grid, 81);
-    for (int i = 0; i < 81; i++) s.cand[i] = grid[i] ? 0 : 0x3FE;
-    for (int i = 0; i < 81; i++)
-        if (grid[i]) {
-            const uint16_t m = (uint16_t)~(1u << grid[i]);
-            for (int k = 0; k < 20; k++) s.cand[kPeers.p[i][k]] &= m;
+    long nodes;
+    *result = solve_one(grid, 0, solution, &nodes);
+    return SV_OK;
+}
+
+// n grids over `threads` host threads, with K14's codes and node accounting (k14_solve.hip): result 2 = the budget of max_nodes was
+// spent (max_nodes == 0: none), 3 = active[f] == 0; nodes[f] as the kernel reports it, saturated at INT32_MAX.
+extern "C" int sv_solve_sudoku_batch_host(const uint8_t *grid, const uint8_t *active, int n, int max_nodes, uint8_t *solution, int8_t *result,
+                                          int32_t *nodes, int threads)
+{
+    if (n < 0 || max_nodes < 0 || threads < 1) return sv_fail(SV_ERR_BAD_ARG, "sv_solve_sudoku_batch_host: need n >= 0, max_nodes >= 0, threads >= 1");
+    if (n == 0) return SV_OK;
+    if (!grid || !solution || !result) return sv_fail(SV_ERR_BAD_ARG, "sv_solve_sudoku_batch_host: NULL argument");
+    WorkerPool::instance().parallel_for(n, threads, [&](int f) {
+        const uint8_t *g = grid + (size_t)f * 81;
+        uint8_t *out = solution + (size_t)f * 81;
+        long count = 0;
+        if (active && !active[f]) {
+            if (out != g) memcpy(out, g, 81);
+            result[f] = SV_SOLVE_SKIPPED;
+        } else {
+            result[f] = (int8_t)solve_one(g, max_nodes, out, &count);
         }
-    if (search(s)) { memcpy(solution, s.g, 81); *result = 1; }
-    else *result = 0;
+        if (nodes) nodes[f] = (int32_t)std::min(count, (long)INT32_MAX);
+    });
     return SV_OK;
 }

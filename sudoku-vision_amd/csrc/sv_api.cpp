@@ -685,6 +685,18 @@ extern "C" int sv_propagate_constraints(sv_ctx *ctx, const uint8_t *digits, cons
                                      S(stream));
 }
 
+extern "C" int sv_solve_sudoku_batch(sv_ctx *ctx, const uint8_t *grid, const uint8_t *active, int n, int max_nodes, uint8_t *solution, int8_t *result,
+                                     int32_t *nodes, void *stream)
+{
+    REQUIRE(ctx, "NULL argument");
+    REQUIRE(n >= 0, "n out of range");
+    REQUIRE(max_nodes >= 1 && max_nodes <= SV_SOLVE_MAX_NODES, "need 1 <= max_nodes <= 65536");
+    if (n == 0) return SV_OK;
+    REQUIRE(grid, "NULL argument");
+    REQUIRE(((uintptr_t)nodes & 3) == 0, "misaligned argument");
+    return svk_solve_sudoku_batch(grid, active, n, max_nodes, solution, result, nodes, S(stream));
+}
+
 extern "C" int sv_frame_quality_stats_u8(sv_ctx *ctx, const uint8_t *img, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int channels,
                                          int64_t *lap_sum, int64_t *lap_sqsum, uint32_t *hist, void *stream)
 {

@@ -261,5 +261,8 @@ int svk_harris_corners(sv_ctx *ctx, const u8 *gray, int n, int H, int W, ptrdiff
 int svk_warp_affine(sv_ctx *ctx, const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const double *fwd, int dh, int dw, int border, u8 *dst,
                     hipStream_t s);
 
+// k14_solve.hip
+int svk_solve_sudoku_batch(const u8 *grid, const u8 *active, int n, int max_nodes, u8 *solution, int8_t *result, int *nodes, hipStream_t s);
+
 // host helpers
 void sv_gaussian_taps_f32(int n, float *out);

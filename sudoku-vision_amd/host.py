@@ -220,6 +220,29 @@ def solve_sudoku(grid):
     return res.value, out.reshape(9, 9)
 
 
+def solve_sudoku_batch(grids, active=None, max_nodes=0, threads=None):
+    """grids uint8 [n,81] or [n,9,9] (host), active [n] or None (all) -> (result int8 [n], solution uint8 [n,9,9], nodes int32 [n]):
+    sv_solve_sudoku_batch_host, the host counterpart of Context.solve_sudoku with the same codes (1 solved, 0 no solution, -1 invalid,
+    2 the budget of max_nodes search nodes was spent, 3 not active), solutions and node counts.  max_nodes=0: no budget."""
+    g = np.asarray(grids)
+    if g.dtype != np.uint8 or g.ndim not in (2, 3) or g.shape[1:] not in ((81,), (9, 9)):
+        raise TypeError("expected uint8 [n,81] or [n,9,9]")
+    g = np.ascontiguousarray(g)
+    n = g.shape[0]
+    if active is not None:
+        active = np.ascontiguousarray(np.asarray(active).reshape(-1) != 0, np.uint8)
+        if active.shape != (n,):
+            raise ValueError("active must hold one entry per grid")
+    if not 0 <= int(max_nodes) < 2 ** 31:
+        raise ValueError("max_nodes must be 0 (no budget) or positive")
+    result, solution, nodes = np.empty(n, np.int8), np.empty((n, 9, 9), np.uint8), np.empty(n, np.int32)
+    threads = threads or max(1, min(n, os.cpu_count() or 1))
+    _native.check(_native.lib().sv_solve_sudoku_batch_host(g.ctypes.data_as(C.c_void_p), active.ctypes.data_as(C.c_void_p) if active is not None else None,
+                                                           n, int(max_nodes), solution.ctypes.data_as(C.c_void_p), result.ctypes.data_as(C.c_void_p),
+                                                           nodes.ctypes.data_as(C.c_void_p), int(threads)), "sv_solve_sudoku_batch_host")
+    return result, solution, nodes
+
+
 # ---- JPEG front end, host half (csrc/host_jpeg.cpp): header parsing and Huffman decoding -------------------
 def jpeg_parse(data: bytes):
     """-> _native.JpegInfo (sv_jpeg_info).  Raises NativeError for non-JPEG data and for unsupported JPEG flavours."""

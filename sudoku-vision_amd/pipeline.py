@@ -65,7 +65,7 @@ def gpu_local_cpus(device):
 
 class FramePipeline:
     def __init__(self, ctx: Context, H: int, W: int, chunk: int = 32, host_threads=None, min_area_ratio=0.1, glue=0, despeckle=True, sparse=True, depth=5, cpu_affinity="auto", bits_direct=True,
-                 quality=False, resolve=False, propagate=False):
+                 quality=False, resolve=False, propagate=False, solve=False, solve_max_nodes=4096):
         self.ctx, self.H, self.W, self.chunk = ctx, H, W, chunk
         # chunks in flight.  A chunk's chain is K1 -> D2H -> search -> K2/K3, and chunk i's K1 is only issued once chunk i-depth+1's search has
         # returned: with too few in flight the period is (K1 + D2H + search) / (depth - 1), not the slowest stage
@@ -124,6 +124,10 @@ class FramePipeline:
         # propagate=True: run() also returns run_v2's constraint propagation (pipeline/run_v2.py:373-391, csrc/k10_propagate.hip), one more
         # launch per chunk on s_cls: on the repaired digits when resolve=True, else on the recognised ones
         self.propagate = bool(propagate)
+        # solve=True: run() also returns run_v2's last stage, the solver (pipeline/run_v2.py:393-407, csrc/k14_solve.hip), one more launch per
+        # chunk on s_cls, on the grid the stages before it end with, for the frames run_v2 would hand to it.  A frame that spends
+        # solve_max_nodes search nodes is reported as such (Context.SOLVE_BUDGET), not finished on the host
+        self.solve, self.solve_max_nodes = bool(solve), int(solve_max_nodes)
         ctx.reserve(chunk * 81)
 
     def _search(self, slot, m, ev):
@@ -157,7 +161,8 @@ class FramePipeline:
                 f"{self.host_threads} host threads -> K2 -> K3, {self.chunk}-frame chunks, {self.depth} in flight"
                 + (f", host threads on the GPU's NUMA node ({len(self.cpus)} CPUs)" if self.cpus else "")
                 + (", then top-3 -> K9 (validation + beam-search conflict repair) per chunk" if self.resolve else "")
-                + (", then K10 (constraint propagation) per chunk" if self.propagate else ""))
+                + (", then K10 (constraint propagation) per chunk" if self.propagate else "")
+                + (f", then K14 (solver, {self.solve_max_nodes} search nodes per frame at most) per chunk" if self.solve else ""))
 
     def run(self, frames, out=None, repeat=1, total=None):
         """frames u8 [n,H,W,3] on the context's device -> dict(digits u8[n,81], logits f32[n,81,10], conf f32[n,81],
@@ -169,7 +174,9 @@ class FramePipeline:
         frame whose grid was not found; with propagate=True also propagated_digits u8[n,81] (the grid after run_v2's constraint propagation
         of resolved_digits, or of digits without resolve=True), propagate_valid bool[n] (False: run_v2 reports the frame `invalid`),
         contradiction_cell u8[n] (9 * row + col, 255 = none) and n_propagated u8[n] (cells the propagation filled), on the device; zeros,
-        False and 255 for a frame whose grid was not found.  repeat > 1 streams the pool that many times through the
+        False and 255 for a frame whose grid was not found; with solve=True also solution u8[n,81], solve_result int8[n] and solve_nodes
+        int32[n] (Context.solve_sudoku of propagated_digits, else resolved_digits, else digits, for the frames with propagate_valid, or
+        without propagate=True those whose grid was found; the others are Context.SOLVE_SKIPPED), on the device.  repeat > 1 streams the pool that many times through the
         pipeline without draining it in between (steady-state throughput measurement); total = k streams exactly k frames,
         cycling the pool (the k-th frame is pool frame k mod n: BASELINE configs[3]'s shard of 100,000 frames); both need chunk | n."""
         n = frames.shape[0]
@@ -207,6 +214,10 @@ class FramePipeline:
             propagate_ok = torch.empty((n,), dtype=torch.uint8, device=dev)
             out.update(propagated_digits=torch.empty((n, 81), dtype=torch.uint8, device=dev), propagate_valid=propagate_ok.view(torch.bool),
                        contradiction_cell=torch.empty((n,), dtype=torch.uint8, device=dev), n_propagated=torch.empty((n,), dtype=torch.uint8, device=dev))
+        if self.solve:
+            solve_in = out["propagated_digits" if self.propagate else "resolved_digits" if self.resolve else "digits"]
+            out.update(solution=torch.empty((n, 81), dtype=torch.uint8, device=dev), solve_result=torch.empty((n,), dtype=torch.int8, device=dev),
+                       solve_nodes=torch.empty((n,), dtype=torch.int32, device=dev))
         if total is None:
             starts = [(s0, min(self.chunk, n - s0)) for _ in range(repeat) for s0 in range(0, n, self.chunk)]
         else:
@@ -235,6 +246,7 @@ class FramePipeline:
                     self.ctx.propagate_constraints(out["resolved_digits" if self.resolve else "digits"][s:s + m],
                                                    out={"grid": out["propagated_digits"][s:s + m], "is_valid": propagate_ok[s:s + m],
                                                         "contradiction_cell": out["contradiction_cell"][s:s + m], "n_resolved": out["n_propagated"][s:s + m]})
+                lost = None
                 if not found.all():
                     lost = torch.from_numpy(~found).to(dev)
                     out["digits"][s:s + m][lost] = 0
@@ -247,6 +259,10 @@ class FramePipeline:
                         for key in ("resolved_digits", "num_conflicts", "n_corrections"):
                             out[key][s:s + m][lost] = 0
                         resolve_ok[s:s + m][lost] = 0
+                if self.solve:                    # after the lost frames were cleared: their grids are empty and they are not active
+                    self.ctx.solve_sudoku(solve_in[s:s + m], propagate_ok[s:s + m] if self.propagate else None if lost is None else ~lost,
+                                          max_nodes=self.solve_max_nodes,
+                                          out={"solution": out["solution"][s:s + m], "result": out["solve_result"][s:s + m], "nodes": out["solve_nodes"][s:s + m]})
                 ev = torch.cuda.Event(blocking=True)      # the waiting thread sleeps instead of spinning: the box's CPU quota is for the search
                 ev.record(self.s_cls)
                 free_ev[slot] = ev
@@ -328,7 +344,7 @@ def _corners_behind_filters(ctx, frames, binary_dev=None, min_area_ratio=0.1):
     return host.find_grid_corners(b[0].cpu().numpy(), min_area_ratio)
 
 
-def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1", resolve=False, propagate=False, component_filter=False, grid="v1"):
+def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1", resolve=False, propagate=False, component_filter=False, grid="v1", solve=False):
     """One BGR image (numpy uint8 [H,W,3], or a CUDA uint8 tensor of that shape) -> dict(grid 9x9 list, digits, confidences, corners) or None when no
     grid is found -- the call order of pipeline/run.py:261-312, preprocess_cell (:73-95) included by default.
     top_k > 1 adds run_v2's per-cell `alternatives` (pipeline/run_v2.py:165-178): 81 lists of (digit, prob), best excluded.
@@ -348,6 +364,10 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     propagate=True: run_v2's constraint propagation (pipeline/run_v2.py:373-391) on the device, of `resolved_grid` when resolve=True and of
     `grid` otherwise, with the cells' confidences: `propagation` (is_valid, iterations, contradiction_cell as (row, col) or None,
     cells_resolved as (row, col, digit) in the reference's order) and `propagated_grid` (what run_v2 hands to the solver).
+    solve=True: run_v2's solver stage (pipeline/run_v2.py:393-407) on the device (Context.solve_sudoku), of `propagated_grid` when
+    propagate=True (and only if the propagation was valid, as in run_v2), else of `resolved_grid`, else of `grid`: `solve_result` (1 solved,
+    0 no solution, -1 invalid, 3 not attempted), `solution` (9x9; the input grid unless solved) and `solve_nodes`.  A frame that spends the
+    device's node budget is finished by the unbounded host solver, so 2 is never reported.
     component_filter=True (opt-in; for photos, where the host corner search is what takes the time): the binary goes to the host behind
     the exact filters K4 and K11 (_corners_behind_filters), as a bit image where W % 32 == 0.  Same result, keys and values.
     grid="v2": the corners come from run_v2's detection (pipeline/run_v2.py:287), cv.grid_v2.detect_grid(binary, gray), which falls back
@@ -405,12 +425,25 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
         res["alternatives"] = [[(int(idx[i, j]), float(prob[i, j])) for j in range(1, top_k)] for i in range(81)]
     if propagate:
         cells, conf = resolved if resolve else (out["digits"], out["conf"])
-        state = {k: v[0].cpu().numpy() for k, v in ctx.propagate_constraints(cells, conf).items()}
+        prop_dev = ctx.propagate_constraints(cells, conf)
+        state = {k: v[0].cpu().numpy() for k, v in prop_dev.items()}
         bad, g = int(state["contradiction_cell"]), state["grid"]
         res["propagation"] = {"is_valid": bool(state["is_valid"]), "iterations": int(state["iterations"]),
                               "contradiction_cell": None if bad == 255 else (bad // 9, bad % 9),
                               "cells_resolved": [(int(x) // 9, int(x) % 9, int(v)) for x, v in state["resolved"][:int(state["n_resolved"])]]}
         res["propagated_grid"] = [[int(g[r * 9 + c]) for c in range(9)] for r in range(9)]
+    if solve:
+        if propagate:
+            given, active = prop_dev["grid"], prop_dev["is_valid"]
+        else:
+            given, active = (resolved[0] if resolve else out["digits"]), None
+        solved = ctx.solve_sudoku(given, active)
+        code, sol, nodes = (solved[k][0].cpu().numpy() for k in ("result", "solution", "nodes"))
+        if int(code) == Context.SOLVE_BUDGET:                 # the device's budget is spent: the host finishes the frame, without one
+            codes, sols, counts = host.solve_sudoku_batch(given.cpu().numpy(), threads=1)
+            code, sol, nodes = codes[0], sols[0].reshape(81), counts[0]
+        res["solve_result"], res["solve_nodes"] = int(code), int(nodes)
+        res["solution"] = [[int(sol[r * 9 + c]) for c in range(9)] for r in range(9)]
     if quality:
         from .cv import grid_quality
         if binary_dev is None:                                # component_filter=True never made the byte image

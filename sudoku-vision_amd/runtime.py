@@ -872,6 +872,35 @@ class Context:
                     "sv_propagate_constraints")
         return out
 
+    # name, per-frame shape, dtype: the order of sv_solve_sudoku_batch's output arguments
+    _SOLVE_OUT = (("solution", (81,), torch.uint8), ("result", (), torch.int8), ("nodes", (), torch.int32))
+    SOLVE_BUDGET, SOLVE_SKIPPED, SOLVE_MAX_NODES = 2, 3, 65536        # include/sudoku_vision_hip.h
+
+    def solve_sudoku(self, digits, active=None, max_nodes=4096, out=None):
+        """run_v2's run_solver (pipeline/run_v2.py:393-407, solver/src/sudoku.c) for n grids in one launch (sv_solve_sudoku_batch, csrc/k14_solve.hip):
+        digits u8 [n,81] (0 = empty), active u8 or bool [n] or None (all; a frame with 0 is not solved) -> dict of device tensors:
+        solution u8 [n,81] (= digits unless result is 1), result int8 [n] (1 solved, 0 no solution, -1 invalid input, SOLVE_BUDGET: max_nodes
+        search nodes were entered and the frame is undecided -- host.solve_sudoku_batch finishes such frames --, SOLVE_SKIPPED: not active),
+        nodes int32 [n] (search nodes entered; the root is 1; 0 for results -1 and SOLVE_SKIPPED).  Results, solutions and node counts equal
+        host.solve_sudoku_batch's at the same max_nodes, 1..65536.  out: a dict of some of those names -> contiguous tensors to write into;
+        only they are returned (None: all of them, newly allocated)."""
+        digits = _dev_tensor(digits, "digits", torch.uint8, self.device, shape=(None, 81)).contiguous()
+        n = digits.shape[0]
+        if active is not None:
+            active = _dev_tensor(active, "active", (torch.uint8, torch.bool), self.device, shape=(n,)).contiguous()
+        shapes = {name: ((n,) + shape, dtype) for name, shape, dtype in self._SOLVE_OUT}
+        if out is None:
+            out = {name: torch.empty(shape, dtype=dtype, device=self.device) for name, (shape, dtype) in shapes.items()}
+        else:
+            unknown = set(out) - set(shapes)
+            if unknown:
+                raise KeyError(f"not outputs of solve_sudoku: {sorted(unknown)}")
+            for name, t in out.items():
+                self._out(t, *shapes[name], name)
+        self._check(self._lib.sv_solve_sudoku_batch(self._h, _ptr(digits), _opt_ptr(active), n, int(max_nodes),
+                                                    *[_opt_ptr(out.get(name)) for name, _, _ in self._SOLVE_OUT], _stream_ptr()), "sv_solve_sudoku_batch")
+        return out
+
     # ---- run_v2's preprocessing (cv/preprocess_v2.py, csrc/k7_preprocess_v2.hip) -------------------
     # Every method takes gray u8 [n,H,W] on device (rows may be padded, frames may have gaps) and returns new dense tensors.
     MORPH_DILATE, MORPH_ERODE, MORPH_CLOSE, MORPH_OPEN = 0, 1, 2, 3
