@@ -740,6 +740,28 @@ int sv_warp_affine_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n, int H, int
                       const double *M /*dev, n*6*/, int dst_h, int dst_w, int border_value, uint8_t *dst /*dev, n*dst_h*dst_w*/,
                       void *stream);
 
+/* ---- K15: the motion gate of a camera feed, cv/stabilizer.py (MotionDetector) ----------------------------------------- */
+
+/* MotionDetector.update, cv/stabilizer.py:264-291, called for n consecutive frames of one feed, in one launch:
+ *   small[i]  = cv2.resize(gray(frames[i]), (dw, dh)) (:273-277; the detector's size is dw, dh = 160, 120); gray = cv2.cvtColor(BGR2GRAY)
+ *               for channels 3, the frame itself for channels 1
+ *   counts[i] = the pixels with |small[i] - small[i-1]| > threshold (:284-285), small[-1] = prev_small; counts[0] = 0 when
+ *               prev_small is NULL (the detector's first frame, :279-281)
+ * The caller compares counts[i] / (dh*dw) with min_area_ratio (:287-291) and keeps small[n-1] as the next call's prev_small.
+ * The comparison is the reference's float comparison, exact: a difference d is an integer, so d > threshold <=> d > floor(threshold);
+ * a NaN threshold counts nothing.
+ * Resize: cv2's 8-bit INTER_LINEAR as sv_resize_linear_u8 states it (11-bit coefficients from the float32 source coordinate, edge taps
+ * clamped with weights 2048 / 0, (((b0*(t0>>4))>>16) + ((b1*(t1>>4))>>16) + 2) >> 2), upscaling included; a frame that already is
+ * dh x dw is copied; and a frame of exactly 2*dh x 2*dw takes the 2x2 mean (s00 + s01 + s10 + s11 + 2) >> 2, because cv2.resize
+ * replaces INTER_LINEAR by INTER_AREA at an exact factor of two on both axes (OpenCV's resize.cpp; cv2 is not available to pin it
+ * against).  sv_resize_linear_u8 does not have that last case.  Only the taps are read and converted to gray: no full-size gray
+ * image exists.
+ * Any H, W, dh, dw >= 1 (dh*dw < 2^31 - 256), any pitch >= W*channels, frame_stride bytes between frames, any alignment.  prev_small
+ * must not overlap small.  No allocation, no host synchronisation: a memset of counts and one kernel launch on `stream`. */
+int sv_motion_update_u8(sv_ctx *ctx, const uint8_t *frames /*dev*/, int n, int H, int W, int channels /*1 or 3 (BGR)*/,
+                        ptrdiff_t pitch, ptrdiff_t frame_stride, const uint8_t *prev_small /*dev, dh*dw, or NULL*/, float threshold,
+                        uint8_t *small /*dev, n*dh*dw*/, int32_t *counts /*dev, n*/, int dh, int dw, void *stream);
+
 /* ---- the whole device-resident path ----------------------------------------------------------- */
 
 /* frames + homographies -> 81 digits per frame: K2 then K3 on `stream`, no host sync.

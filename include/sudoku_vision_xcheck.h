@@ -1,6 +1,6 @@
 /*
  * sudoku_vision_xcheck.h -- the extra entry points of libsudokuvision_xcheck.so, a TEST-ONLY superset build of libsudokuvision_hip.so
- * (csrc/Makefile: the product's own objects + csrc/x_cnn_round1.hip and csrc/k1_threshold_mm.hip).  It carries independent second implementations of
+ * (csrc/Makefile: the product's own objects + csrc/x_cnn_round1.hip, csrc/k1_threshold_mm.hip and csrc/x_motion.cpp).  It carries independent second implementations of
  * two stages so that tests/ and tests/fuzz_gpu.py can compare the product's kernels with them on the GPU; the product library does not
  * contain them and no Python module of the sudoku-vision_amd package loads this one.  Everything in sudoku_vision_hip.h is exported here as well.
  */
@@ -34,6 +34,13 @@ int sv_preprocess_mm_u8(sv_ctx *ctx, const uint8_t *bgr /*dev*/, int n, int H, i
  * threshold to decide and which were therefore decided with cv2's exact float sequence.  The first call on a context switches the
  * counter on and returns 0.  capacity: reserved (0).  Synchronises the device. */
 int sv_preprocess_stats(sv_ctx *ctx, unsigned *ambiguous, unsigned long *capacity);
+
+/* The launch shape of sv_motion_update_u8 for batches of more than one frame (csrc/k15_motion.hip): the product's single launch, in
+ * which a thread computes its pixel of the previous frame again, or the two-launch shape that writes every small image first and
+ * counts in a second pass.  Same outputs, bit for bit; tools/time_motion.py measures one against the other. */
+#define SVX_MOTION_ONE_LAUNCH 0
+#define SVX_MOTION_TWO_PASS 1
+int svx_ctx_set_motion_shape(sv_ctx *ctx, int shape);
 
 #ifdef __cplusplus
 }

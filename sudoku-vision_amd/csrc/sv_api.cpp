@@ -697,6 +697,20 @@ extern "C" int sv_solve_sudoku_batch(sv_ctx *ctx, const uint8_t *grid, const uin
     return svk_solve_sudoku_batch(grid, active, n, max_nodes, solution, result, nodes, S(stream));
 }
 
+extern "C" int sv_motion_update_u8(sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, int channels, ptrdiff_t pitch, ptrdiff_t frame_stride,
+                                   const uint8_t *prev_small, float threshold, uint8_t *small, int32_t *counts, int dh, int dw, void *stream)
+{
+    REQUIRE(ctx && frames && small && counts, "NULL argument");
+    REQUIRE(channels == 1 || channels == 3, "channels must be 1 or 3");
+    REQUIRE(n > 0 && n < 65536 && H > 0 && W > 0 && pitch >= (ptrdiff_t)W * channels, "bad shape");
+    REQUIRE(n == 1 || frame_stride >= pitch * (H - 1) + (ptrdiff_t)W * channels, "frames overlap (frame_stride too small)");
+    REQUIRE(dh > 0 && dw > 0 && (long)dh * dw <= 0x7fffff00L, "bad target size");
+    REQUIRE(((uintptr_t)counts & 3) == 0, "misaligned counts");
+    const long small_bytes = (long)n * dh * dw;
+    REQUIRE(!prev_small || prev_small + (long)dh * dw <= small || small + small_bytes <= prev_small, "prev_small overlaps small");
+    return svk_motion_update(ctx, frames, n, H, W, channels, pitch, frame_stride, prev_small, threshold, small, counts, dh, dw, S(stream));
+}
+
 extern "C" int sv_frame_quality_stats_u8(sv_ctx *ctx, const uint8_t *img, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int channels,
                                          int64_t *lap_sum, int64_t *lap_sqsum, uint32_t *hist, void *stream)
 {

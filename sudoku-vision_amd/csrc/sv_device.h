@@ -115,15 +115,20 @@ __device__ __forceinline__ void sv_warp_sample(const u8 *img, int H, int W, ptrd
 }
 
 // cv2.resize INTER_LINEAR 8-bit axis table entry (cv/extract.py:52): source offset + two 11-bit weights.
-__device__ __forceinline__ void sv_resize_axis(int s_len, int d_len, int d, int &ofs, int &w0, int &w1)
+// scale = 1 / (d_len / s_len), two double divisions (sv_resize_axis below, or the same two on the host: IEEE either way).
+__device__ __forceinline__ void sv_resize_axis_scaled(double scale, int d, int &ofs, int &w0, int &w1)
 {
-    const double scale = __ddiv_rn(1.0, __ddiv_rn((double)d_len, (double)s_len));
     float f = (float)__dadd_rn(__dmul_rn(__dadd_rn((double)d, 0.5), scale), -0.5);
     const int s = (int)floorf(f);
     f = __fsub_rn(f, (float)s);
     ofs = s;
     w0 = __float2int_rn(__fmul_rn(__fsub_rn(1.f, f), 2048.f));
     w1 = __float2int_rn(__fmul_rn(f, 2048.f));
+}
+
+__device__ __forceinline__ void sv_resize_axis(int s_len, int d_len, int d, int &ofs, int &w0, int &w1)
+{
+    sv_resize_axis_scaled(__ddiv_rn(1.0, __ddiv_rn((double)d_len, (double)s_len)), d, ofs, w0, w1);
 }
 
 // ---- the fc2 -> argmax -> softmax[argmax] epilogue of every fc head (pipeline/run.py:139-143), in f32 on the VALU ----

@@ -103,6 +103,7 @@ struct sv_ctx {
     int precision = 0;          // SV_PREC_F32 / SV_PREC_BF16 (sv_ctx_set_precision)
     int cnn_kernels = 0;        // SV_CNN_AUTO / _F16PAIR / _F32MFMA (sv_ctx_set_cnn_kernels)
     bool x_fc_frame = false;    // x_cnn_round1.hip (svx_ctx_set_fc_frame_kernel): k_fc_head_frame for large batches; never set in the product
+    int x_motion_shape = 0;     // k15_motion.hip: 1 = the two-launch shape (x_motion.cpp, svx_ctx_set_motion_shape); never set in the product
 #ifdef SV_DEV
     int dev_ablate = 0;         // k3_cnn_h2.hip: the ablation / stamp bits of k_conv_features_h2 (sv_dev_set_h2_ablate, svk_cnn_forward_h2)
 #endif
@@ -263,6 +264,10 @@ int svk_warp_affine(sv_ctx *ctx, const u8 *src, int n, int H, int W, ptrdiff_t p
 
 // k14_solve.hip
 int svk_solve_sudoku_batch(const u8 *grid, const u8 *active, int n, int max_nodes, u8 *solution, int8_t *result, int *nodes, hipStream_t s);
+
+// k15_motion.hip
+int svk_motion_update(sv_ctx *ctx, const u8 *frames, int n, int H, int W, int C, ptrdiff_t pitch, ptrdiff_t frame_stride, const u8 *prev_small,
+                      float threshold, u8 *small, int32_t *counts, int dh, int dw, hipStream_t s);
 
 // host helpers
 void sv_gaussian_taps_f32(int n, float *out);

@@ -457,6 +457,64 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     return res
 
 
+def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, preprocess="v1", grid="v1", stabilizer=None, motion_detector=None):
+    """A camera feed: the loop of cv/stabilizer.py:308-335 followed by this library's recognition.  frames: an iterable of BGR frames
+    (numpy uint8 [H,W,3] or CUDA uint8 tensors).  A generator; per frame it yields a dict:
+        motion        the motion gate's verdict (cv.stabilizer.MotionDetector.update); True: the frame is skipped, every other entry
+                      but `motion` is None / False, and the stabiliser does not see it
+        detected      a grid was found in this frame
+        stabilized    the StabilizedResult of cv.stabilizer.GridStabilizer.update(corners or None)
+        corners_used  the stabilised corners K2 warped with, float32 [4,2]; None when there are none or they define no homography
+        digits, confidence   the 81 digits and their confidences read at corners_used, else None
+    preprocess, grid: "v1" | "v2" as in recognize_image (grid="v1": K1's binary and the host contour search; "v2":
+    cv.grid_v2.detect_grid).  stabilizer, motion_detector: the GridStabilizer / MotionDetector to use (default: new ones with the
+    reference's defaults).  With the default use_kalman=True the stabilised corners of the first min_detections - 1 detections are
+    exact zeros (cv/stabilizer.py), which define no homography: those frames yield digits=None.  FramePipeline is the tool for independent
+    frames; this is for one feed, frame by frame."""
+    from .runtime import default_context
+    from .cv import stabilizer as stab
+    if grid not in ("v1", "v2"):
+        raise ValueError(f"grid must be 'v1' or 'v2', got {grid!r}")
+    if preprocess not in ("v1", "v2"):
+        raise ValueError(f"preprocess must be 'v1' or 'v2', got {preprocess!r}")
+    ctx = ctx or default_context()
+    if model_state_dict is not None:
+        ctx.load_state_dict(model_state_dict)
+    stabilizer = stabilizer or stab.GridStabilizer()
+    motion_detector = motion_detector or stab.MotionDetector()
+    if motion_detector.ctx is None:
+        motion_detector.ctx = ctx
+    for image in frames:
+        if isinstance(image, torch.Tensor):
+            frame = image.contiguous()[None]
+        else:
+            frame = torch.from_numpy(np.ascontiguousarray(image)).to(ctx.device)[None]
+        res = {"motion": motion_detector.update(frame[0]), "detected": False, "stabilized": None, "corners_used": None, "digits": None,
+               "confidence": None}
+        if res["motion"]:
+            yield res
+            continue
+        if preprocess == "v2":
+            from .cv import preprocess_v2
+            binary_dev = preprocess_v2.preprocess_multi_strategy(frame[0]).binary
+        else:
+            binary_dev = ctx.preprocess(frame)[0]
+        if grid == "v2":
+            from .cv import grid_v2
+            corners = grid_v2.detect_grid(binary_dev, ctx.gray(frame)[0]).corners
+        else:
+            corners = host.find_grid_corners(binary_dev.cpu().numpy())
+        res["detected"] = corners is not None
+        res["stabilized"] = s = stabilizer.update(None if corners is None else np.asarray(corners, np.float32))
+        if s.corners is not None:
+            used = np.asarray(s.corners, np.float32)
+            minv, ok = Context.corners_to_minv_batch(used[None])
+            if ok[0]:
+                out = ctx.frames_to_digits(frame, ctx.minv_to_device(minv), glue=glue)
+                res["corners_used"], res["digits"], res["confidence"] = used, out["digits"][0].cpu().numpy(), out["conf"][0].cpu().numpy()
+        yield res
+
+
 def _validate_and_resolve(ctx, idx, prob):
     """pipeline/run_v2.py:347-371 on one frame's top-k (device tensors [1,81,k]): validate; if invalid, search; take the search's cells
     if it succeeded or left fewer conflicts -- one launch, with the acceptance rule applied in the kernel."""

@@ -983,6 +983,39 @@ class Context:
         out = tuple(_back(t, was_tensor) for t in out)
         return out[0] if len(out) == 1 else out
 
+    # ---- motion gate (cv/stabilizer.py, csrc/k15_motion.hip) -----------------------------------------
+    def motion_update(self, frames, prev_small=None, threshold=30.0, dsize=(160, 120), out=None):
+        """MotionDetector.update for n consecutive frames of one feed (sv_motion_update_u8).  frames u8 [n,H,W,3] (BGR) or [n,H,W]
+        (gray) on device, rows may be padded and frames may have gaps; prev_small u8 [dh,dw] on device: the small image of the frame
+        before frames[0], None at the start of a feed; dsize = (dw, dh) as cv2.resize takes it.
+        -> (small u8 [n,dh,dw], counts int32 [n]) on device: small[i] = cv2.resize(gray(frames[i]), dsize), counts[i] = pixels with
+        |small[i] - small[i-1]| > threshold (counts[0] = 0 without prev_small).  threshold is compared as the reference compares it, a
+        Python float against integer differences: d > threshold <=> d > floor(threshold).  out: optional (small, counts) to write
+        into; small may not be prev_small.  A wrong dtype, device, rank or prev_small shape is a ValueError."""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.device != self.device:
+            raise ValueError(f"frames must be a uint8 tensor on {self.device}")
+        if frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] != 3) or 0 in frames.shape:
+            raise ValueError(f"frames must have shape [n,H,W,3] or [n,H,W], got {list(frames.shape)}")
+        ch = 3 if frames.dim() == 4 else 1
+        frames, pitch, fstride = _batch_layout(frames, self.device, "frames", ch)
+        n, H, W = frames.shape[0], frames.shape[1], frames.shape[2]
+        dw, dh = int(dsize[0]), int(dsize[1])
+        if dw < 1 or dh < 1:
+            raise ValueError(f"dsize must be positive, got {dsize}")
+        if prev_small is not None:
+            if not isinstance(prev_small, torch.Tensor) or prev_small.dtype != torch.uint8 or prev_small.device != self.device:
+                raise ValueError(f"prev_small must be a uint8 tensor on {self.device}")
+            if tuple(prev_small.shape) != (dh, dw):
+                raise ValueError(f"prev_small must have shape [{dh},{dw}], got {list(prev_small.shape)}")
+            prev_small = prev_small.contiguous()
+        t = float(threshold)
+        t = 255.0 if not t < 255.0 else (-1.0 if t < 0.0 else float(int(t)))       # floor, exact in the library's float32
+        out = out or (None, None)
+        small, counts = self._out(out[0], (n, dh, dw), torch.uint8, "small"), self._out(out[1], (n,), torch.int32, "counts")
+        self._check(self._lib.sv_motion_update_u8(self._h, _ptr(frames), n, H, W, ch, pitch, fstride, _opt_ptr(prev_small), t, _ptr(small),
+                                                  _ptr(counts), dh, dw, _stream_ptr()), "sv_motion_update_u8")
+        return small, counts
+
     def warp_affine(self, img, M, dsize, border_value=0):
         """cv2.warpAffine(img, M, dsize=(w, h), INTER_LINEAR, BORDER_CONSTANT, border_value) on gray u8 (sv_warp_affine_u8).  img [H,W] with M
         [2,3], or [n,H,W] with M [n,2,3]: the forward matrices, float64 (numpy or a tensor).  A numpy image or a CUDA tensor; a tensor
