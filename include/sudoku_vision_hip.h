@@ -762,6 +762,44 @@ int sv_motion_update_u8(sv_ctx *ctx, const uint8_t *frames /*dev*/, int n, int H
                         ptrdiff_t pitch, ptrdiff_t frame_stride, const uint8_t *prev_small /*dev, dh*dw, or NULL*/, float threshold,
                         uint8_t *small /*dev, n*dh*dw*/, int32_t *counts /*dev, n*/, int dh, int dw, void *stream);
 
+/* ---- K16: the solution drawn into the camera frame ------------------------------------------------------------------------ */
+
+#define SV_OVERLAY_GRID 450    /* the solution layer: 9 x 9 cells of SV_OVERLAY_CELL texels (pipeline/overlay.py:27) */
+#define SV_OVERLAY_CELL 50
+#define SV_OVERLAY_MARGIN 3    /* rows and columns 0..2 and 47..49 of every glyph are zero */
+
+/* The 8-bit coverage atlas of the digits 1..9, [9][50][50] (glyph d-1 draws digit d, one texel per pixel of the 450 x 450 layer),
+ * copied into the context together with the default palette.  Rows and columns 0..2 and 47..49 of every glyph must be zero:
+ * SV_ERR_BAD_ARG otherwise, checked before anything is uploaded.  Synchronous, like the weight loaders. */
+int sv_set_overlay_glyphs(sv_ctx *ctx, const uint8_t *atlas /*host, 9*50*50*/);
+
+/* The forward homography of sv_corners_to_minv_batch: M = cv2.getPerspectiveTransform(ordered, inset corners -> (0,0)..(S-1,S-1)),
+ * frame -> grid, the matrix that function inverts.  Same arguments and the same ok rule (ok[f] = 0 exactly where it is 0 there);
+ * a degenerate quad gives ok[f] = 0 and m[f] = identity. */
+int sv_corners_to_m_batch(const float *corners /*host*/, int n, int out_size, float inset_ratio,
+                          double *m /*host*/, uint8_t *ok /*host, n*/);
+
+/* Draws 81 digits per frame into n BGR frames, in one launch.  The result is defined by three steps.
+ *   Layers (450 x 450, never materialised): A[i][j] = atlas[d-1][i%50][j%50] with d = digits[f][(i/50)*9 + j/50], 0 where d == 0,
+ *     d > 9 or the cell's class >= k; B[i][j] = A[i-2][j-2] >> 1 for i, j >= 2, else 0 (the drop shadow); both 0 outside [0,450).
+ *   Warp: a = cv2.warpPerspective(A, M, (W,H), INTER_LINEAR | WARP_INVERSE_MAP, BORDER_CONSTANT 0) and s likewise from B, in the
+ *     arithmetic of sv_warp_perspective_u8 with the W x H frame as the destination: blocks of bh = min(16,H) rows by
+ *     bw = min(1024/bh, W) columns counted from the frame's origin, the homography m[f] (frame -> grid, sv_corners_to_m_batch)
+ *     evaluated in double at the block origin and stepped by M0*x1, W = 32/W (0 where W is 0), clamped to int32, rounded half to
+ *     even, >> 5 saturated to int16, five fraction bits, four taps with 15-bit weights, (sum + 2^14) >> 15.
+ *   Blend, per channel c, in integers: t = shadow ? (f*(255-s) + 127)/255 : f;  out = (t*(255-a) + palette[cls][c]*a + 127)/255,
+ *     cls = the class of the cell that holds the top-left tap, (clamp(Y>>5,0,449)/50, clamp(X>>5,0,449)/50).
+ * classes NULL: class 0 everywhere.  palette NULL: the default, k = 3: BGR (255,100,0) solved, (0,0,0) original, (0,0,255) low
+ * confidence (pipeline/overlay.py:63-71).  active NULL: every frame; a frame with active[f] == 0 is copied unchanged.
+ * dst == frames (then dst_pitch, dst_stride must equal pitch, img_stride) draws in place and touches only the 64 x 16 blocks that
+ * the grid's square can reach; otherwise dst must not overlap frames: it receives a device copy of the frames and is then drawn
+ * into.  Any H, W >= 1 (H <= 16*65535), pitch >= 3*W, any alignment; n < 65536, 1 <= k <= 256: SV_ERR_BAD_ARG otherwise;
+ * SV_ERR_NO_WEIGHTS before sv_set_overlay_glyphs.  No allocation, no host synchronisation. */
+int sv_render_overlay_u8(sv_ctx *ctx, const uint8_t *frames /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
+                         const double *m /*dev, n*9*/, const uint8_t *digits /*dev, n*81*/, const uint8_t *classes /*dev, n*81, or NULL*/,
+                         const uint8_t *palette /*dev, k*3 BGR, or NULL*/, int k, const uint8_t *active /*dev, n, or NULL*/,
+                         int shadow, uint8_t *dst /*dev; may equal frames*/, ptrdiff_t dst_pitch, ptrdiff_t dst_stride, void *stream);
+
 /* ---- the whole device-resident path ----------------------------------------------------------- */
 
 /* frames + homographies -> 81 digits per frame: K2 then K3 on `stream`, no host sync.

@@ -108,6 +108,9 @@ SIGNATURES = {
     "sv_find_grid_corners_v2_batch_u8": [_p, _i, _i, _i, _pd, _pd, _d, _d, _p, _p, _i],
     "sv_hough_lines_p_u8": [_p, _i, _i, _pd, _d, _d, _i, _i, _i, _p, _i, _p],
     "sv_motion_update_u8": [_p, _p, _i, _i, _i, _i, _pd, _pd, _p, _f, _p, _p, _i, _i, _p],
+    "sv_corners_to_m_batch": [_p, _i, _i, _f, _p, _p],
+    "sv_set_overlay_glyphs": [_p, _p],
+    "sv_render_overlay_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p, _p, _p, _i, _p, _i, _p, _pd, _pd, _p],
 }
 _RESTYPES = {"sv_last_error": C.c_char_p, "sv_sparse_bits_record_bytes": C.c_long}
 # what libsudokuvision_xcheck.so exports on top of SIGNATURES (include/sudoku_vision_xcheck.h)

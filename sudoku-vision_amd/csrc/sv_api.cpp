@@ -321,7 +321,8 @@ bool invert3(const double *S, double *D)
 
 }  // namespace
 
-static bool corners_to_minv_one(const float *corners, int out_size, float inset_ratio, double *minv)
+// M = getPerspectiveTransform(ordered, inset corners -> the square), frame -> grid
+static bool corners_to_m_one(const float *corners, int out_size, float inset_ratio, double *M)
 {
     float o[8], in[8];
     order_points(corners, o);
@@ -336,8 +337,13 @@ static bool corners_to_minv_one(const float *corners, int out_size, float inset_
     }
     const float S = (float)(out_size - 1);
     const float dst[8] = {0, 0, S, 0, S, S, 0, S};
+    return perspective_transform(in, dst, M);
+}
+
+static bool corners_to_minv_one(const float *corners, int out_size, float inset_ratio, double *minv)
+{
     double M[9];
-    return perspective_transform(in, dst, M) && invert3(M, minv);
+    return corners_to_m_one(corners, out_size, inset_ratio, M) && invert3(M, minv);
 }
 
 extern "C" int sv_corners_to_minv(const float *corners, int n, int out_size, float inset_ratio, double *minv)
@@ -356,6 +362,18 @@ extern "C" int sv_corners_to_minv_batch(const float *corners, int n, int out_siz
     for (int f = 0; f < n; f++) {
         ok[f] = corners_to_minv_one(corners + 8 * f, out_size, inset_ratio, minv + 9 * f) ? 1 : 0;
         if (!ok[f]) memcpy(minv + 9 * f, ident, sizeof ident);
+    }
+    return SV_OK;
+}
+
+extern "C" int sv_corners_to_m_batch(const float *corners, int n, int out_size, float inset_ratio, double *m, uint8_t *ok)
+{
+    if (!corners || !m || !ok || n <= 0 || out_size < 2) return sv_fail(SV_ERR_BAD_ARG, "sv_corners_to_m_batch: bad argument");
+    static const double ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int f = 0; f < n; f++) {
+        double minv[9];                      // the ok rule of sv_corners_to_minv_batch: M exists and can be inverted
+        ok[f] = corners_to_m_one(corners + 8 * f, out_size, inset_ratio, m + 9 * f) && invert3(m + 9 * f, minv) ? 1 : 0;
+        if (!ok[f]) memcpy(m + 9 * f, ident, sizeof ident);
     }
     return SV_OK;
 }
@@ -709,6 +727,51 @@ extern "C" int sv_motion_update_u8(sv_ctx *ctx, const uint8_t *frames, int n, in
     const long small_bytes = (long)n * dh * dw;
     REQUIRE(!prev_small || prev_small + (long)dh * dw <= small || small + small_bytes <= prev_small, "prev_small overlaps small");
     return svk_motion_update(ctx, frames, n, H, W, channels, pitch, frame_stride, prev_small, threshold, small, counts, dh, dw, S(stream));
+}
+
+extern "C" int sv_set_overlay_glyphs(sv_ctx *ctx, const uint8_t *atlas)
+{
+    REQUIRE(atlas, "NULL argument");
+    // the zero margin first: nothing is uploaded from an atlas that lacks it
+    for (int g = 0; g < 9; g++)
+        for (int i = 0; i < SV_OVERLAY_CELL; i++)
+            for (int j = 0; j < SV_OVERLAY_CELL; j++) {
+                const bool margin = i < SV_OVERLAY_MARGIN || i >= SV_OVERLAY_CELL - SV_OVERLAY_MARGIN || j < SV_OVERLAY_MARGIN || j >= SV_OVERLAY_CELL - SV_OVERLAY_MARGIN;
+                if (margin && atlas[(g * SV_OVERLAY_CELL + i) * SV_OVERLAY_CELL + j])
+                    return sv_fail(SV_ERR_BAD_ARG, "%s: glyph %d has a non-zero texel at row %d, column %d of its margin (rows and columns 0..2 and 47..49 must be zero)",
+                                   __func__, g, i, j);
+            }
+    REQUIRE(ctx, "NULL argument");
+    return svk_set_overlay_glyphs(ctx, atlas);
+}
+
+extern "C" int sv_render_overlay_u8(sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const double *m,
+                                    const uint8_t *digits, const uint8_t *classes, const uint8_t *palette, int k, const uint8_t *active, int shadow,
+                                    uint8_t *dst, ptrdiff_t dst_pitch, ptrdiff_t dst_stride, void *stream)
+{
+    REQUIRE(ctx && frames && m && digits && dst, "NULL argument");
+    REQUIRE_FRAMES();
+    REQUIRE(H <= 16 * 65535, "bad shape");
+    REQUIRE(dst_pitch >= 3 * (ptrdiff_t)W, "bad shape");
+    const ptrdiff_t row = 3 * (ptrdiff_t)W;
+    REQUIRE(n == 1 || (img_stride >= pitch * (H - 1) + row && dst_stride >= dst_pitch * (H - 1) + row), "frames overlap (stride too small)");
+    REQUIRE(!palette || (k >= 1 && k <= 256), "need 1 <= k <= 256");
+    REQUIRE(((uintptr_t)m & 7) == 0, "misaligned m");
+    if (!ctx->overlay_set) return sv_fail(SV_ERR_NO_WEIGHTS, "%s: no glyph atlas (sv_set_overlay_glyphs)", __func__);
+    if (dst != frames) {
+        const uint8_t *src_end = frames + img_stride * (n - 1) + pitch * (H - 1) + row, *dst_end = dst + dst_stride * (n - 1) + dst_pitch * (H - 1) + row;
+        REQUIRE(dst_end <= frames || src_end <= dst, "dst overlaps frames (pass dst == frames to draw in place)");
+        // the rest of the frame is a copy: all of it is copied, then the blocks the grid reaches are drawn in place
+        if (n == 1 || (img_stride == pitch * H && dst_stride == dst_pitch * H))
+            SV_HIP(hipMemcpy2DAsync(dst, (size_t)dst_pitch, frames, (size_t)pitch, (size_t)row, (size_t)n * H, hipMemcpyDeviceToDevice, S(stream)));
+        else
+            for (int f = 0; f < n; f++)
+                SV_HIP(hipMemcpy2DAsync(dst + f * dst_stride, (size_t)dst_pitch, frames + f * img_stride, (size_t)pitch, (size_t)row, (size_t)H,
+                                        hipMemcpyDeviceToDevice, S(stream)));
+    } else {
+        REQUIRE(dst_pitch == pitch && (n == 1 || dst_stride == img_stride), "in place: dst_pitch and dst_stride must equal pitch and img_stride");
+    }
+    return svk_render_overlay(ctx, dst, n, H, W, dst_pitch, dst_stride, m, digits, classes, palette, palette ? k : 3, active, shadow != 0, S(stream));
 }
 
 extern "C" int sv_frame_quality_stats_u8(sv_ctx *ctx, const uint8_t *img, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int channels,

@@ -95,10 +95,12 @@ struct sv_ctx {
     sv_scratch grid2;           // k13_grid_v2.hip: the Harris response, tile and frame maxima, candidate counts and sort keys
     sv_scratch k1_list;         // k1_threshold_mm.hip: optional diagnostic counter (pixels decided by the exact evaluation), sv_preprocess_stats; 16 bytes
     sv_scratch range_flag;      // int [2]: the per-call kernel choice for f32 inputs (k3_cnn.hip k_input_range)
+    sv_scratch overlay;         // k16_overlay.hip: the glyph atlas u8 [9][50][50], then the default palette u8 [3][3]
+    bool overlay_set = false;   // sv_set_overlay_glyphs has filled `overlay`
     // sv_ctx_destroy frees through this and nothing else: a new buffer goes in here
     template <class F> void for_each_scratch(F f)
     {
-        for (sv_scratch *b : {&v3_act, &features, &cells, &cells2, &jpeg_planes, &pp2, &cc, &grid2, &k1_list, &range_flag}) f(*b);
+        for (sv_scratch *b : {&v3_act, &features, &cells, &cells2, &jpeg_planes, &pp2, &cc, &grid2, &k1_list, &range_flag, &overlay}) f(*b);
     }
     int precision = 0;          // SV_PREC_F32 / SV_PREC_BF16 (sv_ctx_set_precision)
     int cnn_kernels = 0;        // SV_CNN_AUTO / _F16PAIR / _F32MFMA (sv_ctx_set_cnn_kernels)
@@ -268,6 +270,11 @@ int svk_solve_sudoku_batch(const u8 *grid, const u8 *active, int n, int max_node
 // k15_motion.hip
 int svk_motion_update(sv_ctx *ctx, const u8 *frames, int n, int H, int W, int C, ptrdiff_t pitch, ptrdiff_t frame_stride, const u8 *prev_small,
                       float threshold, u8 *small, int32_t *counts, int dh, int dw, hipStream_t s);
+
+// k16_overlay.hip
+int svk_set_overlay_glyphs(sv_ctx *ctx, const u8 *atlas);
+int svk_render_overlay(sv_ctx *ctx, u8 *img, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const double *m, const u8 *digits, const u8 *classes,
+                       const u8 *palette, int k, const u8 *active, bool shadow, hipStream_t s);
 
 // host helpers
 void sv_gaussian_taps_f32(int n, float *out);

@@ -344,7 +344,7 @@ def _corners_behind_filters(ctx, frames, binary_dev=None, min_area_ratio=0.1):
     return host.find_grid_corners(b[0].cpu().numpy(), min_area_ratio)
 
 
-def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1", resolve=False, propagate=False, component_filter=False, grid="v1", solve=False):
+def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, top_k=0, quality=False, preprocess="v1", model="v1", resolve=False, propagate=False, component_filter=False, grid="v1", solve=False, overlay=False):
     """One BGR image (numpy uint8 [H,W,3], or a CUDA uint8 tensor of that shape) -> dict(grid 9x9 list, digits, confidences, corners) or None when no
     grid is found -- the call order of pipeline/run.py:261-312, preprocess_cell (:73-95) included by default.
     top_k > 1 adds run_v2's per-cell `alternatives` (pipeline/run_v2.py:165-178): 81 lists of (digit, prob), best excluded.
@@ -373,8 +373,13 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     grid="v2": the corners come from run_v2's detection (pipeline/run_v2.py:287), cv.grid_v2.detect_grid(binary, gray), which falls back
     to Hough lines, a de-rotated contour search and Harris corners + RANSAC where the contour search alone finds nothing; the result
     carries `detection_method`, `detection_confidence` and `rotation_angle`, and `corners` are the ordered float32 corners.
-    component_filter does not apply to it."""
+    component_filter does not apply to it.
+    overlay=True (needs solve=True, else ValueError): `overlay`, a uint8 tensor [H,W,3] on the device: the image with the cells the
+    solver filled in drawn at `corners` (Context.render_overlay with resolve/overlay.py's overlay_cells of the solver's input and
+    `solution`) when solve_result is 1, otherwise an unchanged copy of the image."""
     from .runtime import default_context
+    if overlay and not solve:
+        raise ValueError("overlay=True needs solve=True: there is nothing to draw without a solution")
     if grid not in ("v1", "v2"):
         raise ValueError(f"grid must be 'v1' or 'v2', got {grid!r}")
     if preprocess not in ("v1", "v2"):
@@ -444,6 +449,8 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
             code, sol, nodes = codes[0], sols[0].reshape(81), counts[0]
         res["solve_result"], res["solve_nodes"] = int(code), int(nodes)
         res["solution"] = [[int(sol[r * 9 + c]) for c in range(9)] for r in range(9)]
+        if overlay:
+            res["overlay"] = _draw_solution(ctx, frames, corners, given[0].cpu().numpy(), sol, int(code) == 1)[0]
     if quality:
         from .cv import grid_quality
         if binary_dev is None:                                # component_filter=True never made the byte image
@@ -457,7 +464,7 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     return res
 
 
-def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, preprocess="v1", grid="v1", stabilizer=None, motion_detector=None):
+def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, preprocess="v1", grid="v1", stabilizer=None, motion_detector=None, overlay=False, solve_max_nodes=4096):
     """A camera feed: the loop of cv/stabilizer.py:308-335 followed by this library's recognition.  frames: an iterable of BGR frames
     (numpy uint8 [H,W,3] or CUDA uint8 tensors).  A generator; per frame it yields a dict:
         motion        the motion gate's verdict (cv.stabilizer.MotionDetector.update); True: the frame is skipped, every other entry
@@ -466,6 +473,11 @@ def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_
         stabilized    the StabilizedResult of cv.stabilizer.GridStabilizer.update(corners or None)
         corners_used  the stabilised corners K2 warped with, float32 [4,2]; None when there are none or they define no homography
         digits, confidence   the 81 digits and their confidences read at corners_used, else None
+    overlay=True adds three entries: the recognised digits go to the solver (Context.solve_sudoku with solve_max_nodes; the host
+    finishes a frame that spends the budget, as in recognize_image), and
+        solution, solve_result   the 81 solved digits (the recognised ones unless solve_result is 1) and the solver's verdict, else None
+        frame_out     a uint8 tensor [H,W,3] on the device: the frame with the cells the solver filled in drawn at corners_used
+                      (Context.render_overlay) where solve_result is 1; the input frame itself for a skipped or unsolved frame
     preprocess, grid: "v1" | "v2" as in recognize_image (grid="v1": K1's binary and the host contour search; "v2":
     cv.grid_v2.detect_grid).  stabilizer, motion_detector: the GridStabilizer / MotionDetector to use (default: new ones with the
     reference's defaults).  With the default use_kalman=True the stabilised corners of the first min_detections - 1 detections are
@@ -491,6 +503,8 @@ def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_
             frame = torch.from_numpy(np.ascontiguousarray(image)).to(ctx.device)[None]
         res = {"motion": motion_detector.update(frame[0]), "detected": False, "stabilized": None, "corners_used": None, "digits": None,
                "confidence": None}
+        if overlay:
+            res.update(solution=None, solve_result=None, frame_out=frame[0])
         if res["motion"]:
             yield res
             continue
@@ -512,7 +526,26 @@ def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_
             if ok[0]:
                 out = ctx.frames_to_digits(frame, ctx.minv_to_device(minv), glue=glue)
                 res["corners_used"], res["digits"], res["confidence"] = used, out["digits"][0].cpu().numpy(), out["conf"][0].cpu().numpy()
+                if overlay:
+                    solved = ctx.solve_sudoku(out["digits"], max_nodes=solve_max_nodes)
+                    code, sol = int(solved["result"][0]), solved["solution"][0].cpu().numpy()
+                    if code == Context.SOLVE_BUDGET:
+                        codes, sols, _ = host.solve_sudoku_batch(res["digits"][None], threads=1)
+                        code, sol = int(codes[0]), sols[0].reshape(81)
+                    res["solution"], res["solve_result"] = sol, code
+                    if code == 1:
+                        res["frame_out"] = _draw_solution(ctx, frame, used, res["digits"], sol, True)[0]
         yield res
+
+
+def _draw_solution(ctx, frame, corners, given, solution, solved):
+    """frame u8 [1,H,W,3] on the device -> a new [1,H,W,3]: the cells of `solution` that `given` leaves empty drawn at `corners`
+    (the iOS rule, resolve/overlay.py overlay_cells) when `solved`, else an unchanged copy."""
+    m, ok = Context.corners_to_m_batch(np.asarray(corners, np.float32).reshape(1, 4, 2))
+    given, solution = np.asarray(given, np.uint8).reshape(81), np.asarray(solution, np.uint8).reshape(81)
+    digits = np.where(given != 0, 0, solution).astype(np.uint8)
+    active = torch.tensor([bool(solved) and bool(ok[0])], dtype=torch.bool, device=ctx.device)
+    return ctx.render_overlay(frame, ctx.minv_to_device(m), torch.from_numpy(digits[None]).to(ctx.device), active=active)
 
 
 def _validate_and_resolve(ctx, idx, prob):

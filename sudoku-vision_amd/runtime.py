@@ -467,6 +467,17 @@ class Context:
                                                              out.ctypes.data_as(C.c_void_p), ok.ctypes.data_as(C.c_void_p)), "sv_corners_to_minv_batch")
         return out, ok.astype(bool)
 
+    @staticmethod
+    def corners_to_m_batch(corners, output_size=450, inset_ratio=0.0):
+        """The forward homographies of corners_to_minv_batch (sv_corners_to_m_batch): corners [n,4,2] (host, any order) ->
+        (m float64 [n,3,3] frame -> grid, ok bool [n]); m[f] is the identity where ok[f] is False.  render_overlay takes them."""
+        c = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 8))
+        out = np.empty((c.shape[0], 3, 3), np.float64)
+        ok = np.empty(c.shape[0], np.uint8)
+        _native.check(_native.lib().sv_corners_to_m_batch(c.ctypes.data_as(C.c_void_p), c.shape[0], int(output_size), float(inset_ratio),
+                                                          out.ctypes.data_as(C.c_void_p), ok.ctypes.data_as(C.c_void_p)), "sv_corners_to_m_batch")
+        return out, ok.astype(bool)
+
     def minv_to_device(self, minv):
         return torch.from_numpy(np.ascontiguousarray(minv, np.float64)).to(self.device)
 
@@ -1015,6 +1026,64 @@ class Context:
         self._check(self._lib.sv_motion_update_u8(self._h, _ptr(frames), n, H, W, ch, pitch, fstride, _opt_ptr(prev_small), t, _ptr(small),
                                                   _ptr(counts), dh, dw, _stream_ptr()), "sv_motion_update_u8")
         return small, counts
+
+    # ---- the solution drawn into the frame (resolve/overlay.py, csrc/k16_overlay.hip) ----------------------------------
+    def set_overlay_glyphs(self, atlas):
+        """atlas uint8 [9,50,50] (host): the coverage glyphs of the digits 1..9 that render_overlay draws (sv_set_overlay_glyphs).  Rows and
+        columns 0..2 and 47..49 of every glyph must be zero (NativeError SV_ERR_BAD_ARG otherwise)."""
+        a = np.asarray(atlas)
+        if a.dtype != np.uint8 or a.shape != (9, 50, 50):
+            raise ValueError(f"atlas must be uint8 [9,50,50], got {a.dtype} {list(a.shape)}")
+        a = np.ascontiguousarray(a)
+        self._check(self._lib.sv_set_overlay_glyphs(self._h, a.ctypes.data_as(C.c_void_p)), "sv_set_overlay_glyphs")
+        self._overlay_glyphs = True
+
+    def render_overlay(self, frames, m_dev, digits, classes=None, palette=None, active=None, shadow=True, out=None):
+        """Draws 81 digits per frame into BGR frames, in one launch (sv_render_overlay_u8; include/sudoku_vision_hip.h defines every
+        pixel).  frames u8 [n,H,W,3] on device (rows may be padded, frames may have gaps: cropped views are read in place); m_dev f64
+        [n,3,3] on device, frame -> grid (corners_to_m_batch); digits u8 [n,81], 0 = nothing drawn; classes u8 [n,81] or None (class 0
+        everywhere): the row of `palette` a cell is drawn in; palette u8 [k,3] BGR on device or None: (255,100,0) solved, (0,0,0)
+        original, (0,0,255) low confidence (pipeline/overlay.py:63-71); a cell with a class >= k is not drawn; active u8 or bool [n] or
+        None: frames with 0 come back unchanged; shadow: the drop shadow.  out: None allocates the destination, out=frames draws in
+        place, any other u8 [n,H,W,3] tensor (rows may be padded) that does not overlap frames receives the result.  The first call
+        sets the default glyphs (overlay_font.default_atlas()) unless set_overlay_glyphs was called."""
+        _dev_tensor(frames, "frames", torch.uint8, self.device, shape=(None, None, None, 3))
+        in_place = out is frames or (isinstance(out, torch.Tensor) and out.data_ptr() == frames.data_ptr() and out.shape == frames.shape and
+                                     out.stride() == frames.stride() and out.dtype == frames.dtype)
+        src, pitch, fstride = _frame_layout(frames, self.device)
+        if in_place and src is not frames:
+            raise ValueError("frames with this layout cannot be drawn in place (rows must be dense in memory)")
+        n, H, W = src.shape[0], src.shape[1], src.shape[2]
+        if 0 in (n, H, W):
+            raise ValueError(f"frames must not be empty, got {list(frames.shape)}")
+        m_dev = self._minv(m_dev, n)
+        digits = _dev_tensor(digits, "digits", torch.uint8, self.device, shape=(n, 81)).contiguous()
+        if classes is not None:
+            classes = _dev_tensor(classes, "classes", torch.uint8, self.device, shape=(n, 81)).contiguous()
+        k = 3
+        if palette is not None:
+            palette = _dev_tensor(palette, "palette", torch.uint8, self.device, shape=(None, 3)).contiguous()
+            k = palette.shape[0]
+            if not 1 <= k <= 256:
+                raise ValueError(f"palette must have 1..256 rows, got {k}")
+        if active is not None:
+            active = _dev_tensor(active, "active", (torch.uint8, torch.bool), self.device, shape=(n,)).contiguous()
+        if in_place:
+            dst, dpitch, dstride = src, pitch, fstride
+        elif out is None:
+            dst = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
+            dpitch, dstride = 3 * W, 3 * W * H
+        else:
+            _dev_tensor(out, "out", torch.uint8, self.device, shape=(n, H, W, 3))
+            dst, dpitch, dstride = _frame_layout(out, self.device)
+            if dst is not out:
+                raise ValueError("out with this layout cannot be written in place (rows must be dense in memory)")
+        if not getattr(self, "_overlay_glyphs", False):
+            from . import overlay_font
+            self.set_overlay_glyphs(overlay_font.default_atlas())
+        self._check(self._lib.sv_render_overlay_u8(self._h, _ptr(src), n, H, W, pitch, fstride, _ptr(m_dev), _ptr(digits), _opt_ptr(classes), _opt_ptr(palette), k,
+                                                   _opt_ptr(active), int(bool(shadow)), _ptr(dst), dpitch, dstride, _stream_ptr()), "sv_render_overlay_u8")
+        return frames if in_place else (dst if out is None else out)
 
     def warp_affine(self, img, M, dsize, border_value=0):
         """cv2.warpAffine(img, M, dsize=(w, h), INTER_LINEAR, BORDER_CONSTANT, border_value) on gray u8 (sv_warp_affine_u8).  img [H,W] with M
