@@ -49,7 +49,8 @@ typedef enum sv_status {
 
 /* ---- library / context ------------------------------------------------------------------------ */
 
-int sv_version(void);                               /* ABI version, currently 2 (2: sv_timing_end takes the array length; sv_ctx_set_cnn_kernels) */
+int sv_version(void);                               /* ABI version, currently 2 (2: sv_timing_end takes the array length; sv_ctx_set_cnn_kernels).  Entries added
+                                                     * since, the JPEG encoder's among them, are additions within version 2: nothing that existed changed */
 const char *sv_last_error(void);                    /* thread-local, never NULL */
 
 /* Creates a context on HIP device `device` (replaces nothing: the reference keeps no state except
@@ -608,6 +609,54 @@ int sv_jpeg_reconstruct_sparse_scaled_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *in
                                              const uint32_t *offsets /*dev*/, const int16_t *values /*dev*/,
                                              const uint16_t *quant /*dev, 192*/, uint8_t *bgr /*dev*/, ptrdiff_t pitch,
                                              void *stream, int scale_denom);
+
+/* ---- JPEG encoder -- what cv2.imwrite does after the path ends (pipeline/run.py:431: cv2.imwrite(args.output, overlay)).  Baseline JPEG, 8-bit,
+ * gray or YCbCr 4:4:4 / 4:2:2 / 4:2:0, optional restart interval.  The mirror image of the decoder above: colour conversion, down-sampling, edge
+ * replication, the forward DCT (libjpeg's JDCT_ISLOW) and quantisation run on the GPU and leave the coefficients in the decoder's own layouts
+ * (dense, or the compact mask + values form that crosses PCIe); the serial Huffman bit packing runs on the host (threads: restart intervals of
+ * one image, or images of a batch).  The file is the one libjpeg-turbo writes with its defaults -- Annex K Huffman tables, no optimize_coding,
+ * baseline-forced quantiser tables, JFIF 1.01 header, density 1:1 -- byte for byte.  Progressive, optimised tables, arithmetic coding, 12-bit
+ * samples, EXIF: not written. */
+#define SV_JPEG_444 0
+#define SV_JPEG_422 1
+#define SV_JPEG_420 2
+typedef struct sv_jpeg_enc {
+    sv_jpeg_info info;              /* the geometry in the decoder's terms (orientation 1, out size = size); coef_count as above */
+    int quality;                    /* 1..100 */
+    uint16_t quant[192];            /* quantiser steps, natural order, per component (chroma twice) */
+    uint32_t recip[192];            /* ceil(2^32 / (8 * quant)): the device quantiser's multipliers */
+    long out_bound;                 /* bytes that hold the file whatever the image */
+} sv_jpeg_enc;
+
+/* components 1 (gray; sampling ignored) or 3; sampling SV_JPEG_444 / _422 / _420; quality 1..100 (jpeg_set_quality, force_baseline);
+ * restart: MCUs per restart interval, 0..65535 (0 = none).  Anything else, or a non-positive size, or a side above 65535: SV_ERR_BAD_ARG. */
+int sv_jpeg_encode_plan(int width, int height, int components, int sampling, int quality, int restart, sv_jpeg_enc *plan);
+/* Bytes that hold the file of an image whose sparse form has values_count values (far below plan->out_bound for real images) */
+long sv_jpeg_encode_bound(const sv_jpeg_enc *plan, long values_count);
+
+/* Device half, n frames of plan's size (BGR: plan of 3 components; gray: of 1), row pitch `pitch` >= row bytes and frame stride img_stride
+ * in bytes, any alignment; asynchronous on `stream`.  Dense output: coef != NULL receives n * coef_count values in sv_jpeg_entropy_decode's
+ * layout (16-byte aligned).  Sparse output: masks, offsets (n * coef_count / 64 each), values (n * coef_count: frame f's values start at
+ * f * coef_count; offsets are relative to that) and counts (n: values of each frame, so the host copies only that prefix) -- all four or none;
+ * exactly what sv_jpeg_entropy_decode_sparse produces for the file, so sv_jpeg_reconstruct_sparse_bgr_u8 takes a frame's records as they are.
+ * With coef == NULL the dense blocks live in the context's scratch.  SV_ERR_BAD_ARG: NULL frames, no output at all, n outside 1..65535,
+ * pitch < row bytes, a plan whose component count does not match the entry. */
+int sv_jpeg_forward_bgr_u8(sv_ctx *ctx, const sv_jpeg_enc *plan, const uint8_t *bgr /*dev*/, int n, ptrdiff_t pitch, ptrdiff_t img_stride,
+                           int16_t *coef /*dev or NULL*/, uint64_t *masks /*dev or NULL*/, uint32_t *offsets /*dev*/, int16_t *values /*dev*/,
+                           uint32_t *counts /*dev*/, void *stream);
+int sv_jpeg_forward_gray_u8(sv_ctx *ctx, const sv_jpeg_enc *plan, const uint8_t *gray /*dev*/, int n, ptrdiff_t pitch, ptrdiff_t img_stride,
+                            int16_t *coef /*dev or NULL*/, uint64_t *masks /*dev or NULL*/, uint32_t *offsets /*dev*/, int16_t *values /*dev*/,
+                            uint32_t *counts /*dev*/, void *stream);
+
+/* Host half: one frame's sparse records -> the file.  values_count: the frame's count; records that refer beyond it, a zero value under a set
+ * mask bit or a value no baseline code exists for are SV_ERR_BAD_ARG.  *out_size bytes are written; SV_ERR_BUFFER (with *out_size = what is
+ * needed) when out_cap is too small.  threads > 1 work on restart intervals; the bytes do not depend on threads. */
+int sv_jpeg_entropy_encode(const sv_jpeg_enc *plan, const uint64_t *masks /*host*/, const uint32_t *offsets /*host*/, const int16_t *values /*host*/,
+                           long values_count, uint8_t *out /*host*/, size_t out_cap, size_t *out_size, int threads);
+/* n frames of one plan over `threads` host threads.  status[i] = per-image sv_status; returns the first failure. */
+int sv_jpeg_entropy_encode_batch(const sv_jpeg_enc *plan, int n, const uint64_t *const *masks, const uint32_t *const *offsets,
+                                 const int16_t *const *values, const long *values_count, uint8_t *const *outs, const size_t *out_caps,
+                                 size_t *out_sizes, int threads, int *status /*n*/);
 
 /* ---- quality gate: the per-pixel statistics of cv/grid_quality.py (pipeline/run_v2.py:299-311) ------------------------- */
 

@@ -73,6 +73,12 @@ SIGNATURES = {
     "sv_jpeg_scaled_size": [_p, _i, _p, _p],
     "sv_jpeg_reconstruct_scaled_bgr_u8": [_p, _p, _p, _p, _p, _pd, _p, _i],
     "sv_jpeg_reconstruct_sparse_scaled_bgr_u8": [_p, _p, _p, _p, _p, _p, _p, _pd, _p, _i],
+    "sv_jpeg_encode_plan": [_i, _i, _i, _i, _i, _i, _p],
+    "sv_jpeg_encode_bound": [_p, _l],
+    "sv_jpeg_forward_bgr_u8": [_p, _p, _p, _i, _pd, _pd, _p, _p, _p, _p, _p, _p],
+    "sv_jpeg_forward_gray_u8": [_p, _p, _p, _i, _pd, _pd, _p, _p, _p, _p, _p, _p],
+    "sv_jpeg_entropy_encode": [_p, _p, _p, _p, _l, _p, C.c_size_t, _p, _i],
+    "sv_jpeg_entropy_encode_batch": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p],
     "sv_softmax_topk_f32": [_p, _p, _l, _i, _p, _p, _p],
     "sv_resolve_conflicts": [_p, _p, _p, _l, _i, _i, _i, _d, _i] + [_p] * 14,
     "sv_propagate_constraints": [_p, _p, _p, _l, _i] + [_p] * 9,
@@ -112,7 +118,7 @@ SIGNATURES = {
     "sv_set_overlay_glyphs": [_p, _p],
     "sv_render_overlay_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p, _p, _p, _i, _p, _i, _p, _pd, _pd, _p],
 }
-_RESTYPES = {"sv_last_error": C.c_char_p, "sv_sparse_bits_record_bytes": C.c_long}
+_RESTYPES = {"sv_last_error": C.c_char_p, "sv_sparse_bits_record_bytes": C.c_long, "sv_jpeg_encode_bound": C.c_long}
 # what libsudokuvision_xcheck.so exports on top of SIGNATURES (include/sudoku_vision_xcheck.h)
 XCHECK_SIGNATURES = {
     "sv_preprocess_stats": [_p, _p, _p],
@@ -127,6 +133,10 @@ class JpegInfo(C.Structure):
     """sv_jpeg_info of include/sudoku_vision_hip.h"""
     _fields_ = [(n, C.c_int) for n in ("width", "height", "out_width", "out_height", "components", "h_samp", "v_samp",
                                         "orientation", "restart_interval")] + [("coef_count", C.c_long), ("sparse_capacity", C.c_long)]
+
+class JpegEnc(C.Structure):
+    """sv_jpeg_enc of include/sudoku_vision_hip.h"""
+    _fields_ = [("info", JpegInfo), ("quality", C.c_int), ("quant", C.c_uint16 * 192), ("recip", C.c_uint32 * 192), ("out_bound", C.c_long)]
 
 
 _lib = None

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "sv_internal.h"
@@ -554,5 +555,306 @@ extern "C" int sv_jpeg_entropy_decode_batch(const uint8_t *const *datas, const s
     else WorkerPool::instance().parallel_for(n, threads, [&](int i) { one(i, 1); });
     for (int i = 0; i < n; i++)
         if (status[i] != SV_OK) return sv_fail(status[i], "sv_jpeg_entropy_decode_batch: image %d failed (see status[])", i);
+    return SV_OK;
+}
+
+// ---- the encoder's host half (cv2.imwrite at pipeline/run.py:431) ----------------------------------------
+// The device half (k17_jpeg_encode.hip) leaves a frame as the sparse records above; what remains is serial: the marker segments jcmarker.c
+// writes, and the Huffman bit stream of jchuff.c with the Annex K tables -- DC differences, (run, size) symbols over the mask's set bits (the
+// runs of zeros are the gaps between them: one count-trailing-zeros per coefficient, no pass over the 64 positions), ZRL, EOB, 0xFF stuffing,
+// 1-bit padding at the end of every restart interval.  Restart intervals are independent bit streams: `threads` contiguous runs of them are
+// packed in parallel and concatenated.
+namespace {
+
+// T.81 Annex K.3: code counts per length 1..16, then the symbols
+const uint8_t kDcLumaBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+const uint8_t kDcChromaBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kAcLumaBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+const uint8_t kAcLumaVals[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1,
+    0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
+    0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a,
+    0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
+    0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3,
+    0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+const uint8_t kAcChromaBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+const uint8_t kAcChromaVals[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1,
+    0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
+    0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69,
+    0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
+    0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca,
+    0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+// T.81 Annex K.1, natural order
+const uint8_t kBaseLuma[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                               18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+const uint8_t kBaseChroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+
+struct EncCodes {
+    uint32_t code[256];
+    uint8_t len[256];                                              // 0: the table has no code for the symbol
+    void define(const uint8_t *counts, const uint8_t *symbols)
+    {
+        memset(len, 0, sizeof len);
+        memset(code, 0, sizeof code);
+        uint32_t c = 0;
+        int k = 0;
+        for (int l = 1; l <= 16; l++) {
+            for (int i = 0; i < counts[l - 1]; i++, k++, c++) { code[symbols[k]] = c; len[symbols[k]] = (uint8_t)l; }
+            c <<= 1;
+        }
+    }
+};
+
+struct EncTables {
+    EncCodes dc[2], ac[2];                                         // [0] luma, [1] chroma
+    EncTables()
+    {
+        dc[0].define(kDcLumaBits, kDcVals); dc[1].define(kDcChromaBits, kDcVals);
+        ac[0].define(kAcLumaBits, kAcLumaVals); ac[1].define(kAcChromaBits, kAcChromaVals);
+    }
+};
+const EncTables &enc_tables() { static const EncTables t; return t; }
+
+constexpr long kEncHeaderMax = 640;                                // SOI 2, APP0 18, DQT 2 x 69, SOF0 19, DHT 432, DRI 6, SOS 14, EOI 2 = 631
+// A block costs at most 20 bits of DC, 3 ZRL of 11 bits and an EOB of 4; a non-zero AC value at most 16 + 10.  Twice that for stuffing.
+constexpr long kEncBlockBytes = 2 * ((57 + 63 * 26 + 7) / 8) + 8;
+
+long enc_intervals(const sv_jpeg_enc &p)
+{
+    const sv_jpeg_info &f = p.info;
+    const long nmcu = (long)((f.width + 8 * f.h_samp - 1) / (8 * f.h_samp)) * ((f.height + 8 * f.v_samp - 1) / (8 * f.v_samp));
+    return f.restart_interval > 0 ? (nmcu + f.restart_interval - 1) / f.restart_interval : 1;
+}
+
+long enc_bound(const sv_jpeg_enc &p, long values)
+{
+    const long blocks = p.info.coef_count / 64;
+    return kEncHeaderMax + 2 * ((57 * blocks + 26 * values + 7) / 8) + 3 * enc_intervals(p) + 8;
+}
+
+// Bits go into a growing byte vector, most significant first; 0xFF is followed by a stuffed zero byte
+struct BitSink {
+    std::vector<uint8_t> buf;
+    size_t pos = 0;
+    uint64_t acc = 0;
+    int n = 0;                                                     // bits held in acc, < 8 between calls
+
+    inline void room(size_t bytes) { if (buf.size() - pos < bytes) buf.resize(std::max(buf.size() * 2, pos + bytes + 4096)); }
+    inline void put(uint32_t bits, int len)                        // len <= 32; room() was called for what a block can take
+    {
+        acc = (acc << len) | bits;
+        n += len;
+        while (n >= 8) {
+            const uint8_t b = (uint8_t)(acc >> (n - 8));
+            buf[pos++] = b;
+            if (b == 0xFF) buf[pos++] = 0;
+            n -= 8;
+        }
+    }
+    inline void pad() { if (n) put((1u << (8 - n)) - 1, 8 - n); acc = 0; }
+    inline void raw(uint8_t b) { buf[pos++] = b; }
+};
+
+inline int bit_size(int v) { const unsigned a = (unsigned)(v < 0 ? -v : v); return a ? 32 - __builtin_clz(a) : 0; }
+
+// Restart intervals [k0, k1) of a frame -> sink.  Returns SV_OK or SV_ERR_BAD_ARG (message set) for records no baseline file can hold.
+int encode_intervals(const sv_jpeg_enc &p, const uint64_t *masks, const uint32_t *offsets, const int16_t *values, long values_count, long k0, long k1, BitSink &sink)
+{
+    const sv_jpeg_info &f = p.info;
+    const EncTables &T = enc_tables();
+    const int mcu_cols = (f.width + 8 * f.h_samp - 1) / (8 * f.h_samp), mcu_rows = (f.height + 8 * f.v_samp - 1) / (8 * f.v_samp);
+    const long nmcu = (long)mcu_cols * mcu_rows, per = f.restart_interval > 0 ? f.restart_interval : nmcu;
+    int ch[3], cv[3], bw[3];
+    long boff[3], off = 0;
+    for (int c = 0; c < f.components; c++) {
+        ch[c] = c == 0 ? f.h_samp : 1; cv[c] = c == 0 ? f.v_samp : 1;
+        bw[c] = mcu_cols * ch[c];
+        boff[c] = off;
+        off += (long)bw[c] * mcu_rows * cv[c];
+    }
+    for (long k = k0; k < k1; k++) {
+        if (k > 0) { sink.room(2); sink.raw(0xFF); sink.raw((uint8_t)(0xD0 + ((k - 1) & 7))); }
+        int pred[3] = {0, 0, 0};
+        const long m1 = std::min(nmcu, (k + 1) * per);
+        for (long mi = k * per; mi < m1; mi++) {
+            const int mx = (int)(mi % mcu_cols), my = (int)(mi / mcu_cols);
+            for (int c = 0; c < f.components; c++) {
+                const EncCodes &dct = T.dc[c > 0], &act = T.ac[c > 0];
+                for (int v = 0; v < cv[c]; v++)
+                    for (int u = 0; u < ch[c]; u++) {
+                        const long bi = boff[c] + (long)(my * cv[c] + v) * bw[c] + (mx * ch[c] + u);
+                        const uint64_t mask = masks[bi];
+                        const long first = (long)offsets[bi];
+                        if (first + __builtin_popcountll(mask) > values_count)
+                            return sv_fail(SV_ERR_BAD_ARG, "jpeg encode: block %ld refers to values beyond values_count %ld", bi, values_count);
+                        const int16_t *val = values + first;
+                        sink.room((size_t)kEncBlockBytes);
+                        const int dc = (mask & 1) ? *val++ : 0;
+                        if ((mask & 1) && dc == 0) return sv_fail(SV_ERR_BAD_ARG, "jpeg encode: block %ld has a zero value under a set mask bit", bi);
+                        const int diff = dc - pred[c];
+                        pred[c] = dc;
+                        int size = bit_size(diff);
+                        if (size > 11) return sv_fail(SV_ERR_BAD_ARG, "jpeg encode: block %ld: DC difference %d has no baseline code", bi, diff);
+                        sink.put(dct.code[size], dct.len[size]);
+                        if (size) sink.put((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << size) - 1), size);
+                        uint64_t rest = mask >> 1;
+                        int pos = 0;                               // zigzag position of the last coefficient coded
+                        while (rest) {
+                            int run = __builtin_ctzll(rest);
+                            rest = (rest >> run) >> 1;
+                            pos += run + 1;
+                            const int a = *val++;
+                            size = bit_size(a);
+                            if (size == 0 || size > 10) return sv_fail(SV_ERR_BAD_ARG, "jpeg encode: block %ld: AC value %d has no baseline code", bi, a);
+                            for (; run > 15; run -= 16) sink.put(act.code[0xF0], act.len[0xF0]);
+                            const int sym = run << 4 | size;
+                            sink.put(act.code[sym] << size | ((uint32_t)(a < 0 ? a - 1 : a) & ((1u << size) - 1)), act.len[sym] + size);
+                        }
+                        if (pos < 63) sink.put(act.code[0], act.len[0]);
+                    }
+            }
+        }
+        sink.pad();
+    }
+    return SV_OK;
+}
+
+size_t write_header(const sv_jpeg_enc &p, uint8_t *o)
+{
+    const sv_jpeg_info &f = p.info;
+    uint8_t *s = o;
+    auto seg = [&](int marker, int payload) { *o++ = 0xFF; *o++ = (uint8_t)marker; *o++ = (uint8_t)((payload + 2) >> 8); *o++ = (uint8_t)(payload + 2); };
+    *o++ = 0xFF; *o++ = 0xD8;
+    seg(0xE0, 14);
+    const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    memcpy(o, jfif, 14); o += 14;
+    for (int t = 0; t < (f.components == 3 ? 2 : 1); t++) {
+        seg(0xDB, 65);
+        *o++ = (uint8_t)t;
+        for (int i = 0; i < 64; i++) *o++ = (uint8_t)p.quant[64 * t + kNatural[i]];
+    }
+    seg(0xC0, 6 + 3 * f.components);
+    *o++ = 8; *o++ = (uint8_t)(f.height >> 8); *o++ = (uint8_t)f.height; *o++ = (uint8_t)(f.width >> 8); *o++ = (uint8_t)f.width; *o++ = (uint8_t)f.components;
+    for (int c = 0; c < f.components; c++) { *o++ = (uint8_t)(c + 1); *o++ = (uint8_t)(c == 0 ? f.h_samp << 4 | f.v_samp : 0x11); *o++ = (uint8_t)(c > 0); }
+    const struct { int id; const uint8_t *bits, *vals; int n; } dht[4] = {{0x00, kDcLumaBits, kDcVals, 12}, {0x10, kAcLumaBits, kAcLumaVals, 162},
+                                                                         {0x01, kDcChromaBits, kDcVals, 12}, {0x11, kAcChromaBits, kAcChromaVals, 162}};
+    for (int t = 0; t < (f.components == 3 ? 4 : 2); t++) {
+        seg(0xC4, 17 + dht[t].n);
+        *o++ = (uint8_t)dht[t].id;
+        memcpy(o, dht[t].bits, 16); o += 16;
+        memcpy(o, dht[t].vals, (size_t)dht[t].n); o += dht[t].n;
+    }
+    if (f.restart_interval) { seg(0xDD, 2); *o++ = (uint8_t)(f.restart_interval >> 8); *o++ = (uint8_t)f.restart_interval; }
+    seg(0xDA, 4 + 2 * f.components);
+    *o++ = (uint8_t)f.components;
+    for (int c = 0; c < f.components; c++) { *o++ = (uint8_t)(c + 1); *o++ = (uint8_t)(c == 0 ? 0x00 : 0x11); }
+    *o++ = 0; *o++ = 63; *o++ = 0;
+    return (size_t)(o - s);
+}
+
+bool enc_plan_ok(const sv_jpeg_enc *p)
+{
+    if (!p) return false;
+    const sv_jpeg_info &f = p->info;
+    return f.width > 0 && f.height > 0 && f.width < 65536 && f.height < 65536 && (f.components == 1 || f.components == 3) &&
+           ((f.h_samp == 1 && f.v_samp == 1) || (f.components == 3 && f.h_samp == 2 && (f.v_samp == 1 || f.v_samp == 2))) && f.restart_interval >= 0 &&
+           f.restart_interval < 65536 && f.coef_count > 0;
+}
+
+int entropy_encode(const sv_jpeg_enc &p, const uint64_t *masks, const uint32_t *offsets, const int16_t *values, long values_count, uint8_t *out, size_t out_cap,
+                   size_t *out_size, int threads)
+{
+    const long intervals = enc_intervals(p);
+    const int chunks = (int)std::max(1L, std::min((long)threads, intervals));
+    std::vector<BitSink> sinks((size_t)chunks);
+    std::vector<int> rcs((size_t)chunks, SV_OK);
+    std::vector<std::string> msgs((size_t)chunks);
+    WorkerPool::instance().parallel_for(chunks, chunks, [&](int c) {
+        rcs[c] = encode_intervals(p, masks, offsets, values, values_count, intervals * c / chunks, intervals * (c + 1) / chunks, sinks[c]);
+        if (rcs[c]) msgs[c] = sv_last_error();                     // the message lives on the worker's thread
+    });
+    for (int c = 0; c < chunks; c++)
+        if (rcs[c]) return sv_fail(rcs[c], "%s", msgs[c].c_str());
+    uint8_t head[kEncHeaderMax];
+    const size_t hn = write_header(p, head);
+    size_t total = hn + 2;
+    for (const BitSink &s : sinks) total += s.pos;
+    *out_size = total;
+    if (total > out_cap) return sv_fail(SV_ERR_BUFFER, "jpeg encode: the file takes %zu bytes, the buffer holds %zu", total, out_cap);
+    memcpy(out, head, hn);
+    size_t at = hn;
+    for (const BitSink &s : sinks) { if (s.pos) memcpy(out + at, s.buf.data(), s.pos); at += s.pos; }
+    out[at++] = 0xFF; out[at++] = 0xD9;
+    return SV_OK;
+}
+
+}  // namespace
+
+extern "C" int sv_jpeg_encode_plan(int width, int height, int components, int sampling, int quality, int restart, sv_jpeg_enc *plan)
+{
+    if (!plan) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_encode_plan: NULL argument");
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_encode_plan: size %d x %d (1..65535)", width, height);
+    if (components != 1 && components != 3) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_encode_plan: %d components (1 or 3)", components);
+    if (components == 3 && sampling != SV_JPEG_444 && sampling != SV_JPEG_422 && sampling != SV_JPEG_420)
+        return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_encode_plan: unknown sampling %d", sampling);
+    if (quality < 1 || quality > 100) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_encode_plan: quality %d (1..100)", quality);
+    if (restart < 0 || restart > 65535) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_encode_plan: restart interval %d (0..65535)", restart);
+    memset(plan, 0, sizeof *plan);
+    sv_jpeg_info &f = plan->info;
+    f.width = f.out_width = width; f.height = f.out_height = height;
+    f.components = components;
+    f.h_samp = components == 3 && sampling != SV_JPEG_444 ? 2 : 1;
+    f.v_samp = components == 3 && sampling == SV_JPEG_420 ? 2 : 1;
+    f.orientation = 1;
+    f.restart_interval = restart;
+    const long mcu_cols = (width + 8 * f.h_samp - 1) / (8 * f.h_samp), mcu_rows = (height + 8 * f.v_samp - 1) / (8 * f.v_samp);
+    f.coef_count = 64 * mcu_cols * mcu_rows * (components == 3 ? f.h_samp * f.v_samp + 2 : 1);
+    f.sparse_capacity = f.coef_count;
+    plan->quality = quality;
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;       // jpeg_quality_scaling
+    for (int c = 0; c < 3; c++)
+        for (int i = 0; i < 64; i++) {
+            const int q = std::min(255, std::max(1, ((c == 0 ? kBaseLuma[i] : kBaseChroma[i]) * scale + 50) / 100));
+            plan->quant[64 * c + i] = (uint16_t)q;
+            plan->recip[64 * c + i] = (uint32_t)(((1ull << 32) + 8 * q - 1) / (8 * q));
+        }
+    plan->out_bound = enc_bound(*plan, f.coef_count);
+    return SV_OK;
+}
+
+extern "C" long sv_jpeg_encode_bound(const sv_jpeg_enc *plan, long values_count)
+{
+    if (!enc_plan_ok(plan) || values_count < 0) return -1;
+    return enc_bound(*plan, std::min(values_count, plan->info.coef_count));
+}
+
+extern "C" int sv_jpeg_entropy_encode(const sv_jpeg_enc *plan, const uint64_t *masks, const uint32_t *offsets, const int16_t *values, long values_count, uint8_t *out,
+                                      size_t out_cap, size_t *out_size, int threads)
+{
+    if (!plan || !masks || !offsets || !values || !out || !out_size) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_entropy_encode: NULL argument");
+    if (!enc_plan_ok(plan) || values_count < 0) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_entropy_encode: bad plan or values_count");
+    return entropy_encode(*plan, masks, offsets, values, values_count, out, out_cap, out_size, threads < 1 ? 1 : threads);
+}
+
+// Images of a batch over the pool's threads; every image packs its restart intervals serially (a worker's nested parallel_for runs inline)
+extern "C" int sv_jpeg_entropy_encode_batch(const sv_jpeg_enc *plan, int n, const uint64_t *const *masks, const uint32_t *const *offsets, const int16_t *const *values,
+                                            const long *values_count, uint8_t *const *outs, const size_t *out_caps, size_t *out_sizes, int threads, int *status)
+{
+    if (!plan || !masks || !offsets || !values || !values_count || !outs || !out_caps || !out_sizes || !status || n <= 0)
+        return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_entropy_encode_batch: bad argument");
+    if (!enc_plan_ok(plan)) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_entropy_encode_batch: bad plan");
+    if (threads < 1) threads = 1;
+    auto one = [&](int i, int inner) {
+        out_sizes[i] = 0;
+        const bool ok = masks[i] && offsets[i] && values[i] && outs[i] && values_count[i] >= 0;
+        status[i] = ok ? entropy_encode(*plan, masks[i], offsets[i], values[i], values_count[i], outs[i], out_caps[i], out_sizes + i, inner) : SV_ERR_BAD_ARG;
+    };
+    if (threads == 1 || n == 1) for (int i = 0; i < n; i++) one(i, n == 1 ? threads : 1);
+    else WorkerPool::instance().parallel_for(n, threads, [&](int i) { one(i, 1); });
+    for (int i = 0; i < n; i++)
+        if (status[i] != SV_OK) return sv_fail(status[i], "sv_jpeg_entropy_encode_batch: image %d failed (see status[])", i);
     return SV_OK;
 }

@@ -978,6 +978,44 @@ extern "C" int sv_jpeg_reconstruct_sparse_scaled_bgr_u8(sv_ctx *ctx, const sv_jp
     return jpeg_reconstruct(false, ctx, info, nullptr, masks, offsets, values, quant, bgr, pitch, stream, scale_denom);
 }
 
+// The two forward entries of the encoder; channels 3 (BGR) or 1 (gray)
+static int jpeg_forward(const char *fn, int channels, sv_ctx *ctx, const sv_jpeg_enc *plan, const uint8_t *src, int n, ptrdiff_t pitch, ptrdiff_t img_stride, int16_t *coef,
+                        uint64_t *masks, uint32_t *offsets, int16_t *values, uint32_t *counts, void *stream)
+{
+    REQUIRE_AS(fn, ctx && plan && src, "NULL argument");
+    const bool any = masks || offsets || values || counts, all = masks && offsets && values && counts;
+    REQUIRE_AS(fn, any == all, "masks, offsets, values and counts come together");
+    REQUIRE_AS(fn, coef || all, "no output asked for");
+    REQUIRE_AS(fn, n > 0 && n < 65536, "n must be in 1..65535");
+    const sv_jpeg_info &info = plan->info;
+    sv_jpeg_enc want;                                               // a plan is only ever what sv_jpeg_encode_plan made of its six arguments
+    const int sampling = info.h_samp == 1 ? SV_JPEG_444 : info.v_samp == 1 ? SV_JPEG_422 : SV_JPEG_420;
+    if (sv_jpeg_encode_plan(info.width, info.height, info.components, sampling, plan->quality, info.restart_interval, &want) != SV_OK ||
+        memcmp(want.quant, plan->quant, sizeof want.quant) != 0 || memcmp(want.recip, plan->recip, sizeof want.recip) != 0 || want.out_bound != plan->out_bound ||
+        want.info.h_samp != info.h_samp || want.info.v_samp != info.v_samp ||      // the kernels size their tiles by these: v_samp 3 must not reach them
+        want.info.coef_count != info.coef_count || want.info.sparse_capacity != info.sparse_capacity || want.info.orientation != info.orientation ||
+        want.info.out_width != info.out_width || want.info.out_height != info.out_height)
+        return sv_fail(SV_ERR_BAD_ARG, "%s: the plan was not made by sv_jpeg_encode_plan", fn);
+    REQUIRE_AS(fn, info.components == channels, channels == 3 ? "a BGR frame needs a plan of 3 components" : "a gray frame needs a plan of 1 component");
+    REQUIRE_AS(fn, pitch >= (ptrdiff_t)channels * info.width, "pitch smaller than a row");
+    REQUIRE_AS(fn, n == 1 || img_stride >= pitch * (ptrdiff_t)(info.height - 1) + (ptrdiff_t)channels * info.width, "frames overlap");
+    REQUIRE_AS(fn, ((uintptr_t)coef & 15) == 0 && ((uintptr_t)masks & 7) == 0 && ((uintptr_t)offsets & 3) == 0 && ((uintptr_t)values & 1) == 0 && ((uintptr_t)counts & 3) == 0,
+               "misaligned output");
+    return svk_jpeg_forward(ctx, plan, src, channels, n, pitch, img_stride, coef, masks, offsets, values, counts, S(stream));
+}
+
+extern "C" int sv_jpeg_forward_bgr_u8(sv_ctx *ctx, const sv_jpeg_enc *plan, const uint8_t *bgr, int n, ptrdiff_t pitch, ptrdiff_t img_stride, int16_t *coef, uint64_t *masks,
+                                      uint32_t *offsets, int16_t *values, uint32_t *counts, void *stream)
+{
+    return jpeg_forward("sv_jpeg_forward_bgr_u8", 3, ctx, plan, bgr, n, pitch, img_stride, coef, masks, offsets, values, counts, stream);
+}
+
+extern "C" int sv_jpeg_forward_gray_u8(sv_ctx *ctx, const sv_jpeg_enc *plan, const uint8_t *gray, int n, ptrdiff_t pitch, ptrdiff_t img_stride, int16_t *coef, uint64_t *masks,
+                                       uint32_t *offsets, int16_t *values, uint32_t *counts, void *stream)
+{
+    return jpeg_forward("sv_jpeg_forward_gray_u8", 1, ctx, plan, gray, n, pitch, img_stride, coef, masks, offsets, values, counts, stream);
+}
+
 // K2 into the caller's cells (or the context's), then the forward `model` selects: 0 DigitCNN, 1 DigitCNNv3, 2 DigitCNNv3Light
 static int frames_to_digits(const char *fn, int model, sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv,
                             int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)

@@ -5,8 +5,15 @@ does not decode (progressive, arithmetic, CMYK, 12-bit) raise NativeError instea
 
 `cv2.imread(path, cv2.IMREAD_REDUCED_COLOR_2)` becomes `imread(path, reduce=reduce_from_flags(IMREAD_REDUCED_COLOR_2))`, or
 `imread(path, reduce=2)`: libjpeg's reduced-size decode, bit-identical to cv2's, never reconstructed at full size.
+
+`cv2.imwrite(path, img)` (pipeline/run.py:431) and `cv2.imencode('.jpg', img)` become `imwrite` / `imencode` here, with cv2's signatures and
+return conventions: a baseline JPEG, quality 95 and 4:2:0 unless `params` says otherwise, byte for byte the file libjpeg-turbo writes.  The
+image may be a numpy array or a CUDA tensor (the frame K16 drew into stays in HBM).  What this encoder does not write -- another extension,
+progressive or optimised files -- raises ValueError; nothing falls back to another encoder.
 """
 import os
+
+import numpy as np
 
 from . import _native
 from .runtime import Context, default_context
@@ -17,6 +24,17 @@ IMREAD_REDUCED_COLOR_2 = 17
 IMREAD_REDUCED_COLOR_4 = 33
 IMREAD_REDUCED_COLOR_8 = 65
 _REDUCE_OF_FLAGS = {IMREAD_COLOR: 1, IMREAD_REDUCED_COLOR_2: 2, IMREAD_REDUCED_COLOR_4: 4, IMREAD_REDUCED_COLOR_8: 8}
+
+# cv2's values
+IMWRITE_JPEG_QUALITY = 1
+IMWRITE_JPEG_PROGRESSIVE = 2
+IMWRITE_JPEG_OPTIMIZE = 3
+IMWRITE_JPEG_RST_INTERVAL = 4
+IMWRITE_JPEG_SAMPLING_FACTOR = 7
+IMWRITE_JPEG_SAMPLING_FACTOR_420 = 0x221111
+IMWRITE_JPEG_SAMPLING_FACTOR_422 = 0x211111
+IMWRITE_JPEG_SAMPLING_FACTOR_444 = 0x111111
+_SAMPLING_OF_FACTOR = {IMWRITE_JPEG_SAMPLING_FACTOR_420: "420", IMWRITE_JPEG_SAMPLING_FACTOR_422: "422", IMWRITE_JPEG_SAMPLING_FACTOR_444: "444"}
 
 
 def reduce_from_flags(flags):
@@ -50,3 +68,57 @@ def imread(path, device=False, ctx=None, threads=1, reduce=1):
     except OSError:
         return None
     return imdecode(data, device=device, ctx=ctx, threads=threads, reduce=reduce)
+
+
+def _encode_args(params):
+    """cv2's flat [id, value, id, value, ...] list -> Context.imencode's keyword arguments"""
+    params = [] if params is None else [int(p) for p in params]
+    if len(params) % 2:
+        raise ValueError("params is a flat list of (id, value) pairs")
+    kw = {"quality": 95, "sampling": "420", "restart": 0}
+    for pid, value in zip(params[0::2], params[1::2]):
+        if pid == IMWRITE_JPEG_QUALITY:
+            kw["quality"] = min(max(value, 0), 100) or 1            # cv2 clamps to 0..100; libjpeg takes 0 as 1
+        elif pid == IMWRITE_JPEG_SAMPLING_FACTOR:
+            if value not in _SAMPLING_OF_FACTOR:
+                raise ValueError(f"IMWRITE_JPEG_SAMPLING_FACTOR {value:#x}: 4:4:4, 4:2:2 and 4:2:0 are written here")
+            kw["sampling"] = _SAMPLING_OF_FACTOR[value]
+        elif pid == IMWRITE_JPEG_RST_INTERVAL:
+            if not 0 <= value <= 65535:
+                raise ValueError(f"IMWRITE_JPEG_RST_INTERVAL {value}: 0..65535")
+            kw["restart"] = value
+        elif pid in (IMWRITE_JPEG_OPTIMIZE, IMWRITE_JPEG_PROGRESSIVE):
+            if value:
+                raise ValueError("optimised Huffman tables and progressive files are not written here (baseline JPEG with the standard tables only)")
+        else:
+            raise ValueError(f"imwrite parameter id {pid} is not one this encoder knows")
+    return kw
+
+
+def imencode(ext, img, params=None, ctx=None, threads=1):
+    """cv2.imencode: (True, uint8 numpy array [bytes]).  ext: '.jpg' / '.jpeg' / '.jpe'; img: uint8 [H,W,3] BGR or [H,W] gray, numpy or CUDA tensor."""
+    import torch
+    if str(ext).lower() not in (".jpg", ".jpeg", ".jpe"):
+        raise ValueError(f"imencode {ext!r}: only JPEG ('.jpg', '.jpeg', '.jpe') is written here")
+    kw = _encode_args(params)
+    ctx = ctx or default_context()
+    if not isinstance(img, torch.Tensor):
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3)):
+            raise ValueError(f"imencode: expected a uint8 image [H,W], [H,W,1] or [H,W,3], got {img.dtype} {list(img.shape)}")
+        if img.ndim == 3 and img.shape[2] == 1:
+            img = img[:, :, 0]
+        img = torch.from_numpy(np.ascontiguousarray(img)).to(ctx.device)
+    data = ctx.imencode(img, threads=threads, **kw)
+    return True, np.frombuffer(data, np.uint8)
+
+
+def imwrite(path, img, params=None, ctx=None, threads=1):
+    """cv2.imwrite: True when the file was written, False when it could not be (cv2.imwrite does not raise for that)."""
+    ok, data = imencode(os.path.splitext(os.fspath(path))[1], img, params, ctx=ctx, threads=threads)
+    try:
+        with open(os.fspath(path), "wb") as f:
+            f.write(data.tobytes())
+    except OSError:
+        return False
+    return ok

@@ -464,7 +464,7 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     return res
 
 
-def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, preprocess="v1", grid="v1", stabilizer=None, motion_detector=None, overlay=False, solve_max_nodes=4096):
+def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, preprocess="v1", grid="v1", stabilizer=None, motion_detector=None, overlay=False, solve_max_nodes=4096, encode=False):
     """A camera feed: the loop of cv/stabilizer.py:308-335 followed by this library's recognition.  frames: an iterable of BGR frames
     (numpy uint8 [H,W,3] or CUDA uint8 tensors).  A generator; per frame it yields a dict:
         motion        the motion gate's verdict (cv.stabilizer.MotionDetector.update); True: the frame is skipped, every other entry
@@ -478,6 +478,8 @@ def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_
         solution, solve_result   the 81 solved digits (the recognised ones unless solve_result is 1) and the solver's verdict, else None
         frame_out     a uint8 tensor [H,W,3] on the device: the frame with the cells the solver filled in drawn at corners_used
                       (Context.render_overlay) where solve_result is 1; the input frame itself for a skipped or unsolved frame
+    encode=True (needs overlay=True, else ValueError) adds
+        jpeg          the bytes of frame_out as a JPEG file (Context.imencode: quality 95, 4:2:0, cv2.imwrite's defaults)
     preprocess, grid: "v1" | "v2" as in recognize_image (grid="v1": K1's binary and the host contour search; "v2":
     cv.grid_v2.detect_grid).  stabilizer, motion_detector: the GridStabilizer / MotionDetector to use (default: new ones with the
     reference's defaults).  With the default use_kalman=True the stabilised corners of the first min_detections - 1 detections are
@@ -489,6 +491,8 @@ def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_
         raise ValueError(f"grid must be 'v1' or 'v2', got {grid!r}")
     if preprocess not in ("v1", "v2"):
         raise ValueError(f"preprocess must be 'v1' or 'v2', got {preprocess!r}")
+    if encode and not overlay:
+        raise ValueError("encode=True needs overlay=True: frame_out is what gets encoded")
     ctx = ctx or default_context()
     if model_state_dict is not None:
         ctx.load_state_dict(model_state_dict)
@@ -506,6 +510,8 @@ def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_
         if overlay:
             res.update(solution=None, solve_result=None, frame_out=frame[0])
         if res["motion"]:
+            if encode:
+                res["jpeg"] = ctx.imencode(res["frame_out"])
             yield res
             continue
         if preprocess == "v2":
@@ -535,6 +541,8 @@ def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_
                     res["solution"], res["solve_result"] = sol, code
                     if code == 1:
                         res["frame_out"] = _draw_solution(ctx, frame, used, res["digits"], sol, True)[0]
+        if encode:
+            res["jpeg"] = ctx.imencode(res["frame_out"])
         yield res
 
 
@@ -625,14 +633,18 @@ def check_constraints(grid):
     return out
 
 
-def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confidence=0.7, component_filter=False, reduce=1, grid="v1"):
+def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confidence=0.7, component_filter=False, reduce=1, grid="v1", output=None):
     """run_pipeline(image_path) of pipeline/run.py:244-355 on the MI355X path: JPEG -> frame in HBM (imgcodecs) -> K1 -> host
     corner search -> K2 (warped 450x450 grid kept, as the reference keeps it) -> preprocess_cell + DigitCNN (K3) -> constraint
     check -> in-process solver.  Same PipelineResult fields, same error strings, same partial results on failure.
     component_filter=True: the corner search reads the binary behind the exact filters K4 and K11 (recognize_image); same result.
     reduce = 2, 4 or 8: the JPEG is decoded at 1/reduce of its size (cv2.IMREAD_REDUCED_COLOR_*) and everything downstream runs on that frame.
     grid="v2": the corners come from cv.grid_v2.detect_grid (recognize_image); the result then has the attributes detection_method,
-    detection_confidence and rotation_angle (run_v2's PipelineResult fields)."""
+    detection_confidence and rotation_angle (run_v2's PipelineResult fields).
+    output: a .jpg path; when the puzzle is solved, the frame with the solution drawn in (Context.render_overlay) is written there by
+    imgcodecs.imwrite, as run.py's --output does (pipeline/run.py:419-432); the result then has the attribute output_written.  Like every
+    other stage, writing reports and does not raise: a path that is not a .jpg, or one that cannot be written, leaves output_written False and
+    "Output failed: ..." in error, with the solved result otherwise intact."""
     from . import imgcodecs
     from .runtime import default_context
     if grid not in ("v1", "v2"):
@@ -724,6 +736,15 @@ def run_pipeline(image_path, state_dict=None, ctx=None, debug=False, low_confide
         res.error = f"Solver error: {e}"
         return res
     res.time_solver = time.time() - t_solver
+    if ok and output is not None:
+        try:
+            drawn = _draw_solution(ctx, frame[None], corners, digits, np.asarray(solution, np.uint8).reshape(81), True)[0]
+            res.output_written = imgcodecs.imwrite(output, drawn, ctx=ctx)
+            if not res.output_written:
+                res.error = f"Output failed: cannot write {output}"
+        except Exception as e:                               # noqa: BLE001
+            res.output_written = False
+            res.error = f"Output failed: {e}"
     res.time_total = time.time() - t_total
     res.success = ok
     return res

@@ -673,6 +673,124 @@ class Context:
         ev.record(torch.cuda.current_stream(self.device))
         return out
 
+    # ---- JPEG encoder (cv2.imwrite, pipeline/run.py:431) -----------------------------------------------
+    JPEG_SAMPLINGS = {"444": 0, "422": 1, "420": 2}
+    _ENC_CHUNK_BYTES = 128 << 20                                       # device staging of one chunk of an imencode_batch
+
+    def jpeg_encode_plan(self, width, height, channels, quality=95, sampling="420", restart=0):
+        """sv_jpeg_encode_plan, cached: the geometry, quantiser tables and size bounds of one (shape, quality, sampling, restart).
+        ValueError for what the encoder does not write."""
+        if not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+            raise ValueError(f"quality must be an integer in 1..100, not {quality!r}")
+        if str(sampling) not in self.JPEG_SAMPLINGS:
+            raise ValueError(f"sampling must be '444', '422' or '420', not {sampling!r}")
+        if not isinstance(restart, (int, np.integer)) or not 0 <= restart <= 65535:
+            raise ValueError(f"restart must be an integer in 0..65535 (MCUs), not {restart!r}")
+        if channels not in (1, 3) or not (0 < width < 65536 and 0 < height < 65536):
+            raise ValueError(f"cannot encode a {height} x {width} image of {channels} channels")
+        key = (int(width), int(height), int(channels), int(quality), str(sampling), int(restart))
+        plans = self.__dict__.setdefault("_jpeg_plans", {})
+        if key not in plans:
+            plan = _native.JpegEnc()
+            self._check(self._lib.sv_jpeg_encode_plan(*key[:3], self.JPEG_SAMPLINGS[key[4]], key[3], key[5], C.byref(plan)), "sv_jpeg_encode_plan")
+            plans[key] = plan
+        return plans[key]
+
+    def _enc_frames(self, frames):
+        """frames of an encode call -> (u8 tensor [n,H,W,3] or [n,H,W] on this device, channels).  A list is stacked; a tensor, views and padded
+        rows included, is passed on as it is (the kernel reads any row pitch)."""
+        if isinstance(frames, (list, tuple)):
+            if not frames:
+                raise ValueError("no frames")
+            for f in frames:
+                _dev_tensor(f, "frames[i]", torch.uint8, self.device, ndim=(2, 3))
+            if any(f.shape != frames[0].shape for f in frames):
+                raise ValueError("the frames of a batch share a shape (a batch shares its plan)")
+            frames = torch.stack(list(frames))
+        _dev_tensor(frames, "frames", torch.uint8, self.device, ndim=(3, 4))
+        if frames.dim() == 4 and frames.shape[3] != 3:
+            raise ValueError(f"colour frames are [n,H,W,3] BGR, got {list(frames.shape)}")
+        if frames.numel() == 0:
+            raise ValueError(f"empty frames {list(frames.shape)}")
+        return frames, 3 if frames.dim() == 4 else 1
+
+    def jpeg_forward(self, frames, plan, dense=False):
+        """The device half alone (sv_jpeg_forward_bgr_u8 / _gray_u8) on the current stream.  dense: int16 [n, coef_count] in the decoder's layout.
+        Otherwise the sparse transport form: (masks u64 [n, blocks], offsets u32 [n, blocks], values i16 [n, coef_count], counts u32 [n])."""
+        frames, ch = self._enc_frames(frames)
+        x, pitch, stride = _batch_layout(frames, self.device, "frames", ch)
+        n, ncoef = x.shape[0], int(plan.info.coef_count)
+        if (plan.info.height, plan.info.width, plan.info.components) != (x.shape[1], x.shape[2], ch):
+            raise ValueError("the plan was made for another shape")
+        fn = self._lib.sv_jpeg_forward_bgr_u8 if ch == 3 else self._lib.sv_jpeg_forward_gray_u8
+        if dense:
+            coef = torch.empty((n, ncoef), dtype=torch.int16, device=self.device)
+            self._check(fn(self._h, C.byref(plan), _ptr(x), n, pitch, stride, _ptr(coef), None, None, None, None, _stream_ptr()), "sv_jpeg_forward")
+            return coef
+        masks = torch.empty((n, ncoef // 64), dtype=torch.int64, device=self.device)
+        offsets = torch.empty((n, ncoef // 64), dtype=torch.int32, device=self.device)
+        values = torch.empty((n, ncoef), dtype=torch.int16, device=self.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=self.device)
+        self._check(fn(self._h, C.byref(plan), _ptr(x), n, pitch, stride, None, _ptr(masks), _ptr(offsets), _ptr(values), _ptr(counts), _stream_ptr()), "sv_jpeg_forward")
+        return masks, offsets, values, counts
+
+    def _enc_pinned(self, nbytes):
+        cur = getattr(self, "_enc_pin", None)
+        if cur is None or cur.numel() < nbytes:
+            self._enc_pin = cur = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8).pin_memory()
+        return cur
+
+    def imencode_batch(self, frames, quality=95, sampling="420", restart=0, threads=1):
+        """cv2.imencode('.jpg', frame)[1].tobytes() for every frame of a uint8 CUDA batch [n,H,W,3] (BGR) or [n,H,W] (gray), or a list of
+        same-shaped frames -> list of bytes, each the file libjpeg-turbo writes (baseline, Annex K tables, JFIF header; cv2's defaults are quality
+        95 and 4:2:0).  The GPU computes the quantised coefficients in the compact mask + values form (csrc/k17_jpeg_encode.hip), only
+        the used part of which crosses PCIe into pinned memory; `threads` host threads pack the Huffman bit streams (csrc/host_jpeg.cpp),
+        one image each.  restart: MCUs per restart interval (0: none).  Synchronises the current stream."""
+        frames, ch = self._enc_frames(frames)
+        n, H, W = frames.shape[:3]
+        plan = self.jpeg_encode_plan(W, H, ch, quality, sampling, restart)
+        ncoef, nb = int(plan.info.coef_count), int(plan.info.coef_count) // 64
+        step = max(1, min(n, self._ENC_CHUNK_BYTES // (12 * nb + 4 * ncoef)))
+        stream = torch.cuda.current_stream(self.device)
+        out = []
+        for at in range(0, n, step):
+            m = min(step, n - at)
+            masks, offsets, values, counts = self.jpeg_forward(frames[at:at + m], plan)
+            cb = (4 * m + 63) // 64 * 64                               # counts, then the masks and the offsets of the chunk
+            head = cb + 12 * nb * m
+            pin = self._enc_pinned(head)
+            pin[:4 * m].view(torch.int32).copy_(counts, non_blocking=True)
+            pin[cb:cb + 8 * nb * m].view(torch.int64).copy_(masks.view(-1), non_blocking=True)
+            pin[cb + 8 * nb * m:head].view(torch.int32).copy_(offsets.view(-1), non_blocking=True)
+            stream.synchronize()
+            used = [int(c) for c in pin[:4 * m].view(torch.int32).tolist()]
+            starts = np.concatenate([[0], np.cumsum([2 * u + 2 for u in used])]).astype(np.int64) + head       # never an empty stretch
+            if pin.numel() < starts[-1]:
+                keep = pin[:head].clone()
+                pin = self._enc_pinned(int(starts[-1]))
+                pin[:head].copy_(keep)
+            for i, u in enumerate(used):
+                if u:
+                    pin[int(starts[i]):int(starts[i]) + 2 * u].view(torch.int16).copy_(values[i, :u], non_blocking=True)
+            stream.synchronize()
+            pb = pin.data_ptr()
+            bounds = [int(self._lib.sv_jpeg_encode_bound(C.byref(plan), u)) for u in used]
+            bufs = [np.empty(b, np.uint8) for b in bounds]
+            VP = C.c_void_p * m
+            sizes, status = (C.c_size_t * m)(), (C.c_int * m)()
+            self._check(self._lib.sv_jpeg_entropy_encode_batch(
+                C.byref(plan), m, VP(*[pb + cb + 8 * nb * i for i in range(m)]), VP(*[pb + cb + 8 * nb * m + 4 * nb * i for i in range(m)]),
+                VP(*[pb + int(s) for s in starts[:m]]), (C.c_long * m)(*used), VP(*[b.ctypes.data for b in bufs]), (C.c_size_t * m)(*bounds), sizes,
+                int(threads), status), "sv_jpeg_entropy_encode_batch")
+            out += [bufs[i][:sizes[i]].tobytes() for i in range(m)]
+        return out
+
+    def imencode(self, frame, quality=95, sampling="420", restart=0, threads=1):
+        """One uint8 CUDA frame [H,W,3] (BGR) or [H,W] (gray), any row pitch -> the bytes of its JPEG file (imencode_batch of one frame; `threads`
+        work on restart intervals when restart > 0)."""
+        _dev_tensor(frame, "frame", torch.uint8, self.device, ndim=(2, 3))
+        return self.imencode_batch(frame[None], quality, sampling, restart, threads)[0]
+
     def softmax_topk(self, logits, k=3):
         """F.softmax(logits, 1).topk(k) (pipeline/run_v2.py:165-178): (index u8 [B,k], prob f32 [B,k]), best first."""
         logits = _dev_tensor(logits, "logits", torch.float32, self.device).reshape(-1, 10).contiguous()
