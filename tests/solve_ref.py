@@ -4,7 +4,8 @@ sv_solve_sudoku_batch_host add to it: a count of the search nodes and a budget f
 solve_sudoku (:72-81).  A node is one entry into solve_with_candidates; the root is node 1; a node that would be entered with
 max_nodes already entered ends the puzzle with BUDGET (max_nodes == 0: no budget).
 
-Also the puzzle sets the solver tests share: the goldens, the crafted cases and the seeded sparse set."""
+Also the puzzle sets the solver tests share: the goldens, the crafted cases, the seeded sparse set, and the hard set whose searches go
+deep and leave branches, with its one budgeted run (capped) and the budgets derived from it (edge_cases, edge_budgets)."""
 import functools
 import importlib.util
 import os
@@ -116,13 +117,23 @@ def _propagate(grid, cands, stats):
     return 0
 
 
+def _left(stats):
+    """A node returns False: one more level left since the last node was entered."""
+    stats["left"] += 1
+    stats["most_left"] = max(stats["most_left"], stats["left"])
+    return False
+
+
 def _solve_with_candidates(grid, cands, stats, depth):
     if stats["max_nodes"] and stats["nodes"] == stats["max_nodes"]:
         raise _Budget
     stats["nodes"] += 1
     stats["depth"] = max(stats["depth"], depth)
+    if stats["left"]:
+        stats["reentries"] += 1
+        stats["left"] = 0
     if _propagate(grid, cands, stats) < 0:
-        return False
+        return _left(stats)
     if all(grid[i][j] != 0 for i in range(9) for j in range(9)):
         return True
     best, min_count = None, 10
@@ -133,7 +144,7 @@ def _solve_with_candidates(grid, cands, stats, depth):
                 if count < min_count:
                     min_count, best = count, (i, j)
     if best is None:
-        return False
+        return _left(stats)
     cell_cands = cands[best[0]][best[1]]
     for num in range(1, 10):
         if cell_cands & (1 << num):
@@ -144,22 +155,27 @@ def _solve_with_candidates(grid, cands, stats, depth):
                 for i in range(9):
                     grid[i][:] = grid_copy[i]
                 return True
-    return False
+    return _left(stats)
 
 
 def solve(grid, max_nodes=0):
-    """grid: 81 or 9x9 integers -> (result, solution int64 [81], nodes, depth, sweeps): solution = grid unless result is SOLVED; depth is
-    the deepest node's (the root's is 1)."""
+    """grid: 81 or 9x9 integers -> (result, solution int64 [81], nodes, depth, sweeps, most_left, reentries): solution = grid unless
+    result is SOLVED; depth is the deepest node's (the root's is 1).  A level is left when its node returns without a solution:
+    most_left is the most levels left between two consecutive node entries, or between the last entry and the end of a search that
+    found nothing (a contradiction in a node whose parent has a digit left to try is 1; K14 pops most_left - 1 levels of its stack,
+    since a node whose propagation fails is never pushed); reentries counts the nodes entered after a level was left, whose state
+    therefore comes from an older level than the one entered last."""
     g0 = [int(v) for v in np.asarray(grid).reshape(81)]
     grid = [g0[9 * r:9 * r + 9] for r in range(9)]
     if not _validate_grid(grid):
-        return INVALID, np.array(g0), 0, 0, 0
-    stats = {"nodes": 0, "max_nodes": int(max_nodes), "depth": 0, "sweeps": 0}
+        return INVALID, np.array(g0), 0, 0, 0, 0, 0
+    stats = {"nodes": 0, "max_nodes": int(max_nodes), "depth": 0, "sweeps": 0, "left": 0, "most_left": 0, "reentries": 0}
     try:
         ok = _solve_with_candidates(grid, _init_candidates(grid), stats, 1)
     except _Budget:
-        return BUDGET, np.array(g0), stats["nodes"], stats["depth"], stats["sweeps"]
-    return (SOLVED if ok else NOSOLUTION), np.array(sum(grid, []) if ok else g0), stats["nodes"], stats["depth"], stats["sweeps"]
+        return BUDGET, np.array(g0), stats["nodes"], stats["depth"], stats["sweeps"], stats["most_left"], stats["reentries"]
+    return ((SOLVED if ok else NOSOLUTION), np.array(sum(grid, []) if ok else g0), stats["nodes"], stats["depth"], stats["sweeps"],
+            stats["most_left"], stats["reentries"])
 
 
 # ---- puzzle sets --------------------------------------------------------------------------------------------------------------------
@@ -193,6 +209,39 @@ def sparse_set():
     out[0::2] = P[plain].reshape(256, 81)
     out[1::2] = P[wrong].reshape(256, 81)
     return out
+
+
+HARD_SEEDS = (("inkala", "8..........36......7..9.2...5...7.......457.....1...3...1....68..85...1..9....4.."),
+              ("impossible", ".....5.8....6.1.43..........1.5........1.6...3.......553.....61........4........."),
+              ("hard1", "4.....8.5.3..........7......2.....6.....8.4......1.......6.3.7.5..2.....1.4......"))
+HARD_MORPHS = 24
+HARD_CAP = 4096
+
+
+def _morph(g, rng):
+    """A symmetry of the grid (transpose, rows within bands, bands, the same for columns, a relabelling of the digits): as solvable
+    as g, but another row-major, ascending-digit decision order, so another search tree."""
+    G = g.reshape(9, 9).copy()
+    if rng.integers(2):
+        G = G.T.copy()
+
+    def perm():
+        return np.concatenate([3 * b + rng.permutation(3) for b in rng.permutation(3)])
+    G = G[perm()][:, perm()]
+    relabel = np.concatenate([[0], rng.permutation(9) + 1]).astype(np.uint8)
+    return relabel[G].reshape(81)
+
+
+@functools.lru_cache(maxsize=None)
+def hard_set():
+    """Puzzles whose search goes deep and leaves branches: the three seeds of HARD_SEEDS, then 24 morphs of each from one
+    default_rng(11) consumed in that order -> uint8 [75,81].  Seed k is puzzle k; its morph m is puzzle 3 + 24 * k + m.  The
+    `impossible` family has no solution, and most of its members do not show that within any budget the entries take."""
+    seeds = [np.array([0 if ch == "." else int(ch) for ch in text], np.uint8) for _, text in HARD_SEEDS]
+    assert all(s.shape == (81,) for s in seeds)
+    rng = np.random.default_rng(11)
+    morphs = [_morph(s, rng) for s in seeds for _ in range(HARD_MORPHS)]
+    return np.stack(seeds + morphs).astype(np.uint8)
 
 
 FULL = np.array([[(3 * (r % 3) + r // 3 + c) % 9 + 1 for c in range(9)] for r in range(9)], np.uint8)     # a valid filled grid
@@ -242,6 +291,8 @@ def puzzles_of(which):
         return sparse_set().astype(np.int64)
     if which == "crafted":
         return crafted()[1].astype(np.int64)
+    if which == "hard":
+        return hard_set().astype(np.int64)
     return goldens()[int(which[-1])][1].reshape(-1, 81).astype(np.int64)
 
 
@@ -263,10 +314,51 @@ def expected(which, max_nodes):
 
 
 @functools.lru_cache(maxsize=None)
+def capped(which, cap):
+    """One run of the restatement on a whole set under a budget of cap nodes, for the sets unbounded() cannot finish ('hard': some
+    45 s at 4096) -> (result int8 [n], solution uint8 [n,81], nodes int32 [n], depth int32 [n], most_left int32 [n], reentries int32
+    [n]).  Shared: leave the arrays as they are."""
+    assert cap > 0
+    rows = [solve(p, cap) for p in puzzles_of(which)]
+    return (np.array([r[0] for r in rows], np.int8), np.stack([np.clip(r[1], 0, 255) for r in rows]).astype(np.uint8),
+            *(np.array([r[k] for r in rows], np.int32) for k in (2, 3, 5, 6)))
+
+
+def expected_capped(which, cap, b):
+    """The restatement's (result, solution, nodes) on a set under a budget 1 <= b <= cap, from the capped run alone: the search is
+    deterministic, so a run under b is the first b nodes of a run under cap (tests/test_solve_ref.py::test_budget_is_a_prefix).  A
+    puzzle whose capped run ended by itself within b nodes keeps its answer; every other one spends the budget."""
+    assert 1 <= b <= cap
+    res, sol, nodes = (a.copy() for a in capped(which, cap)[:3])
+    spent = (res == BUDGET) | ((res != INVALID) & (nodes > b))
+    res[spent], nodes[spent] = BUDGET, b
+    sol[spent] = as_bytes(puzzles_of(which))[spent]
+    return res, sol, nodes
+
+
+def edge_cases(res, nodes):
+    """From a run of the hard set under HARD_CAP (the restatement's or the host's, which tests/test_solve_ref.py holds equal) ->
+    [(name, puzzle, k)]: every puzzle refuted within the cap, the solved puzzles with the most and the fewest nodes and inkala itself,
+    each with its node count k.  Budget k is the least that lets the puzzle end by itself, k - 1 the largest it spends."""
+    refuted = np.flatnonzero(res == NOSOLUTION)
+    solved = np.flatnonzero(res == SOLVED)
+    assert len(refuted) >= 2 and len(solved) >= 2 and res[0] == SOLVED
+    picks = [(f"refuted{j}", int(i)) for j, i in enumerate(refuted)]
+    picks += [("most", int(solved[np.argmax(nodes[solved])])), ("fewest", int(solved[np.argmin(nodes[solved])])), ("inkala", 0)]
+    return [(name, i, int(nodes[i])) for name, i in picks]
+
+
+def edge_budgets(res, nodes):
+    """-> the budgets the hard set is run under beside HARD_CAP, ascending: k and k - 1 of every edge case, and four fixed ones."""
+    ks = {b for _, _, k in edge_cases(res, nodes) for b in (k, k - 1) if b >= 1}
+    return tuple(sorted(ks | {48, 49, 256, 1024}))
+
+
+@functools.lru_cache(maxsize=None)
 def backtracking_case():
     """Index into the sparse set of the first solvable puzzle that has to leave a wrong branch: more nodes than its deepest level."""
     for i, p in enumerate(sparse_set()):
-        res, _, nodes, depth, _ = solve(p)
+        res, _, nodes, depth = solve(p)[:4]
         if res == SOLVED and nodes > depth:
             return i
     raise AssertionError("the sparse set holds no puzzle that backtracks")

@@ -132,6 +132,115 @@ def test_out_tensors_partial_out_and_argument_ranges(ctx):
         ctx.solve_sudoku(P.cpu())
 
 
+# ---- the hard set (tests/solve_ref.py): searches that go deep, leave several levels at once, reuse levels, refute late or spend 4096 ------
+def _hard_edges():
+    """The host's run of the hard set at the default budget (tests/test_solve_ref.py holds it to the restatement) and the budgets on
+    either side of the nodes where its searches end: the restatement's own run takes the better part of a minute, this one a moment."""
+    res, _, nodes = host_batch(sr.hard_set(), max_nodes=sr.HARD_CAP)
+    return sr.edge_cases(res, nodes), sr.edge_budgets(res, nodes)
+
+
+HARD_EDGES, EDGE_BUDGETS = _hard_edges()
+
+
+def test_hard_set_matches_the_host_at_the_default_budget(ctx):
+    P = sr.hard_set()
+    want = host_batch(P, max_nodes=4096)
+    got = run(ctx, P, max_nodes=4096)
+    same(got, want, "hard set, max_nodes=4096")
+    res, sol, nodes = got
+    assert set(res.tolist()) == {0, 1, 2}
+    spent = res == sr.BUDGET
+    assert (nodes[spent] == 4096).all() and (sol[spent] == P[spent]).all() and (sol[res == 0] == P[res == 0]).all()
+    assert ((res == 0) & (nodes > 1000)).sum() >= 2 and spent.sum() >= 10
+
+
+@pytest.mark.parametrize("max_nodes", EDGE_BUDGETS)
+def test_hard_set_matches_the_host_at_edge_budgets(ctx, max_nodes):
+    """With the k nodes its search takes a puzzle is solved or refuted in exactly k: the last node spent on the last failing leaf is
+    NOSOLUTION, not BUDGET.  With k - 1 it is BUDGET."""
+    P = sr.hard_set()
+    want = host_batch(P, max_nodes=max_nodes)
+    got = run(ctx, P, max_nodes=max_nodes)
+    same(got, want, f"hard set, max_nodes={max_nodes}")
+    res, sol, nodes = got
+    spent = res == sr.BUDGET
+    assert spent.any() and (nodes[spent] == max_nodes).all() and (sol[spent] == P[spent]).all()
+    full = host_batch(P, max_nodes=sr.HARD_CAP)
+    for name, i, k in HARD_EDGES:
+        if max_nodes == k:
+            assert (res[i], nodes[i]) == (full[0][i], k) and res[i] != sr.BUDGET and (sol[i] == full[1].reshape(-1, 81)[i]).all(), name
+        if max_nodes == k - 1:
+            assert (res[i], nodes[i]) == (sr.BUDGET, k - 1) and (sol[i] == P[i]).all(), name
+
+
+def test_hard_and_easy_and_skipped_share_a_launch(ctx):
+    """Hard, sparse and crafted frames interleaved, every fifth switched off: a frame's answer does not depend on its neighbours, not
+    even on one that runs 4096 nodes beside it."""
+    names, grids = sr.crafted()
+    hard, easy = sr.hard_set(), sr.sparse_set()[:75]
+    P = np.empty((150, 81), np.uint8)
+    P[0::2], P[1::2] = hard, easy
+    P = np.concatenate([P[:77], grids, P[77:]])                          # the crafted cases in the middle: 75 + 75 + 6 frames
+    n = len(P)
+    assert n == 150 + len(names) and n % 64 and n % 5
+    active = (np.arange(n) % 5 != 2).astype(np.uint8)
+    is_hard = np.zeros(n, bool)
+    is_hard[:77:2] = True
+    is_hard[77 + len(names) + 1::2] = True
+    assert is_hard.sum() == 75 and (P[is_hard] == hard).all()
+    off = active == 0
+    assert (off & is_hard).sum() >= 10 and (off & ~is_hard).sum() >= 10
+    got = run(ctx, P, active=active)
+    same(got, host_batch(P, active=active, max_nodes=4096), "hard, easy and skipped frames in one launch")
+    res, sol, nodes = got
+    assert (res[off] == sr.SKIPPED).all() and (nodes[off] == 0).all() and (sol[off] == P[off]).all()
+    alone = run(ctx, P)
+    for a, b in zip(got, alone):
+        assert (a[~off] == b[~off]).all()
+    long = np.flatnonzero((nodes == 4096) & (res == sr.BUDGET))
+    assert len(long) >= 10
+    each = host_batch(P, max_nodes=4096)                                 # every frame's own answer, nothing switched off
+    for i in long:
+        for j in (i - 1, i + 1):
+            if 0 <= j < n and not off[j]:
+                assert res[j] == each[0][j] and nodes[j] == each[2][j] and (sol[j] == each[1].reshape(-1, 81)[j]).all(), (i, j)
+
+
+def test_two_launches_of_the_hard_set_agree(ctx):
+    """A stack level left over from the launch before, or from the frame a workgroup's LDS held before, changes nothing."""
+    P = torch.from_numpy(sr.hard_set()).to(ctx.device)
+    runs = []
+    for _ in range(2):
+        out = {"solution": torch.full((75, 81), 77, dtype=torch.uint8, device=ctx.device),
+               "result": torch.full((75,), 77, dtype=torch.int8, device=ctx.device),
+               "nodes": torch.full((75,), 77, dtype=torch.int32, device=ctx.device)}
+        got = ctx.solve_sudoku(P, None, 4096, out)
+        assert all(got[k] is out[k] for k in out)
+        runs.append(tuple(out[k].cpu().numpy() for k in ("result", "solution", "nodes")))
+    same(runs[1], runs[0], "the second launch against the first")
+    same(runs[0], host_batch(sr.hard_set(), max_nodes=4096), "out= against the host")
+    assert not (runs[0][0] == 77).any()                                 # (77 is a node count the set has: the host comparison covers nodes)
+
+
+def test_hard_frames_at_the_largest_budget(ctx):
+    """`impossible` and its first two morphs under the entry's largest budget of 65536 nodes.  One wave runs one puzzle, so the launch
+    is as long as its slowest frame: 178.5 ms of wall time on an MI355X for the launch with its copies (two frames spend all 65536
+    nodes, some 2.7 µs per node; the first morph is refuted after 3842).  The limit of 10 s below is the one past which this test
+    would have had to go down to 16384 nodes."""
+    import time
+    P = sr.hard_set()[[1, 27, 28]]
+    want = host_batch(P, max_nodes=65536)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    got = run(ctx, P, max_nodes=65536)
+    wall = time.perf_counter() - t0
+    print(f"K14, 3 frames at max_nodes=65536: {wall * 1e3:.1f} ms; result {got[0].tolist()} nodes {got[2].tolist()}")
+    same(got, want, "the impossible family, max_nodes=65536")
+    assert (got[0] != 1).all() and (got[2] > 4096).sum() >= 2 and (got[1] == P).all()
+    assert wall < 10.0
+
+
 # ---- the pipeline: the batch of tests/test_gpu_propagate.py, whose recognised logits are replaced by chosen ones --------------------------
 @pytest.fixture(scope="module")
 def pool(golden_dir):
