@@ -770,7 +770,9 @@ int sv_count_nonzero_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n, int H, i
  * lies at squared distance < min_distance^2 (integers); at most max_corners (1..SV_HARRIS_MAX_CORNERS) are kept.
  * corners[f][i] = (x, y) as float, counts[f] = corners of frame f.  cand_capacity: room for candidates per frame in the
  * context's scratch; a frame with more fails the call with SV_ERR_BUFFER (the message names the count) -- never a shorter
- * list.  response: NULL, or where to leave the response images (else they live in the context's scratch).  H, W >= 3.
+ * list.  response: NULL, or where to leave the response images (else they live in the context's scratch).
+ * 3 <= H, W <= 65535, SV_ERR_BAD_ARG otherwise: the selection keeps a corner as two 16-bit coordinates and a candidate's
+ * raster index y*W + x in 32 bits, and H*W < 2^32 follows from the two limits (nothing else bounds the product).
  * The call waits for `stream` (the status depends on the candidate counts). */
 #define SV_HARRIS_MAX_CORNERS 4096
 int sv_harris_corners_u8(sv_ctx *ctx, const uint8_t *gray /*dev*/, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,

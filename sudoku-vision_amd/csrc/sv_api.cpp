@@ -894,7 +894,9 @@ extern "C" int sv_harris_corners_u8(sv_ctx *ctx, const uint8_t *gray, int n, int
 {
     REQUIRE(ctx && gray && corners && counts, "NULL argument");
     REQUIRE_PLANES();
-    REQUIRE(H >= 3 && W >= 3 && W < 65536, "a frame must be at least 3x3");
+    REQUIRE(H >= 3 && W >= 3, "a frame must be at least 3x3");
+    // with REQUIRE_PLANES' H < 65536: k_harris_select keeps a corner as x | y << 16, and the raster index y * W + x fits 32 bits
+    REQUIRE(W < 65536, "W must be below 65536");
     REQUIRE(max_corners >= 1 && max_corners <= SV_HARRIS_MAX_CORNERS, "max_corners must be in 1..SV_HARRIS_MAX_CORNERS");
     REQUIRE(quality_level >= 0 && quality_level <= 1 && min_distance >= 0 && min_distance < 32768 && k == k, "bad quality_level, min_distance or k");
     REQUIRE(cand_capacity >= 1 && cand_capacity <= (1 << 24), "cand_capacity must be in 1..2^24");

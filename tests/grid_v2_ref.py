@@ -59,18 +59,22 @@ def harris_candidates(resp, quality_level):
     return cand
 
 
-def harris_corners(gray, max_corners=100, quality_level=0.01, min_distance=10, k=0.04):
-    """-> (corners float32 [m,2] as (x, y), response float32 [H,W], number of candidates)."""
+def harris_corners(gray, max_corners=100, quality_level=0.01, min_distance=10, k=0.04, window=None):
+    """-> (corners float32 [m,2] as (x, y), response float32 [H,W], number of candidates).
+    window: MUTANT -- a candidate is compared with the first `window` kept corners only."""
     resp = harris_response(gray, k)
     cand = harris_candidates(resp, quality_level)
-    kept = []
+    kept = np.zeros((max(min(len(cand), int(max_corners)), 1), 2), np.int64)          # (x, y) of the corners kept so far
+    n = 0
     md2 = int(min_distance) * int(min_distance)
     for _, y, x in cand:
-        if len(kept) >= max_corners:
+        if n >= max_corners:
             break
-        if all((x - kx) * (x - kx) + (y - ky) * (y - ky) >= md2 for kx, ky in kept):
-            kept.append((x, y))
-    return np.array(kept, F).reshape(-1, 2), resp, len(cand)
+        d = kept[:n if window is None else min(n, window)] - (x, y)
+        if ((d * d).sum(axis=1) >= md2).all():
+            kept[n] = (x, y)
+            n += 1
+    return kept[:n].astype(F), resp, len(cand)
 
 
 # ---- cv2.warpAffine(INTER_LINEAR, BORDER_CONSTANT) on u8 ------------------------------------------------------------------
@@ -112,6 +116,20 @@ def _sat_int(v):
     return np.clip(np.rint(v), -2147483648.0, 2147483647.0).astype(np.int64)
 
 
+def _sat_int_half_away(v):
+    """MUTANT of _sat_int: a tie goes away from zero (C's lround), not to the even neighbour."""
+    v = np.asarray(v, np.float64)
+    return np.clip(np.sign(v) * np.floor(np.abs(v) + 0.5), -2147483648.0, 2147483647.0).astype(np.int64)
+
+
+def _sat_int_truncating(v):
+    """MUTANT of _sat_int: the fraction is dropped (a C cast)."""
+    return np.clip(np.trunc(v), -2147483648.0, 2147483647.0).astype(np.int64)
+
+
+WARP_ROUNDINGS = {"half_even": _sat_int, "half_away": _sat_int_half_away, "truncate": _sat_int_truncating}
+
+
 def _wrap32(v):
     return ((v + 2 ** 31) % 2 ** 32) - 2 ** 31
 
@@ -128,7 +146,24 @@ def invert_affine(M):
     return [A11, m1, b1, m3, A22, b2]
 
 
-def warp_affine(src, M, dsize, border_value=0):
+def warp_coords(M, dsize, rounding="half_even"):
+    """-> (X, Y) int64 [h,w]: the source position of every destination pixel in 1/32 px (cell X >> 5, fraction X & 31).
+    rounding: WARP_ROUNDINGS; anything but "half_even" is a mutant."""
+    sat = WARP_ROUNDINGS[rounding]
+    dw, dh = dsize
+    m = invert_affine(M)
+    xs = np.arange(dw, dtype=np.float64)
+    ys = np.arange(dh, dtype=np.float64)
+    adelta = sat(m[0] * xs * 1024.0)
+    bdelta = sat(m[3] * xs * 1024.0)
+    X0 = _wrap32(sat((m[1] * ys + m[2]) * 1024.0) + 16)
+    Y0 = _wrap32(sat((m[4] * ys + m[5]) * 1024.0) + 16)
+    X = _wrap32(X0[:, None] + adelta[None, :]) >> 5
+    Y = _wrap32(Y0[:, None] + bdelta[None, :]) >> 5
+    return X, Y
+
+
+def warp_affine(src, M, dsize, border_value=0, rounding="half_even"):
     """src u8 [H,W], M forward 2x3, dsize (w, h) -> u8 [h,w]."""
     global _TAB
     if _TAB is None:
@@ -136,15 +171,7 @@ def warp_affine(src, M, dsize, border_value=0):
     src = np.asarray(src, np.uint8)
     H, W = src.shape
     dw, dh = dsize
-    m = invert_affine(M)
-    xs = np.arange(dw, dtype=np.float64)
-    ys = np.arange(dh, dtype=np.float64)
-    adelta = _sat_int(m[0] * xs * 1024.0)
-    bdelta = _sat_int(m[3] * xs * 1024.0)
-    X0 = _wrap32(_sat_int((m[1] * ys + m[2]) * 1024.0) + 16)
-    Y0 = _wrap32(_sat_int((m[4] * ys + m[5]) * 1024.0) + 16)
-    X = _wrap32(X0[:, None] + adelta[None, :]) >> 5
-    Y = _wrap32(Y0[:, None] + bdelta[None, :]) >> 5
+    X, Y = warp_coords(M, dsize, rounding)
     sx = np.clip(X >> 5, -32768, 32767)
     sy = np.clip(Y >> 5, -32768, 32767)
     w = _TAB[Y & 31, X & 31]                                 # [dh,dw,4]
@@ -448,3 +475,117 @@ def detect_grid(binary, gray=None, try_rotation=True, try_multiple_methods=True)
         if quad is not None:
             return {"corners": quad, "confidence": confidence, "method": method, "rotation_angle": angle, "debug_info": debug}
     return {"corners": None, "confidence": 0, "method": "none", "rotation_angle": 0, "debug_info": debug}
+
+
+# ---- inputs of the hard-case tests: tests/test_grid_v2_ref.py states on the CPU what each one does to the restatement, --------------
+# ---- tests/test_gpu_grid_v2.py runs them through K13 ------------------------------------------------------------------------------
+def noise(shape, seed):
+    return np.random.RandomState(seed).randint(0, 256, shape).astype(np.uint8)
+
+
+# k_harris_response's tile is 64 x 16 (pixel halo 2, derivative halo 1): exact tiles, then last tiles one, two, one and three pixels
+# high and one, two, one and 63 wide, whose reflected halo lies inside the neighbouring tile's area
+TILING_SHAPES = ((16, 64), (17, 65), (18, 66), (33, 129), (19, 127))
+
+
+def corner_squares(shape, inset=1, level=30, value=255):
+    """A bright 2x2 square `inset` pixels from both borders in each image corner: every response that is not zero lies in the last tile's
+    reflected halo.  inset 1 gives one candidate per corner; inset 0 puts the maximum on pixel (0, 0) and leaves no candidate."""
+    img = np.full(shape, level, np.uint8)
+    lo, hi = slice(inset, inset + 2), slice(-inset - 2, -inset or None)
+    img[lo, lo] = img[lo, hi] = img[hi, lo] = img[hi, hi] = value
+    return img
+
+
+def border_maximum_frame():
+    """20x30, level 10: [0,0] = 255 puts the frame maximum on the outermost pixel frame, which is never a candidate; a faint L of
+    three pixels near the middle is the only thing the threshold can leave."""
+    img = np.full((20, 30), 10, np.uint8)
+    img[0, 0] = 255
+    img[10, 15] = img[11, 15] = img[11, 16] = 60
+    return img
+
+
+def checkerboard(shape=(96, 96), period=8):
+    yy, xx = np.mgrid[0:shape[0], 0:shape[1]]
+    return (((yy // period) + (xx // period)) % 2 * 255).astype(np.uint8)
+
+
+def wide_range_noise(shape=(48, 80), seed=11):
+    """Noise whose left half has its contrast cut to two grey levels: at quality_level = 0 the candidates span eleven orders of magnitude."""
+    img = noise(shape, seed)
+    half = shape[1] // 2
+    img[:, :half] = 128 + (img[:, :half] & 1)
+    return img
+
+
+MANY = ((192, 256), 1)             # noise(*MANY): 2771 candidates at quality_level 0.01, so the bitonic sort runs on P = 4096 keys
+OVER_CAP = ((224, 320), 2)         # 4156 candidates: more than SV_HARRIS_MAX_CORNERS = 4096
+POWER_OF_TWO = ((20, 67), 1)       # exactly 64 candidates: no padding key is written
+
+
+def uneven_batch():
+    """Three frames of MANY's shape whose candidate counts differ by more than a factor of ten each: noise (2771), a checkerboard of
+    period 32 (140), two squares (8)."""
+    shape = MANY[0]
+    few = np.full(shape, 40, np.uint8)
+    for (y, x), v in (((20, 30), 255), ((170, 200), 200)):
+        few[y:y + 2, x:x + 2] = v
+    return np.stack([noise(*MANY), checkerboard(shape, 32), few])
+
+
+def square_column(height, squares, width=5, level=40):
+    """A frame `width` wide: one 2x2 square per (row, value) at columns 1..2, rows row-1..row.  Its response has two equal maxima,
+    at (x, y) = (2, row-1) and (2, row); raster order takes the upper one first."""
+    img = np.full((height, width), level, np.uint8)
+    for row, value in squares:
+        img[row - 1:row + 1, 1:3] = value
+    return img
+
+
+TALL = 65600                                                    # more rows than 16 bits count
+TALL_SQUARES = ((10, 200), (30000, 180), (65546, 255))          # the strongest lies exactly 65536 rows below the first
+TALL_PAIR = ((65546, 255), (65550, 200), (100, 180))            # two squares 4 rows apart, both beyond row 65536
+LIMIT = 65535                                                   # the tallest frame sv_harris_corners_u8 takes
+LIMIT_SQUARES = ((10, 200), (30000, 180), (65520, 255), (65524, 190), (32762, 220), (32770, 210))    # rows with bit 15 set; a pair 4 and a pair 8 apart
+
+
+# the affine warp
+FRACTION_SOURCES = {"period 1": checkerboard((36, 36), 1), "period 3": checkerboard((36, 36), 3)}       # 0 and 255 only
+FRACTION_DSIZE = (72, 72)
+
+
+def fraction_sweep_matrix():
+    """Forward matrix whose inverse is the scale 33/32 with the translation (-1.5, -1.40625): a step of one destination pixel moves the
+    source position by 33/32 px, so the fraction walks through all 32 values, in x and in y, inside the source and beyond each border."""
+    s = 32.0 / 33.0
+    return np.array([[s, 0, 1.5 * s], [0, s, 1.40625 * s]], np.float64)
+
+
+TIE_DSIZE = (512, 4)
+_T = 33.0 / 2048                   # M3 * x * 1024 = -16.5 x: a tie at every odd x
+
+
+def tie_cases():
+    """name -> (source, forward matrix, the mutant rounding it shows).  Every inverse is exact in double.
+    A tie shows only where the two roundings land on different sides of a multiple of 32 (X = (X0 + adelta) >> 5, X0 = ... + 16):
+    * delta: Y0 = 1024 y + 16 and bdelta = rint(-16.5 x) is even at a tie, so Y0 + bdelta is even, and so is the nearest multiple of 32:
+      the neighbour one below (half away from zero) can cross it, the neighbour one above (truncation) cannot -- on this matrix
+      truncation and half-to-even give the same pixels, whatever the source.
+    * delta, odd: the same with 1/1024 px of translation, Y0 = 1024 y + 17: now only truncation can cross.
+    * translation: b1 = -16.5/1024 (half-to-even -16, away -17: X0 = 0 or -1) and b2 = 15.5/1024 (half-to-even 16, truncated 15:
+      Y0 = 32 or 31), so each mutant moves every pixel by 1/32 px, one in x and one in y."""
+    rows = np.zeros((12, 520), np.uint8)
+    rows[::2] = 255
+    return {"delta": (rows, np.array([[1, 0, 0], [_T, 1, 0]], np.float64), "half_away"),
+            "delta, odd": (rows, np.array([[1, 0, 0], [_T, 1, -1.0 / 1024]], np.float64), "truncate"),
+            "translation": (checkerboard((12, 520), 1), np.array([[1, 0, 16.5 / 1024], [0, 1, -15.5 / 1024]], np.float64), "both")}
+
+
+DEGENERATE_MATRICES = {
+    "singular": [[2, 4, 1], [1, 2, 3]],                        # D = 0: the inverse is all zeros, every pixel is src[0,0]
+    "far": [[1, 0, 1e12], [0, 1, 0]],                          # sat_int saturates, the cell clamps to -32768: all border
+    "tiny": [[1e-7, 0, 0], [0, 1e-7, 0]],                      # adelta and Y0 saturate at 2^31 - 1; + 16 and X0 + adelta wrap in int32
+    "flip": [[-1, 0, 12.25], [0, -0.75, 6.5]],                 # negative scale
+}
+

@@ -1,6 +1,8 @@
 """cv/grid_v2.py on the GPU against tests/grid_v2_ref.py: the Harris response and corner list and the affine warp of
-csrc/k13_grid_v2.hip bit for bit, detect_grid end to end on small synthetic frames that reach each of its methods, and the
-grid="v2" hook of the pipeline."""
+csrc/k13_grid_v2.hip bit for bit -- on plain frames first, then on inputs built for the branches those do not reach (last tiles a
+pixel wide, thresholds that tie, more than 2048 candidates, frames at the size limit, every bilinear fraction, rounding ties,
+degenerate matrices) --, detect_grid end to end on small synthetic frames that reach each of its methods, and the grid="v2" hook
+of the pipeline."""
 import os
 
 import numpy as np
@@ -125,6 +127,176 @@ def test_warp_affine_identity_and_batch(ctx):
     assert isinstance(got, torch.Tensor) and got.shape == (2, 52, 81)
     for f in range(2):
         assert (got[f].cpu().numpy() == R.warp_affine(pair[f], mats[f], (81, 52), 17)).all()
+
+
+# ---- Harris where the frames above do not reach ----------------------------------------------------------------------------
+# The inputs come from grid_v2_ref.py; tests/test_grid_v2_ref.py asserts on the CPU what each one does to the restatement (which
+# branch of the kernels it is built for), so that a weak input fails there and not silently here.
+@pytest.mark.parametrize("shape", R.TILING_SHAPES)
+def test_harris_last_tile_one_or_two_pixels(ctx, shape):
+    _check_harris(ctx, R.noise(shape, 5), max_corners=200, quality_level=0.01, min_distance=2)
+    inset, _ = _check_harris(ctx, R.corner_squares(shape), max_corners=10, quality_level=0.01, min_distance=3)
+    assert len(inset) == 4
+    flush, _ = _check_harris(ctx, R.corner_squares(shape, inset=0), max_corners=10, quality_level=0.01, min_distance=3)
+    assert len(flush) == 0
+
+
+def test_harris_frame_maximum_on_the_border(ctx):
+    img = R.border_maximum_frame()
+    one, ncand = _check_harris(ctx, img, max_corners=10, quality_level=0.01, min_distance=1)
+    assert ncand == 1 and one.tolist() == [[15, 11]]
+    assert (ctx.harris_corners(img, max_corners=10, min_distance=1, cand_capacity=1) == one).all()       # P = 1: the sort does not run
+    none, ncand = _check_harris(ctx, img, max_corners=10, quality_level=1.0, min_distance=1)
+    assert ncand == 0 and len(none) == 0                     # the only value that reaches the maximum lies on the excluded frame
+
+
+@pytest.mark.parametrize("quality", [1.0, 0.0])
+@pytest.mark.parametrize("max_corners,min_distance", [(100, 10), (4096, 0), (4096, 1)])
+def test_harris_checkerboard_at_both_ends_of_quality(ctx, quality, max_corners, min_distance):
+    want, ncand = _check_harris(ctx, R.checkerboard(), max_corners=max_corners, quality_level=quality, min_distance=min_distance)
+    assert ncand == 484 and (len(want) == 484 or min_distance == 10)          # v == quality * max is kept
+
+
+@pytest.mark.parametrize("min_distance", [0, 3])
+def test_harris_quality_zero_orders_tiny_responses(ctx, min_distance):
+    _, ncand = _check_harris(ctx, R.wide_range_noise(), max_corners=4096, quality_level=0.0, min_distance=min_distance)
+    assert ncand > 100
+
+
+@pytest.mark.parametrize("k", [0.25, 0.0])
+def test_harris_k_extremes(ctx, k):
+    want, ncand = _check_harris(ctx, _noise((37, 53), 1), max_corners=100, quality_level=0.01, min_distance=3, k=k)
+    assert (ncand == 0 and len(want) == 0) if k else ncand > 50              # k = 0.25: the maximum is negative, no corner in a frame that is not flat
+
+
+@pytest.mark.parametrize("min_distance", [2, 0, 5])
+def test_harris_more_than_2048_candidates(ctx, min_distance):
+    want, ncand = _check_harris(ctx, R.noise(*R.MANY), max_corners=4096, quality_level=0.01, min_distance=min_distance)
+    assert 2048 < ncand <= 4096 and (len(want) == ncand if min_distance < 5 else 1024 < len(want) < ncand)     # at 5 the rule drops hundreds
+
+
+def test_harris_power_of_two_candidates_in_exactly_that_capacity(ctx):
+    import sudoku_vision_amd as sva
+    img = R.noise(*R.POWER_OF_TWO)
+    want, ncand = _check_harris(ctx, img, max_corners=100, quality_level=0.01, min_distance=3)
+    assert ncand == 64
+    assert (ctx.harris_corners(img, max_corners=100, min_distance=3, cand_capacity=64) == want).all()
+    with pytest.raises(sva._native.NativeError, match="SV_ERR_BUFFER"):
+        ctx.harris_corners(img, max_corners=100, min_distance=3, cand_capacity=63)
+
+
+def test_harris_max_corners_caps(ctx):
+    img = R.noise(*R.OVER_CAP)
+    full, ncand = _check_harris(ctx, img, max_corners=4096, quality_level=0.01, min_distance=0)          # SV_HARRIS_MAX_CORNERS
+    assert ncand > 4096 and len(full) == 4096
+    one, _ = _check_harris(ctx, img, max_corners=1, quality_level=0.01, min_distance=0)
+    assert one.tolist() == full[:1].tolist()
+    import sudoku_vision_amd as sva
+    with pytest.raises(sva._native.NativeError, match="SV_ERR_BAD_ARG"):
+        ctx.harris_corners(img, max_corners=4097)
+
+
+def test_harris_batch_of_uneven_candidate_counts(ctx):
+    frames = R.uneven_batch()
+    kw = dict(max_corners=4096, quality_level=0.01, min_distance=2)
+    corners, counts, resp = ctx.harris_corners(frames, want_response=True, **kw)
+    assert corners.shape == (3, 4096, 2) and counts.shape == (3,)
+    sizes = []
+    for f in range(3):
+        want, want_resp, ncand = R.harris_corners(frames[f], **kw)
+        sizes.append(ncand)
+        assert (_bits(resp[f]) == _bits(want_resp)).all()
+        assert int(counts[f]) == len(want) and (corners[f, :len(want)] == want).all()
+        assert (ctx.harris_corners(frames[f], **kw) == want).all()                                   # the same frame alone
+    assert sizes[0] > 10 * sizes[1] and sizes[1] > 10 * sizes[2] > 0
+
+
+@pytest.mark.parametrize("squares", [R.TALL_SQUARES, R.TALL_PAIR], ids=["65536 rows apart", "a pair beyond row 65536"])
+def test_harris_refuses_rows_beyond_16_bits(ctx, squares):
+    """k_harris_select keeps a corner as x | y << 16; the entry takes no frame in which that could alias (test_grid_v2_ref.py has the
+    lists a wider kernel would have to give)."""
+    import sudoku_vision_amd as sva
+    with pytest.raises(sva._native.NativeError, match="SV_ERR_BAD_ARG: sv_harris_corners_u8: bad shape"):
+        ctx.harris_corners(R.square_column(R.TALL, squares), quality_level=0.01, min_distance=8)
+    with pytest.raises(sva._native.NativeError, match="SV_ERR_BAD_ARG: sv_harris_corners_u8: W must be below 65536"):
+        ctx.harris_corners(np.ascontiguousarray(R.square_column(R.TALL, squares).T), quality_level=0.01, min_distance=8)
+
+
+def test_harris_tallest_and_widest_frame(ctx):
+    img = R.square_column(R.LIMIT, R.LIMIT_SQUARES)
+    want, ncand = _check_harris(ctx, img, max_corners=100, quality_level=0.01, min_distance=8)
+    assert ncand == 12 and want.tolist() == [[2, 65519], [2, 32761], [2, 32769], [2, 9], [2, 29999]]
+    wide, ncand = _check_harris(ctx, np.ascontiguousarray(img.T), max_corners=100, quality_level=0.01, min_distance=8)
+    assert ncand == 12 and len(wide) == 5 and wide[0, 0] > 65500
+
+
+# ---- warpAffine where the rotations above do not reach ----------------------------------------------------------------------
+def _check_warp(ctx, src, matrix, dsize, border):
+    want = R.warp_affine(src, matrix, dsize, border)
+    got = ctx.warp_affine(src, np.asarray(matrix, np.float64), dsize, border)
+    assert got.dtype == np.uint8 and got.shape == want.shape == (dsize[1], dsize[0])
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, f"{len(bad)} pixels differ, first at {bad[0].tolist()}: {got[tuple(bad[0])]} != {want[tuple(bad[0])]}"
+    return want
+
+
+@pytest.mark.parametrize("border", [0, 255, 128])
+@pytest.mark.parametrize("source", list(R.FRACTION_SOURCES))
+def test_warp_affine_every_fraction_pair_inside_and_at_each_border(ctx, source, border):
+    _check_warp(ctx, R.FRACTION_SOURCES[source], R.fraction_sweep_matrix(), R.FRACTION_DSIZE, border)
+
+
+@pytest.mark.parametrize("case", list(R.tie_cases()))
+@pytest.mark.parametrize("border", [0, 128])
+def test_warp_affine_ties_round_half_to_even(ctx, case, border):
+    src, matrix, shows = R.tie_cases()[case]
+    want = _check_warp(ctx, src, matrix, R.TIE_DSIZE, border)
+    for rounding in ("half_away", "truncate"):
+        if shows in (rounding, "both"):
+            assert (R.warp_affine(src, matrix, R.TIE_DSIZE, border, rounding=rounding) != want).sum() >= 8
+
+
+@pytest.mark.parametrize("case", list(R.DEGENERATE_MATRICES))
+def test_warp_affine_degenerate_matrices(ctx, case):
+    src = R.noise((9, 13), 3)
+    want = _check_warp(ctx, src, R.DEGENERATE_MATRICES[case], (17, 6), 77)
+    if case == "singular":
+        assert (want == src[0, 0]).all()
+    if case == "far":
+        assert (want == 77).all()
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (1, 9), (9, 1)])
+def test_warp_affine_sources_with_no_inside(ctx, shape):
+    src = R.noise(shape, 4)
+    want = _check_warp(ctx, src, [[1.3, 0.2, 1.7], [-0.1, 1.6, 2.2]], (16, 12), 200)
+    assert (want == 200).any() and (want != 200).any()
+    _check_warp(ctx, src, [[1, 0, 0], [0, 1, 0]], (shape[1] + 1, shape[0] + 1), 9)
+
+
+@pytest.mark.parametrize("dsize", [(1, 1), (65, 5)])
+def test_warp_affine_destination_sizes(ctx, dsize):
+    want = _check_warp(ctx, _noise((45, 70), 8), R.rotation_matrix((10, 3), -21.0, 0.8), dsize, 31)
+    assert dsize == (1, 1) or ((want == 31).any() and (want != 31).any())
+
+
+def test_warp_affine_gapped_batch_one_matrix_per_frame(ctx):
+    """Padded rows, gaps between the frames and an odd base address (test_gpu_preprocess_v2._gapped's layout) over a buffer of 0xA5."""
+    n, H, W = 3, 23, 37
+    imgs = np.stack([_noise((H, W), 20 + i) for i in range(n)])
+    pitch, offset = W + 5, 1
+    fstride = pitch * H + 13
+    buf = torch.full((offset + n * fstride + 64,), 0xA5, dtype=torch.uint8, device=ctx.device)
+    view = buf[offset:].as_strided((n, H, W), (fstride, pitch, 1))
+    view.copy_(torch.from_numpy(imgs).to(ctx.device))
+    assert view.data_ptr() % 2 == 1 and not view.is_contiguous()
+    mats = np.stack([R.rotation_matrix((18, 11), 33.0, 1.1), np.array([[0.7, -0.3, 6.5], [0.25, 1.2, -2.75]]), np.array([[-1, 0, W - 0.5], [0, 1, 0.25]])])
+    got = ctx.warp_affine(view, mats, (41, 29), 0x5A)
+    assert isinstance(got, torch.Tensor) and got.shape == (n, 29, 41)
+    for f in range(n):
+        want = R.warp_affine(imgs[f], mats[f], (41, 29), 0x5A)
+        assert (got[f].cpu().numpy() == want).all(), f
+        assert (want == 0x5A).any() and (want != 0x5A).any() and not (want == 0xA5).all()
 
 
 # ---- detect_grid end to end -----------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """CPU: the host half of the cv/grid_v2.py drop-in against tests/grid_v2_ref.py -- the Hough transform line for line, cv::RNG's
-generator, the v2 contour search, and the module's host heuristics on hand-computed cases."""
+generator, the v2 contour search, and the module's host heuristics on hand-computed cases; and what the hard inputs of
+tests/test_gpu_grid_v2.py do to the restatement (test_input_*)."""
 import os
 import subprocess
 import sys
@@ -242,3 +243,129 @@ def test_ransac_draws_the_reference_sequence(host):
         np.random.choice(len(pts), 4, replace=False)
     assert np.random.randint(1 << 30) == after
     assert m.fit_quadrilateral_ransac(pts[:3], (240, 320)) is None
+
+
+# ---- the inputs of tests/test_gpu_grid_v2.py's hard cases: what each must do to the restatement, so that a weak input fails here ----
+def _candidates(img, quality_level=0.01, k=0.04):
+    resp = R.harris_response(img, k)
+    return R.harris_candidates(resp, quality_level), resp
+
+
+def test_input_tiling_frames_have_corners_in_the_last_tile():
+    for shape in R.TILING_SHAPES:
+        H, W = shape
+        cand, _ = _candidates(R.corner_squares(shape))
+        where = {(y < 3, x < 3) for _, y, x in cand if (y < 3 or y >= H - 3) and (x < 3 or x >= W - 3)}
+        assert len(cand) == 4 and len(where) == 4, (shape, cand)          # one candidate in each image corner
+        resp = R.harris_response(R.corner_squares(shape, inset=0))          # flush with the corner: the maximum is a border pixel
+        assert np.argmax(resp) == 0 and all(resp[y, x] == resp[0, 0] for y in (0, -1) for x in (0, -1))
+        assert R.harris_candidates(resp, 0.01) == []
+        assert len(_candidates(R.noise(shape, 5))[0]) > 8
+    assert [(H % 16, W % 64) for H, W in R.TILING_SHAPES] == [(0, 0), (1, 1), (2, 2), (1, 1), (3, 63)]     # the last tile's height and width
+
+
+def test_input_frame_maximum_on_the_border():
+    img = R.border_maximum_frame()
+    resp = R.harris_response(img)
+    y, x = np.unravel_index(np.argmax(resp), resp.shape)
+    assert (y, x) == (0, 0) and resp.max() > 0                            # the argmax is on the outermost pixel frame
+    assert [(y, x) for _, y, x in R.harris_candidates(resp, 0.01)] == [(11, 15)]
+    assert R.harris_candidates(resp, 1.0) == []                           # nothing reaches the maximum but the border pixel itself
+    assert len(R.harris_corners(img, quality_level=1.0)[0]) == 0
+
+
+def test_input_checkerboard_484_equal_responses():
+    board = R.checkerboard()
+    for q in (0.0, 0.01, 1.0):
+        cand, resp = _candidates(board, q)
+        assert len(cand) == 484 and len({c[0] for c in cand}) == 1 and cand[0][0] == resp.max()      # v == t at quality_level 1
+    for md in (0, 1):
+        assert len(R.harris_corners(board, 4096, 1.0, md)[0]) == 484      # 484 > 64: several rounds of the loop over the kept corners
+
+
+def test_input_quality_zero_keeps_tiny_maxima():
+    cand, _ = _candidates(R.wide_range_noise(), 0.0)
+    assert len(cand) > 100 and 0 < cand[-1][0] < 1e-6 * cand[0][0]
+    assert len({c[0] for c in cand}) > 50
+
+
+def test_input_large_k_leaves_a_negative_maximum():
+    img = R.noise((37, 53), 1)
+    resp = R.harris_response(img, 0.25)
+    assert -1e-6 < resp.max() < 0 and resp.min() < resp.max()             # not flat, and still no corner
+    assert R.harris_candidates(resp, 0.01) == []
+    assert len(_candidates(img, 0.01, 0.0)[0]) > 50
+
+
+def test_input_candidate_counts():
+    many, _ = _candidates(R.noise(*R.MANY))
+    assert 2048 < len(many) <= 4096 and len(many) == 2771                 # P = 4096: P/2 > 1024, two trips per thread
+    # at min_distance 2 no candidate of this frame falls; at 5 hundreds do, most of them to a kept corner beyond the first 64
+    kw = dict(max_corners=4096, quality_level=0.01)
+    assert len(R.harris_corners(R.noise(*R.MANY), min_distance=2, **kw)[0]) == len(many)
+    spaced = R.harris_corners(R.noise(*R.MANY), min_distance=5, **kw)[0]
+    first_64_only = R.harris_corners(R.noise(*R.MANY), min_distance=5, window=64, **kw)[0]
+    assert 1024 < len(spaced) < len(first_64_only) and (spaced[:64] == first_64_only[:64]).all()
+    assert len(_candidates(R.noise(*R.OVER_CAP))[0]) > 4096
+    n = len(_candidates(R.noise(*R.POWER_OF_TWO))[0])
+    assert n == 64 and n & (n - 1) == 0
+    assert len(_candidates(R.border_maximum_frame())[0]) == 1
+    counts = [len(_candidates(f)[0]) for f in R.uneven_batch()]
+    assert counts[0] == 2771 and counts[0] > 10 * counts[1] and counts[1] > 10 * counts[2] and counts[2] > 0, counts
+
+
+def test_input_tall_frames_expected_lists():
+    """What the minimum-distance rule gives with true row numbers.  A kernel that kept a row in 16 bits would see (2, 65545) as (2, 9)
+    and drop the real (2, 9); in the second frame it would see (2, 65545) and (2, 65549) as rows 9 and 13 and still drop the weaker."""
+    want, _, ncand = R.harris_corners(R.square_column(R.TALL, R.TALL_SQUARES), quality_level=0.01, min_distance=8)
+    assert ncand == 6 and want.tolist() == [[2, 65545], [2, 9], [2, 29999]]
+    want, _, ncand = R.harris_corners(R.square_column(R.TALL, R.TALL_PAIR), quality_level=0.01, min_distance=8)
+    assert ncand == 6 and want.tolist() == [[2, 65545], [2, 99]]          # (2, 65549) is 4 rows from a stronger corner
+    want, _, ncand = R.harris_corners(R.square_column(R.LIMIT, R.LIMIT_SQUARES), quality_level=0.01, min_distance=8)
+    assert ncand == 12 and want.tolist() == [[2, 65519], [2, 32761], [2, 32769], [2, 9], [2, 29999]]    # 8 rows apart: both kept
+
+
+def test_input_fraction_sweep_reaches_every_pair_inside_and_outside():
+    H = W = 36
+    assert all(s.shape == (H, W) and set(np.unique(s)) == {0, 255} for s in R.FRACTION_SOURCES.values())
+    X, Y = R.warp_coords(R.fraction_sweep_matrix(), R.FRACTION_DSIZE)
+    sx, sy, a, b = X >> 5, Y >> 5, X & 31, Y & 31
+    pair = a * 32 + b
+    all_inside = (sx >= 0) & (sx + 1 < W) & (sy >= 0) & (sy + 1 < H)
+    assert len(np.unique(pair)) == 1024
+    assert len(np.unique(pair[all_inside])) == 1024
+    assert len(np.unique(pair[~all_inside])) == 1024
+    for cells, frac, edge in ((sy, b, -1), (sy, b, H - 1), (sx, a, -1), (sx, a, W - 1)):          # each border row and column, between two taps
+        assert ((cells == edge) & (frac != 0)).sum() >= 32
+
+
+def test_input_rounding_mutants_are_visible():
+    dw, dh = R.TIE_DSIZE
+    for name, (src, M, shows) in R.tie_cases().items():
+        inv = R.invert_affine(M)
+        assert all(float(v * 2048).is_integer() for v in inv), inv         # exact: the ties are ties
+        for border in (0, 128):
+            true = R.warp_affine(src, M, R.TIE_DSIZE, border)
+            diff = {r: int((R.warp_affine(src, M, R.TIE_DSIZE, border, rounding=r) != true).sum()) for r in ("half_away", "truncate")}
+            for r in ("half_away", "truncate"):
+                if shows in (r, "both"):
+                    assert diff[r] >= 8, (name, border, diff)
+            if name == "delta":
+                assert diff["truncate"] == 0                               # tie_cases' docstring says why
+    x = np.arange(dw, dtype=np.float64)
+    ties = np.abs(-R._T * x * 1024.0 % 1.0) == 0.5
+    assert ties[1::2].all() and not ties[::2].any()
+
+
+def test_input_degenerate_matrices():
+    src = R.noise((9, 13), 3)
+    out = {k: R.warp_affine(src, np.array(M, np.float64), (17, 6), 77) for k, M in R.DEGENERATE_MATRICES.items()}
+    assert R.invert_affine(R.DEGENERATE_MATRICES["singular"]) == [0.0] * 6 and src[0, 0] != 77
+    assert (out["singular"] == src[0, 0]).all()
+    assert (out["far"] == 77).all()
+    assert out["tiny"][0, 0] == src[0, 0] and (out["tiny"].ravel()[1:] == 77).all()
+    inv = R.invert_affine(R.DEGENERATE_MATRICES["tiny"])
+    assert inv[0] * 1 * 1024.0 > 2 ** 31                                   # adelta saturates at x = 1 ...
+    X, _ = R.warp_coords(R.DEGENERATE_MATRICES["tiny"], (17, 6))
+    assert (X[0, 1:] < 0).all()                                            # ... and 16 + (2^31 - 1) wrapped to a negative position
+    assert (out["flip"] != 77).sum() > 40 and (out["flip"] == 77).any()
