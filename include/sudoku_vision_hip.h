@@ -658,6 +658,58 @@ int sv_jpeg_entropy_encode_batch(const sv_jpeg_enc *plan, int n, const uint64_t 
                                  const int16_t *const *values, const long *values_count, uint8_t *const *outs, const size_t *out_caps,
                                  size_t *out_sizes, int threads, int *status /*n*/);
 
+/* ---- PNG encoder -- the lossless way out of HBM (pipeline/run.py --output solved.png, tools/extract_cells.py's warped_grid.png and cell_r_c.png).
+ * 8 bits per sample, non-interlaced, colour type 2 (RGB, from BGR frames) or 0 (gray); chunks IHDR, one IDAT, IEND.  The IDAT payload is a zlib
+ * stream: 78 01, the bands' deflate streams in order, the final empty block 03 00, the Adler-32 of the filtered bytes.  A band is band_rows whole
+ * rows, filtered from original neighbours and compressed on its own (distance-1 matches only, Z_RLE; one dynamic Huffman block, or one stored block
+ * when that is no larger), ended on a byte boundary by an empty stored block: the GPU writes every band in parallel (csrc/k18_png_encode.hip), the host
+ * adds the container and the checksums (csrc/host_png.cpp).  No libz, no libpng.  16-bit samples, alpha, palettes, interlacing: not written. */
+#define SV_PNG_FILTER_NONE 0
+#define SV_PNG_FILTER_SUB 1             /* cv2's default when no compression parameter is given */
+#define SV_PNG_FILTER_UP 2
+#define SV_PNG_FILTER_AVERAGE 3
+#define SV_PNG_FILTER_PAETH 4
+#define SV_PNG_FILTER_ADAPTIVE 5        /* per row the filter with the smallest sum of abs((int8) byte); the lowest number on a tie */
+#define SV_PNG_RLE 0                    /* literals and distance-1 matches of 3..258 bytes */
+#define SV_PNG_HUFFMAN_ONLY 1           /* literals only */
+#define SV_PNG_STORED 2                 /* stored blocks only */
+typedef struct sv_png_enc {
+    int width, height, channels;        /* channels 1 (gray) or 3 (BGR in, RGB in the file) */
+    int filter, strategy;
+    int band_rows, bands;               /* rows of a band (the last band has the rest), bands of a frame */
+    long row_bytes;                     /* 1 + width * channels: filter-type byte and samples */
+    long filtered_bytes;                /* height * row_bytes */
+    long slot_bytes;                    /* device scratch of one band */
+    long stream_bound;                  /* bytes that hold a frame's bands whatever the image: filtered_bytes + 10 * bands */
+    long out_bound;                     /* bytes that hold the file whatever the image */
+} sv_png_enc;
+
+/* channels 1 or 3; filter SV_PNG_FILTER_*; strategy SV_PNG_*; band_rows 0 = automatic (about 32 KB of filtered bytes, at most 512 rows), else
+ * 1..512 rows with band_rows * row_bytes <= 65535.  Anything else, a NULL plan, or a side outside 1..65535: SV_ERR_BAD_ARG.  A row of more than
+ * 65,535 filtered bytes (width above 21,844 BGR pixels): SV_ERR_UNSUPPORTED. */
+int sv_png_encode_plan(int width, int height, int channels, int filter, int strategy, int band_rows, sv_png_enc *plan);
+
+/* Device half, n frames of plan's size (BGR: a plan of 3 channels; gray: of 1), row pitch `pitch` >= row bytes and frame stride frame_stride in
+ * bytes, any alignment; asynchronous on `stream`.  stream_out receives frame f's bands, contiguous and in order, at f * plan->stream_bound;
+ * band_len, adler and status (n * plan->bands each, 4-byte aligned) the length of every band's piece, the Adler-32 of its filtered bytes and 0 (a
+ * status other than 0 means the band did not fit its slot: its length is 0 and the frame's stream is not a PNG's; the bound makes that
+ * impossible).  The per-band slots live in the context's scratch.  SV_ERR_BAD_ARG: NULL arguments, n outside 1..65535, pitch < row bytes, frames
+ * that overlap, a plan sv_png_encode_plan did not make or of the other entry's channel count, misaligned outputs. */
+int sv_png_deflate_bgr_u8(sv_ctx *ctx, const sv_png_enc *plan, const uint8_t *bgr /*dev*/, int n, ptrdiff_t pitch, ptrdiff_t frame_stride,
+                          uint8_t *stream_out /*dev*/, uint32_t *band_len /*dev*/, uint32_t *adler /*dev*/, uint32_t *status /*dev*/, void *stream);
+int sv_png_deflate_gray_u8(sv_ctx *ctx, const sv_png_enc *plan, const uint8_t *gray /*dev*/, int n, ptrdiff_t pitch, ptrdiff_t frame_stride,
+                           uint8_t *stream_out /*dev*/, uint32_t *band_len /*dev*/, uint32_t *adler /*dev*/, uint32_t *status /*dev*/, void *stream);
+
+/* Host half: one frame's bands (their bytes back to back, band_len[plan->bands], adler[plan->bands]) -> the file.  Each band's bytes must be a
+ * deflate stream of that band's filtered bytes that ends on a byte boundary without a final block, adler[] the Adler-32 of those filtered bytes.
+ * A length above the band's share of stream_bound is SV_ERR_BAD_ARG.  *out_size bytes are written; SV_ERR_BUFFER (with *out_size = what is
+ * needed) when out_cap is too small. */
+int sv_png_assemble(const sv_png_enc *plan, const uint8_t *stream /*host*/, const uint32_t *band_len /*host*/, const uint32_t *adler /*host*/,
+                    uint8_t *out /*host*/, size_t out_cap, size_t *out_size);
+/* n frames of one plan over `threads` host threads.  status[i] = per-image sv_status; returns the first failure. */
+int sv_png_assemble_batch(const sv_png_enc *plan, int n, const uint8_t *const *streams, const uint32_t *const *band_len, const uint32_t *const *adler,
+                          uint8_t *const *outs, const size_t *out_caps, size_t *out_sizes, int threads, int *status /*n*/);
+
 /* ---- quality gate: the per-pixel statistics of cv/grid_quality.py (pipeline/run_v2.py:299-311) ------------------------- */
 
 /* The integer sums behind compute_sharpness (cv/grid_quality.py:48-62) and compute_contrast (:65-87) for n frames:

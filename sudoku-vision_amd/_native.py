@@ -79,6 +79,11 @@ SIGNATURES = {
     "sv_jpeg_forward_gray_u8": [_p, _p, _p, _i, _pd, _pd, _p, _p, _p, _p, _p, _p],
     "sv_jpeg_entropy_encode": [_p, _p, _p, _p, _l, _p, C.c_size_t, _p, _i],
     "sv_jpeg_entropy_encode_batch": [_p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p],
+    "sv_png_encode_plan": [_i, _i, _i, _i, _i, _i, _p],
+    "sv_png_deflate_bgr_u8": [_p, _p, _p, _i, _pd, _pd, _p, _p, _p, _p, _p],
+    "sv_png_deflate_gray_u8": [_p, _p, _p, _i, _pd, _pd, _p, _p, _p, _p, _p],
+    "sv_png_assemble": [_p, _p, _p, _p, _p, C.c_size_t, _p],
+    "sv_png_assemble_batch": [_p, _i, _p, _p, _p, _p, _p, _p, _i, _p],
     "sv_softmax_topk_f32": [_p, _p, _l, _i, _p, _p, _p],
     "sv_resolve_conflicts": [_p, _p, _p, _l, _i, _i, _i, _d, _i] + [_p] * 14,
     "sv_propagate_constraints": [_p, _p, _p, _l, _i] + [_p] * 9,
@@ -137,6 +142,11 @@ class JpegInfo(C.Structure):
 class JpegEnc(C.Structure):
     """sv_jpeg_enc of include/sudoku_vision_hip.h"""
     _fields_ = [("info", JpegInfo), ("quality", C.c_int), ("quant", C.c_uint16 * 192), ("recip", C.c_uint32 * 192), ("out_bound", C.c_long)]
+
+class PngEnc(C.Structure):
+    """sv_png_enc of include/sudoku_vision_hip.h"""
+    _fields_ = [(n, C.c_int) for n in ("width", "height", "channels", "filter", "strategy", "band_rows", "bands")] + \
+               [(n, C.c_long) for n in ("row_bytes", "filtered_bytes", "slot_bytes", "stream_bound", "out_bound")]
 
 
 _lib = None

@@ -1018,6 +1018,36 @@ extern "C" int sv_jpeg_forward_gray_u8(sv_ctx *ctx, const sv_jpeg_enc *plan, con
     return jpeg_forward("sv_jpeg_forward_gray_u8", 1, ctx, plan, gray, n, pitch, img_stride, coef, masks, offsets, values, counts, stream);
 }
 
+// The two deflate entries of the PNG encoder; channels 3 (BGR) or 1 (gray)
+static int png_deflate(const char *fn, int channels, sv_ctx *ctx, const sv_png_enc *plan, const uint8_t *src, int n, ptrdiff_t pitch, ptrdiff_t frame_stride, uint8_t *stream_out,
+                       uint32_t *band_len, uint32_t *adler, uint32_t *status, void *stream)
+{
+    REQUIRE_AS(fn, ctx && plan && src && stream_out && band_len && adler && status, "NULL argument");
+    REQUIRE_AS(fn, n > 0 && n < 65536, "n must be in 1..65535");
+    sv_png_enc want;                                                // a plan is only ever what sv_png_encode_plan made of its six arguments
+    if (sv_png_encode_plan(plan->width, plan->height, plan->channels, plan->filter, plan->strategy, plan->band_rows, &want) != SV_OK || want.band_rows != plan->band_rows ||
+        want.bands != plan->bands || want.row_bytes != plan->row_bytes || want.filtered_bytes != plan->filtered_bytes || want.slot_bytes != plan->slot_bytes ||
+        want.stream_bound != plan->stream_bound || want.out_bound != plan->out_bound)
+        return sv_fail(SV_ERR_BAD_ARG, "%s: the plan was not made by sv_png_encode_plan", fn);
+    REQUIRE_AS(fn, plan->channels == channels, channels == 3 ? "a BGR frame needs a plan of 3 channels" : "a gray frame needs a plan of 1 channel");
+    REQUIRE_AS(fn, pitch >= (ptrdiff_t)channels * plan->width, "pitch smaller than a row");
+    REQUIRE_AS(fn, n == 1 || frame_stride >= pitch * (ptrdiff_t)(plan->height - 1) + (ptrdiff_t)channels * plan->width, "frames overlap");
+    REQUIRE_AS(fn, ((uintptr_t)band_len & 3) == 0 && ((uintptr_t)adler & 3) == 0 && ((uintptr_t)status & 3) == 0, "misaligned output");
+    return svk_png_deflate(ctx, plan, src, n, pitch, frame_stride, stream_out, band_len, adler, status, S(stream));
+}
+
+extern "C" int sv_png_deflate_bgr_u8(sv_ctx *ctx, const sv_png_enc *plan, const uint8_t *bgr, int n, ptrdiff_t pitch, ptrdiff_t frame_stride, uint8_t *stream_out,
+                                     uint32_t *band_len, uint32_t *adler, uint32_t *status, void *stream)
+{
+    return png_deflate("sv_png_deflate_bgr_u8", 3, ctx, plan, bgr, n, pitch, frame_stride, stream_out, band_len, adler, status, stream);
+}
+
+extern "C" int sv_png_deflate_gray_u8(sv_ctx *ctx, const sv_png_enc *plan, const uint8_t *gray, int n, ptrdiff_t pitch, ptrdiff_t frame_stride, uint8_t *stream_out,
+                                      uint32_t *band_len, uint32_t *adler, uint32_t *status, void *stream)
+{
+    return png_deflate("sv_png_deflate_gray_u8", 1, ctx, plan, gray, n, pitch, frame_stride, stream_out, band_len, adler, status, stream);
+}
+
 // K2 into the caller's cells (or the context's), then the forward `model` selects: 0 DigitCNN, 1 DigitCNNv3, 2 DigitCNNv3Light
 static int frames_to_digits(const char *fn, int model, sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv,
                             int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)

@@ -91,6 +91,7 @@ struct sv_ctx {
     long n_cells = 0;           // what features, cells and cells2 hold (sv_ensure_scratch); nonzero only while all three are allocated
     sv_scratch jpeg_planes;     // decoded component planes (MCU-padded) between the IDCT and the colour kernel
     sv_scratch jpeg_enc;        // k17_jpeg_encode.hip: the dense coefficient blocks of a sparse-only encode, int16 [n][coef_count]
+    sv_scratch png_enc;         // k18_png_encode.hip: the per-band slots of a deflate call, u8 [n][bands][slot_bytes]
     sv_scratch pp2;             // k7_preprocess_v2.hip: element rows + doubling planes + the close/open intermediate, or CLAHE's tile histograms + LUTs
     sv_scratch cc;              // k11_components.hip: run numbering, union-find parents and bounding boxes (layout at the top of that file)
     sv_scratch grid2;           // k13_grid_v2.hip: the Harris response, tile and frame maxima, candidate counts and sort keys
@@ -101,7 +102,7 @@ struct sv_ctx {
     // sv_ctx_destroy frees through this and nothing else: a new buffer goes in here
     template <class F> void for_each_scratch(F f)
     {
-        for (sv_scratch *b : {&v3_act, &features, &cells, &cells2, &jpeg_planes, &jpeg_enc, &pp2, &cc, &grid2, &k1_list, &range_flag, &overlay}) f(*b);
+        for (sv_scratch *b : {&v3_act, &features, &cells, &cells2, &jpeg_planes, &jpeg_enc, &png_enc, &pp2, &cc, &grid2, &k1_list, &range_flag, &overlay}) f(*b);
     }
     int precision = 0;          // SV_PREC_F32 / SV_PREC_BF16 (sv_ctx_set_precision)
     int cnn_kernels = 0;        // SV_CNN_AUTO / _F16PAIR / _F32MFMA (sv_ctx_set_cnn_kernels)
@@ -280,6 +281,10 @@ int svk_render_overlay(sv_ctx *ctx, u8 *img, int n, int H, int W, ptrdiff_t pitc
 // k17_jpeg_encode.hip (channels 3: BGR, 1: gray; coef nullptr: dense blocks in ctx->jpeg_enc; masks nullptr: dense output only)
 int svk_jpeg_forward(sv_ctx *ctx, const sv_jpeg_enc *plan, const u8 *src, int channels, int n, ptrdiff_t pitch, ptrdiff_t img_stride, int16_t *coef, uint64_t *masks,
                      uint32_t *offsets, int16_t *values, uint32_t *counts, hipStream_t s);
+
+// k18_png_encode.hip (the plan's channels say BGR or gray; the slots live in ctx->png_enc)
+int svk_png_deflate(sv_ctx *ctx, const sv_png_enc *plan, const u8 *src, int n, ptrdiff_t pitch, ptrdiff_t frame_stride, u8 *stream, uint32_t *band_len, uint32_t *adler,
+                    uint32_t *status, hipStream_t s);
 
 // host helpers
 void sv_gaussian_taps_f32(int n, float *out);

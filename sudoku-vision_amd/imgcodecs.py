@@ -10,6 +10,10 @@ does not decode (progressive, arithmetic, CMYK, 12-bit) raise NativeError instea
 return conventions: a baseline JPEG, quality 95 and 4:2:0 unless `params` says otherwise, byte for byte the file libjpeg-turbo writes.  The
 image may be a numpy array or a CUDA tensor (the frame K16 drew into stays in HBM).  What this encoder does not write -- another extension,
 progressive or optimised files -- raises ValueError; nothing falls back to another encoder.
+
+PNG is written under names of its own: `imencode_png(img, params)` and `imwrite_png(path, img, params)` are `cv2.imencode('.png', img, params)` and
+`cv2.imwrite('x.png', img, params)`: lossless 8-bit RGB or gray files compressed on the GPU (csrc/k18_png_encode.hip).  `imencode('.png', ...)` and
+`imwrite('x.png', ...)` themselves still raise ValueError.
 """
 import os
 
@@ -35,6 +39,16 @@ IMWRITE_JPEG_SAMPLING_FACTOR_420 = 0x221111
 IMWRITE_JPEG_SAMPLING_FACTOR_422 = 0x211111
 IMWRITE_JPEG_SAMPLING_FACTOR_444 = 0x111111
 _SAMPLING_OF_FACTOR = {IMWRITE_JPEG_SAMPLING_FACTOR_420: "420", IMWRITE_JPEG_SAMPLING_FACTOR_422: "422", IMWRITE_JPEG_SAMPLING_FACTOR_444: "444"}
+
+# cv2's values
+IMWRITE_PNG_COMPRESSION = 16
+IMWRITE_PNG_STRATEGY = 17
+IMWRITE_PNG_BILEVEL = 18
+IMWRITE_PNG_STRATEGY_DEFAULT = 0
+IMWRITE_PNG_STRATEGY_FILTERED = 1
+IMWRITE_PNG_STRATEGY_HUFFMAN_ONLY = 2
+IMWRITE_PNG_STRATEGY_RLE = 3
+IMWRITE_PNG_STRATEGY_FIXED = 4
 
 
 def reduce_from_flags(flags):
@@ -116,6 +130,69 @@ def imencode(ext, img, params=None, ctx=None, threads=1):
 def imwrite(path, img, params=None, ctx=None, threads=1):
     """cv2.imwrite: True when the file was written, False when it could not be (cv2.imwrite does not raise for that)."""
     ok, data = imencode(os.path.splitext(os.fspath(path))[1], img, params, ctx=ctx, threads=threads)
+    try:
+        with open(os.fspath(path), "wb") as f:
+            f.write(data.tobytes())
+    except OSError:
+        return False
+    return ok
+
+
+def _png_args(params):
+    """cv2's flat [id, value, ...] list -> Context.imencode_png's keyword arguments.  With no parameter cv2 writes the Sub filter on every row,
+    Z_BEST_SPEED and Z_RLE, and so does this.  IMWRITE_PNG_COMPRESSION 0: stored blocks only.  1..9: cv2 then leaves libpng's own row filtering
+    on, here the adaptive filter (per row the smallest sum of absolute values); the level changes NOTHING else -- this encoder has one effort,
+    distance-1 matches and one Huffman code per band, so 1 and 9 write the same bytes."""
+    params = [] if params is None else [int(p) for p in params]
+    if len(params) % 2:
+        raise ValueError("params is a flat list of (id, value) pairs")
+    kw = {"filter": "sub", "strategy": "rle"}
+    stored = False
+    for pid, value in zip(params[0::2], params[1::2]):
+        if pid == IMWRITE_PNG_COMPRESSION:
+            level = min(max(value, 0), 9)                               # cv2 clamps to 0..9
+            stored = level == 0
+            if level:
+                kw["filter"] = "adaptive"
+        elif pid == IMWRITE_PNG_STRATEGY:
+            if value == IMWRITE_PNG_STRATEGY_RLE:
+                kw["strategy"] = "rle"
+            elif value == IMWRITE_PNG_STRATEGY_HUFFMAN_ONLY:
+                kw["strategy"] = "huffman_only"
+            else:
+                raise ValueError(f"IMWRITE_PNG_STRATEGY {value}: IMWRITE_PNG_STRATEGY_RLE and _HUFFMAN_ONLY are written here (matches at distance 1 only)")
+        elif pid == IMWRITE_PNG_BILEVEL:
+            if value:
+                raise ValueError("bi-level PNG files are not written here (8 bits per sample only)")
+        else:
+            raise ValueError(f"imwrite parameter id {pid} is not one this PNG encoder knows")
+    if stored:
+        kw["strategy"] = "stored"
+    return kw
+
+
+def imencode_png(img, params=None, ctx=None, threads=1):
+    """cv2.imencode('.png', img, params): (True, uint8 numpy array [bytes]).  img: uint8 [H,W,3] BGR, [H,W] or [H,W,1] gray, numpy or CUDA tensor
+    (views with dense rows are read in place by their pitch).  params: see _png_args; anything this encoder does not write raises ValueError."""
+    import torch
+    kw = _png_args(params)
+    ctx = ctx or default_context()
+    if not isinstance(img, torch.Tensor):
+        img = np.asarray(img)
+        if img.dtype != np.uint8:
+            raise ValueError(f"imencode_png: expected a uint8 image, got {img.dtype}")
+        img = torch.from_numpy(np.ascontiguousarray(img)).to(ctx.device)
+    if img.dtype != torch.uint8 or img.dim() not in (2, 3) or (img.dim() == 3 and img.shape[2] not in (1, 3)) or img.numel() == 0:
+        raise ValueError(f"imencode_png: expected a uint8 image [H,W], [H,W,1] or [H,W,3], got {img.dtype} {list(img.shape)}")
+    if img.dim() == 3 and img.shape[2] == 1:
+        img = img[:, :, 0]
+    data = ctx.imencode_png(img, threads=threads, **kw)
+    return True, np.frombuffer(data, np.uint8)
+
+
+def imwrite_png(path, img, params=None, ctx=None, threads=1):
+    """cv2.imwrite(path, img, params) for a PNG file, whatever the path's extension: True when the file was written, False when it could not be."""
+    ok, data = imencode_png(img, params, ctx=ctx, threads=threads)
     try:
         with open(os.fspath(path), "wb") as f:
             f.write(data.tobytes())

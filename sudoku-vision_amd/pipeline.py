@@ -464,6 +464,14 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     return res
 
 
+def _encode_frame_out(ctx, res, encode):
+    """recognize_stream's encode: True -> res["jpeg"], "png" -> res["png"]"""
+    if encode == "png":
+        res["png"] = ctx.imencode_png(res["frame_out"])
+    else:
+        res["jpeg"] = ctx.imencode(res["frame_out"])
+
+
 def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_RUNPY, preprocess="v1", grid="v1", stabilizer=None, motion_detector=None, overlay=False, solve_max_nodes=4096, encode=False):
     """A camera feed: the loop of cv/stabilizer.py:308-335 followed by this library's recognition.  frames: an iterable of BGR frames
     (numpy uint8 [H,W,3] or CUDA uint8 tensors).  A generator; per frame it yields a dict:
@@ -480,6 +488,8 @@ def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_
                       (Context.render_overlay) where solve_result is 1; the input frame itself for a skipped or unsolved frame
     encode=True (needs overlay=True, else ValueError) adds
         jpeg          the bytes of frame_out as a JPEG file (Context.imencode: quality 95, 4:2:0, cv2.imwrite's defaults)
+    encode="png" (needs overlay=True too) adds instead
+        png           the bytes of frame_out as a PNG file (Context.imencode_png: Sub filter, Z_RLE, cv2.imwrite's defaults)
     preprocess, grid: "v1" | "v2" as in recognize_image (grid="v1": K1's binary and the host contour search; "v2":
     cv.grid_v2.detect_grid).  stabilizer, motion_detector: the GridStabilizer / MotionDetector to use (default: new ones with the
     reference's defaults).  With the default use_kalman=True the stabilised corners of the first min_detections - 1 detections are
@@ -511,7 +521,7 @@ def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_
             res.update(solution=None, solve_result=None, frame_out=frame[0])
         if res["motion"]:
             if encode:
-                res["jpeg"] = ctx.imencode(res["frame_out"])
+                _encode_frame_out(ctx, res, encode)
             yield res
             continue
         if preprocess == "v2":
@@ -542,7 +552,7 @@ def recognize_stream(frames, model_state_dict=None, ctx=None, glue=Context.GLUE_
                     if code == 1:
                         res["frame_out"] = _draw_solution(ctx, frame, used, res["digits"], sol, True)[0]
         if encode:
-            res["jpeg"] = ctx.imencode(res["frame_out"])
+            _encode_frame_out(ctx, res, encode)
         yield res
 
 

@@ -791,6 +791,91 @@ class Context:
         _dev_tensor(frame, "frame", torch.uint8, self.device, ndim=(2, 3))
         return self.imencode_batch(frame[None], quality, sampling, restart, threads)[0]
 
+    # ---- PNG encoder (cv2.imwrite of a .png path: pipeline/run.py --output solved.png, tools/extract_cells.py) ------------------------
+    PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+    PNG_STRATEGIES = {"rle": 0, "huffman_only": 1, "stored": 2}
+
+    def png_encode_plan(self, width, height, channels, filter="sub", strategy="rle", band_rows=0):
+        """sv_png_encode_plan, cached: the bands and size bounds of one (shape, filter, strategy, band_rows).  band_rows 0: automatic.
+        ValueError for what the encoder does not write."""
+        if str(filter) not in self.PNG_FILTERS:
+            raise ValueError(f"filter must be one of {sorted(self.PNG_FILTERS)}, not {filter!r}")
+        if str(strategy) not in self.PNG_STRATEGIES:
+            raise ValueError(f"strategy must be one of {sorted(self.PNG_STRATEGIES)}, not {strategy!r}")
+        if not isinstance(band_rows, (int, np.integer)) or band_rows < 0:
+            raise ValueError(f"band_rows must be a non-negative integer, not {band_rows!r}")
+        if channels not in (1, 3) or not (0 < width < 65536 and 0 < height < 65536):
+            raise ValueError(f"cannot encode a {height} x {width} image of {channels} channels")
+        key = (int(width), int(height), int(channels), str(filter), str(strategy), int(band_rows))
+        plans = self.__dict__.setdefault("_png_plans", {})
+        if key not in plans:
+            plan = _native.PngEnc()
+            self._check(self._lib.sv_png_encode_plan(*key[:3], self.PNG_FILTERS[key[3]], self.PNG_STRATEGIES[key[4]], key[5], C.byref(plan)), "sv_png_encode_plan")
+            plans[key] = plan
+        return plans[key]
+
+    def png_deflate(self, frames, plan):
+        """The device half alone (sv_png_deflate_bgr_u8 / _gray_u8) on the current stream: (stream u8 [n, stream_bound], band_len u32 [n, bands],
+        adler u32 [n, bands], status u32 [n, bands]).  Frame f's bands lie back to back at the start of stream[f]; sum(band_len[f]) bytes count."""
+        frames, ch = self._enc_frames(frames)
+        x, pitch, stride = _batch_layout(frames, self.device, "frames", ch)
+        n = x.shape[0]
+        if x.shape[1] == 1:
+            pitch = max(pitch, x.shape[2] * ch)                        # the stride of a one-row dimension is whatever the view left there
+        if (plan.height, plan.width, plan.channels) != (x.shape[1], x.shape[2], ch):
+            raise ValueError("the plan was made for another shape")
+        stream = torch.empty((n, int(plan.stream_bound)), dtype=torch.uint8, device=self.device)
+        band_len, adler, status = (torch.empty((n, int(plan.bands)), dtype=torch.int32, device=self.device) for _ in range(3))
+        fn = self._lib.sv_png_deflate_bgr_u8 if ch == 3 else self._lib.sv_png_deflate_gray_u8
+        self._check(fn(self._h, C.byref(plan), _ptr(x), n, pitch, stride, _ptr(stream), _ptr(band_len), _ptr(adler), _ptr(status), _stream_ptr()), "sv_png_deflate")
+        return stream, band_len, adler, status
+
+    def imencode_png_batch(self, frames, filter="sub", strategy="rle", threads=1, band_rows=0):
+        """cv2.imencode('.png', frame)[1].tobytes() for every frame of a uint8 CUDA batch [n,H,W,3] (BGR) or [n,H,W] (gray), or a list of
+        same-shaped frames -> list of bytes: 8-bit RGB or gray PNG files, IHDR + one IDAT + IEND.  Lossless; the pixels are what any PNG reader gives
+        back, the bytes are this encoder's own (bands of rows compressed independently on the GPU, csrc/k18_png_encode.hip).  The defaults are
+        cv2's: the Sub filter and distance-1 matches (Z_RLE).  Only the compressed bytes and the bands' lengths cross PCIe; `threads` host
+        threads add the container and the checksums (csrc/host_png.cpp), one image each.  Synchronises the current stream."""
+        frames, ch = self._enc_frames(frames)
+        n, H, W = frames.shape[:3]
+        plan = self.png_encode_plan(W, H, ch, filter, strategy, band_rows)
+        bands, bound = int(plan.bands), int(plan.stream_bound)
+        step = max(1, min(n, self._ENC_CHUNK_BYTES // (bound + 12 * bands)))
+        stream = torch.cuda.current_stream(self.device)
+        out = []
+        for at in range(0, n, step):
+            m = min(step, n - at)
+            data, band_len, adler, status = self.png_deflate(frames[at:at + m], plan)
+            head = 12 * bands * m                                      # the lengths, Adler sums and statuses of the chunk
+            pin = self._enc_pinned(head)
+            for k, t in enumerate((band_len, adler, status)):
+                pin[4 * bands * m * k:4 * bands * m * (k + 1)].view(torch.int32).copy_(t.view(-1), non_blocking=True)
+            stream.synchronize()
+            meta = pin[:head].view(torch.int32).numpy().view(np.uint32).reshape(3, m, bands).copy()
+            if meta[2].any():
+                raise _native.NativeError("sv_png_deflate: a band did not fit its slot")
+            used = meta[0].sum(axis=1, dtype=np.int64)
+            starts = np.concatenate([[0], np.cumsum(used + 1)]).astype(np.int64)                               # never an empty stretch
+            pin = self._enc_pinned(int(starts[-1]))
+            for i in range(m):
+                if used[i]:
+                    pin[int(starts[i]):int(starts[i] + used[i])].copy_(data[i, :int(used[i])], non_blocking=True)
+            stream.synchronize()
+            pb = pin.data_ptr()
+            bufs = [np.empty(int(u) + 80, np.uint8) for u in used]
+            VP = C.c_void_p * m
+            sizes, rcs = (C.c_size_t * m)(), (C.c_int * m)()
+            self._check(self._lib.sv_png_assemble_batch(
+                C.byref(plan), m, VP(*[pb + int(s) for s in starts[:m]]), VP(*[meta[0, i].ctypes.data for i in range(m)]), VP(*[meta[1, i].ctypes.data for i in range(m)]),
+                VP(*[b.ctypes.data for b in bufs]), (C.c_size_t * m)(*[b.size for b in bufs]), sizes, int(threads), rcs), "sv_png_assemble_batch")
+            out += [bufs[i][:sizes[i]].tobytes() for i in range(m)]
+        return out
+
+    def imencode_png(self, frame, filter="sub", strategy="rle", threads=1, band_rows=0):
+        """One uint8 CUDA frame [H,W,3] (BGR) or [H,W] (gray), any row pitch -> the bytes of its PNG file (imencode_png_batch of one frame)."""
+        _dev_tensor(frame, "frame", torch.uint8, self.device, ndim=(2, 3))
+        return self.imencode_png_batch(frame[None], filter, strategy, threads, band_rows)[0]
+
     def softmax_topk(self, logits, k=3):
         """F.softmax(logits, 1).topk(k) (pipeline/run_v2.py:165-178): (index u8 [B,k], prob f32 [B,k]), best first."""
         logits = _dev_tensor(logits, "logits", torch.float32, self.device).reshape(-1, 10).contiguous()
