@@ -710,6 +710,59 @@ int sv_png_assemble(const sv_png_enc *plan, const uint8_t *stream /*host*/, cons
 int sv_png_assemble_batch(const sv_png_enc *plan, int n, const uint8_t *const *streams, const uint32_t *const *band_len, const uint32_t *const *adler,
                           uint8_t *const *outs, const size_t *out_caps, size_t *out_sizes, int threads, int *status /*n*/);
 
+/* ---- PNG decoder -- cv2.imread(path) for a .png (pipeline/run.py:250, pipeline/run_v2.py, tools/extract_cells.py reading back warped_grid.png
+ * and cell_r_c.png).  Split as the JPEG decoder is: the serial entropy stage (inflate) runs on host threads (csrc/host_png.cpp, no libz, no
+ * libpng), the unfilter and the expansion to BGR on the GPU (csrc/k19_png_decode.hip).  Colour types 0, 2, 3, 4, 6 at every bit depth the
+ * specification allows, non-interlaced.  The frame is what cv2.imread(path, IMREAD_COLOR) returns: 16-bit samples keep their high byte, gray
+ * samples below 8 bits are scaled by bit replication, palette indices go through PLTE, alpha is dropped (not composited), gray is replicated
+ * and RGB becomes BGR; tRNS, gAMA and every other ancillary chunk are ignored.  Adam7, IMREAD_UNCHANGED / _GRAYSCALE / _ANYDEPTH: not decoded. */
+#define SV_PNG_MAX_FILTERED_BYTES (1L << 29)  /* 512 MiB of filtered bytes per image; a larger file is SV_ERR_UNSUPPORTED */
+#define SV_PNG_MAX_SIDE 65535                 /* as for the encoder; a larger side is SV_ERR_UNSUPPORTED */
+#define SV_PNG_PALETTE_STRIDE 1024            /* device palette of one image: 256 RGB entries, then the entry count as a uint32 at byte 768 */
+typedef struct sv_png_info {
+    int width, height;
+    int bit_depth;                      /* 1, 2, 4, 8, 16 */
+    int color_type;                     /* 0 gray, 2 RGB, 3 palette, 4 gray + alpha, 6 RGB + alpha */
+    int interlace;                      /* 0 (a file with 1, Adam7, is refused) */
+    int channels;                       /* samples per pixel in the file: 1, 3, 1, 2, 4 */
+    int bpp;                            /* the filters' left distance: max(1, channels * bit_depth / 8) */
+    int palette_entries;                /* 0 without PLTE */
+    long row_bytes;                     /* ceil(width * channels * bit_depth / 8) */
+    long filtered_bytes;                /* height * (1 + row_bytes): what the zlib stream must inflate to, exactly */
+    long idat_offset;                   /* the first IDAT chunk's offset in the file */
+    uint8_t palette[768];               /* PLTE's RGB entries, zero beyond palette_entries */
+} sv_png_info;
+
+/* Signature, chunk walk, the CRC-32 of every critical chunk, IHDR, PLTE (pipeline/run.py:250: what cv2.imread checks before it decodes).
+ * SV_ERR_UNSUPPORTED: an Adam7 file, filtered_bytes above SV_PNG_MAX_FILTERED_BYTES, a side above SV_PNG_MAX_SIDE.  SV_ERR_BAD_ARG: anything
+ * malformed -- a bad signature or CRC, a missing IHDR, IDAT or IEND, chunks out of order, IDATs that are not consecutive, colour type 3 without
+ * PLTE, an unknown critical chunk, a (colour type, depth) pair the specification does not have, a side of 0.  Ancillary chunks are skipped unread. */
+int sv_png_parse(const uint8_t *data /*host*/, size_t size, sv_png_info *info);
+
+/* The IDAT payloads, taken as one zlib stream without copying them together (a block, a code or the header may straddle chunks), inflated into
+ * filtered[0 .. info->filtered_bytes) (pipeline/run.py:250: the serial half of cv2.imread).  cap < filtered_bytes is SV_ERR_BUFFER; nothing past
+ * filtered_bytes is ever written and inflation stops the moment the stream would produce more.  row_filter (height bytes, may be NULL) receives
+ * each row's filter byte.  SV_ERR_BAD_ARG for every malformed stream: a bad zlib header (CM != 8, window > 32 K, FDICT, FCHECK), truncated
+ * input, stored LEN != ~NLEN, block type 3, an over-subscribed code, an incomplete code (but a single code of one bit, which zlib accepts), a
+ * code-length repeat without a previous length or past HLIT + HDIST, no end-of-block code, a distance before the start of the output, a wrong
+ * Adler-32, fewer or more than filtered_bytes bytes, a filter byte above 4. */
+int sv_png_inflate(const uint8_t *data /*host*/, size_t size, const sv_png_info *info, uint8_t *filtered /*host*/, size_t cap, uint8_t *row_filter /*host or NULL*/);
+/* n files over `threads` host threads.  status[i] = per-image sv_status; returns the first failure. */
+int sv_png_inflate_batch(const uint8_t *const *datas, const size_t *sizes, const sv_png_info *infos, int n, uint8_t *const *filtered, const size_t *caps,
+                         uint8_t *const *row_filters /*or NULL*/, int threads, int *status /*n*/);
+
+/* Device half (pipeline/run.py:250: the rest of cv2.imread, the frame left in HBM for K1/K2): n images of info's geometry, image i's filtered
+ * bytes at filtered + i * info->filtered_bytes, -> BGR frames, row pitch `pitch` >= 3 * width, frame i at out + i * frame_stride; asynchronous on
+ * `stream`, never synchronises with the host; the unfiltered samples live in the context's scratch.  row_filter: n * height filter bytes on the
+ * device (what sv_png_inflate copied out); the kernels find the segments of rows from them, and a value above 4 is taken as 0 (None).  palette:
+ * n * SV_PNG_PALETTE_STRIDE bytes for colour type 3, else NULL.  status (n uint32, 4-byte aligned) is zeroed on the stream, then bit 0 of
+ * status[i] is set when image i held a palette index past its palette's end (that pixel is black; cv2 fails on such a file).  Only the
+ * geometry fields of info are read.  SV_ERR_BAD_ARG: NULL arguments, n outside 1..65535, pitch < 3 * width, frames that overlap, an info
+ * sv_png_parse would not have produced. */
+int sv_png_reconstruct_bgr_u8(sv_ctx *ctx, const sv_png_info *info, const uint8_t *filtered /*dev*/, const uint8_t *row_filter /*dev*/,
+                              const uint8_t *palette /*dev or NULL*/, int n, uint8_t *out /*dev*/, ptrdiff_t pitch, ptrdiff_t frame_stride,
+                              uint32_t *status /*dev*/, void *stream);
+
 /* ---- quality gate: the per-pixel statistics of cv/grid_quality.py (pipeline/run_v2.py:299-311) ------------------------- */
 
 /* The integer sums behind compute_sharpness (cv/grid_quality.py:48-62) and compute_contrast (:65-87) for n frames:

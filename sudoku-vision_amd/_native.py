@@ -84,6 +84,10 @@ SIGNATURES = {
     "sv_png_deflate_gray_u8": [_p, _p, _p, _i, _pd, _pd, _p, _p, _p, _p, _p],
     "sv_png_assemble": [_p, _p, _p, _p, _p, C.c_size_t, _p],
     "sv_png_assemble_batch": [_p, _i, _p, _p, _p, _p, _p, _p, _i, _p],
+    "sv_png_parse": [_p, C.c_size_t, _p],
+    "sv_png_inflate": [_p, C.c_size_t, _p, _p, C.c_size_t, _p],
+    "sv_png_inflate_batch": [_p, _p, _p, _i, _p, _p, _p, _i, _p],
+    "sv_png_reconstruct_bgr_u8": [_p, _p, _p, _p, _p, _i, _p, _pd, _pd, _p, _p],
     "sv_softmax_topk_f32": [_p, _p, _l, _i, _p, _p, _p],
     "sv_resolve_conflicts": [_p, _p, _p, _l, _i, _i, _i, _d, _i] + [_p] * 14,
     "sv_propagate_constraints": [_p, _p, _p, _l, _i] + [_p] * 9,
@@ -147,6 +151,13 @@ class PngEnc(C.Structure):
     """sv_png_enc of include/sudoku_vision_hip.h"""
     _fields_ = [(n, C.c_int) for n in ("width", "height", "channels", "filter", "strategy", "band_rows", "bands")] + \
                [(n, C.c_long) for n in ("row_bytes", "filtered_bytes", "slot_bytes", "stream_bound", "out_bound")]
+
+class PngInfo(C.Structure):
+    """sv_png_info of include/sudoku_vision_hip.h"""
+    _fields_ = [(n, C.c_int) for n in ("width", "height", "bit_depth", "color_type", "interlace", "channels", "bpp", "palette_entries")] + \
+               [(n, C.c_long) for n in ("row_bytes", "filtered_bytes", "idat_offset")] + [("palette", C.c_uint8 * 768)]
+
+PNG_PALETTE_STRIDE = 1024
 
 
 _lib = None

@@ -1048,6 +1048,21 @@ extern "C" int sv_png_deflate_gray_u8(sv_ctx *ctx, const sv_png_enc *plan, const
     return png_deflate("sv_png_deflate_gray_u8", 1, ctx, plan, gray, n, pitch, frame_stride, stream_out, band_len, adler, status, stream);
 }
 
+// The PNG decoder's device half.  Only the geometry of the info is used, and only one sv_png_parse could have produced.
+extern "C" int sv_png_reconstruct_bgr_u8(sv_ctx *ctx, const sv_png_info *info, const uint8_t *filtered, const uint8_t *row_filter, const uint8_t *palette, int n, uint8_t *out,
+                                         ptrdiff_t pitch, ptrdiff_t frame_stride, uint32_t *status, void *stream)
+{
+    REQUIRE(ctx && info && filtered && row_filter && out && status, "NULL argument");
+    REQUIRE(n > 0 && n < 65536, "n must be in 1..65535");
+    REQUIRE(sv_png_geometry_ok(info), "the info was not made by sv_png_parse");
+    const int type = info->color_type;
+    REQUIRE(type != 3 || palette, "colour type 3 needs a palette");
+    REQUIRE(pitch >= 3 * (ptrdiff_t)info->width, "pitch smaller than a row");
+    REQUIRE(n == 1 || frame_stride >= pitch * (ptrdiff_t)(info->height - 1) + 3 * (ptrdiff_t)info->width, "frames overlap");
+    REQUIRE(((uintptr_t)status & 3) == 0 && ((uintptr_t)palette & 3) == 0, "misaligned status or palette");
+    return svk_png_reconstruct(ctx, info, filtered, row_filter, type == 3 ? palette : nullptr, n, out, pitch, frame_stride, status, S(stream));
+}
+
 // K2 into the caller's cells (or the context's), then the forward `model` selects: 0 DigitCNN, 1 DigitCNNv3, 2 DigitCNNv3Light
 static int frames_to_digits(const char *fn, int model, sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv,
                             int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)

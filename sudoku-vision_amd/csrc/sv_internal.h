@@ -92,6 +92,7 @@ struct sv_ctx {
     sv_scratch jpeg_planes;     // decoded component planes (MCU-padded) between the IDCT and the colour kernel
     sv_scratch jpeg_enc;        // k17_jpeg_encode.hip: the dense coefficient blocks of a sparse-only encode, int16 [n][coef_count]
     sv_scratch png_enc;         // k18_png_encode.hip: the per-band slots of a deflate call, u8 [n][bands][slot_bytes]
+    sv_scratch png_dec;         // k19_png_decode.hip: the unfiltered samples u8 [n][H][row_bytes], then the segment job list
     sv_scratch pp2;             // k7_preprocess_v2.hip: element rows + doubling planes + the close/open intermediate, or CLAHE's tile histograms + LUTs
     sv_scratch cc;              // k11_components.hip: run numbering, union-find parents and bounding boxes (layout at the top of that file)
     sv_scratch grid2;           // k13_grid_v2.hip: the Harris response, tile and frame maxima, candidate counts and sort keys
@@ -102,7 +103,7 @@ struct sv_ctx {
     // sv_ctx_destroy frees through this and nothing else: a new buffer goes in here
     template <class F> void for_each_scratch(F f)
     {
-        for (sv_scratch *b : {&v3_act, &features, &cells, &cells2, &jpeg_planes, &jpeg_enc, &png_enc, &pp2, &cc, &grid2, &k1_list, &range_flag, &overlay}) f(*b);
+        for (sv_scratch *b : {&v3_act, &features, &cells, &cells2, &jpeg_planes, &jpeg_enc, &png_enc, &png_dec, &pp2, &cc, &grid2, &k1_list, &range_flag, &overlay}) f(*b);
     }
     int precision = 0;          // SV_PREC_F32 / SV_PREC_BF16 (sv_ctx_set_precision)
     int cnn_kernels = 0;        // SV_CNN_AUTO / _F16PAIR / _F32MFMA (sv_ctx_set_cnn_kernels)
@@ -285,6 +286,13 @@ int svk_jpeg_forward(sv_ctx *ctx, const sv_jpeg_enc *plan, const u8 *src, int ch
 // k18_png_encode.hip (the plan's channels say BGR or gray; the slots live in ctx->png_enc)
 int svk_png_deflate(sv_ctx *ctx, const sv_png_enc *plan, const u8 *src, int n, ptrdiff_t pitch, ptrdiff_t frame_stride, u8 *stream, uint32_t *band_len, uint32_t *adler,
                     uint32_t *status, hipStream_t s);
+
+// k19_png_decode.hip (the unfiltered samples and the job list live in ctx->png_dec)
+int svk_png_reconstruct(sv_ctx *ctx, const sv_png_info *info, const u8 *filtered, const u8 *row_filter, const u8 *palette, int n, u8 *out, ptrdiff_t pitch,
+                        ptrdiff_t frame_stride, uint32_t *status, hipStream_t s);
+
+// host_png.cpp: whether an sv_png_info's geometry is one sv_png_parse produces (format table, limits, derived fields)
+bool sv_png_geometry_ok(const sv_png_info *info);
 
 // host helpers
 void sv_gaussian_taps_f32(int n, float *out);

@@ -278,3 +278,48 @@ def jpeg_entropy_decode_sparse(data: bytes, threads=1):
                                                               vals.ctypes.data_as(C.c_void_p), vals.size, C.byref(used), quant.ctypes.data_as(C.c_void_p), int(threads)),
                   "sv_jpeg_entropy_decode_sparse")
     return info, masks, offs, vals[:used.value], quant
+
+
+# ---- PNG front end, host half (csrc/host_png.cpp): the container's parser and the inflater ---------------------
+def png_parse(data: bytes):
+    """-> _native.PngInfo (sv_png_info).  Raises NativeError: SV_ERR_BAD_ARG for anything that is not a well-formed PNG file, SV_ERR_UNSUPPORTED
+    for an Adam7 file or one above the size limits."""
+    info = _native.PngInfo()
+    _native.check(_native.lib().sv_png_parse(data, len(data), C.byref(info)), "sv_png_parse")
+    return info
+
+
+def png_inflate(data: bytes, info=None, filtered=None):
+    """-> (info, filtered uint8 [filtered_bytes], row_filter uint8 [height]): the IDAT chunks' zlib stream inflated, and each row's filter byte.
+    `filtered` may be a caller-owned (e.g. pinned) contiguous uint8 array; fewer than info.filtered_bytes bytes raise SV_ERR_BUFFER.  Every
+    malformed stream raises NativeError (SV_ERR_BAD_ARG)."""
+    info = info or png_parse(data)
+    if filtered is None:
+        filtered = np.empty(info.filtered_bytes, np.uint8)
+    if filtered.dtype != np.uint8 or not filtered.flags.c_contiguous:
+        raise ValueError("filtered must be a contiguous uint8 array")
+    row_filter = np.empty(info.height, np.uint8)
+    _native.check(_native.lib().sv_png_inflate(data, len(data), C.byref(info), filtered.ctypes.data_as(C.c_void_p), filtered.size,
+                                               row_filter.ctypes.data_as(C.c_void_p)), "sv_png_inflate")
+    return info, filtered[:info.filtered_bytes], row_filter
+
+
+def png_inflate_batch(datas, infos=None, threads=None):
+    """-> (infos, [filtered], [row_filter], status int [n]) over `threads` host threads; a file that fails has its sv_status in status[i] (0: fine)
+    and nothing is raised for it.  A file sv_png_parse refuses raises."""
+    datas = [bytes(d) for d in datas]
+    n = len(datas)
+    infos = infos or [png_parse(d) for d in datas]
+    if len(infos) != n:
+        raise ValueError(f"{len(infos)} infos for {n} files")
+    arr = (_native.PngInfo * n)(*infos)
+    outs = [np.empty(int(i.filtered_bytes), np.uint8) for i in infos]
+    rows = [np.empty(int(i.height), np.uint8) for i in infos]
+    VP = C.c_void_p * n
+    status = (C.c_int * n)()
+    if not threads:                                                     # the CPUs this process may run on, 16 at the most: never the whole host
+        cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        threads = max(1, min(n, cpus, 16))
+    _native.lib().sv_png_inflate_batch((C.c_char_p * n)(*datas), (C.c_size_t * n)(*[len(d) for d in datas]), arr, n, VP(*[o.ctypes.data for o in outs]),
+                                       (C.c_size_t * n)(*[o.size for o in outs]), VP(*[r.ctypes.data for r in rows]), int(threads), status)
+    return infos, outs, rows, np.array(list(status), np.int32)

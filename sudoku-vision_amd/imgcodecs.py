@@ -14,6 +14,10 @@ progressive or optimised files -- raises ValueError; nothing falls back to anoth
 PNG is written under names of its own: `imencode_png(img, params)` and `imwrite_png(path, img, params)` are `cv2.imencode('.png', img, params)` and
 `cv2.imwrite('x.png', img, params)`: lossless 8-bit RGB or gray files compressed on the GPU (csrc/k18_png_encode.hip).  `imencode('.png', ...)` and
 `imwrite('x.png', ...)` themselves still raise ValueError.
+
+PNG is read under names of its own too: `imdecode_png(buf)` and `imread_png(path)` are `cv2.imdecode(buf, IMREAD_COLOR)` and `cv2.imread(path)` for
+PNG files of every colour type and bit depth, non-interlaced: inflate on host threads (csrc/host_png.cpp), unfilter and expansion to BGR on the
+GPU (csrc/k19_png_decode.hip).  `imread` and `imdecode` themselves still take JPEG only.
 """
 import os
 
@@ -136,6 +140,31 @@ def imwrite(path, img, params=None, ctx=None, threads=1):
     except OSError:
         return False
     return ok
+
+
+def imdecode_png(buf, device=False, ctx=None, threads=1):
+    """cv2.imdecode(buf, IMREAD_COLOR) for the bytes of a PNG file: a BGR uint8 image [H,W,3] whatever the file's colour type and bit depth (16-bit
+    samples keep their high byte, gray is replicated, palettes are looked up, alpha is dropped), or None for a file cv2 would fail to read.
+    device=True keeps it on the GPU (CUDA uint8 tensor).  An Adam7 file raises NativeError (SV_ERR_UNSUPPORTED) instead of returning a wrong image."""
+    data = bytes(buf)
+    ctx = ctx or default_context()
+    try:
+        img = ctx.imdecode_png(data, threads=threads)
+    except _native.NativeError as e:
+        if "SV_ERR_BAD_ARG" not in str(e):                              # only a malformed file is None; a failed launch or allocation is not a bad file
+            raise
+        return None
+    return img if device else img.cpu().numpy()
+
+
+def imread_png(path, device=False, ctx=None, threads=1):
+    """cv2.imread(path) for a PNG file, whatever the path's extension; None also when the file cannot be opened."""
+    try:
+        with open(os.fspath(path), "rb") as f:
+            data = f.read()
+    except OSError:
+        return None
+    return imdecode_png(data, device=device, ctx=ctx, threads=threads)
 
 
 def _png_args(params):

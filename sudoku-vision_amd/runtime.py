@@ -876,6 +876,91 @@ class Context:
         _dev_tensor(frame, "frame", torch.uint8, self.device, ndim=(2, 3))
         return self.imencode_png_batch(frame[None], filter, strategy, threads, band_rows)[0]
 
+    # ---- PNG decoder (cv2.imread of a .png path: pipeline/run.py:250, tools/extract_cells.py's files read back) -------------------------
+    _PNG_CHUNK_BYTES = 512 << 20                                       # filtered bytes staged per set of launches of an imdecode_png_batch
+
+    def png_reconstruct(self, info, filtered, row_filter, palette=None, out=None):
+        """The device half alone (sv_png_reconstruct_bgr_u8) on the current stream.  filtered u8 [n, filtered_bytes], row_filter u8 [n, height],
+        palette u8 [n, 1024] (colour type 3) on the device -> (out u8 [n,H,W,3], status i32 [n]); status[i] & 1: image i held a palette index past
+        its palette's end.  out: a caller's [n,H,W,3] view with dense pixels (row padding and gaps between frames are left untouched)."""
+        n, H, W = filtered.shape[0], int(info.height), int(info.width)
+        _dev_tensor(filtered, "filtered", torch.uint8, self.device, shape=(n, int(info.filtered_bytes)))
+        _dev_tensor(row_filter, "row_filter", torch.uint8, self.device, shape=(n, H))
+        if palette is not None:
+            _dev_tensor(palette, "palette", torch.uint8, self.device, shape=(n, _native.PNG_PALETTE_STRIDE))
+        if not (filtered.is_contiguous() and row_filter.is_contiguous() and (palette is None or palette.is_contiguous())):
+            raise ValueError("filtered, row_filter and palette must be contiguous")
+        if out is None:
+            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
+        _dev_tensor(out, "out", torch.uint8, self.device, shape=(n, H, W, 3))
+        st = out.stride()
+        pitch = st[1] if H > 1 else max(st[1], 3 * W)
+        stride = st[0] if n > 1 else pitch * H
+        if st[3] != 1 or st[2] != 3 or pitch < 3 * W or (n > 1 and stride < pitch * (H - 1) + 3 * W):
+            raise ValueError("out must be a [n,H,W,3] view with dense pixels and rows and frames that do not overlap")
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._check(self._lib.sv_png_reconstruct_bgr_u8(self._h, C.byref(info), _ptr(filtered), _ptr(row_filter), _opt_ptr(palette), n, _ptr(out), pitch, stride,
+                                                        _ptr(status), _stream_ptr()), "sv_png_reconstruct_bgr_u8")
+        return out, status
+
+    def imdecode_png_batch(self, datas, threads=16, out=None):
+        """PNG files of ONE geometry (size, bit depth, colour type; anything else is a ValueError) -> uint8 CUDA tensor [n,H,W,3], each frame what
+        cv2.imdecode(buf, IMREAD_COLOR) returns.  `threads` host threads inflate into pinned memory (csrc/host_png.cpp), the filtered bytes cross
+        PCIe in one copy and one set of launches unfilters and expands them (csrc/k19_png_decode.hip); batches above 512 MiB of filtered bytes go
+        in several such sets.  NativeError for a file that is malformed (SV_ERR_BAD_ARG) or not decoded here (SV_ERR_UNSUPPORTED: Adam7).  Returns
+        after the last launch, but for palette files, whose indices the GPU checks: those synchronise the current stream."""
+        from . import host
+        datas = [bytes(d) for d in datas]
+        n = len(datas)
+        if n == 0:
+            raise ValueError("imdecode_png_batch needs at least one file")
+        infos = [host.png_parse(d) for d in datas]
+        info = infos[0]
+        key = lambda i: (i.width, i.height, i.bit_depth, i.color_type)
+        if any(key(i) != key(info) for i in infos):
+            raise ValueError("imdecode_png_batch: the files differ in size, bit depth or colour type")
+        H, W, fb, ps = int(info.height), int(info.width), int(info.filtered_bytes), _native.PNG_PALETTE_STRIDE
+        if out is None:
+            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
+        _dev_tensor(out, "out", torch.uint8, self.device, shape=(n, H, W, 3))
+        paletted = info.color_type == 3
+        step = max(1, min(n, self._PNG_CHUNK_BYTES // (fb + H + ps)))
+        stream = torch.cuda.current_stream(self.device)
+        flags = []
+        for at in range(0, n, step):
+            m = min(step, n - at)
+            rows_at = m * fb
+            pal_at = (rows_at + m * H + 63) // 64 * 64
+            total = pal_at + (m * ps if paletted else 0)
+            pin, dev, ev = self._jpeg_staging(total)
+            pb = pin.data_ptr()
+            VP = C.c_void_p * m
+            status = (C.c_int * m)()
+            chunk = infos[at:at + m]
+            self._check(self._lib.sv_png_inflate_batch((C.c_char_p * m)(*datas[at:at + m]), (C.c_size_t * m)(*[len(d) for d in datas[at:at + m]]),
+                                                       (_native.PngInfo * m)(*chunk), m, VP(*[pb + i * fb for i in range(m)]), (C.c_size_t * m)(*([fb] * m)),
+                                                       VP(*[pb + rows_at + i * H for i in range(m)]), int(threads), status), "sv_png_inflate_batch")
+            pal = None
+            if paletted:
+                host_pal = pin[pal_at:total].numpy().reshape(m, ps)
+                for i, inf in enumerate(chunk):
+                    host_pal[i, :768] = np.frombuffer(bytes(inf.palette), np.uint8)
+                    host_pal[i, 768:772] = np.frombuffer(np.uint32(inf.palette_entries).tobytes(), np.uint8)
+                pal = dev[pal_at:total].view(m, ps)
+            dev[:total].copy_(pin[:total], non_blocking=True)
+            _, st = self.png_reconstruct(info, dev[:rows_at].view(m, fb), dev[rows_at:rows_at + m * H].view(m, H), pal, out[at:at + m])
+            ev.record(stream)
+            flags.append(st)
+        if paletted:
+            bad = torch.cat(flags).cpu()
+            if bad.any():
+                raise _native.NativeError(f"imdecode_png: SV_ERR_BAD_ARG: image {int(bad.nonzero()[0])} holds a palette index past its palette's end")
+        return out
+
+    def imdecode_png(self, data: bytes, threads=1, out=None):
+        """cv2.imdecode / cv2.imread of a PNG file -> BGR uint8 CUDA tensor [H,W,3] (imdecode_png_batch of one file; out: a [H,W,3] view)."""
+        return self.imdecode_png_batch([data], threads, None if out is None else out[None])[0]
+
     def softmax_topk(self, logits, k=3):
         """F.softmax(logits, 1).topk(k) (pipeline/run_v2.py:165-178): (index u8 [B,k], prob f32 [B,k]), best first."""
         logits = _dev_tensor(logits, "logits", torch.float32, self.device).reshape(-1, 10).contiguous()
