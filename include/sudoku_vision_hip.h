@@ -610,6 +610,39 @@ int sv_jpeg_reconstruct_sparse_scaled_bgr_u8(sv_ctx *ctx, const sv_jpeg_info *in
                                              const uint16_t *quant /*dev, 192*/, uint8_t *bgr /*dev*/, ptrdiff_t pitch,
                                              void *stream, int scale_denom);
 
+/* Grayscale read: cv2.imread(path, cv2.IMREAD_GRAYSCALE) and IMREAD_REDUCED_GRAYSCALE_2 / _4 / _8 of a JPEG file (ml/datasets.py:81,153,
+ * ml/evaluate.py:67, tools/augment_data.py:328,361, tools/dataset_stats.py:211,245, tools/label_cells.py:42).  OpenCV asks libjpeg for
+ * JCS_GRAYSCALE, and libjpeg then returns the inverse DCT of the Y component and never decodes Cb or Cr -- not the gray conversion of the colour
+ * image.  So does this: the luma mode of the entropy decoder parses the chroma blocks of an interleaved scan (to stay in step with the bit
+ * stream) and stores Y's alone; the device half transforms them straight into the caller's [H, W] image.  Bit-identical to libjpeg-turbo's
+ * JCS_GRAYSCALE output at scale_denom 1, 2, 4 and 8; the EXIF orientation is applied as imread applies it.  Every file the colour entries refuse
+ * is refused here with the same status.
+ *
+ * sv_jpeg_parse_luma fills sv_jpeg_info as sv_jpeg_parse does, except coef_count and sparse_capacity: they count Y's blocks (64 values each)
+ * and the room Y's values may need.  Size staging from them, and hand this info to the reconstruct entries below.
+ * Y's blocks lie in scan order: MCU after MCU (row-major), the h_samp x v_samp blocks of an MCU row-major; so the block at raster position
+ * (bx, by) is record ((by / v_samp) * mcu_cols + bx / h_samp) * h_samp * v_samp + (by % v_samp) * h_samp + bx % h_samp, with
+ * mcu_cols = ceil(width / (8 * h_samp)).  For a single-component file this is sv_jpeg_entropy_decode's layout.  quant: Y's 64 steps alone. */
+int sv_jpeg_parse_luma(const uint8_t *data /*host*/, size_t size, sv_jpeg_info *info);
+int sv_jpeg_entropy_decode_luma(const uint8_t *data /*host*/, size_t size, int16_t *coef /*host, coef_count*/,
+                                uint16_t *quant /*host, 64*/, int threads);
+int sv_jpeg_entropy_decode_luma_sparse(const uint8_t *data /*host*/, size_t size, uint64_t *masks /*host, coef_count/64*/,
+                                       uint32_t *offsets /*host, coef_count/64*/, int16_t *values /*host, values_cap*/,
+                                       long values_cap, long *values_used, uint16_t *quant /*host, 64*/, int threads);
+int sv_jpeg_entropy_decode_luma_batch(const uint8_t *const *datas, const size_t *sizes, int n, int16_t *const *coefs /*host or NULL*/,
+                                      uint64_t *const *masks, uint32_t *const *offsets, int16_t *const *values,
+                                      const long *values_cap, long *values_used, uint16_t *quants /*host, n*64*/,
+                                      int threads, int *status /*n*/);
+/* Device half: Y records -> gray image, ceil(out_height / scale_denom) x ceil(out_width / scale_denom) bytes, row pitch `pitch` bytes (any
+ * alignment), asynchronous on `stream`.  No scratch memory.  Status codes are those of the BGR entries. */
+int sv_jpeg_reconstruct_gray_u8(sv_ctx *ctx, const sv_jpeg_info *info /*sv_jpeg_parse_luma's*/, const int16_t *coef /*dev*/,
+                                const uint16_t *quant /*dev, 64*/, uint8_t *gray /*dev*/, ptrdiff_t pitch, void *stream,
+                                int scale_denom);
+int sv_jpeg_reconstruct_sparse_gray_u8(sv_ctx *ctx, const sv_jpeg_info *info /*sv_jpeg_parse_luma's*/, const uint64_t *masks /*dev*/,
+                                       const uint32_t *offsets /*dev*/, const int16_t *values /*dev*/,
+                                       const uint16_t *quant /*dev, 64*/, uint8_t *gray /*dev*/, ptrdiff_t pitch,
+                                       void *stream, int scale_denom);
+
 /* ---- JPEG encoder -- what cv2.imwrite does after the path ends (pipeline/run.py:431: cv2.imwrite(args.output, overlay)).  Baseline JPEG, 8-bit,
  * gray or YCbCr 4:4:4 / 4:2:2 / 4:2:0, optional restart interval.  The mirror image of the decoder above: colour conversion, down-sampling, edge
  * replication, the forward DCT (libjpeg's JDCT_ISLOW) and quantisation run on the GPU and leave the coefficients in the decoder's own layouts

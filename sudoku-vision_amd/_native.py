@@ -73,6 +73,12 @@ SIGNATURES = {
     "sv_jpeg_scaled_size": [_p, _i, _p, _p],
     "sv_jpeg_reconstruct_scaled_bgr_u8": [_p, _p, _p, _p, _p, _pd, _p, _i],
     "sv_jpeg_reconstruct_sparse_scaled_bgr_u8": [_p, _p, _p, _p, _p, _p, _p, _pd, _p, _i],
+    "sv_jpeg_parse_luma": [_p, C.c_size_t, _p],
+    "sv_jpeg_entropy_decode_luma": [_p, C.c_size_t, _p, _p, _i],
+    "sv_jpeg_entropy_decode_luma_sparse": [_p, C.c_size_t, _p, _p, _p, _l, _p, _p, _i],
+    "sv_jpeg_entropy_decode_luma_batch": [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p],
+    "sv_jpeg_reconstruct_gray_u8": [_p, _p, _p, _p, _p, _pd, _p, _i],
+    "sv_jpeg_reconstruct_sparse_gray_u8": [_p, _p, _p, _p, _p, _p, _p, _pd, _p, _i],
     "sv_jpeg_encode_plan": [_i, _i, _i, _i, _i, _i, _p],
     "sv_jpeg_encode_bound": [_p, _l],
     "sv_jpeg_forward_bgr_u8": [_p, _p, _p, _i, _pd, _pd, _p, _p, _p, _p, _p, _p],

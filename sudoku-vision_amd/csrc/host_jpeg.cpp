@@ -78,6 +78,7 @@ struct Header {
     bool quant_defined[4] = {false, false, false, false};
     HuffTable dc[4], ac[4];
     long coef_count = 0;
+    long luma_count = 0;                                           // coefficients of component 0 alone
     size_t first_scan = 0;                                         // offset of the first SOS marker
 };
 
@@ -220,20 +221,22 @@ scanned:
         off += (long)h.comp[c].bw * h.comp[c].bh * 64;
     }
     h.coef_count = off;
+    h.luma_count = (long)h.comp[0].bw * h.comp[0].bh * 64;
     return SV_OK;
 }
 
-long sparse_capacity(const Header &h, size_t size);
+long sparse_capacity(const Header &h, size_t size, bool luma);
 
-void export_info(const Header &h, size_t size, sv_jpeg_info *o)
+// luma: the counts of the luma-only decode (Y's blocks alone) in place of the file's
+void export_info(const Header &h, size_t size, sv_jpeg_info *o, bool luma = false)
 {
-    o->sparse_capacity = sparse_capacity(h, size);
+    o->sparse_capacity = sparse_capacity(h, size, luma);
     const bool swap = h.orientation >= 5;
     o->width = h.width; o->height = h.height;
     o->out_width = swap ? h.height : h.width; o->out_height = swap ? h.width : h.height;
     o->components = h.ncomp; o->h_samp = h.hmax; o->v_samp = h.vmax;
     o->orientation = h.orientation; o->restart_interval = h.restart_interval;
-    o->coef_count = h.coef_count;
+    o->coef_count = luma ? h.luma_count : h.coef_count;
 }
 
 // ---- the bit stream of one restart interval ----------------------------------------------------------
@@ -310,7 +313,10 @@ struct SparseOut { uint64_t *masks; uint32_t *offs; int16_t *vals; };
 // Insufficient data, as libjpeg handles it (jdhuff.c: insufficient_data, reset at every restart): once decoding needs bits the
 // interval does not hold, the block being decoded and every later block of the interval stay zero (they reconstruct as mid-grey),
 // which is what cv2.imread / Pillow(LOAD_TRUNCATED_IMAGES) show for the tail of a cut file.
-template <bool SPARSE, class Out>
+// LUMA: the output holds component 0 alone, in scan order -- MCU after MCU, an MCU's h x v blocks row-major -- so that a block's raster position
+// follows from its index (k20_jpeg_gray.hip: luma_record).  The other components' blocks are parsed, as they must be to stay in step with the bit
+// stream and the DC predictors, and stored nowhere.
+template <bool SPARSE, bool LUMA, class Out>
 long decode_interval(const Header &h, const Scan &scan, const uint8_t *b, const uint8_t *e, long m0, long m1, const Out &out, long vpos, long vlimit)
 {
     BitStream bs(b, e);
@@ -322,18 +328,22 @@ long decode_interval(const Header &h, const Scan &scan, const uint8_t *b, const 
             const ScanComponent &s = scan.sc[i];
             const Component &c = h.comp[s.comp];
             const HuffTable &dct = h.dc[s.dc], &act = h.ac[s.ac];
+            const bool keep = !LUMA || s.comp == 0;
             for (int v = 0; v < s.nv; v++)
                 for (int u = 0; u < s.nh; u++) {
-                    const long bi = c.offset / 64 + (long)(my * s.nv + v) * c.bw + (mx * s.nh + u);
+                    const int bx = mx * s.nh + u, by = my * s.nv + v;
+                    const long bi = LUMA ? ((long)(by / c.v) * h.mcu_cols + bx / c.h) * (c.h * c.v) + (by % c.v) * c.h + bx % c.h
+                                         : c.offset / 64 + (long)by * c.bw + bx;
+                    int16_t skipped[64];                            // LUMA: where a block of another component is decoded to
                     int16_t *blk = nullptr;
                     uint64_t mask = 0;
                     const long vstart = vpos;
                     if constexpr (!SPARSE) {
-                        blk = out.coef + bi * 64;
-                        memset(blk, 0, 64 * sizeof(int16_t));       // cleared while the lines are about to be written anyway
+                        blk = keep ? out.coef + bi * 64 : skipped;
+                        if (keep) memset(blk, 0, 64 * sizeof(int16_t));      // cleared while the lines are about to be written anyway
                     }
                     if (dead) {
-                        if constexpr (SPARSE) { out.masks[bi] = 0; out.offs[bi] = (uint32_t)vstart; }
+                        if constexpr (SPARSE) { if (keep) { out.masks[bi] = 0; out.offs[bi] = (uint32_t)vstart; } }
                         continue;
                     }
                     bool full = false;                              // sparse: the interval's stretch of the value stream is used up
@@ -341,7 +351,7 @@ long decode_interval(const Header &h, const Scan &scan, const uint8_t *b, const 
                     const int t = bs.symbol(dct) & 15;
                     if (t) pred[i] += bs.take_signed(t);
                     if constexpr (SPARSE) {
-                        if ((int16_t)pred[i]) {
+                        if ((int16_t)pred[i] && keep) {
                             if (vpos < vlimit) { mask = 1; out.vals[vpos++] = (int16_t)pred[i]; } else full = true;
                         }
                     } else blk[0] = (int16_t)pred[i];
@@ -366,7 +376,7 @@ long decode_interval(const Header &h, const Scan &scan, const uint8_t *b, const 
                             val = bs.take_signed(size);
                         }
                         if constexpr (SPARSE) {
-                            if ((int16_t)val) {
+                            if ((int16_t)val && keep) {
                                 if (vpos < vlimit) { mask |= 1ull << k; out.vals[vpos++] = (int16_t)val; } else full = true;
                             }
                         } else blk[kNatural[k]] = (int16_t)val;
@@ -376,9 +386,9 @@ long decode_interval(const Header &h, const Scan &scan, const uint8_t *b, const 
                         dead = true;
                         mask = 0;
                         vpos = vstart;
-                        if constexpr (!SPARSE) memset(blk, 0, 64 * sizeof(int16_t));
+                        if constexpr (!SPARSE) { if (keep) memset(blk, 0, 64 * sizeof(int16_t)); }
                     }
-                    if constexpr (SPARSE) { out.masks[bi] = mask; out.offs[bi] = (uint32_t)vstart; }
+                    if constexpr (SPARSE) { if (keep) { out.masks[bi] = mask; out.offs[bi] = (uint32_t)vstart; } }
                 }
         }
     }
@@ -405,7 +415,7 @@ size_t split_intervals(const uint8_t *d, size_t size, size_t pos, std::vector<st
     }
 }
 
-template <bool SPARSE, class Out>
+template <bool SPARSE, bool LUMA, class Out>
 int entropy_decode(const uint8_t *d, size_t size, Header &h, const Out &out, int threads, long vals_cap, long *vals_used)
 {
     bool first = true;
@@ -436,10 +446,11 @@ int entropy_decode(const uint8_t *d, size_t size, Header &h, const Out &out, int
         const uint8_t *tail = s + 1 + 2 * scan.ns;
         if (tail[0] != 0 || tail[1] != 63 || tail[2] != 0) return sv_fail(SV_ERR_UNSUPPORTED, "jpeg: spectral selection / successive approximation in a sequential file");
         if (first && scan.ns < h.ncomp) {                          // only a full interleave reaches (and clears) every block: a
-            if constexpr (SPARSE) {                                // component's own block grid leaves the MCU padding blocks out
-                memset(out.masks, 0, (size_t)(h.coef_count / 64) * sizeof(uint64_t));
-                memset(out.offs, 0, (size_t)(h.coef_count / 64) * sizeof(uint32_t));
-            } else memset(out.coef, 0, (size_t)h.coef_count * sizeof(int16_t));
+            const long count = LUMA ? h.luma_count : h.coef_count; // component's own block grid leaves the MCU padding blocks out
+            if constexpr (SPARSE) {
+                memset(out.masks, 0, (size_t)(count / 64) * sizeof(uint64_t));
+                memset(out.offs, 0, (size_t)(count / 64) * sizeof(uint32_t));
+            } else memset(out.coef, 0, (size_t)count * sizeof(int16_t));
         }
         first = false;
         if (scan.ns == 1) {                                        // non-interleaved: the component's own block grid
@@ -458,7 +469,8 @@ int entropy_decode(const uint8_t *d, size_t size, Header &h, const Out &out, int
             vstart[0] = vbase;
             for (long k = 0; k < need; k++) {
                 long blocks = 0;
-                for (int i = 0; i < scan.ns; i++) blocks += (long)scan.sc[i].nh * scan.sc[i].nv;
+                for (int i = 0; i < scan.ns; i++)
+                    if (!LUMA || scan.sc[i].comp == 0) blocks += (long)scan.sc[i].nh * scan.sc[i].nv;
                 const long m0 = k * per, m1 = std::min(nmcu, m0 + per);
                 vstart[k + 1] = vstart[k] + std::min(interval_value_bound(iv[k].second - iv[k].first), (m1 - m0) * blocks * 64);
             }
@@ -467,7 +479,7 @@ int entropy_decode(const uint8_t *d, size_t size, Header &h, const Out &out, int
         const Header &hc = h;
         WorkerPool::instance().parallel_for((int)need, threads, [&](int k) {
             const long m0 = (long)k * per, m1 = std::min(nmcu, m0 + per);
-            vend[k] = decode_interval<SPARSE>(hc, scan, d + iv[k].first, d + iv[k].second, m0, m1, out, vstart[k], SPARSE ? vstart[k + 1] : 0);
+            vend[k] = decode_interval<SPARSE, LUMA>(hc, scan, d + iv[k].first, d + iv[k].second, m0, m1, out, vstart[k], SPARSE ? vstart[k + 1] : 0);
         });
         if constexpr (SPARSE) {
             vbase = vstart[need];
@@ -487,11 +499,28 @@ int fill_quant(const Header &h, uint16_t *quant)
     return SV_OK;
 }
 
-long sparse_capacity(const Header &h, size_t size)
+long sparse_capacity(const Header &h, size_t size, bool luma)
 {
     const long nmcu = (long)h.mcu_cols * h.mcu_rows;
     const long intervals = h.restart_interval > 0 ? (nmcu + h.restart_interval - 1) / h.restart_interval : 1;
-    return std::min(h.coef_count, 4 * (long)size + 2 * 3 * intervals + 64);
+    // a single-component file: the luma mode is the existing decode
+    if (!luma || h.ncomp == 1) return std::min(h.coef_count, 4 * (long)size + 2 * 3 * intervals + 64);
+    // Y's values lie in the one scan that holds Y; in a scan of its own an MCU is a single block, so there are at most this many intervals
+    const long yint = h.restart_interval > 0 ? (h.luma_count / 64 + h.restart_interval - 1) / h.restart_interval : 1;
+    return std::min(h.luma_count, 4 * (long)size + 2 * yint + 64);
+}
+
+// One file, start to end: the header, every component's quantiser steps, the scan loop.  LUMA: the steps of all three components are still
+// looked up (a refusal of the full decode is a refusal here), quant receives Y's 64 alone.
+template <bool SPARSE, bool LUMA, class Out>
+int decode_file(const uint8_t *data, size_t size, Header &h, const Out &out, uint16_t *quant, int threads, long vals_cap, long *vals_used)
+{
+    uint16_t all[192];
+    int rc = parse_header(data, size, h);
+    if (rc || (rc = fill_quant(h, LUMA ? all : quant))) return rc;
+    if (LUMA) memcpy(quant, all, 64 * sizeof(uint16_t));
+    if (vals_used) *vals_used = 0;
+    return entropy_decode<SPARSE, LUMA>(data, size, h, out, threads, vals_cap, vals_used);
 }
 
 }  // namespace
@@ -507,13 +536,28 @@ extern "C" int sv_jpeg_parse(const uint8_t *data, size_t size, sv_jpeg_info *inf
     return SV_OK;
 }
 
+extern "C" int sv_jpeg_parse_luma(const uint8_t *data, size_t size, sv_jpeg_info *info)
+{
+    if (!data || !info) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_parse_luma: NULL argument");
+    std::unique_ptr<Header> h(new Header);
+    const int rc = parse_header(data, size, *h);
+    if (rc) return rc;
+    export_info(*h, size, info, true);
+    return SV_OK;
+}
+
 extern "C" int sv_jpeg_entropy_decode(const uint8_t *data, size_t size, int16_t *coef, uint16_t *quant, int threads)
 {
     if (!data || !coef || !quant) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_entropy_decode: NULL argument");
     std::unique_ptr<Header> h(new Header);
-    int rc = parse_header(data, size, *h);
-    if (rc || (rc = fill_quant(*h, quant))) return rc;
-    return entropy_decode<false>(data, size, *h, DenseOut{coef}, threads < 1 ? 1 : threads, 0, nullptr);
+    return decode_file<false, false>(data, size, *h, DenseOut{coef}, quant, threads < 1 ? 1 : threads, 0, nullptr);
+}
+
+extern "C" int sv_jpeg_entropy_decode_luma(const uint8_t *data, size_t size, int16_t *coef, uint16_t *quant, int threads)
+{
+    if (!data || !coef || !quant) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_entropy_decode_luma: NULL argument");
+    std::unique_ptr<Header> h(new Header);
+    return decode_file<false, true>(data, size, *h, DenseOut{coef}, quant, threads < 1 ? 1 : threads, 0, nullptr);
 }
 
 extern "C" int sv_jpeg_entropy_decode_sparse(const uint8_t *data, size_t size, uint64_t *masks, uint32_t *offsets, int16_t *values, long values_cap,
@@ -521,41 +565,56 @@ extern "C" int sv_jpeg_entropy_decode_sparse(const uint8_t *data, size_t size, u
 {
     if (!data || !masks || !offsets || !values || !values_used || !quant) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_entropy_decode_sparse: NULL argument");
     std::unique_ptr<Header> h(new Header);
-    int rc = parse_header(data, size, *h);
-    if (rc || (rc = fill_quant(*h, quant))) return rc;
-    *values_used = 0;
-    return entropy_decode<true>(data, size, *h, SparseOut{masks, offsets, values}, threads < 1 ? 1 : threads, values_cap, values_used);
+    return decode_file<true, false>(data, size, *h, SparseOut{masks, offsets, values}, quant, threads < 1 ? 1 : threads, values_cap, values_used);
+}
+
+extern "C" int sv_jpeg_entropy_decode_luma_sparse(const uint8_t *data, size_t size, uint64_t *masks, uint32_t *offsets, int16_t *values, long values_cap,
+                                                  long *values_used, uint16_t *quant, int threads)
+{
+    if (!data || !masks || !offsets || !values || !values_used || !quant) return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_entropy_decode_luma_sparse: NULL argument");
+    std::unique_ptr<Header> h(new Header);
+    return decode_file<true, true>(data, size, *h, SparseOut{masks, offsets, values}, quant, threads < 1 ? 1 : threads, values_cap, values_used);
 }
 
 // Images of a batch over the pool's threads; every image decodes its restart intervals serially (a worker's nested
-// parallel_for runs inline).  Dense when `coefs` is given, sparse when masks/offsets/values are.
-extern "C" int sv_jpeg_entropy_decode_batch(const uint8_t *const *datas, const size_t *sizes, int n, int16_t *const *coefs, uint64_t *const *masks,
-                                            uint32_t *const *offsets, int16_t *const *values, const long *values_cap, long *values_used,
-                                            uint16_t *quants, int threads, int *status)
+// parallel_for runs inline).  Dense when `coefs` is given, sparse when masks/offsets/values are.  LUMA: image i's quantiser steps are 64, not 192.
+template <bool LUMA>
+static int entropy_decode_batch(const char *fn, const uint8_t *const *datas, const size_t *sizes, int n, int16_t *const *coefs, uint64_t *const *masks,
+                                uint32_t *const *offsets, int16_t *const *values, const long *values_cap, long *values_used, uint16_t *quants, int threads, int *status)
 {
     const bool sparse = coefs == nullptr;
     if (!datas || !sizes || !quants || !status || n <= 0 || (sparse && (!masks || !offsets || !values || !values_cap || !values_used)))
-        return sv_fail(SV_ERR_BAD_ARG, "sv_jpeg_entropy_decode_batch: bad argument");
+        return sv_fail(SV_ERR_BAD_ARG, "%s: bad argument", fn);
     if (threads < 1) threads = 1;
     std::vector<std::unique_ptr<Header>> hs((size_t)n);
     auto one = [&](int i, int inner_threads) {
         hs[i].reset(new Header);
         const bool ok = datas[i] && (sparse ? (masks[i] && offsets[i] && values[i]) : coefs[i] != nullptr);
-        int rc = ok ? parse_header(datas[i], sizes[i], *hs[i]) : SV_ERR_BAD_ARG;
-        if (!rc) rc = fill_quant(*hs[i], quants + 192 * (size_t)i);
-        if (!rc) {
-            if (sparse) {
-                values_used[i] = 0;
-                rc = entropy_decode<true>(datas[i], sizes[i], *hs[i], SparseOut{masks[i], offsets[i], values[i]}, inner_threads, values_cap[i], values_used + i);
-            } else rc = entropy_decode<false>(datas[i], sizes[i], *hs[i], DenseOut{coefs[i]}, inner_threads, 0, nullptr);
-        }
-        status[i] = rc;
+        uint16_t *q = quants + (LUMA ? 64 : 192) * (size_t)i;
+        if (!ok) status[i] = SV_ERR_BAD_ARG;
+        else if (sparse)
+            status[i] = decode_file<true, LUMA>(datas[i], sizes[i], *hs[i], SparseOut{masks[i], offsets[i], values[i]}, q, inner_threads, values_cap[i], values_used + i);
+        else status[i] = decode_file<false, LUMA>(datas[i], sizes[i], *hs[i], DenseOut{coefs[i]}, q, inner_threads, 0, nullptr);
     };
     if (threads == 1 || n == 1) for (int i = 0; i < n; i++) one(i, n == 1 ? threads : 1);
     else WorkerPool::instance().parallel_for(n, threads, [&](int i) { one(i, 1); });
     for (int i = 0; i < n; i++)
-        if (status[i] != SV_OK) return sv_fail(status[i], "sv_jpeg_entropy_decode_batch: image %d failed (see status[])", i);
+        if (status[i] != SV_OK) return sv_fail(status[i], "%s: image %d failed (see status[])", fn, i);
     return SV_OK;
+}
+
+extern "C" int sv_jpeg_entropy_decode_batch(const uint8_t *const *datas, const size_t *sizes, int n, int16_t *const *coefs, uint64_t *const *masks,
+                                            uint32_t *const *offsets, int16_t *const *values, const long *values_cap, long *values_used,
+                                            uint16_t *quants, int threads, int *status)
+{
+    return entropy_decode_batch<false>("sv_jpeg_entropy_decode_batch", datas, sizes, n, coefs, masks, offsets, values, values_cap, values_used, quants, threads, status);
+}
+
+extern "C" int sv_jpeg_entropy_decode_luma_batch(const uint8_t *const *datas, const size_t *sizes, int n, int16_t *const *coefs, uint64_t *const *masks,
+                                                 uint32_t *const *offsets, int16_t *const *values, const long *values_cap, long *values_used,
+                                                 uint16_t *quants, int threads, int *status)
+{
+    return entropy_decode_batch<true>("sv_jpeg_entropy_decode_luma_batch", datas, sizes, n, coefs, masks, offsets, values, values_cap, values_used, quants, threads, status);
 }
 
 // ---- the encoder's host half (cv2.imwrite at pipeline/run.py:431) ----------------------------------------

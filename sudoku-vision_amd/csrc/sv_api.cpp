@@ -916,7 +916,7 @@ extern "C" int sv_warp_affine_u8(sv_ctx *ctx, const uint8_t *src, int n, int H, 
     return svk_warp_affine(ctx, src, n, H, W, pitch, img_stride, M, dst_h, dst_w, border_value, dst, S(stream));
 }
 
-static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *fn, int denom)
+static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *fn, int denom, int channels = 3)
 {
     const char *what = nullptr;
     const bool swap = info->orientation >= 5;
@@ -925,7 +925,7 @@ static int jpeg_info_ok(const sv_jpeg_info *info, ptrdiff_t pitch, const char *f
     else if (!((info->h_samp == 1 && info->v_samp == 1) || (info->h_samp == 2 && (info->v_samp == 1 || info->v_samp == 2)))) what = "sampling must be 1x1, 2x1 or 2x2";
     else if (!(info->orientation >= 1 && info->orientation <= 8)) what = "orientation must be 1..8";
     else if (!(info->out_width == (swap ? info->height : info->width) && info->out_height == (swap ? info->width : info->height))) what = "out_width/out_height do not match the orientation";
-    else if (pitch < 3 * (ptrdiff_t)((info->out_width + denom - 1) / denom)) what = "pitch smaller than a row";
+    else if (pitch < channels * (ptrdiff_t)((info->out_width + denom - 1) / denom)) what = "pitch smaller than a row";
     return what ? sv_fail(SV_ERR_BAD_ARG, "%s: %s", fn, what) : SV_OK;
 }
 
@@ -978,6 +978,34 @@ extern "C" int sv_jpeg_reconstruct_sparse_scaled_bgr_u8(sv_ctx *ctx, const sv_jp
                                                         const uint16_t *quant, uint8_t *bgr, ptrdiff_t pitch, void *stream, int scale_denom)
 {
     return jpeg_reconstruct(false, ctx, info, nullptr, masks, offsets, values, quant, bgr, pitch, stream, scale_denom);
+}
+
+// The two luma-only reconstruct entries (cv2.IMREAD_GRAYSCALE, IMREAD_REDUCED_GRAYSCALE_*).  info: sv_jpeg_parse_luma's
+static int jpeg_reconstruct_gray(bool dense, const sv_jpeg_info *info, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
+                                 const uint16_t *quant, uint8_t *gray, ptrdiff_t pitch, void *stream, int scale_denom)
+{
+    const char *fn = dense ? "sv_jpeg_reconstruct_gray_u8" : "sv_jpeg_reconstruct_sparse_gray_u8";
+    REQUIRE_AS(fn, jpeg_scale_ok(scale_denom), "scale_denom must be 1, 2, 4 or 8");
+    REQUIRE_AS(fn, info && (dense ? coef != nullptr : masks && offsets && values) && quant && gray, "NULL argument");
+    const int rc = jpeg_info_ok(info, pitch, fn, scale_denom, 1);
+    if (rc) return rc;
+    if (dense) REQUIRE_AS(fn, ((uintptr_t)coef & 15) == 0 && ((uintptr_t)quant & 15) == 0, "coef and quant must be 16-byte aligned");
+    else REQUIRE_AS(fn, ((uintptr_t)masks & 7) == 0 && ((uintptr_t)offsets & 3) == 0 && ((uintptr_t)values & 1) == 0 && ((uintptr_t)quant & 15) == 0, "misaligned argument");
+    return svk_jpeg_reconstruct_gray(info, scale_denom, coef, masks, offsets, values, quant, gray, pitch, S(stream), fn);
+}
+
+extern "C" int sv_jpeg_reconstruct_gray_u8(sv_ctx *ctx, const sv_jpeg_info *info, const int16_t *coef, const uint16_t *quant, uint8_t *gray, ptrdiff_t pitch, void *stream,
+                                           int scale_denom)
+{
+    REQUIRE(ctx, "NULL argument");
+    return jpeg_reconstruct_gray(true, info, coef, nullptr, nullptr, nullptr, quant, gray, pitch, stream, scale_denom);
+}
+
+extern "C" int sv_jpeg_reconstruct_sparse_gray_u8(sv_ctx *ctx, const sv_jpeg_info *info, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
+                                                  const uint16_t *quant, uint8_t *gray, ptrdiff_t pitch, void *stream, int scale_denom)
+{
+    REQUIRE(ctx, "NULL argument");
+    return jpeg_reconstruct_gray(false, info, nullptr, masks, offsets, values, quant, gray, pitch, stream, scale_denom);
 }
 
 // The two forward entries of the encoder; channels 3 (BGR) or 1 (gray)

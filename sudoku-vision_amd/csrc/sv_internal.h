@@ -220,6 +220,9 @@ int svk_preprocess_cells(const u8 *cells, long B, u8 *out, hipStream_t s);
 // denom: libjpeg's scale_denom, 1, 2, 4 or 8; dense when coef != nullptr, else sparse; fn: the entry point that was called, for error texts
 int svk_jpeg_reconstruct(sv_ctx *ctx, const sv_jpeg_info *info, int denom, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
                          const uint16_t *quant, u8 *bgr, ptrdiff_t pitch, hipStream_t s, const char *fn);
+// k20_jpeg_gray.hip (info: sv_jpeg_parse_luma's; the image goes straight into `gray`, no scratch)
+int svk_jpeg_reconstruct_gray(const sv_jpeg_info *info, int denom, const int16_t *coef, const uint64_t *masks, const uint32_t *offsets, const int16_t *values,
+                              const uint16_t *quant, u8 *gray, ptrdiff_t pitch, hipStream_t s, const char *fn);
 int svk_softmax_topk(const float *logits, long B, int k, u8 *index, float *prob, hipStream_t s);
 int svk_frame_quality_stats(const u8 *img, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int C, long long *lap_sum, long long *lap_sqsum,
                             uint32_t *hist, hipStream_t s);

@@ -280,6 +280,37 @@ def jpeg_entropy_decode_sparse(data: bytes, threads=1):
     return info, masks, offs, vals[:used.value], quant
 
 
+def jpeg_parse_luma(data: bytes):
+    """-> _native.JpegInfo as jpeg_parse, with coef_count and sparse_capacity those of the luma-only decode (Y's blocks alone)."""
+    info = _native.JpegInfo()
+    _native.check(_native.lib().sv_jpeg_parse_luma(data, len(data), C.byref(info)), "sv_jpeg_parse_luma")
+    return info
+
+
+def jpeg_entropy_decode_luma(data: bytes, threads=1):
+    """-> (info, coef int16 [coef_count], quant uint16 [64]): Y's blocks alone, in scan order (MCU after MCU, an MCU's blocks row-major)."""
+    info = jpeg_parse_luma(data)
+    coef, quant = np.empty(info.coef_count, np.int16), np.empty(64, np.uint16)
+    _native.check(_native.lib().sv_jpeg_entropy_decode_luma(data, len(data), coef.ctypes.data_as(C.c_void_p), quant.ctypes.data_as(C.c_void_p), int(threads)),
+                  "sv_jpeg_entropy_decode_luma")
+    return info, coef, quant
+
+
+def jpeg_entropy_decode_luma_sparse(data: bytes, threads=1):
+    """-> (info, masks uint64 [blocks], offsets uint32 [blocks], values int16 [used], quant uint16 [64]): jpeg_entropy_decode_luma's blocks in
+    the compact transport form."""
+    info = jpeg_parse_luma(data)
+    nb = info.coef_count // 64
+    masks, offs = np.empty(nb, np.uint64), np.empty(nb, np.uint32)
+    vals = np.empty(info.sparse_capacity, np.int16)
+    quant = np.empty(64, np.uint16)
+    used = C.c_long()
+    _native.check(_native.lib().sv_jpeg_entropy_decode_luma_sparse(data, len(data), masks.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
+                                                                   vals.ctypes.data_as(C.c_void_p), vals.size, C.byref(used), quant.ctypes.data_as(C.c_void_p),
+                                                                   int(threads)), "sv_jpeg_entropy_decode_luma_sparse")
+    return info, masks, offs, vals[:used.value], quant
+
+
 # ---- PNG front end, host half (csrc/host_png.cpp): the container's parser and the inflater ---------------------
 def png_parse(data: bytes):
     """-> _native.PngInfo (sv_png_info).  Raises NativeError: SV_ERR_BAD_ARG for anything that is not a well-formed PNG file, SV_ERR_UNSUPPORTED

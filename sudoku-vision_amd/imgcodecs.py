@@ -6,6 +6,9 @@ does not decode (progressive, arithmetic, CMYK, 12-bit) raise NativeError instea
 `cv2.imread(path, cv2.IMREAD_REDUCED_COLOR_2)` becomes `imread(path, reduce=reduce_from_flags(IMREAD_REDUCED_COLOR_2))`, or
 `imread(path, reduce=2)`: libjpeg's reduced-size decode, bit-identical to cv2's, never reconstructed at full size.
 
+`cv2.imread(path, cv2.IMREAD_GRAYSCALE)` (ml/datasets.py:81, tools/label_cells.py:42 and the other dataset readers) becomes `imread(path, gray=True)`,
+or `imread(path, **read_args_from_flags(IMREAD_GRAYSCALE))`: a uint8 [H,W] array, libjpeg's luma-only decode as cv2 performs it, at every `reduce`.
+
 `cv2.imwrite(path, img)` (pipeline/run.py:431) and `cv2.imencode('.jpg', img)` become `imwrite` / `imencode` here, with cv2's signatures and
 return conventions: a baseline JPEG, quality 95 and 4:2:0 unless `params` says otherwise, byte for byte the file libjpeg-turbo writes.  The
 image may be a numpy array or a CUDA tensor (the frame K16 drew into stays in HBM).  What this encoder does not write -- another extension,
@@ -32,6 +35,11 @@ IMREAD_REDUCED_COLOR_2 = 17
 IMREAD_REDUCED_COLOR_4 = 33
 IMREAD_REDUCED_COLOR_8 = 65
 _REDUCE_OF_FLAGS = {IMREAD_COLOR: 1, IMREAD_REDUCED_COLOR_2: 2, IMREAD_REDUCED_COLOR_4: 4, IMREAD_REDUCED_COLOR_8: 8}
+IMREAD_GRAYSCALE = 0
+IMREAD_REDUCED_GRAYSCALE_2 = 16
+IMREAD_REDUCED_GRAYSCALE_4 = 32
+IMREAD_REDUCED_GRAYSCALE_8 = 64
+_REDUCE_OF_GRAY_FLAGS = {IMREAD_GRAYSCALE: 1, IMREAD_REDUCED_GRAYSCALE_2: 2, IMREAD_REDUCED_GRAYSCALE_4: 4, IMREAD_REDUCED_GRAYSCALE_8: 8}
 
 # cv2's values
 IMWRITE_JPEG_QUALITY = 1
@@ -63,14 +71,28 @@ def reduce_from_flags(flags):
         raise ValueError(f"imread flags {flags!r}: only IMREAD_COLOR and IMREAD_REDUCED_COLOR_2/4/8 are decoded here") from None
 
 
-def imdecode(buf, device=False, ctx=None, threads=1, reduce=1):
+def read_args_from_flags(flags):
+    """cv2.imread's flags argument -> {"gray": bool, "reduce": int}, the keyword arguments of imread / imdecode here.  The eight reads this front
+    end performs: IMREAD_COLOR, IMREAD_GRAYSCALE and their REDUCED_*_2/4/8 forms; anything else (IMREAD_UNCHANGED, _ANYDEPTH, _ANYCOLOR, ...) is a
+    ValueError."""
+    for gray, table in ((False, _REDUCE_OF_FLAGS), (True, _REDUCE_OF_GRAY_FLAGS)):
+        try:
+            if not isinstance(flags, bool) and flags in table:
+                return {"gray": gray, "reduce": table[flags]}
+        except TypeError:
+            break
+    raise ValueError(f"imread flags {flags!r}: only IMREAD_COLOR, IMREAD_GRAYSCALE and their REDUCED_*_2/4/8 forms are decoded here")
+
+
+def imdecode(buf, device=False, ctx=None, threads=1, reduce=1, gray=False):
     """bytes of a JPEG file -> BGR image; device=True keeps it on the GPU (CUDA uint8 tensor) for K1/K2.
-    reduce = 2, 4 or 8: the image at 1/reduce of its size, ceil(H / reduce) x ceil(W / reduce)."""
+    reduce = 2, 4 or 8: the image at 1/reduce of its size, ceil(H / reduce) x ceil(W / reduce).
+    gray=True: cv2.IMREAD_GRAYSCALE, a [H,W] image decoded from the Y component alone."""
     reduce = Context.jpeg_reduce_arg(reduce)
     data = bytes(buf)
     ctx = ctx or default_context()
     try:
-        img = ctx.imdecode(data, threads=threads, reduce=reduce)
+        img = ctx.imdecode(data, threads=threads, reduce=reduce, gray=bool(gray))
     except _native.NativeError as e:
         if "SV_ERR_UNSUPPORTED" in str(e):
             raise
@@ -78,14 +100,14 @@ def imdecode(buf, device=False, ctx=None, threads=1, reduce=1):
     return img if device else img.cpu().numpy()
 
 
-def imread(path, device=False, ctx=None, threads=1, reduce=1):
+def imread(path, device=False, ctx=None, threads=1, reduce=1, gray=False):
     reduce = Context.jpeg_reduce_arg(reduce)
     try:
         with open(os.fspath(path), "rb") as f:
             data = f.read()
     except OSError:
         return None
-    return imdecode(data, device=device, ctx=ctx, threads=threads, reduce=reduce)
+    return imdecode(data, device=device, ctx=ctx, threads=threads, reduce=reduce, gray=gray)
 
 
 def _encode_args(params):

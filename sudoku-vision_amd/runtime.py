@@ -566,11 +566,15 @@ class Context:
         cap = int(info.sparse_capacity)
         return (base, base + 8 * nb, base + 12 * nb, cap), base + (12 * nb + 2 * cap + 63) // 64 * 64
 
-    def _jpeg_reconstruct(self, info, db, lay, qoff, out, dense, stream, reduce=1):
-        """Coefficients staged at device address db as _jpeg_layout `lay`, quantisation tables at db + qoff -> BGR in `out`, on `stream`."""
+    def _jpeg_reconstruct(self, info, db, lay, qoff, out, dense, stream, reduce=1, gray=False):
+        """Coefficients staged at device address db as _jpeg_layout `lay`, quantisation tables at db + qoff -> BGR in `out`, on `stream`.
+        gray: Y's records alone (info from sv_jpeg_parse_luma) -> the [H,W] image in `out`."""
         p = [C.c_void_p(db + lay[2])] if dense else [C.c_void_p(db + o) for o in lay[:3]]
         args = (self._h, C.byref(info), *p, C.c_void_p(db + qoff), _ptr(out), out.stride(0), stream)
-        if reduce == 1:
+        if gray:
+            fn = self._lib.sv_jpeg_reconstruct_gray_u8 if dense else self._lib.sv_jpeg_reconstruct_sparse_gray_u8
+            self._check(fn(*args, reduce), "sv_jpeg_reconstruct_gray")
+        elif reduce == 1:
             fn = self._lib.sv_jpeg_reconstruct_bgr_u8 if dense else self._lib.sv_jpeg_reconstruct_sparse_bgr_u8
             self._check(fn(*args), "sv_jpeg_reconstruct")
         else:
@@ -590,9 +594,11 @@ class Context:
         self._check(self._lib.sv_jpeg_scaled_size(C.byref(info), reduce, C.byref(w), C.byref(h)), "sv_jpeg_scaled_size")
         return h.value, w.value
 
-    def imdecode_batch(self, datas, threads=16, dense=False, reduce=1):
+    def imdecode_batch(self, datas, threads=16, dense=False, reduce=1, gray=False):
         """A batch of JPEG files -> uint8 CUDA tensor [n,H,W,3] when all share a shape, else a list of [H,W,3] tensors.
         reduce = 2, 4 or 8 (one value for the batch): libjpeg's reduced-size decode, frames of ceil(H / reduce) x ceil(W / reduce).
+        gray=True: cv2.IMREAD_GRAYSCALE / IMREAD_REDUCED_GRAYSCALE_*, [n,H,W] or a list of [H,W]: the luma-only decode -- only Y's
+        coefficients are stored, staged and copied, and one kernel (csrc/k20_jpeg_gray.hip) writes the image; colour and gray-only files mix.
         Images are Huffman-decoded on `threads` host threads (sv_jpeg_entropy_decode_batch) into pinned memory in the compact
         mask + values form (dense=True: plain int16 blocks), cross PCIe one image per copy, and are reconstructed on the GPU
         back to back.  Returns after the last launch; the next call's host decoding overlaps this call's copies and kernels."""
@@ -600,14 +606,15 @@ class Context:
         reduce = self.jpeg_reduce_arg(reduce)
         n = len(datas)
         datas = [bytes(d) for d in datas]
-        infos = [host.jpeg_parse(d) for d in datas]
+        infos = [(host.jpeg_parse_luma if gray else host.jpeg_parse)(d) for d in datas]
+        ch, qbytes = ((), 128) if gray else ((3,), 384)                # Y's quantiser steps alone, or three components'
         base, lay, total = [], [], 0
         for info in infos:
             base.append(total)
             l, total = self._jpeg_layout(info, total, dense)
             lay.append(l)
         qoff = total
-        total += 384 * n
+        total += qbytes * n
         pin, dev, ev = self._jpeg_staging(total)
         pb, db = pin.data_ptr(), dev.data_ptr()
         VP = C.c_void_p * n
@@ -620,56 +627,63 @@ class Context:
         else:
             args = (None, VP(*[pb + l[0] for l in lay]), VP(*[pb + l[1] for l in lay]), VP(*[pb + l[2] for l in lay]),
                     (C.c_long * n)(*[l[3] for l in lay]), used)
-        self._check(self._lib.sv_jpeg_entropy_decode_batch(bufs, sizes, n, *args, C.c_void_p(pb + qoff), int(threads), status),
-                      "sv_jpeg_entropy_decode_batch")
+        decode = self._lib.sv_jpeg_entropy_decode_luma_batch if gray else self._lib.sv_jpeg_entropy_decode_batch
+        self._check(decode(bufs, sizes, n, *args, C.c_void_p(pb + qoff), int(threads), status), "sv_jpeg_entropy_decode_luma_batch" if gray else "sv_jpeg_entropy_decode_batch")
         shapes = [self._jpeg_out_shape(i, reduce) for i in infos]
         same = all(sh == shapes[0] for sh in shapes)
         if same:
-            out = torch.empty((n, *shapes[0], 3), dtype=torch.uint8, device=self.device)
+            out = torch.empty((n, *shapes[0], *ch), dtype=torch.uint8, device=self.device)
             outs = [out[i] for i in range(n)]
         else:
-            outs = [torch.empty((*sh, 3), dtype=torch.uint8, device=self.device) for sh in shapes]
-        dev[qoff:qoff + 384 * n].copy_(pin[qoff:qoff + 384 * n], non_blocking=True)
+            outs = [torch.empty((*sh, *ch), dtype=torch.uint8, device=self.device) for sh in shapes]
+        dev[qoff:qoff + qbytes * n].copy_(pin[qoff:qoff + qbytes * n], non_blocking=True)
         sent, stream = 0, _stream_ptr()
         for i, (info, l) in enumerate(zip(infos, lay)):
             end = l[2] + 2 * (int(info.coef_count) if dense else used[i])
             dev[base[i]:end].copy_(pin[base[i]:end], non_blocking=True)
-            self._jpeg_reconstruct(info, db, l, qoff + 384 * i, outs[i], dense, stream, reduce)
+            self._jpeg_reconstruct(info, db, l, qoff + qbytes * i, outs[i], dense, stream, reduce, gray)
             sent += end - base[i]
         ev.record(torch.cuda.current_stream(self.device))
         self._jpeg_last_bytes = sent / max(n, 1)
         return out if same else outs
 
-    def imdecode(self, data: bytes, threads=1, out=None, dense=False, reduce=1):
+    def imdecode(self, data: bytes, threads=1, out=None, dense=False, reduce=1, gray=False):
         """cv2.imdecode / cv2.imread of a baseline JPEG -> BGR uint8 CUDA tensor [H,W,3] (EXIF orientation applied).
         Huffman decoding on the host (csrc/host_jpeg.cpp; `threads` work on restart intervals when the file has them) into
         pinned staging memory, everything after it on the GPU.  reduce = 2, 4 or 8: cv2.IMREAD_REDUCED_COLOR_*, the frame is
-        ceil(H / reduce) x ceil(W / reduce) and is never reconstructed at full size."""
+        ceil(H / reduce) x ceil(W / reduce) and is never reconstructed at full size.
+        gray=True: cv2.IMREAD_GRAYSCALE / IMREAD_REDUCED_GRAYSCALE_*, a [H,W] tensor: libjpeg's JCS_GRAYSCALE, the inverse DCT of Y alone
+        (not the gray conversion of the colour image).  out= may be a view whose rows are dense (stride(1) == 1): it is written by its pitch."""
         reduce = self.jpeg_reduce_arg(reduce)
         if out is None and threads <= 1:
-            return self.imdecode_batch([data], 1, dense=dense, reduce=reduce)[0]
+            return self.imdecode_batch([data], 1, dense=dense, reduce=reduce, gray=gray)[0]
         from . import host
         data = bytes(data)
-        info = host.jpeg_parse(data)
+        info = (host.jpeg_parse_luma if gray else host.jpeg_parse)(data)
         lay, qoff = self._jpeg_layout(info, 0, dense)
         pin, dev, ev = self._jpeg_staging(qoff + 384)
         pb, db = pin.data_ptr(), dev.data_ptr()
         if dense:
-            self._check(self._lib.sv_jpeg_entropy_decode(data, len(data), C.c_void_p(pb), C.c_void_p(pb + qoff), int(threads)), "sv_jpeg_entropy_decode")
+            decode = self._lib.sv_jpeg_entropy_decode_luma if gray else self._lib.sv_jpeg_entropy_decode
+            self._check(decode(data, len(data), C.c_void_p(pb), C.c_void_p(pb + qoff), int(threads)), "sv_jpeg_entropy_decode")
             end = 2 * int(info.coef_count)
         else:
             used = C.c_long()
-            self._check(self._lib.sv_jpeg_entropy_decode_sparse(data, len(data), *[C.c_void_p(pb + o) for o in lay[:3]], lay[3], C.byref(used),
-                                                                C.c_void_p(pb + qoff), int(threads)), "sv_jpeg_entropy_decode_sparse")
+            decode = self._lib.sv_jpeg_entropy_decode_luma_sparse if gray else self._lib.sv_jpeg_entropy_decode_sparse
+            self._check(decode(data, len(data), *[C.c_void_p(pb + o) for o in lay[:3]], lay[3], C.byref(used), C.c_void_p(pb + qoff), int(threads)),
+                        "sv_jpeg_entropy_decode_sparse")
             end = lay[2] + 2 * used.value
         dev[:end].copy_(pin[:end], non_blocking=True)
         dev[qoff:qoff + 384].copy_(pin[qoff:qoff + 384], non_blocking=True)
         shape = self._jpeg_out_shape(info, reduce)
+        want = shape if gray else (*shape, 3)
         if out is None:
-            out = torch.empty((*shape, 3), dtype=torch.uint8, device=self.device)
-        elif tuple(out.shape) != (*shape, 3):
-            raise ValueError(f"out must be [{shape[0]}, {shape[1]}, 3], not {list(out.shape)}")
-        self._jpeg_reconstruct(info, db, lay, qoff, out, dense, _stream_ptr(), reduce)
+            out = torch.empty(want, dtype=torch.uint8, device=self.device)
+        elif tuple(out.shape) != want:
+            raise ValueError(f"out must be {list(want)}, not {list(out.shape)}")
+        elif gray and (out.dtype != torch.uint8 or not out.is_cuda or (out.shape[1] > 1 and out.stride(1) != 1) or out.stride(0) < out.shape[1]):
+            raise ValueError("out must be a uint8 CUDA tensor whose rows are dense (a column-offset view of a wider tensor is fine)")
+        self._jpeg_reconstruct(info, db, lay, qoff, out, dense, _stream_ptr(), reduce, gray)
         ev.record(torch.cuda.current_stream(self.device))
         return out
 
