@@ -104,6 +104,14 @@ __global__ __launch_bounds__(MT) void k_motion_count(const u8 *__restrict__ smal
     count_moved(moved, counts, frame);
 }
 
+// Zeroes the counts the workgroups add into.  A kernel and not hipMemsetAsync: captured into a graph, a memset of 16 bytes or more
+// was carried out on the first replay only, and these 4n bytes reach that at four frames.
+__global__ __launch_bounds__(MT) void k_motion_clear(int32_t *__restrict__ counts, int n)
+{
+    const int i = blockIdx.x * MT + threadIdx.x;
+    if (i < n) counts[i] = 0;
+}
+
 }  // namespace
 
 // A u8 difference d against a float threshold t: d > t  <=>  d > floor(t) for finite t; NaN and t >= 255 count nothing, t < 0 everything.
@@ -127,7 +135,8 @@ int svk_motion_update(sv_ctx *ctx, const u8 *frames, int n, int H, int W, int C,
     const dim3 grid((unsigned)((npx + MT - 1) / MT), (unsigned)n);
     // one launch unless the cross-check library asks for the other shape (svx_ctx_set_motion_shape); a single frame has nothing to recompute
     const bool two_pass = n > 1 && ctx->x_motion_shape == 1;
-    SV_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * n, s));
+    hipLaunchKernelGGL(k_motion_clear, dim3((unsigned)((n + MT - 1) / MT)), dim3(MT), 0, s, counts, n);
+    SV_LAUNCH_CHECK("k_motion_clear");
     if (two_pass) {
         if (C == 3) hipLaunchKernelGGL((k_motion<3, false>), grid, dim3(MT), 0, s, frames, g, prev_small, thr, small, counts);
         else        hipLaunchKernelGGL((k_motion<1, false>), grid, dim3(MT), 0, s, frames, g, prev_small, thr, small, counts);

@@ -44,6 +44,16 @@ __device__ inline uint64_t add_bytes(uint64_t x, uint64_t y)
     return ((x & low) + (y & low)) ^ ((x ^ y) & ~low);
 }
 
+// Zeroes the job counter and the per-image status.  A kernel and not hipMemsetAsync: captured into a graph, a 16-byte memset zeroed
+// its target on the first replay only (seen on K6's sums, tests/test_gpu_stream_order.py), and a job counter that is not zero
+// sends k_png_rows' jobs[atomicAdd(count, 1)] past the scratch.
+__global__ __launch_bounds__(256) void k_png_clear(uint32_t *__restrict__ count, uint32_t *__restrict__ status, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *count = 0;
+    if (i < n) status[i] = 0;
+}
+
 __global__ __launch_bounds__(256) void k_png_rows(const u8 *__restrict__ filtered, const u8 *__restrict__ row_filter, DecGeom g, u8 *__restrict__ raw,
                                                   uint32_t *__restrict__ count, uint32_t *__restrict__ jobs)
 {
@@ -159,8 +169,8 @@ int svk_png_reconstruct(sv_ctx *ctx, const sv_png_info *info, const u8 *filtered
     if (rc) return rc;
     u8 *raw = ctx->png_dec.as<u8>();
     uint32_t *count = (uint32_t *)(raw + raw_bytes), *jobs = count + 4;
-    SV_HIP(hipMemsetAsync(count, 0, 16, s));
-    SV_HIP(hipMemsetAsync(status, 0, 4 * (size_t)n, s));
+    hipLaunchKernelGGL(k_png_clear, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, count, status, n);
+    SV_LAUNCH_CHECK("k_png_clear");
     hipLaunchKernelGGL(k_png_rows, dim3((unsigned)((g.H + 3) / 4), (unsigned)n), dim3(256), 0, s, filtered, row_filter, g, raw, count, jobs);
     SV_LAUNCH_CHECK("k_png_rows");
     const unsigned grid = (unsigned)std::min<size_t>(rows, (size_t)ctx->num_cus * 4);

@@ -65,6 +65,18 @@ __device__ __forceinline__ void gray_row(const u8 *row, int x0, int nvalid, int 
     }
 }
 
+// Zeroes the three outputs the stats kernel accumulates into, one frame per workgroup.  A kernel and not hipMemsetAsync: captured
+// into a graph, the two 8n-byte memsets zeroed the sums on the first replay only (tests/test_gpu_stream_order.py), and one launch
+// replays like the stats kernel's own.
+__global__ __launch_bounds__(256) void k_quality_clear(long long *__restrict__ lap_sum, long long *__restrict__ lap_sqsum, uint32_t *__restrict__ hist)
+{
+    hist[(ptrdiff_t)blockIdx.x * 256 + threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        lap_sum[blockIdx.x] = 0;
+        lap_sqsum[blockIdx.x] = 0;
+    }
+}
+
 template <int C, bool VEC>
 __global__ __launch_bounds__(256) void k_frame_quality_stats(const u8 *__restrict__ img, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
                                                              int ntiles, int nsegs, long nitems, long long *__restrict__ lap_sum,
@@ -191,9 +203,8 @@ __global__ __launch_bounds__(256) void k_grid_line_coverage(const void *__restri
 int svk_frame_quality_stats(const u8 *img, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int C, long long *lap_sum, long long *lap_sqsum,
                             uint32_t *hist, hipStream_t s)
 {
-    SV_HIP(hipMemsetAsync(lap_sum, 0, sizeof(long long) * n, s));
-    SV_HIP(hipMemsetAsync(lap_sqsum, 0, sizeof(long long) * n, s));
-    SV_HIP(hipMemsetAsync(hist, 0, sizeof(uint32_t) * 256 * n, s));
+    hipLaunchKernelGGL(k_quality_clear, dim3(n), dim3(256), 0, s, lap_sum, lap_sqsum, hist);
+    SV_LAUNCH_CHECK("k_quality_clear");
     const int ntiles = (W + QTILE - 1) / QTILE, nsegs = (H + QROWS - 1) / QROWS;
     const long nitems = (long)n * ntiles * nsegs;
     const dim3 grid((unsigned)((nitems + 3) / 4));

@@ -240,6 +240,13 @@ __global__ __launch_bounds__(256) void k_gauss21(const u8 *__restrict__ src, int
 // ---- CLAHE --------------------------------------------------------------------------------------------------------------
 constexpr int CLAHE_ROWS = 32;      // tile rows per k_clahe_hist workgroup
 
+// Zeroes the tile histograms, one per workgroup.  A kernel and not hipMemsetAsync: captured into a graph, that memset zeroed the
+// histograms on the first replay only (tests/test_gpu_stream_order.py), and a launch replays like every other launch of the entry.
+__global__ __launch_bounds__(256) void k_clahe_clear(uint32_t *__restrict__ hist)
+{
+    hist[(size_t)blockIdx.x * 256 + threadIdx.x] = 0;
+}
+
 // The image is extended to a multiple of the tile grid at the bottom and the right with BORDER_REFLECT_101 (never written out).
 __global__ __launch_bounds__(256) void k_clahe_hist(const u8 *__restrict__ src, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, int tiles_x, int tw,
                                                     int th, uint32_t *__restrict__ hist)
@@ -324,6 +331,13 @@ __global__ __launch_bounds__(256) void k_clahe_apply(const u8 *__restrict__ src,
 // ---- per-pixel tails ----------------------------------------------------------------------------------------------------
 enum { PW_DIVIDE = 0, PW_BINARY = 1, PW_BINARY_INV = 2, PW_SHADOW = 3, PW_COUNT = 4 };
 
+// Zeroes the per-frame counts k_pointwise adds into: a kernel for the reason k_clahe_clear is one (4n bytes reach 16 at four frames).
+__global__ __launch_bounds__(256) void k_counts_clear(uint32_t *__restrict__ counts, int n)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) counts[i] = 0;
+}
+
 // a workgroup covers 64 x 32 pixels; `other` (dense) is the background (PW_DIVIDE) or the local mean (PW_SHADOW); counts[f] += pixels set
 template <int MODE>
 __global__ __launch_bounds__(256) void k_pointwise(const u8 *__restrict__ src, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
@@ -384,7 +398,10 @@ int morph_once(const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t im
 template <int MODE>
 int pointwise(const u8 *src, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const u8 *other, int param, u8 *dst, uint32_t *counts, hipStream_t s)
 {
-    if (counts) SV_HIP(hipMemsetAsync(counts, 0, sizeof(uint32_t) * n, s));
+    if (counts) {
+        hipLaunchKernelGGL(k_counts_clear, dim3((n + 255) / 256), dim3(256), 0, s, counts, n);
+        SV_LAUNCH_CHECK("k_counts_clear");
+    }
     hipLaunchKernelGGL(k_pointwise<MODE>, dim3((W + 63) / 64, (H + 31) / 32, n), dim3(64, 4), 0, s, src, H, W, pitch, img_stride, other, param, dst, counts);
     SV_LAUNCH_CHECK("k_pointwise");
     return SV_OK;
@@ -458,7 +475,8 @@ int svk_clahe(sv_ctx *ctx, const u8 *src, int n, int H, int W, ptrdiff_t pitch, 
     u8 *base = ctx->pp2.as<u8>();
     uint32_t *hist = (uint32_t *)base;
     u8 *luts = base + hist_bytes;
-    SV_HIP(hipMemsetAsync(hist, 0, hist_bytes, s));
+    hipLaunchKernelGGL(k_clahe_clear, dim3(n * ntiles), dim3(256), 0, s, hist);
+    SV_LAUNCH_CHECK("k_clahe_clear");
     hipLaunchKernelGGL(k_clahe_hist, dim3(ntiles, (th + CLAHE_ROWS - 1) / CLAHE_ROWS, n), dim3(256), 0, s, src, H, W, pitch, img_stride, tiles_x, tw, th, hist);
     SV_LAUNCH_CHECK("k_clahe_hist");
     hipLaunchKernelGGL(k_clahe_lut, dim3(n * ntiles), dim3(256), 0, s, hist, clip_limit, lut_scale, luts);
