@@ -282,14 +282,20 @@ def threshold_otsu(gray):
 
 
 # ---- 9: Sauvola -----------------------------------------------------------------------------------------------------------------
-def threshold_sauvola(gray, window=25, k=0.2):
+def sauvola_threshold_from_sums(s1, s2, window, k):
+    """The float32 threshold of a pixel from its exact window sums of g and g^2 (int64 arrays of any one shape)."""
     inv = 1.0 / float(window * window)
-    mean = (window_sums(gray, window).astype(np.float64) * inv).astype(np.float32)
-    sq = (window_sums(gray, window, square=True).astype(np.float64) * inv).astype(np.float32)
+    mean = (np.asarray(s1).astype(np.float64) * inv).astype(np.float32)
+    sq = (np.asarray(s2).astype(np.float64) * inv).astype(np.float32)
     var = np.maximum(sq - mean * mean, np.float32(0))
     std = np.sqrt(var)
     t = mean * (np.float32(1) + np.float32(k) * (std / np.float32(128) - np.float32(1)))
     assert t.dtype == np.float32
+    return t
+
+
+def threshold_sauvola(gray, window=25, k=0.2):
+    t = sauvola_threshold_from_sums(window_sums(gray, window), window_sums(gray, window, square=True), window, k)
     return np.where(gray.astype(np.float32) < t, 255, 0).astype(np.uint8)
 
 
