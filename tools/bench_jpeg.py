@@ -6,7 +6,6 @@ import io
 import json
 import os
 import sys
-import time
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -17,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.synth import synth_frames  # noqa: E402
+from _timing import event_ms, wall_fps, wall_ms  # noqa: E402
 
 
 def main():
@@ -37,11 +37,8 @@ def main():
 
     with ThreadPoolExecutor(threads) as ex:
         want = list(ex.map(pil, datas))
-        t0 = time.perf_counter()
         reps = 3
-        for _ in range(reps):
-            list(ex.map(pil, datas))
-        pil_fps = n * reps / (time.perf_counter() - t0)
+        pil_fps = wall_fps(lambda: list(ex.map(pil, datas)), n, runs=1, warmup=0, sync=False, iters=reps).median
 
     res = {}
     exact = True
@@ -51,11 +48,8 @@ def main():
         torch.cuda.synchronize()
         got = out.cpu().numpy()
         exact = exact and all((got[i][..., ::-1] == want[i]).all() for i in range(n))
-        t0 = time.perf_counter()
-        for _ in range(2 * reps):
-            ctx.imdecode_batch(datas, threads, dense=dense)
-        torch.cuda.synchronize()
-        res[mode] = {"fps": n * 2 * reps / (time.perf_counter() - t0), "pcie_bytes_per_frame": ctx._jpeg_last_bytes}
+        rate = wall_fps(lambda: ctx.imdecode_batch(datas, threads, dense=dense), n, runs=1, warmup=0, iters=2 * reps).median
+        res[mode] = {"fps": rate, "pcie_bytes_per_frame": ctx._jpeg_last_bytes}
     fps = res["sparse"]["fps"]
 
     # the device half alone
@@ -68,19 +62,9 @@ def main():
     lib = sva._native.lib()
     call = lambda: lib.sv_jpeg_reconstruct_bgr_u8(ctx._h, C.byref(info), C.c_void_p(dcoef.data_ptr()), C.c_void_p(dcoef.data_ptr() + 2 * qoff),
                                                   C.c_void_p(frame.data_ptr()), 1920 * 3, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    for _ in range(5):
-        call()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(50):
-        call()
-    e1.record()
-    torch.cuda.synchronize()
-    dev_ms = e0.elapsed_time(e1) / 50
-    t0 = time.perf_counter()
-    for d in datas[:16]:
-        svh.jpeg_entropy_decode(d, coef=coef, quant=quant)
-    huff_ms = (time.perf_counter() - t0) / 16 * 1e3
+    dev_ms = event_ms(call, iters=50, windows=1, warmup=5).median
+    todo = iter(datas[:16])
+    huff_ms = wall_ms(lambda: svh.jpeg_entropy_decode(next(todo), coef=coef, quant=quant), runs=1, warmup=0, sync=False, iters=min(n, 16)).median
     alg_bytes = info.coef_count * 2 + info.coef_count + info.coef_count + 1080 * 1920 * 3     # coef in, planes out+in, frame out
     print(json.dumps({"metric": "JPEG front end, 1080p 4:2:0 q90 frames/s", "frames": n, "mean_file_kB": mean_kb, "host_threads": threads,
                       "this_build_fps": fps, "transport": res, "pillow_libjpeg_turbo_fps_same_threads": pil_fps, "bit_exact_vs_pillow": bool(exact),

@@ -7,13 +7,14 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 if len(sys.argv) > 1:
     from sudoku_vision_amd import _native
     _native.LIB_PATH = os.path.abspath(sys.argv[1])
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd import host  # noqa: E402
 from sudoku_vision_amd.synth import synth_frames  # noqa: E402
+from _timing import event_ms  # noqa: E402
 
 ctx = sva.default_context()
 frames, _, _ = synth_frames(256, 1080, 1920, seed=1234, device="cuda")
@@ -22,16 +23,8 @@ work = torch.empty_like(src)
 records = torch.empty((256, host.sparse_bits_record_bytes(1080, 1920, 1080 * 60 // 3)), dtype=torch.uint8, device="cuda")
 
 
-def t(fn, n=20):
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / n
+def t(fn):
+    return event_ms(fn, iters=20, windows=1, warmup=1).median
 
 
 t_copy = t(lambda: work.copy_(src))

@@ -6,9 +6,10 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.synth import synth_frames  # noqa: E402
+from _timing import event_ms  # noqa: E402
 
 ctx = sva.default_context()
 frames, corners, _ = synth_frames(256, 1080, 1920, seed=1234, device="cuda")
@@ -37,13 +38,4 @@ if len(sys.argv) > 1:
     torch.cuda.synchronize()
     sys.exit(0)
 for name, fn in (("K1 then K2", separate), ("fused launch", fused)) * 2:
-    for _ in range(50):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(50):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    print(f"{name:14s}: {a.elapsed_time(b) / 50:.4f} ms per 256 frames")
+    print(f"{name:14s}: {event_ms(fn, iters=50, windows=1, warmup=50).median:.4f} ms per 256 frames")

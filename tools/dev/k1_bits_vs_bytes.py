@@ -1,17 +1,11 @@
 import os, sys
-sys.path.insert(0, os.getcwd())
+sys.path[:0] = [os.getcwd(), os.path.join(os.getcwd(), "tools")]
 import torch, sudoku_vision_amd as sva
 from sudoku_vision_amd.synth import synth_frames
+from _timing import event_ms
 ctx = sva.default_context()
 frames = synth_frames(256, 1080, 1920, seed=1, device="cuda")[0]
-def t(fn, reps=30):
-    for _ in range(10): fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps): fn()
-    b.record(); torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
+t = lambda fn: event_ms(fn, iters=30, windows=1, warmup=10).median
 for n in (64, 128, 256):
     f = frames[:n]
     ob = torch.empty((n, 1080, 1920), dtype=torch.uint8, device="cuda")

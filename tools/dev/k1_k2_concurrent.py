@@ -7,9 +7,10 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.synth import random_state_dict, synth_frames  # noqa: E402
+from _timing import event_ms  # noqa: E402
 
 ctx = sva.default_context()
 ctx.load_state_dict(random_state_dict(1234))
@@ -44,13 +45,4 @@ def k2_first():
 
 
 for name, fn in (("K1 -> K2 -> K3", serial), ("(K1 || K2) -> K3", overlapped), ("K2 -> K1 -> K3", k2_first)) * 2:
-    for _ in range(100):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(100):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    print(f"{name:18s}: {a.elapsed_time(b) / 100:.4f} ms per 256 frames")
+    print(f"{name:18s}: {event_ms(fn, iters=100, windows=1, warmup=100).median:.4f} ms per 256 frames")

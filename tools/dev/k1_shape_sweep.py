@@ -6,9 +6,10 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.synth import synth_frames  # noqa: E402
+from _timing import event_ms  # noqa: E402
 
 lib = sva._native.lib()
 ctx = sva.default_context()
@@ -17,17 +18,8 @@ ref = ctx.preprocess_bits(frames).clone()
 ref_b = ctx.preprocess(frames).clone()
 
 
-def ms(fn, reps=40):
-    for _ in range(60):
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
+def ms(fn):
+    return event_ms(fn, iters=40, windows=1, warmup=60).median
 
 
 bits = torch.empty_like(ref)

@@ -7,9 +7,10 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.synth import random_state_dict, synth_frames  # noqa: E402
+from _timing import event_ms  # noqa: E402
 
 ctx = sva.default_context()
 ctx.load_state_dict(random_state_dict(1234))
@@ -60,11 +61,6 @@ def overlapped(steps):
 
 for name, fn in (("serial", serial), ("K2(i+1) under K3(i)", overlapped)) * 2:
     fn(60)
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(sA)
-    fn(100)
-    sA.wait_stream(sB)
-    b.record(sA)
-    torch.cuda.synchronize()
-    print(f"{name:22s}: {a.elapsed_time(b) / 100:.4f} ms per 256-frame step")
+    with torch.cuda.stream(sA):                                        # the events go to sA, which waits for sB before the second one
+        t = event_ms(lambda: (fn(100), sA.wait_stream(sB)), iters=1, windows=1, warmup=0).median
+    print(f"{name:22s}: {t / 100:.4f} ms per 256-frame step")

@@ -7,9 +7,10 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.synth import random_state_dict, synth_frames  # noqa: E402
+from _timing import event_ms  # noqa: E402
 
 ctx = sva.default_context()
 ctx.load_state_dict(random_state_dict(1234))
@@ -26,12 +27,7 @@ for sub in (256, 64, 32, 256, 64, 32):
         step()
     torch.cuda.synchronize()
     ctx.timing_begin()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(50):
-        step()
-    b.record()
-    torch.cuda.synchronize()
+    ms = event_ms(step, iters=50, windows=1, warmup=0).median
     t = ctx.timing_end()
-    print(f"sub-batch {sub:3d}: {a.elapsed_time(b) / 50:.4f} ms per 256 frames; per-kernel sums per 256 frames:",
+    print(f"sub-batch {sub:3d}: {ms:.4f} ms per 256 frames; per-kernel sums per 256 frames:",
           {k: round(v[0] / 50, 4) for k, v in t.items() if v[1]})

@@ -14,6 +14,7 @@ import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd import host  # noqa: E402
 from sudoku_vision_amd.pipeline import FramePipeline, host_cpu_budget  # noqa: E402
 from sudoku_vision_amd.synth import random_state_dict, synth_frames  # noqa: E402
+from _timing import event_ms, wall_ms  # noqa: E402
 
 threads = int(sys.argv[1]) if len(sys.argv) > 1 else max(1, host_cpu_budget() - 2)
 ctx = sva.default_context()
@@ -23,17 +24,8 @@ H, W, CH = 1080, 1920, int(sys.argv[2]) if len(sys.argv) > 2 else 64
 DEPTH = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 
 
-def gpu_ms(fn, reps=30):
-    for _ in range(30):                     # the chip needs tens of milliseconds of load to reach its sustained clock
-        fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
+def gpu_ms(fn):
+    return event_ms(fn, iters=30, windows=1, warmup=30).median     # 30 warm-up calls: the chip needs tens of milliseconds of load to reach its sustained clock
 
 
 for sparse in (False, True):
@@ -52,17 +44,11 @@ for sparse in (False, True):
     t_d2h = gpu_ms(lambda: pipe.pinned[slot].copy_(payload, non_blocking=True))
     torch.cuda.synchronize()
     arr = pipe.pinned[slot].numpy()
-    t0 = time.perf_counter()
-    for _ in range(10):
-        if sparse:
-            c, found = host.find_grid_corners_sparse_batch(arr, H, W, 0.1, 0.02, threads)
-        else:
-            c, found = host.find_grid_corners_bits_batch(arr, H, W, 0.1, 0.02, threads)
-    t_search = (time.perf_counter() - t0) / 10 * 1e3
-    t0 = time.perf_counter()
-    for _ in range(10):
-        minv, ok = sva.Context.corners_to_minv_batch(c.astype(np.float32))
-    t_minv = (time.perf_counter() - t0) / 10 * 1e3
+    search = host.find_grid_corners_sparse_batch if sparse else host.find_grid_corners_bits_batch
+    t_search = wall_ms(lambda: search(arr, H, W, 0.1, 0.02, threads), runs=1, warmup=0, sync=False, iters=10).median
+    c, found = search(arr, H, W, 0.1, 0.02, threads)
+    t_minv = wall_ms(lambda: sva.Context.corners_to_minv_batch(c.astype(np.float32)), runs=1, warmup=0, sync=False, iters=10).median
+    minv, ok = sva.Context.corners_to_minv_batch(c.astype(np.float32))
     md = ctx.minv_to_device(minv.reshape(CH, 9))
     out = {"logits": torch.empty((CH, 81, 10), dtype=torch.float32, device="cuda"), "digits": torch.empty((CH, 81), dtype=torch.uint8, device="cuda"),
            "conf": torch.empty((CH, 81), dtype=torch.float32, device="cuda")}

@@ -6,14 +6,12 @@ synthetic 1080p frames.
 Per frame, all in this process: (a) the host search on one thread behind K4 alone (the path without K11), (b) K11's HIP-event time on the
 K4 output, (c) the host search behind K4 + K11, (d) the bytes that cross to the host before and after (dense bytes or bits; non-zero
 32-bit words of the bit image, what a sparse record would carry), (e) the 8-connected components before and after.  Every timing is the
-median of `repeats` windows after a warm-up.  The claim to check is (b) + (c) < (a).  Needs a GPU; there is no CPU path."""
-import argparse
+median of `repeats` windows after a warm-up (_timing.event_ms for the device, _timing.wall_ms for the host).  The claim to check is (b) + (c) < (a).  Needs a GPU; there is no CPU path."""
 import glob
 import json
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -23,35 +21,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd import host, imgcodecs  # noqa: E402
 from sudoku_vision_amd.synth import synth_frames  # noqa: E402
+import _timing  # noqa: E402
 
 RATIO = 0.1
 
 
-def event_ms(fn, iters, repeats):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return statistics.median(out)
+def device_ms(fn, iters, repeats):
+    return _timing.event_ms(fn, iters, repeats, warmup=3).median
 
 
 def host_ms(fn, iters, repeats):
-    fn()
-    out = []
-    for _ in range(repeats):
-        t = time.perf_counter()
-        for _ in range(iters):
-            fn()
-        out.append((time.perf_counter() - t) * 1e3 / iters)
-    return statistics.median(out)
+    return _timing.wall_ms(fn, repeats, warmup=1, sync=False, iters=iters).median
 
 
 def components(img):
@@ -63,17 +43,17 @@ def measure(ctx, frames, repeats, iters):
     n, H, W = frames.shape[:3]
     k4 = ctx.despeckle(ctx.preprocess(frames)) if RATIO * H * W > 61 * 61 else ctx.preprocess(frames)
     work = torch.empty_like(k4)
-    t_copy = event_ms(lambda: work.copy_(k4), iters, repeats)
+    t_copy = device_ms(lambda: work.copy_(k4), iters, repeats)
     bits_form = W % 32 == 0
     if bits_form:
         packed = torch.empty((n, H, W // 32), dtype=torch.int32, device=frames.device)
         ctx.component_filter(k4, 0.0, packed=packed)                          # ratio 0: a plain pack of K4's output
         wbits = torch.empty_like(packed)
-        t_copyb = event_ms(lambda: wbits.copy_(packed), iters, repeats)
-        t_k11 = event_ms(lambda: ctx.component_filter_bits(wbits.copy_(packed), RATIO), iters, repeats) - t_copyb
+        t_copyb = device_ms(lambda: wbits.copy_(packed), iters, repeats)
+        t_k11 = device_ms(lambda: ctx.component_filter_bits(wbits.copy_(packed), RATIO), iters, repeats) - t_copyb
         after_bits = ctx.component_filter_bits(wbits.copy_(packed), RATIO).cpu().numpy()
         before_bits = packed.cpu().numpy()
-    t_k11_u8 = event_ms(lambda: ctx.component_filter(work.copy_(k4), RATIO, out=work), iters, repeats) - t_copy
+    t_k11_u8 = device_ms(lambda: ctx.component_filter(work.copy_(k4), RATIO, out=work), iters, repeats) - t_copy
     after = ctx.component_filter(k4, RATIO).cpu().numpy()
     before = k4.cpu().numpy()
     recs = []
@@ -100,11 +80,7 @@ def measure(ctx, frames, repeats, iters):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=3)
-    ap.add_argument("--json", default=None)
-    args = ap.parse_args()
+    args = _timing.cli(__doc__, None, [("--repeats", dict(type=int, default=5)), ("--iters", dict(type=int, default=3))])
     ctx = sva.default_context()
     out = {"ratio": RATIO, "repeats": args.repeats, "iters": args.iters, "device": torch.cuda.get_device_name(), "photos": [], "synthetic_1080p": None}
     golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
@@ -123,10 +99,7 @@ def main():
                               "b_plus_c_below_a": bool(med("b_k11_ms") + med("c_host_search_behind_k4_k11_ms") < med("a_host_search_behind_k4_ms"))}
     print(json.dumps(out["synthetic_1080p"]), flush=True)
     out["claim_b_plus_c_below_a_on_every_photo"] = all(r["b_plus_c_below_a"] for r in out["photos"])
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        with open(args.json, "w") as f:
-            json.dump(out, f, indent=1)
+    _timing.emit(out, args.json)
     print("claim (b) + (c) < (a) on every photo:", out["claim_b_plus_c_below_a_on_every_photo"])
 
 

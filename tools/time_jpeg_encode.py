@@ -12,13 +12,12 @@ For 1, 16 and 256 1080p BGR frames, a synthetic frame with the solution drawn in
   e2e_fps          Context.imencode_batch, device tensor in, bytes out
   pillow_fps       Pillow (libjpeg-turbo) encoding the same frames on the same number of threads, including the D2H copy of the raw frames it needs
   d2h_fps          that raw D2H copy alone (into pinned memory)
-Device figures are the median (min, max) over `windows` windows of HIP-event time per call; host figures the median over `windows` runs of
-the wall clock.  stream_wall_ms: host clock per frame of pipeline.recognize_stream(overlay=True) over 40 repeats of one synthetic 1080p frame with
+Device figures are the median (min, max) over `windows` windows of HIP-event time per call (_timing.event_ms); host figures the median over
+`windows` runs of the wall clock (_timing.wall_fps).  stream_wall_ms: host clock per frame of pipeline.recognize_stream(overlay=True) over 40 repeats of one synthetic 1080p frame with
 encode off and on.
     python tools/time_jpeg_encode.py --stream-baseline --root PARENT_CHECKOUT [--json ...]
 times the same loop without the encode argument on another (built) checkout: the parent commit's figure for "encode off".
 Needs a GPU; there is no CPU path."""
-import argparse
 import ctypes as C
 import io
 import json
@@ -39,38 +38,10 @@ sys.path.insert(0, PKG_ROOT)
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd import pipeline  # noqa: E402
 from sudoku_vision_amd.synth import random_state_dict, synth_frames  # noqa: E402
+import _timing  # noqa: E402
 
-HBM_PEAK = 8.0e12
 H, W = 1080, 1920
 ITERS = {1: 400, 16: 40, 256: 3}
-
-
-def event_ms(fn, iters, windows):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    per_call = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        per_call.append(a.elapsed_time(b) / iters)
-    return statistics.median(per_call), min(per_call), max(per_call)
-
-
-def wall_fps(fn, frames, windows):
-    fn()
-    rates = []
-    for _ in range(windows):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        rates.append(frames / (time.perf_counter() - t0))
-    return statistics.median(rates), min(rates), max(rates)
 
 
 def solvable_grid():
@@ -145,26 +116,20 @@ def stream_wall_ms(ctx, frame, given, encode, repeats=40):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--threads", type=int, default=16)
-    ap.add_argument("--json", default=None)
-    ap.add_argument("--root", default=ROOT, help="checkout to import sudoku_vision_amd from")
-    ap.add_argument("--stream-baseline", action="store_true",
-                    help="only recognize_stream(overlay=True) without the encode argument: the figure a checkout from before the encoder gives (--root)")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("time_jpeg_encode.py needs a GPU")
+    args = _timing.cli(__doc__, 5, [
+        ("--threads", dict(type=int, default=16)),
+        ("--root", dict(default=ROOT, help="checkout to import sudoku_vision_amd from")),
+        ("--stream-baseline", dict(action="store_true", help="only recognize_stream(overlay=True) without the encode argument: the figure a checkout "
+                                                             "from before the encoder gives (--root)"))])
+    event_ms = lambda fn, iters: _timing.event_ms(fn, iters, args.windows, warmup=2)[:3]
+    wall_fps = lambda fn, frames: _timing.wall_fps(fn, frames, args.windows, warmup=1)[:3]
     ctx = sva.default_context()
     if args.stream_baseline:
         frame = synth_frames(1, H, W, seed=11, device="cuda")[0][0]
         ctx.load_state_dict(random_state_dict(1234))
         res = {"what": "recognize_stream(overlay=True) wall ms per frame, one synthetic 1080p frame, no encode argument", "package": os.path.dirname(sva.__file__),
                "stream_wall_ms": {"overlay_only": stream_wall_ms(ctx, frame, solvable_grid(), None)}}
-        print(json.dumps(res), flush=True)
-        if args.json:
-            with open(args.json, "w") as fh:
-                json.dump(res, fh, indent=1)
+        _timing.emit(res, args.json)
         return
     res = {"what": "1080p BGR frames, 4:2:0; device: HIP-event ms per call, median (min, max) over windows; host: frames/s, median (min, max); one run",
            "windows": args.windows, "threads": args.threads, "raw_bytes": 3 * H * W, "cases": []}
@@ -185,14 +150,14 @@ def main():
                     want = buf.getvalue()
                 assert got == want, "the encoder's bytes are not Pillow's"
                 case = {"content": name, "quality": quality, "frames": n, "file_bytes": len(got)}
-                case["device_ms"] = event_ms(lambda: ctx.jpeg_forward(frames, plan), ITERS[n], args.windows)
-                case["copy_ms"] = event_ms(lambda: dst.copy_(frames), ITERS[n], args.windows)
-                case["floor_ms"] = frames.numel() / HBM_PEAK * 1e3
+                case["device_ms"] = event_ms(lambda: ctx.jpeg_forward(frames, plan), ITERS[n])
+                case["copy_ms"] = event_ms(lambda: dst.copy_(frames), ITERS[n])
+                case["floor_ms"] = _timing.floor_ms(frames.numel())
                 case["device_over_copy"] = case["device_ms"][0] / case["copy_ms"][0]
                 run, keep, case["pcie_bytes"] = host_only(ctx, frames, plan, args.threads)
-                case["host_fps"] = wall_fps(run, n, args.windows)
+                case["host_fps"] = wall_fps(run, n)
                 del keep
-                case["e2e_fps"] = wall_fps(lambda: ctx.imencode_batch(frames, quality, "420", 0, args.threads), n, args.windows)
+                case["e2e_fps"] = wall_fps(lambda: ctx.imencode_batch(frames, quality, "420", 0, args.threads), n)
 
                 def pillow():
                     pinned.copy_(frames, non_blocking=True)
@@ -204,18 +169,15 @@ def main():
                         Image.fromarray(np.ascontiguousarray(host[i][..., ::-1]), "RGB").save(b, "JPEG", quality=quality, subsampling=2)
                         return b.getvalue()
                     return list(pool.map(one, range(n)))
-                case["pillow_fps"] = wall_fps(pillow, n, args.windows)
-                case["d2h_fps"] = wall_fps(lambda: pinned.copy_(frames, non_blocking=True), n, args.windows)
+                case["pillow_fps"] = wall_fps(pillow, n)
+                case["d2h_fps"] = wall_fps(lambda: pinned.copy_(frames, non_blocking=True), n)
                 res["cases"].append(case)
                 print(json.dumps(case), flush=True)
                 del frames, dst, pinned
     frame = synth_frames(1, H, W, seed=11, device="cuda")[0][0]
     ctx.load_state_dict(random_state_dict(1234))
     res["stream_wall_ms"] = {"encode_off": stream_wall_ms(ctx, frame, solvable_grid(), False), "encode_on": stream_wall_ms(ctx, frame, solvable_grid(), True)}
-    print(json.dumps(res["stream_wall_ms"]), flush=True)
-    if args.json:
-        with open(args.json, "w") as fh:
-            json.dump(res, fh, indent=1)
+    _timing.emit(res, args.json)
 
 
 if __name__ == "__main__":

@@ -11,14 +11,12 @@ For 1 / 16 / 256 copies of one 1080p 4:2:0 quality-95 file (a 1080p crop of test
   pcie_bytes           bytes per image that cross PCIe in imdecode_batch (compact transport), gray and colour
   e2e_fps              imdecode_batch + synchronize, frames per second, wall clock, `threads` host threads, gray and colour
   pillow_fps           Image.draft('L', ...) + np.asarray on a pool of `threads` threads, then one H2D copy of the frames
-Medians over `windows` windows; the first call of everything is a warm-up outside them."""
-import argparse
+Medians over `windows` windows (_timing.event_ms, _timing.wall_fps); the first call of everything is a warm-up outside them."""
 import ctypes as C
 import io
 import json
 import os
 import sys
-import time
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -30,33 +28,9 @@ import jpeg_gray_ref as G  # noqa: E402
 import png_encode_ref as R  # noqa: E402
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd import _native, host  # noqa: E402
+import _timing  # noqa: E402
 
 ITERS = {1: 20, 16: 5, 256: 1}
-
-
-def event_ms(fn, iters, windows):
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return float(np.median(out))
-
-
-def wall_fps(fn, n, windows):
-    fn()
-    out = []
-    for _ in range(windows):
-        t = time.perf_counter()
-        fn()
-        out.append(n / (time.perf_counter() - t))
-    return float(np.median(out))
 
 
 def staged(ctx, arrays, n):
@@ -66,13 +40,9 @@ def staged(ctx, arrays, n):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--threads", type=int, default=16)
-    ap.add_argument("--json", default=None)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("time_jpeg_gray.py needs a GPU")
+    args = _timing.cli(__doc__, 5, [("--threads", dict(type=int, default=16))])
+    event_ms = lambda fn, iters: _timing.event_ms(fn, iters, args.windows, warmup=1).median
+    wall_fps = lambda fn, n, windows=args.windows: _timing.wall_fps(fn, n, windows, warmup=1, sync=False).median  # the calls synchronise themselves
     from PIL import Image
     ctx = sva.default_context()
     lib = _native.lib()
@@ -106,7 +76,7 @@ def main():
             def run_gray():
                 for i in range(n):
                     lib.sv_jpeg_reconstruct_sparse_gray_u8(ctx._h, C.byref(ginfo), p(dm[i]), p(do[i]), p(dv[i]), p(dgq), p(gray[i]), w, stream, d)
-            case["gray_ms"] = event_ms(run_gray, ITERS[n], args.windows)
+            case["gray_ms"] = event_ms(run_gray, ITERS[n])
             assert (gray[n - 1].cpu().numpy() == want).all()
             del dm, do, dv
             (dc,) = staged(ctx, (gcoef,), n)
@@ -114,7 +84,7 @@ def main():
             def run_gray_dense():
                 for i in range(n):
                     lib.sv_jpeg_reconstruct_gray_u8(ctx._h, C.byref(ginfo), p(dc[i]), p(dgq), p(gray[i]), w, stream, d)
-            case["gray_dense_ms"] = event_ms(run_gray_dense, ITERS[n], args.windows)
+            case["gray_dense_ms"] = event_ms(run_gray_dense, ITERS[n])
             assert (gray[0].cpu().numpy() == want).all()
             del dc
             dm, do, dv = staged(ctx, (cm, co, cv), n)
@@ -122,27 +92,27 @@ def main():
             def run_colour():
                 for i in range(n):
                     lib.sv_jpeg_reconstruct_sparse_scaled_bgr_u8(ctx._h, C.byref(cinfo), p(dm[i]), p(do[i]), p(dv[i]), p(dcq), p(bgr[i]), 3 * w, stream, d)
-            case["colour_ms"] = event_ms(run_colour, ITERS[n], args.windows)
+            case["colour_ms"] = event_ms(run_colour, ITERS[n])
             del dm, do, dv
             (dc,) = staged(ctx, (ccoef,), n)
 
             def run_colour_dense():
                 for i in range(n):
                     lib.sv_jpeg_reconstruct_scaled_bgr_u8(ctx._h, C.byref(cinfo), p(dc[i]), p(dcq), p(bgr[i]), 3 * w, stream, d)
-            case["colour_dense_ms"] = event_ms(run_colour_dense, ITERS[n], args.windows)
+            case["colour_dense_ms"] = event_ms(run_colour_dense, ITERS[n])
             del dc
             dst = torch.empty_like(gray)
-            case["copy_ms"] = event_ms(lambda: dst.copy_(gray), ITERS[n], args.windows)
-            case["floor_ms"] = n * (gray_bytes + h * w) / 8e12 * 1e3
+            case["copy_ms"] = event_ms(lambda: dst.copy_(gray), ITERS[n])
+            case["floor_ms"] = _timing.floor_ms(n * (gray_bytes + h * w))
             del dst, bgr
             datas = [data] * n
 
             def e2e(is_gray):
                 ctx.imdecode_batch(datas, threads=args.threads, reduce=d, gray=is_gray)
                 torch.cuda.synchronize()
-            case["e2e_fps"] = {"gray": wall_fps(lambda: e2e(True), n, args.windows)}
+            case["e2e_fps"] = {"gray": wall_fps(lambda: e2e(True), n)}
             case["pcie_bytes"] = {"gray": ctx._jpeg_last_bytes}
-            case["e2e_fps"]["colour"] = wall_fps(lambda: e2e(False), n, args.windows)
+            case["e2e_fps"]["colour"] = wall_fps(lambda: e2e(False), n)
             case["pcie_bytes"]["colour"] = ctx._jpeg_last_bytes
             m = min(n, 64)                                              # the host-only measurement: at most four rounds of the pool
 
@@ -153,10 +123,7 @@ def main():
             case["pillow_fps"] = wall_fps(pillow, m, max(1, args.windows // 2))
             result["cases"].append(case)
             print(json.dumps(case), flush=True)
-    text = json.dumps(result, indent=1)
-    if args.json:
-        with open(args.json, "w") as f:
-            f.write(text + "\n")
+    _timing.emit(result, args.json)
 
 
 if __name__ == "__main__":

@@ -7,17 +7,16 @@ Inputs: tests/golden/sample_1.jpg (3648 x 2736, 4:2:0) and 16 synthetic 1080p fr
 Per reduce, for each input: (a) the HIP-event time of the device half alone (coefficients already in HBM -> BGR frame), through the
 compact and the dense transport; (b) imdecode_batch frames/s, host Huffman stage included (it decodes every coefficient at every
 reduce); (c) on the photo, the wall time of recognize_image on the decoded frame, and whether it finds a grid.  Every timing is the
-median of `repeats` windows after a warm-up.  Each reduce runs in a child process of its own under a time limit; the first child that
+median of `repeats` windows after a warm-up (_timing.event_ms, _timing.wall_ms).  Each reduce runs in a child process of its own under a time limit; the first child that
 fails ends the run.  Needs a GPU; there is no CPU path."""
-import argparse
 import ctypes as C
 import io
 import json
 import os
-import statistics
 import subprocess
 import sys
-import time
+
+import _timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -40,20 +39,9 @@ def step(reduce, repeats):
     stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def median_of(fn, iters, wall=False):
-        for _ in range(2):
-            fn()
-        torch.cuda.synchronize()
-        out = []
-        for _ in range(repeats):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t = time.perf_counter()
-            a.record()
-            for _ in range(iters):
-                fn()
-            b.record()
-            torch.cuda.synchronize()
-            out.append((time.perf_counter() - t) * 1e3 / iters if wall else a.elapsed_time(b) / iters)
-        return statistics.median(out)
+        if wall:
+            return _timing.wall_ms(fn, repeats, warmup=2, iters=iters).median
+        return _timing.event_ms(fn, iters, repeats, warmup=2).median
 
     def device_half_ms(data):
         """coefficients and quantiser steps of one file put into HBM once; then only the reconstruct entry is timed"""
@@ -107,11 +95,8 @@ def step(reduce, repeats):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--json", default=None)
-    ap.add_argument("--step", type=int, default=None, help="(internal) run one reduce in this process and print its record")
-    args = ap.parse_args()
+    args = _timing.cli(__doc__, None, [("--repeats", dict(type=int, default=5)),
+                                       ("--step", dict(type=int, default=None, help="(internal) run one reduce in this process and print its record"))])
     if args.step is not None:
         print("RESULT " + json.dumps(step(args.step, args.repeats)), flush=True)
         return 0
@@ -140,11 +125,7 @@ def main():
                                 "synthetic_device_half_sparse": base["synthetic_1080p"]["device_half"]["sparse_ms"] / r["synthetic_1080p"]["device_half"]["sparse_ms"],
                                 "synthetic_imdecode_batch_fps": r["synthetic_1080p"]["imdecode_batch_fps_16_threads"] / base["synthetic_1080p"]["imdecode_batch_fps_16_threads"]}
                                for r in out["steps"]]
-    print(json.dumps(out["against_reduce_1"]), flush=True)
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        with open(args.json, "w") as f:
-            json.dump(out, f, indent=1)
+    _timing.emit(out, args.json)
     return 0
 
 

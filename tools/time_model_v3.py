@@ -2,14 +2,11 @@
 
     python tools/time_model_v3.py [--iters 20] [--repeats 5] [--json out.json]
 
-Per batch size: HIP-event time per call (median of `repeats` windows of `iters` calls, after a warm-up that also ramps the clock), the
+Per batch size: HIP-event time per call (_timing.event_ms: median of `repeats` windows of `iters` calls, after a warm-up that also ramps the clock), the
 fraction of the 155 TFLOP/s f32 matrix peak that time amounts to (132.5 MFLOP per cell), and, in the same process, PyTorch-ROCm's own
 f32 eval forward of the same weights: the drop-in's module structure evaluated with torch.nn.functional (conv2d, batch_norm with
 running statistics, ...) on the device.  Needs a GPU; there is no CPU path."""
-import argparse
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -19,25 +16,10 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.runtime import _V3_BLOCKS, v3_layout  # noqa: E402
+from _timing import cli, emit, event_ms  # noqa: E402
 
 F32_MATRIX_PEAK = 155e12
 FLOP_PER_CELL = 132.5e6
-
-
-def event_ms(fn, iters, repeats):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return statistics.median(out)
 
 
 def random_state_dict(seed):
@@ -73,13 +55,7 @@ def torch_forward(w, x):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--json", default=None)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("time_model_v3.py needs a GPU")
+    args = cli(__doc__, None, [("--iters", dict(type=int, default=20)), ("--repeats", dict(type=int, default=5))])
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
     ctx = sva.default_context()
@@ -94,18 +70,14 @@ def main():
         iters = max(2, args.iters // (1 if frames < 256 else 4))
         with torch.no_grad():
             diff = float((ctx.cnn3_forward(x) - torch_forward(w, x)).abs().max())
-            ms = event_ms(lambda: ctx.cnn3_forward(x), iters, args.repeats)
-            ms_torch = event_ms(lambda: torch_forward(w, x), iters, args.repeats)
+            ms = event_ms(lambda: ctx.cnn3_forward(x), iters, args.repeats, warmup=3).median
+            ms_torch = event_ms(lambda: torch_forward(w, x), iters, args.repeats, warmup=3).median
         floor = B * FLOP_PER_CELL / F32_MATRIX_PEAK * 1e3
         res["sizes"][str(B)] = {"cells": B, "ms": ms, "floor_ms_at_155TF": floor, "fraction_of_f32_matrix_peak": floor / ms,
                                 "tflops": B * FLOP_PER_CELL / ms / 1e9, "pytorch_rocm_f32_ms": ms_torch, "pytorch_over_ours": ms_torch / ms,
                                 "max_abs_diff_vs_pytorch": diff}
         print(f"B={B:6d}: cnn3_forward {ms:9.4f} ms  ({100 * floor / ms:5.1f} % of 155 TF)   PyTorch-ROCm f32 {ms_torch:9.4f} ms   ratio {ms_torch / ms:5.2f}x   max|diff| {diff:.2e}")
-    text = json.dumps(res, indent=1)
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        with open(args.json, "w") as f:
-            f.write(text + "\n")
+    emit(res, args.json)
 
 
 if __name__ == "__main__":

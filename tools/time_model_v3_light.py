@@ -3,15 +3,12 @@
 
     python tools/time_model_v3_light.py [--iters 20] [--repeats 5] [--json out.json]
 
-Per batch size and model, in one process on one device: HIP-event time per call (median of `repeats` windows of `iters` calls, after a
+Per batch size and model, in one process on one device: HIP-event time per call (_timing.event_ms: median of `repeats` windows of `iters` calls, after a
 warm-up that also ramps the clock; the windows of the things compared alternate), the f32 matrix-pipe floor for the model's FLOP count
 (8.47 MFLOP per cell for Light, 2.13 for Empty) both at the 155 TFLOP/s nominal peak and at the rate an 8192^3 f32 torch.matmul reaches
 in this run, PyTorch-ROCm's own f32 eval forward of the same unfolded model written with torch.nn.functional, and cnn3_forward (K8) with
 Light's speed-up over it.  Needs a GPU; there is no CPU path."""
-import argparse
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -21,28 +18,10 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.runtime import empty_layout, light_layout, v3_layout  # noqa: E402
+from _timing import cli, emit, event_ms  # noqa: E402
 
 F32_MATRIX_PEAK = 155e12
 FLOP_PER_CELL = {"light": 8.47e6, "empty": 2.13e6}
-
-
-def event_ms(fns, iters, repeats):
-    """Median HIP-event time per call of each function of `fns`; the windows alternate between the functions."""
-    for fn in fns:
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    out = [[] for _ in fns]
-    for _ in range(repeats):
-        for k, fn in enumerate(fns):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(iters):
-                fn()
-            b.record()
-            torch.cuda.synchronize()
-            out[k].append(a.elapsed_time(b) / iters)
-    return [statistics.median(o) for o in out]
 
 
 def random_state_dict(layout, seed):
@@ -81,13 +60,7 @@ def torch_empty(w, x):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--json", default=None)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("time_model_v3_light.py needs a GPU")
+    args = cli(__doc__, None, [("--iters", dict(type=int, default=20)), ("--repeats", dict(type=int, default=5))])
     torch.backends.cudnn.allow_tf32 = False
     torch.backends.cuda.matmul.allow_tf32 = False
     ctx = sva.default_context()
@@ -102,7 +75,7 @@ def main():
 
     a = torch.randn(8192, 8192, device="cuda")
     b = torch.randn(8192, 8192, device="cuda")
-    gemm_ms = event_ms([lambda: torch.matmul(a, b)], 5, args.repeats)[0]
+    gemm_ms = event_ms(lambda: torch.matmul(a, b), 5, args.repeats, warmup=3).median
     gemm_rate = 2 * 8192 ** 3 / gemm_ms * 1e3
     del a, b
     print(f"f32 torch.matmul 8192^3: {gemm_ms:.3f} ms = {gemm_rate / 1e12:.1f} TFLOP/s (nominal f32 matrix peak {F32_MATRIX_PEAK / 1e12:.0f})")
@@ -119,7 +92,7 @@ def main():
             for m in ("light", "empty"):
                 diff = float((ours[m](x) - theirs[m](w[m], x)).abs().max())
                 fns = [lambda: ours[m](x), lambda: theirs[m](w[m], x)] + ([lambda: ctx.cnn3_forward(x)] if m == "light" else [])
-                t = event_ms(fns, iters, args.repeats)
+                t = [r.median for r in event_ms(fns, iters, args.repeats, warmup=3)]      # the windows alternate between the functions
                 ms, ms_torch = t[0], t[1]
                 floor = B * FLOP_PER_CELL[m] / F32_MATRIX_PEAK * 1e3
                 row[m] = {"ms": ms, "floor_ms_at_155TF": floor, "floor_ms_at_measured_gemm_rate": B * FLOP_PER_CELL[m] / gemm_rate * 1e3,
@@ -133,11 +106,7 @@ def main():
                     line += f"  K8 {k8_ms:8.4f} ms = {k8_ms / ms:5.1f}x"
                 print(line, flush=True)
         res["sizes"][str(B)] = row
-    text = json.dumps(res, indent=1)
-    if args.json:
-        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-        with open(args.json, "w") as f:
-            f.write(text + "\n")
+    emit(res, args.json)
 
 
 if __name__ == "__main__":

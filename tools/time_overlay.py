@@ -8,13 +8,12 @@ For 1, 16 and 256 synthetic 1080p frames, a small quad (140 px) and a large one 
   copy           dst.copy_(frames): the device copy of the same bytes (what out_of_place cannot be faster than)
   floor          bytes / 8 TB/s: in place, the pixels the reference changes, read and written (3 bytes each way); out of place, all frames
                  read and written
-Every figure is the median (min, max) over `windows` windows of HIP-event time per call; a window repeats the call until it holds tens
+Every figure is the median (min, max) over `windows` windows of HIP-event time per call (_timing.event_ms); a window repeats the call until it holds tens
 of milliseconds of work at least; every shape is warmed up first, and the in-place result of the first frame is compared with the
 out-of-place one before timing.  Drawing in place again and again changes the pixel values, not the work.
 stream_wall_ms: host clock per frame of pipeline.recognize_stream over 40 repeats of one synthetic 1080p frame, the recogniser handed a
 solvable grid, with overlay off and on; the loop synchronises with the host every frame, so it is reported, not judged.
 Needs a GPU; there is no CPU path."""
-import argparse
 import json
 import os
 import statistics
@@ -29,29 +28,12 @@ sys.path.insert(0, ROOT)
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd import pipeline  # noqa: E402
 from sudoku_vision_amd.synth import random_state_dict, synth_frames  # noqa: E402
+from _timing import cli, emit, event_ms, floor_ms  # noqa: E402
 
-HBM_PEAK = 8.0e12
 H, W = 1080, 1920
 ITERS = {1: 2000, 16: 400, 256: 25}
 QUADS = {"small_140px": np.array([[1203, 411], [1342, 420], [1335, 560], [1198, 548]], np.float32),
          "large_980px": np.array([[470, 52], [1452, 40], [1466, 1030], [455, 1018]], np.float32)}
-
-
-def window_ms(fn, iters, windows):
-    """Median, minimum and maximum over `windows` windows of the HIP-event time of one call of fn."""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    per_call = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        per_call.append(a.elapsed_time(b) / iters)
-    return statistics.median(per_call), min(per_call), max(per_call)
 
 
 def stream_wall_ms(ctx, frame, given, overlay, repeats=40):
@@ -83,12 +65,8 @@ def stream_wall_ms(ctx, frame, given, overlay, repeats=40):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--windows", type=int, default=7)
-    ap.add_argument("--json", default=None)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("time_overlay.py needs a GPU")
+    args = cli(__doc__, 7)
+    window_ms = lambda fn, iters: event_ms(fn, iters, args.windows, warmup=3)[:3]
     ctx = sva.default_context()
     gen = torch.Generator(device=ctx.device).manual_seed(1234)
     rs = np.random.RandomState(1)
@@ -108,14 +86,14 @@ def main():
             assert torch.equal(work, dst), "in place and out of place disagree"
             drawn = int((dst[0] != frames[0]).any(-1).sum().item())
             case = {"frames": n, "quad": name, "pixels_changed_in_frame_0": drawn}
-            case["in_place_ms"] = window_ms(lambda: ctx.render_overlay(work, m_dev, digits, out=work), ITERS[n], args.windows)
-            case["out_of_place_ms"] = window_ms(lambda: ctx.render_overlay(frames, m_dev, digits, out=dst), ITERS[n], args.windows)
-            case["copy_ms"] = window_ms(lambda: dst.copy_(frames), ITERS[n], args.windows)
-            case["in_place_ms_again"] = window_ms(lambda: ctx.render_overlay(work, m_dev, digits, out=work), ITERS[n], args.windows)
+            case["in_place_ms"] = window_ms(lambda: ctx.render_overlay(work, m_dev, digits, out=work), ITERS[n])
+            case["out_of_place_ms"] = window_ms(lambda: ctx.render_overlay(frames, m_dev, digits, out=dst), ITERS[n])
+            case["copy_ms"] = window_ms(lambda: dst.copy_(frames), ITERS[n])
+            case["in_place_ms_again"] = window_ms(lambda: ctx.render_overlay(work, m_dev, digits, out=work), ITERS[n])
             case["in_place_floor_bytes"] = 6 * drawn * n
-            case["in_place_floor_ms"] = case["in_place_floor_bytes"] / HBM_PEAK * 1e3
+            case["in_place_floor_ms"] = floor_ms(case["in_place_floor_bytes"])
             case["out_of_place_floor_bytes"] = 2 * frames.numel()
-            case["out_of_place_floor_ms"] = case["out_of_place_floor_bytes"] / HBM_PEAK * 1e3
+            case["out_of_place_floor_ms"] = floor_ms(case["out_of_place_floor_bytes"])
             case["out_of_place_over_copy"] = case["out_of_place_ms"][0] / case["copy_ms"][0]
             res["cases"].append(case)
             print(json.dumps(case), flush=True)
@@ -127,10 +105,7 @@ def main():
     given = ((3 * (r % 3) + r // 3 + c) % 9 + 1).astype(np.uint8)             # a valid solved grid, 45 cells blanked: solvable
     given[np.random.RandomState(2).choice(81, 45, replace=False)] = 0
     res["stream_wall_ms"] = {"overlay_off": stream_wall_ms(ctx, frame, given, False), "overlay_on": stream_wall_ms(ctx, frame, given, True)}
-    print(json.dumps(res, indent=1))
-    if args.json:
-        with open(args.json, "w") as fh:
-            json.dump(res, fh, indent=1)
+    emit(res, args.json)
 
 
 if __name__ == "__main__":

@@ -11,13 +11,11 @@ segment of 1080 rows):
                    on a pool of `threads` threads
   e2e_fps          imdecode_png_batch + synchronize, frames per second, wall clock, `threads` host threads
   pillow_fps       Image.open(...).convert("RGB") on a pool of `threads` threads, then one H2D copy of the frames
-Medians over `windows` windows; the first call of everything is a warm-up outside them."""
-import argparse
+Medians over `windows` windows (_timing.event_ms, _timing.wall_fps); the first call of everything is a warm-up outside them."""
 import io
 import json
 import os
 import sys
-import time
 import zlib
 from concurrent.futures import ThreadPoolExecutor
 
@@ -31,33 +29,9 @@ import png_decode_ref as D  # noqa: E402
 import png_encode_ref as R  # noqa: E402
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd import host  # noqa: E402
+import _timing  # noqa: E402
 
 ITERS = {1: 10, 16: 3, 256: 1}
-
-
-def event_ms(fn, iters, windows):
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return float(np.median(out))
-
-
-def wall_fps(fn, n, windows):
-    fn()
-    out = []
-    for _ in range(windows):
-        t = time.perf_counter()
-        fn()
-        out.append(n / (time.perf_counter() - t))
-    return float(np.median(out))
 
 
 def pillow_rgb(data):
@@ -66,13 +40,9 @@ def pillow_rgb(data):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--threads", type=int, default=16)
-    ap.add_argument("--json", default=None)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("time_png_decode.py needs a GPU")
+    args = _timing.cli(__doc__, 5, [("--threads", dict(type=int, default=16))])
+    event_ms = lambda fn, iters: _timing.event_ms(fn, iters, args.windows, warmup=1).median
+    wall_fps = lambda fn, n, windows=args.windows: _timing.wall_fps(fn, n, windows, warmup=1, sync=False).median  # the calls synchronise themselves
     from PIL import Image
     ctx = sva.default_context()
     img = R.photo_1080p("sample_1.jpg")
@@ -92,22 +62,22 @@ def main():
             f_dev = torch.from_numpy(filtered).to(ctx.device)[None].repeat(n, 1)
             r_dev = torch.from_numpy(row_filter).to(ctx.device)[None].repeat(n, 1)
             out = torch.empty((n, 1080, 1920, 3), dtype=torch.uint8, device=ctx.device)
-            case["device_ms"] = event_ms(lambda: ctx.png_reconstruct(info, f_dev, r_dev, None, out), ITERS[n], args.windows)
+            case["device_ms"] = event_ms(lambda: ctx.png_reconstruct(info, f_dev, r_dev, None, out), ITERS[n])
             assert (out[n - 1].cpu().numpy() == img).all()
             dst = torch.empty_like(f_dev)
-            case["copy_ms"] = event_ms(lambda: dst.copy_(f_dev), ITERS[n], args.windows)
-            case["floor_ms"] = (f_dev.numel() + out.numel()) / 8e12 * 1e3
+            case["copy_ms"] = event_ms(lambda: dst.copy_(f_dev), ITERS[n])
+            case["floor_ms"] = _timing.floor_ms(f_dev.numel() + out.numel())
             del f_dev, r_dev, dst
             datas = [data] * n
             m = min(n, 64)                                              # the host-only measurements: at most four rounds of the pool
             infos = [info] * m
-            case["inflate_fps"] = wall_fps(lambda: host.png_inflate_batch(datas[:m], infos, threads=args.threads), m, args.windows)
-            case["zlib_fps"] = wall_fps(lambda: list(pool.map(zlib.decompress, [payload] * m)), m, args.windows)
+            case["inflate_fps"] = wall_fps(lambda: host.png_inflate_batch(datas[:m], infos, threads=args.threads), m)
+            case["zlib_fps"] = wall_fps(lambda: list(pool.map(zlib.decompress, [payload] * m)), m)
 
             def e2e():
                 ctx.imdecode_png_batch(datas, threads=args.threads, out=out)
                 torch.cuda.synchronize()
-            case["e2e_fps"] = wall_fps(e2e, n, args.windows)
+            case["e2e_fps"] = wall_fps(e2e, n)
 
             def pillow():
                 frames = np.stack(list(pool.map(pillow_rgb, datas[:m])))
@@ -116,10 +86,7 @@ def main():
             case["pillow_fps"] = wall_fps(pillow, m, max(1, args.windows // 2))
             result["cases"].append(case)
             print(json.dumps(case), flush=True)
-    text = json.dumps(result, indent=1)
-    if args.json:
-        with open(args.json, "w") as f:
-            f.write(text + "\n")
+    _timing.emit(result, args.json)
 
 
 if __name__ == "__main__":

@@ -12,12 +12,10 @@ Timing, for 1 / 16 / 256 frames of 1080p BGR (a synthetic frame, and a 1080p cro
   pillow_fps       the same with Pillow's writer, compress_level=1
 --sizes: file size of one synthetic 1080p frame and the 1080p crops of sample_1.jpg and sample_4.jpg against len(zlib_rle(filtered)); the record
 tests/test_gpu_png_encode.py asserts against (the ratio is deterministic)."""
-import argparse
 import io
 import json
 import os
 import sys
-import time
 import zlib
 from concurrent.futures import ThreadPoolExecutor
 
@@ -28,33 +26,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import png_encode_ref as R  # noqa: E402
 import sudoku_vision_amd as sva  # noqa: E402
+import _timing  # noqa: E402
 
 ITERS = {1: 20, 16: 5, 256: 1}
-
-
-def event_ms(fn, iters, windows):
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return float(np.median(out))
-
-
-def wall_fps(fn, n, windows):
-    fn()
-    out = []
-    for _ in range(windows):
-        t = time.perf_counter()
-        fn()
-        out.append(n / (time.perf_counter() - t))
-    return float(np.median(out))
 
 
 def sub_filter(img):
@@ -92,14 +66,9 @@ def sizes(ctx):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--threads", type=int, default=16)
-    ap.add_argument("--sizes", action="store_true")
-    ap.add_argument("--json", default=None)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("time_png_encode.py needs a GPU")
+    args = _timing.cli(__doc__, 5, [("--threads", dict(type=int, default=16)), ("--sizes", dict(action="store_true"))])
+    event_ms = lambda fn, iters: _timing.event_ms(fn, iters, args.windows, warmup=1).median
+    wall_fps = lambda fn, n, windows=args.windows: _timing.wall_fps(fn, n, windows, warmup=1, sync=False).median  # the calls end in a read-back
     ctx = sva.default_context()
     if args.sizes:
         result = sizes(ctx)
@@ -114,13 +83,13 @@ def main():
             for n in (1, 16, 256):
                 frames = torch.from_numpy(img).to(ctx.device)[None].repeat(n, 1, 1, 1)
                 case = {"content": name, "frames": n, "raw_bytes": int(frames.numel())}
-                case["device_ms"] = event_ms(lambda: ctx.png_deflate(frames, plan), ITERS[n], args.windows)
+                case["device_ms"] = event_ms(lambda: ctx.png_deflate(frames, plan), ITERS[n])
                 dst = torch.empty_like(frames)
-                case["copy_ms"] = event_ms(lambda: dst.copy_(frames), ITERS[n], args.windows)
-                case["floor_ms"] = frames.numel() / 8e12 * 1e3
+                case["copy_ms"] = event_ms(lambda: dst.copy_(frames), ITERS[n])
+                case["floor_ms"] = _timing.floor_ms(frames.numel())
                 lens = ctx.png_deflate(frames, plan)[1]
                 case["pcie_bytes"] = int(lens.sum().item()) + 12 * int(lens.numel())
-                case["e2e_fps"] = wall_fps(lambda: ctx.imencode_png_batch(frames, threads=args.threads), n, args.windows)
+                case["e2e_fps"] = wall_fps(lambda: ctx.imencode_png_batch(frames, threads=args.threads), n)
                 m = min(n, 16)                                         # the host writers: at most one round of the pool
 
                 def host(writer):
@@ -130,11 +99,7 @@ def main():
                 case["pillow_fps"] = wall_fps(lambda: host(pillow_file), m, max(1, args.windows // 2))
                 result["cases"].append(case)
                 print(json.dumps(case), flush=True)
-    text = json.dumps(result, indent=1)
-    print(text)
-    if args.json:
-        with open(args.json, "w") as f:
-            f.write(text + "\n")
+    _timing.emit(result, args.json)
 
 
 if __name__ == "__main__":

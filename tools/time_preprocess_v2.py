@@ -2,43 +2,19 @@
 
     python tools/time_preprocess_v2.py [--iters 20] [--repeats 5] [--json out.json]
 
-Per stage: HIP-event time per call (median of `repeats` windows of `iters` calls, after a warm-up that also ramps the clock)
+Per stage: HIP-event time per call (_timing.event_ms: median of `repeats` windows of `iters` calls, after a warm-up that also ramps the clock)
 beside the bytes the stage must move (every input read once, every output written once) over the 8 TB/s HBM peak, and beside
 K1 (sv_preprocess_u8) on the same frames.  preprocess_multi_strategy as a whole is a host clock around one call per frame ending
 in a synchronise (it takes decisions on the host between stages).  normalize_illumination at k = 51 and k = 193 on the same
 1080p frames shows how the large close scales with k.  Needs a GPU; there is no CPU path."""
-import argparse
-import json
 import os
-import statistics
 import sys
-import time
-
-import numpy as np
-import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.cv import preprocess_v2  # noqa: E402
 from sudoku_vision_amd.synth import synth_frames  # noqa: E402
-
-HBM_PEAK = 8.0e12
-
-
-def event_ms(fn, iters, repeats):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return statistics.median(out)
+from _timing import HBM_PEAK_BYTES_PER_S, cli, emit, event_ms, floor_ms, wall_ms  # noqa: E402
 
 
 def stages(ctx, gray, bgr, iters, repeats):
@@ -65,36 +41,27 @@ def stages(ctx, gray, bgr, iters, repeats):
     ]
     res = {}
     for name, fn, nbytes in table:
-        ms = event_ms(fn, iters, repeats)
-        floor = nbytes / HBM_PEAK * 1e3
+        ms = event_ms(fn, iters, repeats, warmup=3).median
+        floor = floor_ms(nbytes)
         res[name] = {"ms": ms, "bytes": nbytes, "floor_ms_at_8TBps": floor, "x_floor": ms / floor}
     return res
 
 
 def whole(frames, repeats):
     """preprocess_multi_strategy, one call per frame, host clock to a synchronise -> median ms per frame."""
-    out = []
-    for _ in range(repeats + 1):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
+    last = []
+
+    def every_frame():
         for f in frames:
-            r = preprocess_v2.preprocess_multi_strategy(f)
-        torch.cuda.synchronize()
-        out.append((time.perf_counter() - t0) * 1e3 / len(frames))
-    return statistics.median(out[1:]), r
+            last[:] = [preprocess_v2.preprocess_multi_strategy(f)]
+    return wall_ms(every_frame, repeats, warmup=1).median / len(frames), last[0]
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--photo", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "sample_4.jpg"))
-    ap.add_argument("--json", default=None)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("time_preprocess_v2.py needs a GPU")
+    photo = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "sample_4.jpg")
+    args = cli(__doc__, None, [("--iters", dict(type=int, default=20)), ("--repeats", dict(type=int, default=5)), ("--photo", dict(default=photo))])
     ctx = sva.default_context()
-    res = {"iters": args.iters, "repeats": args.repeats, "hbm_peak_bytes_per_s": HBM_PEAK}
+    res = {"iters": args.iters, "repeats": args.repeats, "hbm_peak_bytes_per_s": HBM_PEAK_BYTES_PER_S}
 
     frames, _, _ = synth_frames(16, 1080, 1920, seed=1234, device="cuda")
     gray = ctx.gray(frames)
@@ -105,7 +72,8 @@ def main():
     scale = {}
     for k in (51, 193):
         background = ctx.morphology(one, ctx.MORPH_CLOSE, ctx.SHAPE_ELLIPSE, k)
-        scale[str(k)] = event_ms(lambda: ctx.divide_normalize(one, ctx.morphology(one, ctx.MORPH_CLOSE, ctx.SHAPE_ELLIPSE, k)), args.iters, args.repeats)
+        scale[str(k)] = event_ms(lambda: ctx.divide_normalize(one, ctx.morphology(one, ctx.MORPH_CLOSE, ctx.SHAPE_ELLIPSE, k)), args.iters, args.repeats,
+                                 warmup=3).median
         del background
     res["normalize_illumination_1x1080p_ms_by_k"] = dict(scale, ratio_193_over_51=scale["193"] / scale["51"], k_ratio=193 / 51)
     del frames, gray, one
@@ -118,10 +86,7 @@ def main():
     res["1xphoto"] = stages(ctx, ctx.gray(photo[None]), photo[None], max(2, args.iters // 4), args.repeats)
     ms, r = whole([photo], args.repeats)
     res["1xphoto"]["preprocess_multi_strategy (per frame, host clock)"] = {"ms": ms, "method_used": r.method_used, "has_shadow": r.has_shadow}
-    print(json.dumps(res, indent=1))
-    if args.json:
-        with open(args.json, "w") as fh:
-            json.dump(res, fh, indent=1)
+    emit(res, args.json)
 
 
 if __name__ == "__main__":

@@ -2,15 +2,12 @@
 
     python tools/time_quality.py [--frames 256] [--iters 50] [--steps 20] [--json out.json] [--kernels-only]
 
-k_frame_quality_stats: HIP-event time per call, bytes = the BGR frames read once, against the 8 TB/s HBM peak.
+k_frame_quality_stats: HIP-event time per call (_timing.event_ms, one window of `iters` calls after one warm-up call), bytes = the BGR frames read once, against the 8 TB/s HBM peak.
 k_grid_line_coverage (bits variant, as FramePipeline runs it): time per call; it reads a few of the bands' source words only.
 FramePipeline: frames/s with quality off and on, alternated twice in this process (the same frames, chunk and host threads).
 Needs a GPU; there is no CPU path."""
-import argparse
-import json
 import os
 import sys
-import time
 
 import torch
 
@@ -18,32 +15,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.pipeline import FramePipeline, host_cpu_budget  # noqa: E402
 from sudoku_vision_amd.synth import synth_frames, random_state_dict  # noqa: E402
-
-HBM_PEAK = 8.0e12
-
-
-def event_ms(fn, iters):
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
+import _timing  # noqa: E402
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=256)
-    ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--steps", type=int, default=20, help="pipeline: passes over the pool per timed region")
-    ap.add_argument("--json", default=None)
-    ap.add_argument("--kernels-only", action="store_true", help="skip the FramePipeline comparison (counter runs)")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("time_quality.py needs a GPU")
+    args = _timing.cli(__doc__, None, [
+        ("--frames", dict(type=int, default=256)), ("--iters", dict(type=int, default=50)),
+        ("--steps", dict(type=int, default=20, help="pipeline: passes over the pool per timed region")),
+        ("--kernels-only", dict(action="store_true", help="skip the FramePipeline comparison (counter runs)"))])
+    event_ms = lambda fn, iters: _timing.event_ms(fn, iters, windows=1, warmup=1).median
     n, H, W = args.frames, 1080, 1920
     ctx = sva.default_context()
     ctx.load_state_dict(random_state_dict(1234))
@@ -53,7 +33,7 @@ def main():
     outs = ctx.frame_quality_stats(frames)
     ms = event_ms(lambda: ctx.frame_quality_stats(frames, out=outs), args.iters)
     nbytes = n * H * W * 3
-    res["stats"] = {"ms": ms, "bytes": nbytes, "GB_per_s": nbytes / ms / 1e6, "fraction_of_8TBps": nbytes / (ms * 1e-3) / HBM_PEAK,
+    res["stats"] = {"ms": ms, "bytes": nbytes, "GB_per_s": nbytes / ms / 1e6, "fraction_of_8TBps": nbytes / (ms * 1e-3) / _timing.HBM_PEAK_BYTES_PER_S,
                     "target_ms": 0.40}
 
     bits = ctx.preprocess_bits(frames)
@@ -66,7 +46,7 @@ def main():
     res["coverage_u8"] = {"ms": event_ms(lambda: ctx.grid_line_coverage(binary, md, out=cnt), args.iters)}
     del binary
     if args.kernels_only:
-        print(json.dumps(res, indent=1))
+        _timing.emit(res, None)
         return
 
     host_threads = max(1, min(16, host_cpu_budget()) - 2)
@@ -80,18 +60,11 @@ def main():
     for _ in range(2):
         for q in (False, True):
             pipes[q].run(frames, out=out, total=n)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            pipes[q].run(frames, out=out, total=args.steps * n)
-            torch.cuda.synchronize()
-            rates[q].append(args.steps * n / (time.perf_counter() - t0))
+            rates[q].append(_timing.wall_fps(lambda: pipes[q].run(frames, out=out, total=args.steps * n), args.steps * n, runs=1, warmup=0).median)
     off, on = max(rates[False]), max(rates[True])
     res["pipeline"] = {"frames_per_s_quality_off": rates[False], "frames_per_s_quality_on": rates[True], "ratio_best": on / off,
                        "target_ratio": 0.75, "host_threads": host_threads, "note": pipes[True].describe()}
-    print(json.dumps(res, indent=1))
-    if args.json:
-        with open(args.json, "w") as fh:
-            json.dump(res, fh, indent=1)
+    _timing.emit(res, args.json)
 
 
 if __name__ == "__main__":

@@ -1,15 +1,12 @@
 """Times K9 (csrc/k9_resolve.hip, Context.resolve_conflicts into preallocated outputs): HIP-event time of the launch for 256 and 4096 frames of which 0 %, 10 %
 and 100 % break the sudoku rules (frames of tests/resolve_ref.py's generator), next to a device copy of the same top-k arrays (the
 cost of one pass over them), the plain-Python restatement's time per conflicted frame on one CPU core, and FramePipeline frames/s
-with resolve off and on.  Medians of repeated runs after a warm-up, with the spread.
+with resolve off and on.  Medians of repeated runs after a warm-up, with the spread (_timing.event_ms, wall_ms, wall_fps).
 
     python tools/time_resolve.py [--out profiles/NAME.json]"""
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -20,21 +17,8 @@ import resolve_ref as rr  # noqa: E402
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.pipeline import FramePipeline  # noqa: E402
 from sudoku_vision_amd.synth import random_state_dict, synth_frames  # noqa: E402
-
-
-def event_ms(fn, warmup=5, runs=30):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(runs):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b))
-    return {"median_ms": statistics.median(times), "min_ms": min(times), "max_ms": max(times), "runs": runs}
+from _timing import emit, wall_ms  # noqa: E402
+from time_propagate import launch_ms, pipeline_fps  # noqa: E402
 
 
 def main():
@@ -55,19 +39,15 @@ def main():
             di, dp = torch.from_numpy(index[pick]).to(ctx.device), torch.from_numpy(prob[pick]).to(ctx.device)
             oi, op = torch.empty_like(di), torch.empty_like(dp)
             outs = ctx.resolve_conflicts(di, dp)                 # allocated once: the timed calls only launch the kernel
-            k = event_ms(lambda: ctx.resolve_conflicts(di, dp, out=outs))
-            c = event_ms(lambda: (oi.copy_(di), op.copy_(dp)))
+            k = launch_ms(lambda: ctx.resolve_conflicts(di, dp, out=outs))
+            c = launch_ms(lambda: (oi.copy_(di), op.copy_(dp)))
             nbytes = di.numel() + 4 * dp.numel()
             res["kernel"].append({"frames": n, "conflicted_share": share, "conflicted": int(where.size), "resolve": k, "copy_of_topk": c,
                                   "topk_bytes": nbytes, "copy_GBps": 2 * nbytes / c["median_ms"] / 1e6})
             print(res["kernel"][-1], flush=True)
     sub = bad[:64]
-    t = []
-    for _ in range(3):
-        t0 = time.perf_counter()
-        rr.resolve(index[sub], prob[sub])
-        t.append((time.perf_counter() - t0) / sub.size * 1e3)
-    res["restatement_ms_per_conflicted_frame_one_core"] = {"median": statistics.median(t), "min": min(t), "max": max(t)}
+    t = wall_ms(lambda: rr.resolve(index[sub], prob[sub]), runs=3, warmup=0, sync=False)
+    res["restatement_ms_per_conflicted_frame_one_core"] = {"median": t.median / sub.size, "min": t.min / sub.size, "max": t.max / sub.size}
     print(res["restatement_ms_per_conflicted_frame_one_core"], flush=True)
 
     ctx.load_state_dict(random_state_dict(1234))
@@ -75,21 +55,11 @@ def main():
     frames = synth_frames(n, H, W, seed=0, device="cuda")[0].contiguous()
     res["pipeline"] = {}
     for name, on in (("resolve_off", False), ("resolve_on", True), ("resolve_off_again", False)):
-        p = FramePipeline(ctx, H, W, chunk=chunk, resolve=on)
-        p.run(frames)
-        torch.cuda.synchronize()
-        fps = []
-        for _ in range(5):
-            t0 = time.perf_counter()
-            p.run(frames, repeat=repeat)
-            torch.cuda.synchronize()
-            fps.append(n * repeat / (time.perf_counter() - t0))
-        res["pipeline"][name] = {"frames_per_s_median": statistics.median(fps), "min": min(fps), "max": max(fps), "runs": 5,
+        fps = pipeline_fps(FramePipeline(ctx, H, W, chunk=chunk, resolve=on), frames, repeat)
+        res["pipeline"][name] = {"frames_per_s_median": fps.median, "min": fps.min, "max": fps.max, "runs": 5,
                                  "frames": n * repeat, "chunk": chunk, "shape": [H, W]}
         print(name, res["pipeline"][name], flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(res, args.out)
 
 
 if __name__ == "__main__":

@@ -2,15 +2,12 @@
 of two inputs -- what FramePipeline(resolve=True, propagate=True) hands to the solver on synth.py's frames (propagated_digits and
 propagate_valid), and the sparse set of tests/solve_ref.py (17..30 clues, half with one clue falsified) -- next to a device copy of the
 same bytes, sv_solve_sudoku_batch_host on 16 threads with the D2H and H2D copies a caller with device tensors needs around it, and
-FramePipeline(resolve=True, propagate=True) frames/s with solve off and on.  Medians of repeated runs after a warm-up, with the spread.
+FramePipeline(resolve=True, propagate=True) frames/s with solve off and on.  Medians of repeated runs after a warm-up, with the spread (_timing.event_ms, wall_ms, wall_fps).
 
     python tools/time_solve.py [--out profiles/NAME.json]"""
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -21,20 +18,8 @@ import solve_ref as sr  # noqa: E402
 import sudoku_vision_amd as sva  # noqa: E402
 from sudoku_vision_amd.pipeline import FramePipeline  # noqa: E402
 from sudoku_vision_amd.synth import random_state_dict, synth_frames  # noqa: E402
-from time_propagate import event_ms  # noqa: E402
-
-
-def wall_ms(fn, warmup=3, runs=15):
-    for _ in range(warmup):
-        fn()
-    times = []
-    for _ in range(runs):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append((time.perf_counter() - t0) * 1e3)
-    return {"median_ms": statistics.median(times), "min_ms": min(times), "max_ms": max(times), "runs": runs}
+from _timing import emit, wall_ms  # noqa: E402
+from time_propagate import launch_ms, pipeline_fps, spread_ms  # noqa: E402
 
 
 def main():
@@ -55,9 +40,9 @@ def main():
             hg, ha = np.ascontiguousarray(grids[pick]), None if active is None else np.ascontiguousarray(active[pick])
             dg, da = torch.from_numpy(hg).to(ctx.device), None if ha is None else torch.from_numpy(ha).to(ctx.device)
             outs = ctx.solve_sudoku(dg, da)                         # allocated once: the timed calls only launch the kernel
-            k = event_ms(lambda: ctx.solve_sudoku(dg, da, out=outs))
+            k = launch_ms(lambda: ctx.solve_sudoku(dg, da, out=outs))
             og = torch.empty_like(dg)
-            c = event_ms(lambda: og.copy_(dg))
+            c = launch_ms(lambda: og.copy_(dg))
             pg, ps, pr, pn = (torch.empty(s, dtype=t).pin_memory() for s, t in (((n, 81), torch.uint8), ((n, 81), torch.uint8), ((n,), torch.int8), ((n,), torch.int32)))
             hs, hr, hn = (torch.empty_like(outs[key]) for key in ("solution", "result", "nodes"))
 
@@ -66,7 +51,7 @@ def main():
                 r, s, m = sva.host.solve_sudoku_batch(pg.numpy(), active=ha, max_nodes=4096, threads=16)
                 ps.copy_(torch.from_numpy(s.reshape(n, 81))), pr.copy_(torch.from_numpy(r)), pn.copy_(torch.from_numpy(m))
                 hs.copy_(ps, non_blocking=True), hr.copy_(pr, non_blocking=True), hn.copy_(pn, non_blocking=True)
-            h = wall_ms(on_host)
+            h = spread_ms(wall_ms(on_host, runs=15, warmup=3))
             assert all(torch.equal(a, outs[key]) for a, key in ((hs, "solution"), (hr, "result"), (hn, "nodes")))
             result = outs["result"].cpu().numpy()
             res["kernel"].append({"input": name, "frames": n, "solve": k, "copy_of_input": c, "host_16_threads_with_copies": h, "input_bytes": dg.numel(),
@@ -76,21 +61,11 @@ def main():
 
     res["pipeline"] = {}
     for name, on in (("solve_off", False), ("solve_on", True), ("solve_off_again", False), ("solve_on_again", True)):
-        p = FramePipeline(ctx, H, W, chunk=chunk, resolve=True, propagate=True, solve=on)
-        p.run(frames)
-        torch.cuda.synchronize()
-        fps = []
-        for _ in range(5):
-            t0 = time.perf_counter()
-            p.run(frames, repeat=repeat)
-            torch.cuda.synchronize()
-            fps.append(n_pool * repeat / (time.perf_counter() - t0))
-        res["pipeline"][name] = {"frames_per_s_median": statistics.median(fps), "min": min(fps), "max": max(fps), "runs": 5,
+        fps = pipeline_fps(FramePipeline(ctx, H, W, chunk=chunk, resolve=True, propagate=True, solve=on), frames, repeat)
+        res["pipeline"][name] = {"frames_per_s_median": fps.median, "min": fps.min, "max": fps.max, "runs": 5,
                                  "frames": n_pool * repeat, "chunk": chunk, "shape": [H, W], "resolve": True, "propagate": True}
         print(name, res["pipeline"][name], flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
+    emit(res, args.out)
 
 
 if __name__ == "__main__":
