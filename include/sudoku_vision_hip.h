@@ -402,7 +402,8 @@ int sv_cnn_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells /*dev, B*784*/, lo
 #define SV_CNN3_PARAMS_NOSE 679595
 #define SV_CNN3_FEATURES 128
 /* The v3 forward keeps its activations in context scratch, 3 * 32*28*28 floats (301,056 bytes) per cell, for at most this many cells: a
- * larger batch runs as consecutive sub-batches, so the scratch never exceeds SV_V3_SUBBATCH * 301,056 bytes = 147 MiB. */
+ * larger batch runs as consecutive sub-batches, so the scratch never exceeds SV_V3_SUBBATCH * 301,056 bytes = 147 MiB.  sv_ctx_reserve
+ * sizes it for all SV_V3_SUBBATCH cells whatever max_cells is: sv_cnn3_forward_mc_f32 fills them at any batch size. */
 #define SV_V3_SUBBATCH 512
 
 /* blob: the state_dict of DigitCNNv3 (ml/model_v3.py:113-149) flattened in key order, the int64 num_batches_tracked entries skipped:
@@ -428,6 +429,46 @@ int sv_cnn3_forward_f32(sv_ctx *ctx, const float *x /*dev, B*784*/, long B, floa
  * the model (its preprocess_cell is run.py's), SV_GLUE_NORMALIZE the invert + normalise alone. */
 int sv_cnn3_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells /*dev, B*784*/, long B, int glue, float *logits /*dev, B*10*/,
                              uint8_t *digits /*dev or NULL*/, float *conf /*dev or NULL*/, void *stream);
+
+/* MC dropout: DigitCNNv3.forward_with_uncertainty, ml/model_v3.py:186-214.  For each of n_samples samples s and each cell b the forward
+ * runs with the network's three dropouts active -- spatial dropout (:80-92, whole channels, x * keep / (1 - p_spatial)) on layer1's 32 and
+ * layer3's 64 output channels (:167, :170), nn.Dropout(p_fc) on the 128 pooled features (:181) -- and probs = softmax(logits /
+ * temperature).  mean f32 [B,10]: the mean over the samples; std f32 [B,10]: their unbiased standard deviation (divisor n_samples - 1; NaN
+ * for one sample, as torch.std); predicted int64 [B]: the first maximum of mean.  logits_out f32 [n_samples,B,10]: the per-sample logits.
+ * keep*_out u8 [n_samples,B,32], [n_samples,B,64], [n_samples,B,128]: the masks that were used, 1 = keep.  Every output may be NULL.
+ *
+ * DEVIATION, deliberate: BatchNorm keeps its running statistics.  The reference enables dropout with self.train() (:200), which also
+ * switches its eleven BatchNorms to batch statistics and overwrites their running buffers on every sample, so its result depends on
+ * what else is in the batch and every later eval forward changes.  Here nothing of the model is written, a cell's results do not depend
+ * on the rest of the batch, and with both rates 0 every sample's logits are sv_cnn3_forward_f32's bit for bit (std exactly 0).
+ *
+ * Masks.  keep*_in (all three, or all NULL): the caller's masks in the shapes of keep*_out, nonzero = keep; they replace the generator.
+ * Otherwise a keep bit is a pure function of (seed, offset, s, b, site, channel) -- not of B, n_samples or how the work is chunked --
+ * drawn by Philox4x32-10 (csrc/sv_philox.h):
+ *     key     = (seed & 0xffffffff, seed >> 32)
+ *     counter = (b, s, site * 64 + channel / 4 + ((offset >> 32 & 0xffffff) << 8), offset & 0xffffffff)
+ *     the four output words serve channels 4g .. 4g + 3; site 0 = layer1, 1 = layer3, 2 = the features
+ *     keep    = (uint64)word < llrint((1.0 - (double)p) * 4294967296.0)           always at p = 0, never at p = 1
+ * PyTorch's own draw order is not reproduced (it differs between its CPU and GPU backends anyway).  sv_mc_dropout_masks_host is the
+ * same generator on the host.
+ *
+ * Stem and layer1 run once per cell, layers 2..5 per (sample, cell), in chunks of SV_V3_SUBBATCH / n_samples whole cells; results repeat
+ * bit for bit.  Scratch: the forward's activations for SV_V3_SUBBATCH cells plus 49 MiB of the entry's own, constant, sized by
+ * sv_ctx_reserve / sv_load_weights_v3_f32 like the forward's: after sv_ctx_reserve the entry allocates nothing and can be captured in a
+ * hipGraph.  seed, offset and the mask pointers are launch arguments: a replay repeats the captured masks.  Asynchronous on `stream`.
+ * SV_ERR_NO_WEIGHTS and SV_ERR_UNSUPPORTED as sv_cnn3_forward_f32; SV_ERR_BAD_ARG for p_spatial outside [0, 1), p_fc outside [0, 1],
+ * n_samples < 1 or > SV_V3_SUBBATCH, or some but not all of keep*_in.  B = 0 is SV_OK. */
+int sv_cnn3_forward_mc_f32(sv_ctx *ctx, const float *x /*dev, B*784*/, long B, int n_samples, float p_spatial, float p_fc, uint64_t seed, uint64_t offset,
+                           const uint8_t *keep1_in /*dev or NULL*/, const uint8_t *keep3_in /*dev or NULL*/, const uint8_t *keepf_in /*dev or NULL*/,
+                           float *mean /*dev, B*10, or NULL*/, float *std /*dev, B*10, or NULL*/, int64_t *predicted /*dev, B, or NULL*/,
+                           float *logits_out /*dev, n_samples*B*10, or NULL*/, uint8_t *keep1_out /*dev or NULL*/, uint8_t *keep3_out /*dev or NULL*/,
+                           uint8_t *keepf_out /*dev or NULL*/, void *stream);
+
+/* The masks sv_cnn3_forward_mc_f32 draws at (seed, offset) with keep*_in NULL, on the host: keep1 u8 [n_samples,B,32], keep3
+ * [n_samples,B,64], keepf [n_samples,B,128], each or NULL.  Needs no context and no GPU.  SV_ERR_BAD_ARG for the rates as above,
+ * n_samples < 1 or B < 0. */
+int sv_mc_dropout_masks_host(uint64_t seed, uint64_t offset, int n_samples, long B, float p_spatial, float p_fc, uint8_t *keep1 /*host*/,
+                             uint8_t *keep3 /*host*/, uint8_t *keepf /*host*/);
 
 /* sv_frames_to_digits with the v3 model: K2, then sv_cnn3_forward_cells_u8 (pipeline/run_v2.py:149-163 after the warp). */
 int sv_frames_to_digits_v3(sv_ctx *ctx, const uint8_t *frames /*dev*/, int n, int H, int W,

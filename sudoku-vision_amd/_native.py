@@ -103,6 +103,8 @@ SIGNATURES = {
     "sv_load_weights_v3_f32": [_p, _p, _l, _i],
     "sv_cnn3_forward_f32": [_p, _p, _l, _p, _p, _p, _p, _p],
     "sv_cnn3_forward_cells_u8": [_p, _p, _l, _i, _p, _p, _p, _p],
+    "sv_cnn3_forward_mc_f32": [_p, _p, _l, _i, _f, _f, C.c_uint64, C.c_uint64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "sv_mc_dropout_masks_host": [C.c_uint64, C.c_uint64, _i, _l, _f, _f, _p, _p, _p],
     "sv_frames_to_digits_v3": [_p, _p, _i, _i, _i, _pd, _pd, _p, _i, _p, _p, _p, _p, _p],
     "sv_load_weights_v3_light_f32": [_p, _p, _l],
     "sv_cnn3_light_forward_f32": [_p, _p, _l, _p, _p, _p, _p, _p],

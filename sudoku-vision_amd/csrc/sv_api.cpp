@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "sv_internal.h"
+#include "sv_philox.h"
 
 // ---- errors ---------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -99,6 +100,13 @@ static int sv_ensure_scratch_v3(sv_ctx *ctx, long cells)
     return SV_OK;
 }
 
+// the same with room for the MC forward, whose chunks fill all SV_V3_SUBBATCH cells whatever the batch, and its own scratch
+static int sv_ensure_scratch_v3_mc(sv_ctx *ctx)
+{
+    const int rc = sv_ensure_scratch_v3(ctx, SV_V3_SUBBATCH);
+    return rc ? rc : ctx->v3_mc.grow(ctx, svk_v3_mc_scratch_bytes());
+}
+
 extern "C" int sv_ctx_set_precision(sv_ctx *ctx, int precision)
 {
     if (!ctx || (precision != SV_PREC_F32 && precision != SV_PREC_BF16)) return sv_fail(SV_ERR_BAD_ARG, "sv_ctx_set_precision: bad argument");
@@ -112,7 +120,7 @@ extern "C" int sv_ctx_reserve(sv_ctx *ctx, long max_cells)
     SV_HIP(hipSetDevice(ctx->device));
     int rc = ctx->range_flag.grow(ctx, 2 * sizeof(int));                  // sv_cnn_forward_f32's per-call range flag: no hipMalloc after reserve
     if (rc || (rc = sv_ensure_scratch(ctx, max_cells))) return rc;
-    return ctx->w3.loaded ? sv_ensure_scratch_v3(ctx, max_cells) : SV_OK;    // v1-only contexts do not pay for the v3 activations
+    return ctx->w3.loaded ? sv_ensure_scratch_v3_mc(ctx) : SV_OK;            // v1-only contexts do not pay for the v3 activations
 }
 
 // ---- per-kernel timing -------------------------------------------------------------------------------
@@ -196,7 +204,7 @@ extern "C" int sv_load_weights_v3_f32(sv_ctx *ctx, const float *blob, long n_flo
     free_weights(ctx->w3);
     int rc = svk_pack_weights_v3(ctx->w3, blob, use_se != 0);
     if (rc) { free_weights(ctx->w3); return rc; }
-    return ctx->n_cells > 0 ? sv_ensure_scratch_v3(ctx, ctx->n_cells) : SV_OK;
+    return ctx->n_cells > 0 ? sv_ensure_scratch_v3_mc(ctx) : SV_OK;
 }
 
 // the Light and Empty loads: `n_floats` against the model's count, then `pack` into the model's own slot
@@ -583,6 +591,36 @@ static int cnn3_common(sv_ctx *ctx, const void *x, bool u8in, int glue, long B, 
 extern "C" int sv_cnn3_forward_f32(sv_ctx *ctx, const float *x, long B, float *logits, float *features, uint8_t *digits, float *conf, void *stream)
 {
     return cnn3_common(ctx, x, false, SV_GLUE_NORMALIZE, B, logits, features, digits, conf, stream);
+}
+
+extern "C" int sv_cnn3_forward_mc_f32(sv_ctx *ctx, const float *x, long B, int n_samples, float p_spatial, float p_fc, uint64_t seed, uint64_t offset,
+                                      const uint8_t *keep1_in, const uint8_t *keep3_in, const uint8_t *keepf_in, float *mean, float *std, int64_t *predicted,
+                                      float *logits_out, uint8_t *keep1_out, uint8_t *keep3_out, uint8_t *keepf_out, void *stream)
+{
+    REQUIRE(ctx && (x || B == 0), "NULL argument");
+    REQUIRE(B >= 0, "B < 0");
+    if (!ctx->w3.loaded) return sv_fail(SV_ERR_NO_WEIGHTS, "sv_cnn3_forward_mc_f32: call sv_load_weights_v3_f32 first");
+    if (ctx->precision != SV_PREC_F32) return sv_fail(SV_ERR_UNSUPPORTED, "sv_cnn3_forward_mc_f32: the DigitCNNv3 forward has f32 arithmetic only (context is set to SV_PREC_BF16)");
+    REQUIRE(p_spatial >= 0.f && p_spatial < 1.f, "p_spatial outside [0, 1)");
+    REQUIRE(p_fc >= 0.f && p_fc <= 1.f, "p_fc outside [0, 1]");
+    REQUIRE(n_samples >= 1 && n_samples <= SV_V3_SUBBATCH, "n_samples outside 1 .. SV_V3_SUBBATCH");
+    REQUIRE((!keep1_in == !keep3_in) && (!keep1_in == !keepf_in), "keep_in: all three masks or none");
+    if (B == 0) return SV_OK;
+    const int rc = sv_ensure_scratch_v3_mc(ctx);
+    if (rc) return rc;
+    const uint8_t *const in[3] = {keep1_in, keep3_in, keepf_in};
+    uint8_t *const out[3] = {keep1_out, keep3_out, keepf_out};
+    return svk_cnn3_forward_mc(ctx, x, B, n_samples, p_spatial, p_fc, seed, offset, in, mean, std, (long long *)predicted, logits_out, out, S(stream));
+}
+
+extern "C" int sv_mc_dropout_masks_host(uint64_t seed, uint64_t offset, int n_samples, long B, float p_spatial, float p_fc, uint8_t *keep1, uint8_t *keep3,
+                                        uint8_t *keepf)
+{
+    REQUIRE(n_samples >= 1 && B >= 0, "bad shape");
+    REQUIRE(p_spatial >= 0.f && p_spatial < 1.f, "p_spatial outside [0, 1)");
+    REQUIRE(p_fc >= 0.f && p_fc <= 1.f, "p_fc outside [0, 1]");
+    sv_mc_masks_fill(seed, offset, n_samples, B, p_spatial, p_fc, keep1, keep3, keepf);
+    return SV_OK;
 }
 
 extern "C" int sv_cnn3_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells, long B, int glue, float *logits, uint8_t *digits, float *conf, void *stream)

@@ -85,6 +85,7 @@ struct sv_ctx {
     // grow-only scratch; for_each_scratch below lists every one of them
     sv_scratch v3_act;          // k8_cnn_v3.hip: three activation buffers of [v3_cells][32*784] floats
     long v3_cells = 0;          // at most SV_V3_SUBBATCH
+    sv_scratch v3_mc;           // k8_cnn_v3.hip: the MC forward's layer1 outputs, probabilities and keep bytes of one chunk (svk_v3_mc_scratch_bytes)
     sv_scratch features;        // float [cells][49][64] pooled conv2 output
     sv_scratch cells;           // u8 [cells][784]
     sv_scratch cells2;          // u8 [cells][784] preprocess_cell output (SV_GLUE_RUNPY)
@@ -103,7 +104,7 @@ struct sv_ctx {
     // sv_ctx_destroy frees through this and nothing else: a new buffer goes in here
     template <class F> void for_each_scratch(F f)
     {
-        for (sv_scratch *b : {&v3_act, &features, &cells, &cells2, &jpeg_planes, &jpeg_enc, &png_enc, &png_dec, &pp2, &cc, &grid2, &k1_list, &range_flag, &overlay}) f(*b);
+        for (sv_scratch *b : {&v3_act, &v3_mc, &features, &cells, &cells2, &jpeg_planes, &jpeg_enc, &png_enc, &png_dec, &pp2, &cc, &grid2, &k1_list, &range_flag, &overlay}) f(*b);
     }
     int precision = 0;          // SV_PREC_F32 / SV_PREC_BF16 (sv_ctx_set_precision)
     int cnn_kernels = 0;        // SV_CNN_AUTO / _F16PAIR / _F32MFMA (sv_ctx_set_cnn_kernels)
@@ -244,6 +245,9 @@ int svk_pack_weights_v3(sv_weights3 &w, const float *blob, bool use_se);
 long svk_v3_blob_floats(bool use_se);
 size_t svk_v3_scratch_bytes(long cells);
 int svk_cnn3_forward(sv_ctx *ctx, const void *x, bool x_is_u8, long B, float *logits, float *features, u8 *digits, float *conf, hipStream_t s);
+size_t svk_v3_mc_scratch_bytes();
+int svk_cnn3_forward_mc(sv_ctx *ctx, const float *x, long B, int S, float p_spatial, float p_fc, uint64_t seed, uint64_t offset, const u8 *const keep_in[3],
+                        float *mean, float *std, long long *predicted, float *logits_out, u8 *const keep_out[3], hipStream_t s);
 
 // k12_cnn_v3_light.hip
 int svk_pack_weights_light(sv_weights_light &w, const float *blob);

@@ -354,3 +354,20 @@ def png_inflate_batch(datas, infos=None, threads=None):
     _native.lib().sv_png_inflate_batch((C.c_char_p * n)(*datas), (C.c_size_t * n)(*[len(d) for d in datas]), arr, n, VP(*[o.ctypes.data for o in outs]),
                                        (C.c_size_t * n)(*[o.size for o in outs]), VP(*[r.ctypes.data for r in rows]), int(threads), status)
     return infos, outs, rows, np.array(list(status), np.int32)
+
+
+def mc_dropout_masks(seed, offset, n_samples, B, p_spatial=0.1, p_fc=0.5):
+    """The keep masks Context.cnn3_forward_mc draws at (seed, offset) when none are passed in (sv_mc_dropout_masks_host; the generator's
+    layout is in include/sudoku_vision_hip.h): (keep1 u8 [S,B,32], keep3 [S,B,64], keepf [S,B,128]), 1 = keep.  A cell's sample has the
+    same masks whatever B and n_samples are."""
+    S, B = int(n_samples), int(B)
+    if S < 1 or B < 0:
+        raise ValueError(f"n_samples must be at least 1 and B at least 0, got {n_samples}, {B}")
+    if not 0.0 <= float(p_spatial) < 1.0:
+        raise ValueError(f"spatial dropout rate must be in [0, 1), got {p_spatial}")
+    if not 0.0 <= float(p_fc) <= 1.0:
+        raise ValueError(f"dropout rate must be in [0, 1], got {p_fc}")
+    out = tuple(np.empty((S, B, c), np.uint8) for c in (32, 64, 128))
+    _native.check(_native.lib().sv_mc_dropout_masks_host(int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), S, B, float(p_spatial), float(p_fc),
+                                                         *[o.ctypes.data_as(C.c_void_p) for o in out]), "sv_mc_dropout_masks_host")
+    return out

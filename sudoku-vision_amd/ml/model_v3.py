@@ -4,7 +4,12 @@ BatchNorm folded into the convolutions when the weights are packed).  `DigitCNNv
 csrc/k12_cnn_v3_light.hip, one launch per forward.  Inference only, GPU only.  `calibrate_temperature` is plain torch on the logits.
 
 The submodules below exist to hold parameters and buffers under the reference's names, so that a reference checkpoint loads with
-strict=True; none of them is ever called.  Not provided: MC dropout (forward_with_uncertainty needs train-mode dropout)."""
+strict=True; none of them is ever called.
+
+`DigitCNNv3.forward_with_uncertainty` is MC dropout on the GPU (csrc/k8_cnn_v3.hip, sv_cnn3_forward_mc_f32): the three dropouts of the
+reference's forward (ml/model_v3.py:167, :170, :181) are active, BatchNorm is not -- where the reference's self.train() (:200) also puts
+its BatchNorms on batch statistics and overwrites their running buffers, this one leaves the model as it was.  Its masks come from a
+counter-based generator seeded by torch's CUDA generator, not from PyTorch's own draw order."""
 import os
 import sys
 
@@ -42,6 +47,15 @@ class _Block(nn.Module):
         self.shortcut = nn.Sequential(*_conv_bn(cin, cout, 1, stride)) if (stride != 1 or cin != cout) else nn.Identity()
 
 
+class SpatialDropout2d(nn.Module):
+    """Holder of the rate of the reference's spatial dropout (ml/model_v3.py:80-92): whole feature maps are dropped at rate `p`, the kept
+    ones scaled by 1 / (1 - p).  No parameters; forward_with_uncertainty reads `p`."""
+
+    def __init__(self, p: float = 0.5):
+        super().__init__()
+        self.p = p
+
+
 class DigitCNNv3(nn.Module):
     """Residual digit classifier of the reference's ml/model_v3.py:95-149: stem, five residual blocks (32, 64/2, 64, 128/2, 128), global
     average pool, fc; `temperature` calibrates get_confidence."""
@@ -54,7 +68,8 @@ class DigitCNNv3(nn.Module):
         self.stem = nn.Sequential(*_conv_bn(1, 32, 3, 1), nn.ReLU())
         for i, (cin, cout, stride) in enumerate(_rt._V3_BLOCKS, 1):
             setattr(self, f"layer{i}", _Block(cin, cout, stride, self.use_se))
-        self.dropout = nn.Dropout(dropout)          # identity in eval mode, the only mode there is here
+        self.spatial_dropout = SpatialDropout2d(p=0.1)   # after layer1 and layer3; active in forward_with_uncertainty alone
+        self.dropout = nn.Dropout(dropout)          # identity in forward(); forward_with_uncertainty reads its p
         self.fc = nn.Linear(128, num_classes)
         self.temperature = nn.Parameter(torch.ones(1), requires_grad=False)
 
@@ -62,8 +77,9 @@ class DigitCNNv3(nn.Module):
         # parameters AND BatchNorm buffers: running statistics are folded into the packed weights
         return tuple((v.data_ptr(), v._version) for v in self.state_dict(keep_vars=True).values())
 
-    def _context(self, x):
-        ctx = _rt._model_context(x, self.training, "DigitCNNv3", "dropout is identity and BatchNorm uses its running statistics")
+    def _context(self, x, mc_dropout=False):
+        # mc_dropout: forward_with_uncertainty, the one caller that a module in training mode may reach the kernels through
+        ctx = _rt._model_context(x, self.training and not mc_dropout, "DigitCNNv3", "dropout is identity and BatchNorm uses its running statistics")
         key = (id(self), self._weights_key())
         if ctx._weights_v3_key != key:
             ctx.load_state_dict_v3(self.state_dict(), use_se=self.use_se, key=key)
@@ -82,8 +98,28 @@ class DigitCNNv3(nn.Module):
         _, digits, conf = ctx.cnn3_forward(x.to(torch.float32).contiguous(), want_digits=True)
         return digits.to(torch.int64), conf
 
-    def forward_with_uncertainty(self, x, n_samples: int = 10):
-        raise NotImplementedError("DigitCNNv3 (MI355X): MC dropout needs train-mode dropout; this forward is inference only")
+    def forward_with_uncertainty(self, x: torch.Tensor, n_samples: int = 10, *, generator=None):
+        """MC dropout (reference ml/model_v3.py:186-214): (mean, unbiased std, argmax of the mean) of softmax(logits / temperature) over
+        n_samples forwards with `spatial_dropout` (after layer1 and layer3) and `dropout` (on the pooled features) drawing fresh masks,
+        BatchNorm on its running statistics.  The masks are a function of the seed and offset of `generator` (default: the device's
+        CUDA generator, so torch.manual_seed makes a call repeatable), which the call advances; a cell's masks do not depend on the rest
+        of the batch.  Leaves the module in eval mode, as the reference does."""
+        if int(n_samples) < 1:
+            raise ValueError(f"n_samples must be at least 1, got {n_samples}")
+        p_spatial, p_fc = float(self.spatial_dropout.p), float(self.dropout.p)
+        if not 0.0 <= p_spatial < 1.0:
+            raise ValueError(f"spatial_dropout.p must be in [0, 1), got {p_spatial}")
+        if not 0.0 <= p_fc <= 1.0:
+            raise ValueError(f"dropout.p must be in [0, 1], got {p_fc}")
+        if not x.is_cuda:
+            raise NotImplementedError("DigitCNNv3 (MI355X): forward_with_uncertainty runs on the GPU only; there is no CPU fallback")
+        ctx = self._context(x, mc_dropout=True)
+        gen = generator if generator is not None else torch.cuda.default_generators[x.device.index]
+        seed, offset = gen.initial_seed(), gen.get_offset()
+        gen.set_offset(offset + 4)
+        out = ctx.cnn3_forward_mc(x.to(torch.float32).contiguous(), n_samples, p_spatial, p_fc, seed, offset)
+        self.eval()
+        return out
 
     def set_temperature(self, temperature: float):
         with torch.no_grad():

@@ -1040,6 +1040,41 @@ class Context:
         128 pooled features [B,128] come last (f32 input only)."""
         return self._cnn3_forward("sv_cnn3_forward", 128, x, want_digits, want_features, glue)
 
+    def cnn3_forward_mc(self, x, n_samples, p_spatial, p_fc, seed, offset, masks=None, want_logits=False, want_masks=False):
+        """MC dropout, DigitCNNv3.forward_with_uncertainty (ml/model_v3.py:186-214) with BatchNorm on its running statistics
+        (sv_cnn3_forward_mc_f32 has the semantics): x f32 [B,1,28,28] -> (mean_probs f32 [B,10], std_probs f32 [B,10], predicted int64 [B]);
+        with want_logits the per-sample logits f32 [S,B,10] follow, with want_masks the keep masks that were used, a tuple of u8 [S,B,32],
+        [S,B,64], [S,B,128].  masks: such a tuple to use instead of the generator's draw at (seed, offset), which host.mc_dropout_masks
+        restates.  ValueError for n_samples < 1, p_spatial outside [0, 1) or p_fc outside [0, 1].  No host sync."""
+        S = int(n_samples)
+        if S < 1:
+            raise ValueError(f"n_samples must be at least 1, got {n_samples}")
+        if not 0.0 <= float(p_spatial) < 1.0:
+            raise ValueError(f"spatial dropout rate must be in [0, 1), got {p_spatial}")
+        if not 0.0 <= float(p_fc) <= 1.0:
+            raise ValueError(f"dropout rate must be in [0, 1], got {p_fc}")
+        x = _dev_tensor(x, "x", torch.float32, self.device, shape=(None, 1, 28, 28)).contiguous()
+        B = x.shape[0]
+        shapes = ((S, B, 32), (S, B, 64), (S, B, 128))
+        if masks is not None:
+            if len(masks) != 3:
+                raise ValueError("masks: (keep1 [S,B,32], keep3 [S,B,64], keepf [S,B,128])")
+            masks = tuple(_dev_tensor(m, "masks", torch.uint8, self.device, shape=sh).contiguous() for m, sh in zip(masks, shapes))
+        mean = torch.empty((B, 10), dtype=torch.float32, device=self.device)
+        std = torch.empty((B, 10), dtype=torch.float32, device=self.device)
+        pred = torch.empty((B,), dtype=torch.int64, device=self.device)
+        logits = torch.empty((S, B, 10), dtype=torch.float32, device=self.device) if want_logits else None
+        used = tuple(torch.empty(sh, dtype=torch.uint8, device=self.device) for sh in shapes) if want_masks else (None,) * 3
+        self._check(self._lib.sv_cnn3_forward_mc_f32(self._h, _ptr(x), B, S, float(p_spatial), float(p_fc), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                                     *[_opt_ptr(m) for m in (masks or (None,) * 3)], _ptr(mean), _ptr(std), _ptr(pred), _opt_ptr(logits),
+                                                     *[_opt_ptr(m) for m in used], _stream_ptr()), "sv_cnn3_forward_mc_f32")
+        out = (mean, std, pred)
+        if want_logits:
+            out += (logits,)
+        if want_masks:
+            out += (used,)
+        return out
+
     def cnn3_light_forward(self, x, want_digits=False, want_features=False, glue=0):
         """DigitCNNv3Light.forward (ml/model_v3.py), after load_state_dict_v3_light: the arguments and results of cnn3_forward, with 96
         pooled features [B,96]."""
