@@ -535,6 +535,76 @@ int sv_empty_forward_cells_u8(sv_ctx *ctx, const uint8_t *cells /*dev, B*784*/, 
 int sv_softmax_topk_f32(sv_ctx *ctx, const float *logits /*dev, B*10*/, long B, int k,
                         uint8_t *index /*dev, B*k*/, float *prob /*dev, B*k*/, void *stream);
 
+/* ---- K21: model evaluation metrics (ml/evaluate_v2.py:67-220 evaluate_dataset / compute_calibration / find_failures,
+ * ml/train.py:157-190 evaluate) -- the bookkeeping the reference does on the host, one cell and one class at a time, in one pass
+ * over the logits on the device (csrc/k21_eval.hip). */
+#define SV_EVAL_MAX_BINS 64
+#define SV_EVAL_CONF_ONE 1073741824ull   /* 2^30: the unit of the fixed-point confidence sums */
+
+/* The aggregates, one small device block, every field an integer.  A cell is VALID when its ten inputs are finite and its label is
+ * 0..9; only valid cells enter confusion, n, n_correct, n_wrong, the bins and the totals.  A cell with a NaN or Inf input counts in
+ * `nonfinite` and nowhere else; a finite cell whose label is outside 0..9 counts in `bad_labels` and nowhere else.
+ * Confidence sums are sums of (uint64_t)(conf * 2^30).  conf is the largest of ten f32 probabilities that sum to about 1, so
+ * conf >= 0.1 > 2^-7: an f32 that large is a whole multiple of 2^-30, so the product is an integer below 2^31, exact, and so is the
+ * conversion: the sum is the exact sum of the f32 confidences (times 2^30) while B * 2^30 < 2^62, whatever the launch shape and whatever order the atomics land in.  (In probability-input mode
+ * that holds for rows that are probabilities; a largest entry below 2^-7 is truncated to a multiple of 2^-30.) */
+typedef struct sv_eval_stats {
+    uint64_t confusion[10][10];                 /* [label][pred] */
+    uint64_t n, n_correct, n_wrong;             /* valid cells; pred == label; pred != label */
+    uint64_t bad_labels, nonfinite;
+    uint64_t bin_count[SV_EVAL_MAX_BINS];       /* reliability bins (ml/evaluate_v2.py:162-168): cells, correct cells, sum of conf */
+    uint64_t bin_correct[SV_EVAL_MAX_BINS];
+    uint64_t bin_conf[SV_EVAL_MAX_BINS];
+    uint64_t tot_count[3], tot_correct[3], tot_conf[3];   /* the same three sums over [0] all valid, [1] correct, [2] wrong cells */
+} sv_eval_stats;
+
+/* One misclassified cell (ml/evaluate_v2.py:208-217): index = index_base + its position in the call, top3 = its three most probable
+ * classes, most probable first, equal probabilities lowest class first (the selection of sv_softmax_topk_f32). */
+typedef struct sv_eval_failure {
+    int64_t index;
+    int32_t label, pred;
+    float conf, true_prob;
+    int32_t top3_index[3];
+    float top3_prob[3];
+} sv_eval_failure;
+
+/* input f32 [B,10], contiguous: logits (input_is_prob == 0) or probabilities (!= 0: compute_calibration's argument, temperature
+ * must be 1).  labels [B]: int64 (labels_i64 != 0) or int32.  Per cell, in f32:
+ *   p = softmax(input / temperature) by k_softmax_topk's sequence of operations -- z = input / T, m = max z, e = expf(z - m),
+ *   den = e0 + ... + e9 in class order, p = e / den -- so probs is bit-identical to what sv_softmax_topk_f32 returns for the same
+ *   logits at T = 1; in probability mode p = input;
+ *   pred = argmax of the input, ties to the lowest class; conf = p[pred]; true_prob = p[label];
+ *   nll = logsumexp(z) - z[label] = logf(den) - (z[label] - m)   (probability mode: -logf(p[label]));  correct = pred == label.
+ * Per-cell outputs, each [dev] and each may be NULL: probs [B*10], pred [B], conf [B], true_prob [B], nll [B], correct [B].  A cell
+ * that is not finite gets whatever the arithmetic gives (NaN probabilities) and correct 0; a bad label gets true_prob = nll = NaN.
+ * In probability mode a row whose largest entry is outside [0, 1] counts as not finite.
+ * Bins: bin_edges [host, n_bins + 1] non-decreasing doubles, 1 <= n_bins <= SV_EVAL_MAX_BINS (they travel as a kernel argument: the
+ * pointer is not kept).  A cell is in bin i when (double)conf > bin_edges[i] && (double)conf <= bin_edges[i + 1]
+ * (ml/evaluate_v2.py:163); a cell in no bin is in no bin.
+ * stats [dev, 8-byte aligned]: cleared first by a launch on the stream unless accumulate != 0, then added to -- counts per workgroup in
+ * LDS and one integer atomic per non-zero entry and workgroup, no float atomic anywhere -- so one call over B cells and any split of
+ * them into accumulating calls leave the same bytes.
+ * failures [dev, max_failures records, or NULL with max_failures 0]: record r is the r-th wrong valid cell in sample order counted
+ * from the last clear of stats (ml/evaluate_v2.py:203-206: the list stops at max_failures); its place comes from a prefix sum over
+ * the wrong flags (per workgroup counts, one scan launch), not from an atomic append.  stats->n_wrong is the total whatever
+ * max_failures is.  Records past min(n_wrong, max_failures) are not written.
+ * Asynchronous on `stream`; reads nothing back.  Scratch (only with max_failures > 0) lives in the context and only grows: a first
+ * call at a larger B allocates, so warm up before capturing into a graph.
+ * SV_ERR_BAD_ARG: NULL ctx / input / labels / stats / bin_edges, B < 0 or B * 2^30 >= 2^62, index_base < 0, temperature not finite
+ * or <= 0, bad n_bins or edges, max_failures < 0.  B == 0 is SV_OK (stats is still cleared unless accumulate). */
+int sv_eval_metrics(sv_ctx *ctx, const float *input /*dev, B*10*/, int input_is_prob, const void *labels /*dev, B*/, int labels_i64, long B,
+                    long index_base, float temperature, const double *bin_edges /*host, n_bins+1*/, int n_bins, int accumulate,
+                    float *probs /*dev*/, uint8_t *pred /*dev*/, float *conf /*dev*/, float *true_prob /*dev*/, float *nll /*dev*/,
+                    uint8_t *correct /*dev*/, sv_eval_stats *stats /*dev*/, sv_eval_failure *failures /*dev*/, long max_failures, void *stream);
+
+/* sv_eval_metrics, then *stats_host = *stats: that copy and the wait for it are the one synchronisation.  SV_ERR_BAD_ARG (after the
+ * copy: stats_host is filled in and the other cells are counted) when stats_host->bad_labels > 0. */
+int sv_eval_metrics_host(sv_ctx *ctx, const float *input /*dev, B*10*/, int input_is_prob, const void *labels /*dev, B*/, int labels_i64, long B,
+                         long index_base, float temperature, const double *bin_edges /*host, n_bins+1*/, int n_bins, int accumulate,
+                         float *probs /*dev*/, uint8_t *pred /*dev*/, float *conf /*dev*/, float *true_prob /*dev*/, float *nll /*dev*/,
+                         uint8_t *correct /*dev*/, sv_eval_stats *stats /*dev*/, sv_eval_failure *failures /*dev*/, long max_failures,
+                         sv_eval_stats *stats_host /*host*/, void *stream);
+
 /* The validation and correction stage of pipeline/run_v2.py:344-371 for n frames in one launch: validate_predictions
  * (pipeline/validator.py:69-159) on the 81 cells of each frame and, where they break the sudoku rules, ConflictResolver.resolve
  * (pipeline/conflict_resolver.py:58-286): a beam search over the cells' alternatives for the cheapest <= max_corrections corrections.

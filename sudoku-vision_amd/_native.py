@@ -2,6 +2,8 @@
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsudokuvision_hip.so")
 # test-only superset (csrc/Makefile, include/sudoku_vision_xcheck.h): the product's objects plus independent second implementations
@@ -95,6 +97,8 @@ SIGNATURES = {
     "sv_png_inflate_batch": [_p, _p, _p, _i, _p, _p, _p, _i, _p],
     "sv_png_reconstruct_bgr_u8": [_p, _p, _p, _p, _p, _i, _p, _pd, _pd, _p, _p],
     "sv_softmax_topk_f32": [_p, _p, _l, _i, _p, _p, _p],
+    "sv_eval_metrics": [_p, _p, _i, _p, _i, _l, _l, _f, _p, _i, _i] + [_p] * 8 + [_l, _p],
+    "sv_eval_metrics_host": [_p, _p, _i, _p, _i, _l, _l, _f, _p, _i, _i] + [_p] * 8 + [_l, _p, _p],
     "sv_resolve_conflicts": [_p, _p, _p, _l, _i, _i, _i, _d, _i] + [_p] * 14,
     "sv_propagate_constraints": [_p, _p, _p, _l, _i] + [_p] * 9,
     "sv_cnn_forward_f32": [_p, _p, _l, _p, _p, _p, _p],
@@ -164,6 +168,18 @@ class PngInfo(C.Structure):
     """sv_png_info of include/sudoku_vision_hip.h"""
     _fields_ = [(n, C.c_int) for n in ("width", "height", "bit_depth", "color_type", "interlace", "channels", "bpp", "palette_entries")] + \
                [(n, C.c_long) for n in ("row_bytes", "filtered_bytes", "idat_offset")] + [("palette", C.c_uint8 * 768)]
+
+EVAL_MAX_BINS = 64
+
+class EvalStats(C.Structure):
+    """sv_eval_stats of include/sudoku_vision_hip.h"""
+    _fields_ = [("confusion", (C.c_uint64 * 10) * 10)] + [(n, C.c_uint64) for n in ("n", "n_correct", "n_wrong", "bad_labels", "nonfinite")] + \
+               [(n, C.c_uint64 * EVAL_MAX_BINS) for n in ("bin_count", "bin_correct", "bin_conf")] + \
+               [(n, C.c_uint64 * 3) for n in ("tot_count", "tot_correct", "tot_conf")]
+
+# sv_eval_failure of include/sudoku_vision_hip.h, as a numpy record of 48 bytes
+EVAL_FAILURE_DTYPE = np.dtype([("index", "<i8"), ("label", "<i4"), ("pred", "<i4"), ("conf", "<f4"), ("true_prob", "<f4"), ("top3_index", "<i4", (3,)),
+                               ("top3_prob", "<f4", (3,))])
 
 PNG_PALETTE_STRIDE = 1024
 

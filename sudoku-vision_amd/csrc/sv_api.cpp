@@ -708,6 +708,40 @@ extern "C" int sv_softmax_topk_f32(sv_ctx *ctx, const float *logits, long B, int
     return svk_softmax_topk(logits, B, k, index, prob, S(stream));
 }
 
+extern "C" int sv_eval_metrics(sv_ctx *ctx, const float *input, int input_is_prob, const void *labels, int labels_i64, long B, long index_base, float temperature,
+                               const double *bin_edges, int n_bins, int accumulate, float *probs, uint8_t *pred, float *conf, float *true_prob, float *nll,
+                               uint8_t *correct, sv_eval_stats *stats, sv_eval_failure *failures, long max_failures, void *stream)
+{
+    REQUIRE(ctx && stats && bin_edges, "NULL argument");
+    REQUIRE(B >= 0 && B < (1l << 32), "need 0 <= B and B * 2^30 < 2^62");
+    REQUIRE(B == 0 || (input && labels), "NULL argument");
+    REQUIRE(index_base >= 0, "index_base must not be negative");
+    REQUIRE(std::isfinite(temperature) && temperature > 0.f, "temperature must be finite and positive");
+    REQUIRE(!input_is_prob || temperature == 1.f, "probabilities take no temperature");
+    REQUIRE(n_bins >= 1 && n_bins <= SV_EVAL_MAX_BINS, "need 1 <= n_bins <= 64");
+    for (int i = 0; i <= n_bins; i++) REQUIRE(bin_edges[i] == bin_edges[i] && (i == 0 || bin_edges[i] >= bin_edges[i - 1]), "bin_edges must be non-decreasing");
+    REQUIRE(max_failures >= 0 && (failures || max_failures == 0), "max_failures needs a failures buffer");
+    REQUIRE((((uintptr_t)stats | (uintptr_t)failures | (labels_i64 ? (uintptr_t)labels : 0)) & 7) == 0, "misaligned argument");
+    REQUIRE((((uintptr_t)input | (uintptr_t)labels | (uintptr_t)probs | (uintptr_t)conf | (uintptr_t)true_prob | (uintptr_t)nll) & 3) == 0, "misaligned argument");
+    return svk_eval_metrics(ctx, input, input_is_prob != 0, labels, labels_i64 != 0, B, index_base, temperature, bin_edges, n_bins, accumulate != 0, probs, pred, conf,
+                            true_prob, nll, correct, stats, failures, max_failures, S(stream));
+}
+
+extern "C" int sv_eval_metrics_host(sv_ctx *ctx, const float *input, int input_is_prob, const void *labels, int labels_i64, long B, long index_base, float temperature,
+                                    const double *bin_edges, int n_bins, int accumulate, float *probs, uint8_t *pred, float *conf, float *true_prob, float *nll,
+                                    uint8_t *correct, sv_eval_stats *stats, sv_eval_failure *failures, long max_failures, sv_eval_stats *stats_host, void *stream)
+{
+    REQUIRE(stats_host, "NULL argument");
+    const int rc = sv_eval_metrics(ctx, input, input_is_prob, labels, labels_i64, B, index_base, temperature, bin_edges, n_bins, accumulate, probs, pred, conf, true_prob,
+                                   nll, correct, stats, failures, max_failures, stream);
+    if (rc) return rc;
+    SV_HIP(hipMemcpyAsync(stats_host, stats, sizeof(sv_eval_stats), hipMemcpyDeviceToHost, S(stream)));
+    SV_HIP(hipStreamSynchronize(S(stream)));
+    if (stats_host->bad_labels)
+        return sv_fail(SV_ERR_BAD_ARG, "%s: %llu labels outside 0..9 (the other cells are counted)", __func__, (unsigned long long)stats_host->bad_labels);
+    return SV_OK;
+}
+
 extern "C" int sv_resolve_conflicts(sv_ctx *ctx, const uint8_t *index, const float *prob, long n, int k, int beam_width, int max_corrections,
                                     double min_alt_conf, int acceptance_rule, uint8_t *digits, float *conf, uint8_t *index_out, float *prob_out, uint8_t *success,
                                     int32_t *num_conflicts_before, int32_t *num_conflicts_after, uint8_t *conflict_count, uint8_t *n_corrections,

@@ -100,11 +100,12 @@ struct sv_ctx {
     sv_scratch k1_list;         // k1_threshold_mm.hip: optional diagnostic counter (pixels decided by the exact evaluation), sv_preprocess_stats; 16 bytes
     sv_scratch range_flag;      // int [2]: the per-call kernel choice for f32 inputs (k3_cnn.hip k_input_range)
     sv_scratch overlay;         // k16_overlay.hip: the glyph atlas u8 [9][50][50], then the default palette u8 [3][3]
+    sv_scratch eval;            // k21_eval.hip: the failure list's base, per-workgroup wrong counts and per-cell wrong flags (layout at the top of that file)
     bool overlay_set = false;   // sv_set_overlay_glyphs has filled `overlay`
     // sv_ctx_destroy frees through this and nothing else: a new buffer goes in here
     template <class F> void for_each_scratch(F f)
     {
-        for (sv_scratch *b : {&v3_act, &v3_mc, &features, &cells, &cells2, &jpeg_planes, &jpeg_enc, &png_enc, &png_dec, &pp2, &cc, &grid2, &k1_list, &range_flag, &overlay}) f(*b);
+        for (sv_scratch *b : {&v3_act, &v3_mc, &features, &cells, &cells2, &jpeg_planes, &jpeg_enc, &png_enc, &png_dec, &pp2, &cc, &grid2, &k1_list, &range_flag, &overlay, &eval}) f(*b);
     }
     int precision = 0;          // SV_PREC_F32 / SV_PREC_BF16 (sv_ctx_set_precision)
     int cnn_kernels = 0;        // SV_CNN_AUTO / _F16PAIR / _F32MFMA (sv_ctx_set_cnn_kernels)
@@ -297,6 +298,11 @@ int svk_png_deflate(sv_ctx *ctx, const sv_png_enc *plan, const u8 *src, int n, p
 // k19_png_decode.hip (the unfiltered samples and the job list live in ctx->png_dec)
 int svk_png_reconstruct(sv_ctx *ctx, const sv_png_info *info, const u8 *filtered, const u8 *row_filter, const u8 *palette, int n, u8 *out, ptrdiff_t pitch,
                         ptrdiff_t frame_stride, uint32_t *status, hipStream_t s);
+
+// k21_eval.hip (the failure list's scratch lives in ctx->eval)
+int svk_eval_metrics(sv_ctx *ctx, const float *input, bool prob, const void *labels, bool i64, long B, long index_base, float T, const double *bin_edges, int n_bins,
+                     bool accumulate, float *probs, u8 *pred, float *conf, float *true_prob, float *nll, u8 *correct, sv_eval_stats *stats,
+                     sv_eval_failure *failures, long max_failures, hipStream_t s);
 
 // host_png.cpp: whether an sv_png_info's geometry is one sv_png_parse produces (format table, limits, derived fields)
 bool sv_png_geometry_ok(const sv_png_info *info);

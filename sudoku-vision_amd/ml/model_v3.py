@@ -1,7 +1,8 @@
 """MI355X drop-in for the reference's ml/model_v3.py: `DigitCNNv3` keeps the state_dict keys, constructor and call protocol that
 pipeline/run_v2.py:95-128 relies on; forward() runs the hand-written HIP kernels of csrc/k8_cnn_v3.hip (true f32 on the matrix pipe,
 BatchNorm folded into the convolutions when the weights are packed).  `DigitCNNv3Light` and `EmptyClassifier` do the same through
-csrc/k12_cnn_v3_light.hip, one launch per forward.  Inference only, GPU only.  `calibrate_temperature` is plain torch on the logits.
+csrc/k12_cnn_v3_light.hip, one launch per forward.  Forward only, GPU only.  `calibrate_temperature` is plain torch on the logits; the ECE it is meant
+to lower, and every other evaluation metric, is ml/evaluate_v2.py's (csrc/k21_eval.hip).
 
 The submodules below exist to hold parameters and buffers under the reference's names, so that a reference checkpoint loads with
 strict=True; none of them is ever called.

@@ -984,6 +984,83 @@ class Context:
         self._check(self._lib.sv_softmax_topk_f32(self._h, _ptr(logits), B, int(k), _ptr(index), _ptr(prob), _stream_ptr()), "sv_softmax_topk_f32")
         return index, prob
 
+    EVAL_OUTPUTS = {"probs": (torch.float32, (10,)), "pred": (torch.uint8, ()), "conf": (torch.float32, ()), "true_prob": (torch.float32, ()),
+                    "nll": (torch.float32, ()), "correct": (torch.uint8, ())}
+    EVAL_CONF_ONE = 1 << 30
+
+    def eval_stats_buffer(self):
+        """A zeroed sv_eval_stats block on the device, as int64 words (the counts are below 2^63): eval_metrics' `stats`."""
+        return torch.zeros(C.sizeof(_native.EvalStats) // 8, dtype=torch.int64, device=self.device)
+
+    @staticmethod
+    def eval_stats_dict(stats, n_bins):
+        """sv_eval_stats (an _native.EvalStats, or the int64 words of eval_stats_buffer, any device) -> plain dict of Python ints and
+        lists; the confidence sums stay fixed point, in units of 1 / EVAL_CONF_ONE."""
+        if isinstance(stats, torch.Tensor):
+            stats = _native.EvalStats.from_buffer_copy(stats.cpu().numpy().tobytes())
+        out = {"confusion": [[int(v) for v in row] for row in stats.confusion]}
+        for k in ("n", "n_correct", "n_wrong", "bad_labels", "nonfinite"):
+            out[k] = int(getattr(stats, k))
+        for k in ("bin_count", "bin_correct", "bin_conf"):
+            out[k] = [int(v) for v in getattr(stats, k)[:n_bins]]
+        for k in ("tot_count", "tot_correct", "tot_conf"):
+            out[k] = [int(v) for v in getattr(stats, k)]
+        return out
+
+    @staticmethod
+    def eval_failures(failures, count):
+        """The first `count` records of eval_metrics' failure buffer -> numpy structured array (fields of sv_eval_failure)."""
+        raw = failures[:count].cpu().numpy().tobytes()
+        return np.frombuffer(raw, dtype=_native.EVAL_FAILURE_DTYPE).copy()
+
+    def eval_metrics(self, logits, labels, temperature=1.0, n_bins=10, max_failures=0, want=("pred", "conf", "correct"), *, probabilities=False,
+                     bin_edges=None, stats=None, accumulate=False, index_base=0, failures=None, read_back=True):
+        """Evaluation metrics of a batch in one pass (sv_eval_metrics; reference ml/evaluate_v2.py:67-220, ml/train.py:157-190).
+        logits f32 [B,10] (probabilities=True: softmax outputs, compute_calibration's argument), labels int64 or int32 [B].
+        -> (out, agg).  out: the device tensors named in `want` (EVAL_OUTPUTS), "stats" (the sv_eval_stats block, int64 words) and, with
+        max_failures > 0, "failures" (u8 [max_failures,48], sv_eval_failure records: eval_failures decodes them).  agg: eval_stats_dict
+        of the block after the call's one synchronisation -- or None with read_back=False, which reads nothing back and can be captured
+        in a graph.  bin_edges: n_bins + 1 doubles, default np.linspace(0, 1, n_bins + 1).  stats / failures: buffers of an earlier call
+        to go on with (accumulate=True keeps their contents; index_base is added to the failure records' sample index).
+        A label outside 0..9 raises NativeError (SV_ERR_BAD_ARG) from the read-back form; `stats` then still holds every other cell."""
+        logits = _dev_tensor(logits, "logits", torch.float32, self.device, shape=(None, 10)).contiguous()
+        B = logits.shape[0]
+        labels = _dev_tensor(labels, "labels", (torch.int64, torch.int32), self.device, shape=(B,)).contiguous()
+        unknown = [k for k in want if k not in self.EVAL_OUTPUTS]
+        if unknown:
+            raise ValueError(f"want: unknown outputs {unknown}; known: {list(self.EVAL_OUTPUTS)}")
+        n_bins, max_failures = int(n_bins), int(max_failures)
+        edges = np.ascontiguousarray(np.linspace(0, 1, n_bins + 1) if bin_edges is None else bin_edges, dtype=np.float64)
+        if edges.shape != (n_bins + 1,):
+            raise ValueError(f"bin_edges must hold n_bins + 1 = {n_bins + 1} values, got shape {edges.shape}")
+        out = {k: torch.empty((B,) + self.EVAL_OUTPUTS[k][1], dtype=self.EVAL_OUTPUTS[k][0], device=self.device) for k in want}
+        words = C.sizeof(_native.EvalStats) // 8
+        if stats is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the stats buffer of the calls before")
+            stats = torch.empty(words, dtype=torch.int64, device=self.device)
+        _dev_tensor(stats, "stats", torch.int64, self.device, shape=(words,))
+        if max_failures > 0:
+            if failures is None:
+                failures = torch.empty((max_failures, _native.EVAL_FAILURE_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+            _dev_tensor(failures, "failures", torch.uint8, self.device, shape=(max_failures, _native.EVAL_FAILURE_DTYPE.itemsize))
+        else:
+            failures = None
+        if not stats.is_contiguous() or (failures is not None and not failures.is_contiguous()):
+            raise ValueError("stats and failures must be contiguous")
+        args = [self._h, _ptr(logits), int(bool(probabilities)), _ptr(labels), int(labels.dtype == torch.int64), B, int(index_base), float(temperature),
+                edges.ctypes.data_as(C.c_void_p), n_bins, int(bool(accumulate))] + [_opt_ptr(out.get(k)) for k in self.EVAL_OUTPUTS] + \
+               [_ptr(stats), _opt_ptr(failures), max_failures]
+        out["stats"] = stats
+        if failures is not None:
+            out["failures"] = failures
+        if not read_back:
+            self._check(self._lib.sv_eval_metrics(*args, _stream_ptr()), "sv_eval_metrics")
+            return out, None
+        host = _native.EvalStats()
+        self._check(self._lib.sv_eval_metrics_host(*args, C.byref(host), _stream_ptr()), "sv_eval_metrics_host")
+        return out, self.eval_stats_dict(host, n_bins)
+
     def preprocess_cells(self, cells):
         """run.py's preprocess_cell on u8 cells [B,28,28] -> u8 {0,255} [B,28,28]."""
         cells = _dev_tensor(cells, "cells", torch.uint8, self.device, shape=(None, 28, 28)).contiguous()
