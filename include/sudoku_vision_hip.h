@@ -1100,6 +1100,90 @@ int sv_render_overlay_u8(sv_ctx *ctx, const uint8_t *frames /*dev*/, int n, int 
                          const uint8_t *palette /*dev, k*3 BGR, or NULL*/, int k, const uint8_t *active /*dev, n, or NULL*/,
                          int shadow, uint8_t *dst /*dev; may equal frames*/, ptrdiff_t dst_pitch, ptrdiff_t dst_stride, void *stream);
 
+/* ---- K22: batched data augmentation, tools/augment_data.py ------------------------------------------------------------------ */
+
+/* One launch turns n_src gray images into n_out augmented copies: output i loads src[clamp(src_index[i], 0, n_src-1)], runs
+ * steps[i][0 .. clamp(n_steps[i], 0, SV_AUG_MAX_STEPS)) on chip and is stored once.  Between two steps the image is u8, as each of
+ * the reference's functions returns u8.  cv2 is not available, so the arithmetic stated here is the contract; parity with OpenCV
+ * itself is unpinned (as for K13).
+ *
+ * A step record is 96 bytes, 8-byte aligned: int32 op; int32 i[5]; then 72 bytes read as double d[9] or as float f[18].
+ *   SV_AUG_NONE, or any op the kernel does not know: the identity.
+ *   SV_AUG_AFFINE (rotate, translate): d[0..5] the FORWARD 2x3 matrix.  cv2.warpAffine(INTER_LINEAR, BORDER_REPLICATE) in the
+ *     arithmetic of sv_warp_affine_u8 above (the inversion, 1/1024 fixed point, + 16, >> 5, int16 cells, 15-bit weights
+ *     (32-a)(32-b)*32 .. ab*32, (sum + 16384) >> 15), but a tap outside the image reads the nearest pixel (both tap
+ *     coordinates clamped into the image), not a constant.
+ *   SV_AUG_PERSPECTIVE (perspective_warp): d[0..8] the FORWARD 3x3 matrix.  Inverted in double by cofactors times 1/det, every
+ *     product and difference rounded separately (a zero determinant gives the zero matrix, as cv::invert leaves it); then
+ *     sv_warp_perspective_u8's coordinates with the image as one block (width <= 64): X0 = (0 + M1*y) + M2, W = W0 + M6*x,
+ *     W = W ? 32/W : 0, saturated, rounded half to even, >> 5 saturated to int16, five fraction bits; same weights, taps clamped.
+ *   SV_AUG_BRIGHTNESS (adjust_brightness): d[0] = delta.  float32(p) + float32(delta), clipped to [0, 255], truncated.
+ *   SV_AUG_CONTRAST (adjust_contrast): d[0] = factor.  mean = (double)(integer sum of the pixels) / (double)(H*W); then
+ *     ((double)p - mean) * factor + mean in double, each operation rounded, clipped to [0, 255], truncated.  This is what the
+ *     reference computes under NumPy >= 2, where np.mean's float64 scalar promotes the float32 image to float64 (under NumPy 1 the
+ *     same line stayed in float32).
+ *   SV_AUG_BLUR (gaussian_blur): i[0] = k in {1, 3, 5}.  Integer taps [1,2,1] / [1,4,6,4,1] on rows and columns, BORDER_REFLECT_101,
+ *     (S + 8) >> 4 resp. (S + 128) >> 8 of the exact 2-D sum S: sv_blur_u8's rounding.  k = 1 is the identity.
+ *   SV_AUG_SCALE (scale): i[0] = new_w, i[1] = new_h, i[2] = 1 to crop (factor > 1), 0 to pad.  cv2.resize to (new_w, new_h) in
+ *     sv_resize_linear_u8's arithmetic; crop: the H x W window at ((new_h-H)/2, (new_w-W)/2); pad: the scaled image at
+ *     ((H-new_h)/2, (W-new_w)/2) of a plane of 128 (floor divisions).  The scaled image is never materialised.
+ *   SV_AUG_FILL_RECT (random_erasing): columns i[0] .. i[0]+i[2]-1 of rows i[1] .. i[1]+i[3]-1 become i[4].
+ *   SV_AUG_ELASTIC (elastic_transform): i[0] = radius r <= SV_AUG_MAX_RADIUS, i[4] = salt, f[0] = float32(alpha), f[1 + j] = the
+ *     Gaussian tap at distance j = 0..r (sv_augment_elastic_taps).  Per pixel the fields ux, uy = (word >> 8) * 2^-23 - 1 in float32
+ *     (exact) from words 0 and 1 of the pixel's random block; each field is filtered along rows, then along columns, with
+ *     BORDER_REFLECT_101: acc = t[-r]*v[-r]; acc = acc + t[j]*v[j] for j = -r+1 .. r, every product and sum a float32 rounding.
+ *     Then dx = ux' * f[0], map_x = float32(x) + dx (likewise y); cv2.remap(INTER_LINEAR, BORDER_REPLICATE): X = sat(rint(map_x*32)),
+ *     cell X >> 5 saturated to int16, fraction X & 31, the weights above, taps clamped.
+ *   SV_AUG_NOISE_GAUSS (add_noise "gaussian"): d[0] = sigma = intensity*255, i[4] = salt.  From words w0, w1 of the pixel's block, in
+ *     double: u1 = (w0 + 1) * 2^-32, u2 = w1 * 2^-32, z = sqrt(-2 * ln(u1)) * cos(6.283185307179586 * u2); (double)p + sigma*z,
+ *     clipped to [0, 255], truncated.  ln and cos are the platform's double functions (a few ulp apart between libraries).
+ *   SV_AUG_NOISE_SP (add_noise "salt_pepper"): d[0] = intensity/2, i[4] = salt.  255 where w0 * 2^-32 < d[0]; then 0 where
+ *     w1 * 2^-32 < d[0] (pepper over salt, the reference's order).
+ * The random block of a pixel is Philox4x32-10 (csrc/sv_philox.h) with key (seed low, seed high) and counter
+ *   (y*W + x,  g low 32 bits,  (g >> 32) << 8 | step slot,  salt),  g = index_base + i, the output's global index:
+ * a pure function of (seed, g, slot, salt, pixel), never of n_out, the launch shape or how a job is split into calls.  The bits are
+ * not NumPy's: the reference's np.random fields are not reproduced, only their distributions.
+ * 4 <= H, W <= SV_AUG_MAX_SIDE, pitch >= W, n_src, n_out >= 1, 0 <= index_base, index_base + n_out < 2^56: SV_ERR_BAD_ARG otherwise.
+ * Nothing a caller uploads can make the kernel read or write outside its buffers; sv_augment_check_program is what tells a caller
+ * that a program is malformed.  Asynchronous on `stream`, graph-capturable; no allocation, no host synchronisation. */
+#define SV_AUG_MAX_STEPS 10
+#define SV_AUG_MAX_SIDE 64
+#define SV_AUG_MAX_RADIUS 16
+typedef enum sv_aug_op {
+    SV_AUG_NONE = 0, SV_AUG_AFFINE = 1, SV_AUG_PERSPECTIVE = 2, SV_AUG_BRIGHTNESS = 3, SV_AUG_CONTRAST = 4, SV_AUG_BLUR = 5,
+    SV_AUG_SCALE = 6, SV_AUG_FILL_RECT = 7, SV_AUG_ELASTIC = 8, SV_AUG_NOISE_GAUSS = 9, SV_AUG_NOISE_SP = 10
+} sv_aug_op;
+typedef struct sv_aug_step {
+    int32_t op;
+    int32_t i[5];
+    union { double d[9]; float f[18]; };
+} sv_aug_step;
+int sv_augment_u8(sv_ctx *ctx, const uint8_t *src /*dev*/, int n_src, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride,
+                  const sv_aug_step *steps /*dev, n_out*SV_AUG_MAX_STEPS*/, const int32_t *n_steps /*dev, n_out*/,
+                  const int32_t *src_index /*dev, n_out*/, long n_out, uint64_t seed, long index_base,
+                  uint8_t *dst /*dev, n_out*H*W*/, void *stream);
+
+/* What the kernel cannot check, on the host copies of a program: a known op in every used slot, 0 <= n_steps <= SV_AUG_MAX_STEPS,
+ * 0 <= src_index < n_src, finite matrices and scalars, k in {1,3,5}, a scale size of 1 .. 2*side that agrees with its crop / pad flag,
+ * a rectangle inside the image with a value 0..255, an elastic radius <= SV_AUG_MAX_RADIUS and < min(H, W) (REFLECT_101 reflects
+ * once) with finite taps.  SV_ERR_BAD_ARG with a message that names the output and the step.  Needs no context and no GPU. */
+int sv_augment_check_program(const sv_aug_step *steps /*host*/, const int32_t *n_steps /*host*/, const int32_t *src_index /*host*/,
+                             long n_out, int n_src, int H, int W);
+
+/* Host helpers of the program builder, in the library's double arithmetic.
+ * cv2.getRotationMatrix2D((cx, cy), angle_deg, scale): a = angle * (pi/180), alpha = cos(a)*scale, beta = sin(a)*scale,
+ * m = [alpha, beta, (1-alpha)*cx - beta*cy; -beta, alpha, beta*cx + (1-alpha)*cy]. */
+int sv_augment_rotation_matrix(double cx, double cy, double angle_deg, double scale, double *m /*host, 6*/);
+/* cv2.getPerspectiveTransform(src, dst) on four float32 point pairs: the 8x8 elimination of sv_corners_to_m_batch.
+ * SV_ERR_DEGENERATE when the points define no homography. */
+int sv_augment_perspective_matrix(const float *src /*host, 8*/, const float *dst /*host, 8*/, double *m /*host, 9*/);
+/* The float32 taps of cv2.GaussianBlur((0,0), sigma) on a float32 image: radius r = (round(8*sigma + 1) | 1) / 2; in double
+ * v[j] = exp((2j)^2 * (-0.125 / sigma^2)), sum = 2*(v[r] + .. + v[1]) + 1 (added in that order), taps[j] = float(v[j] * (1/sum)),
+ * taps[0] = float(1/sum).  cap < r + 1: SV_ERR_BUFFER with *radius set; sigma not positive and finite: SV_ERR_BAD_ARG. */
+int sv_augment_elastic_taps(double sigma, float *taps /*host, cap*/, int cap, int *radius);
+/* The random words of one output's step slot on the host, the kernel's own generator: words[(y*W + x)*4 + k], k = 0..3. */
+int sv_augment_field_host(uint64_t seed, long index, int slot, uint32_t salt, int H, int W, uint32_t *words /*host, H*W*4*/);
+
 /* ---- the whole device-resident path ----------------------------------------------------------- */
 
 /* frames + homographies -> 81 digits per frame: K2 then K3 on `stream`, no host sync.

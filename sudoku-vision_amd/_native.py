@@ -137,6 +137,12 @@ SIGNATURES = {
     "sv_motion_update_u8": [_p, _p, _i, _i, _i, _i, _pd, _pd, _p, _f, _p, _p, _i, _i, _p],
     "sv_corners_to_m_batch": [_p, _i, _i, _f, _p, _p],
     "sv_set_overlay_glyphs": [_p, _p],
+    "sv_augment_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p, _p, _l, C.c_uint64, _l, _p, _p],
+    "sv_augment_check_program": [_p, _p, _p, _l, _i, _i, _i],
+    "sv_augment_rotation_matrix": [_d, _d, _d, _d, _p],
+    "sv_augment_perspective_matrix": [_p, _p, _p],
+    "sv_augment_elastic_taps": [_d, _p, _i, _p],
+    "sv_augment_field_host": [C.c_uint64, _l, _i, C.c_uint32, _i, _i, _p],
     "sv_render_overlay_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p, _p, _p, _i, _p, _i, _p, _pd, _pd, _p],
 }
 _RESTYPES = {"sv_last_error": C.c_char_p, "sv_sparse_bits_record_bytes": C.c_long, "sv_jpeg_encode_bound": C.c_long}
@@ -180,6 +186,12 @@ class EvalStats(C.Structure):
 # sv_eval_failure of include/sudoku_vision_hip.h, as a numpy record of 48 bytes
 EVAL_FAILURE_DTYPE = np.dtype([("index", "<i8"), ("label", "<i4"), ("pred", "<i4"), ("conf", "<f4"), ("true_prob", "<f4"), ("top3_index", "<i4", (3,)),
                                ("top3_prob", "<f4", (3,))])
+
+# sv_aug_step of include/sudoku_vision_hip.h as a numpy record of 96 bytes: d and f name the same 72 bytes
+AUG_MAX_STEPS, AUG_MAX_SIDE, AUG_MAX_RADIUS = 10, 64, 16
+AUG_STEP_DTYPE = np.dtype({"names": ["op", "i", "d", "f"], "formats": ["<i4", ("<i4", (5,)), ("<f8", (9,)), ("<f4", (18,))], "offsets": [0, 4, 24, 24],
+                           "itemsize": 96})
+AUG_NONE, AUG_AFFINE, AUG_PERSPECTIVE, AUG_BRIGHTNESS, AUG_CONTRAST, AUG_BLUR, AUG_SCALE, AUG_FILL_RECT, AUG_ELASTIC, AUG_NOISE_GAUSS, AUG_NOISE_SP = range(11)
 
 PNG_PALETTE_STRIDE = 1024
 

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <vector>
 
+#include "sv_augment_host.h"
 #include "sv_internal.h"
 #include "sv_philox.h"
 
@@ -275,39 +276,8 @@ void order_points(const float *p, float *o)
     for (int i = 0; i < 4; i++) { o[2 * i] = p[2 * pick[i]]; o[2 * i + 1] = p[2 * pick[i] + 1]; }
 }
 
-// cv2.getPerspectiveTransform: 8x8 LU with partial pivoting in double, OpenCV's elimination order
-bool perspective_transform(const float *src, const float *dst, double *M)
-{
-    double a[8][9];  // augmented [A | b]
-    for (int i = 0; i < 4; i++) {
-        const double sx = src[2 * i], sy = src[2 * i + 1], dx = dst[2 * i], dy = dst[2 * i + 1];
-        const double r0[9] = {sx, sy, 1, 0, 0, 0, -sx * dx, -sy * dx, dx};
-        const double r1[9] = {0, 0, 0, sx, sy, 1, -sx * dy, -sy * dy, dy};
-        memcpy(a[i], r0, sizeof r0);
-        memcpy(a[i + 4], r1, sizeof r1);
-    }
-    for (int i = 0; i < 8; i++) {
-        int piv = i;
-        for (int j = i + 1; j < 8; j++)
-            if (std::fabs(a[j][i]) > std::fabs(a[piv][i])) piv = j;
-        if (!(std::fabs(a[piv][i]) >= 2.220446049250313e-16 * 100)) return false;  // also rejects NaN
-        if (piv != i)
-            for (int j = i; j < 9; j++) std::swap(a[i][j], a[piv][j]);
-        const double d = -1 / a[i][i];
-        for (int j = i + 1; j < 8; j++) {
-            const double alpha = a[j][i] * d;
-            for (int k = i + 1; k < 9; k++) a[j][k] += alpha * a[i][k];
-        }
-    }
-    for (int i = 7; i >= 0; i--) {
-        double s = a[i][8];
-        for (int k = i + 1; k < 8; k++) s -= a[i][k] * a[k][8];
-        a[i][8] = s / a[i][i];
-    }
-    for (int i = 0; i < 8; i++) M[i] = a[i][8];
-    M[8] = 1.0;
-    return true;
-}
+// cv2.getPerspectiveTransform: sv_augment_host.h (K22's builder solves the same system)
+bool perspective_transform(const float *src, const float *dst, double *M) { return sv_perspective_transform(src, dst, M); }
 
 // cv::invert for 3x3 doubles: cofactors scaled by 1/det
 bool invert3(const double *S, double *D)
@@ -1193,4 +1163,61 @@ extern "C" int sv_frames_to_digits_v3(sv_ctx *ctx, const uint8_t *frames, int n,
 extern "C" int sv_frames_to_digits_v3_light(sv_ctx *ctx, const uint8_t *frames, int n, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride, const double *minv, int glue, uint8_t *cells, float *logits, uint8_t *digits, float *conf, void *stream)
 {
     return frames_to_digits("sv_frames_to_digits_v3_light", 2, ctx, frames, n, H, W, pitch, frame_stride, minv, glue, cells, logits, digits, conf, stream);
+}
+
+// ---- K22: data augmentation (k22_augment.hip; the host rules live in sv_augment_host.h) ----
+extern "C" int sv_augment_u8(sv_ctx *ctx, const uint8_t *src, int n_src, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const sv_aug_step *steps,
+                             const int32_t *n_steps, const int32_t *src_index, long n_out, uint64_t seed, long index_base, uint8_t *dst, void *stream)
+{
+    REQUIRE(ctx && src && steps && n_steps && src_index && dst, "NULL argument");
+    REQUIRE(n_src >= 1 && n_out >= 1 && n_out <= 0x7fffffffL, "n_src and n_out must be at least 1 (n_out below 2^31)");
+    REQUIRE(H >= 4 && W >= 4 && H <= SV_AUG_MAX_SIDE && W <= SV_AUG_MAX_SIDE, "sides must be 4 .. SV_AUG_MAX_SIDE");
+    REQUIRE(pitch >= W && (n_src == 1 || img_stride >= pitch * (H - 1) + W), "bad pitch or image stride");
+    REQUIRE(index_base >= 0 && index_base < (1L << 56) - n_out, "index_base + n_out must stay below 2^56");
+    REQUIRE((uintptr_t)steps % 8 == 0, "steps must be 8-byte aligned");
+    return svk_augment(ctx, src, n_src, H, W, pitch, img_stride, steps, n_steps, src_index, n_out, seed, index_base, dst, S(stream));
+}
+
+extern "C" int sv_augment_check_program(const sv_aug_step *steps, const int32_t *n_steps, const int32_t *src_index, long n_out, int n_src, int H, int W)
+{
+    char msg[256];
+    const int rc = sv_aug_check_program(steps, n_steps, src_index, n_out, n_src, H, W, msg, sizeof msg);
+    return rc ? sv_fail(rc, "sv_augment_check_program: %s", msg) : SV_OK;
+}
+
+extern "C" int sv_augment_rotation_matrix(double cx, double cy, double angle_deg, double scale, double *m)
+{
+    REQUIRE(m, "NULL argument");
+    sv_aug_rotation_matrix(cx, cy, angle_deg, scale, m);
+    return SV_OK;
+}
+
+extern "C" int sv_augment_perspective_matrix(const float *src, const float *dst, double *m)
+{
+    REQUIRE(src && dst && m, "NULL argument");
+    if (!sv_perspective_transform(src, dst, m)) return sv_fail(SV_ERR_DEGENERATE, "sv_augment_perspective_matrix: the points define no homography");
+    return SV_OK;
+}
+
+extern "C" int sv_augment_elastic_taps(double sigma, float *taps, int cap, int *radius)
+{
+    REQUIRE(taps && radius, "NULL argument");
+    const int r = sv_aug_elastic_radius(sigma);
+    REQUIRE(r >= 0, "sigma must be positive and finite");
+    *radius = r;
+    if (cap < r + 1) return sv_fail(SV_ERR_BUFFER, "sv_augment_elastic_taps: sigma %g needs %d taps, room for %d", sigma, r + 1, cap);
+    sv_aug_elastic_taps(sigma, r, taps);
+    return SV_OK;
+}
+
+extern "C" int sv_augment_field_host(uint64_t seed, long index, int slot, uint32_t salt, int H, int W, uint32_t *words)
+{
+    REQUIRE(words, "NULL argument");
+    REQUIRE(H >= 1 && W >= 1 && H <= SV_AUG_MAX_SIDE && W <= SV_AUG_MAX_SIDE, "sides must be 1 .. SV_AUG_MAX_SIDE");
+    REQUIRE(index >= 0 && index < (1L << 56) && slot >= 0 && slot < 256, "index or slot outside the counter layout");
+    for (int p = 0; p < H * W; p++) {
+        const sv_philox4 w = sv_aug_draw(seed, (uint64_t)index, slot, salt, (uint32_t)p);
+        for (int k = 0; k < 4; k++) words[4 * p + k] = w.v[k];
+    }
+    return SV_OK;
 }

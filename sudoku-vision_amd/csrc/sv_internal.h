@@ -304,6 +304,10 @@ int svk_eval_metrics(sv_ctx *ctx, const float *input, bool prob, const void *lab
                      bool accumulate, float *probs, u8 *pred, float *conf, float *true_prob, float *nll, u8 *correct, sv_eval_stats *stats,
                      sv_eval_failure *failures, long max_failures, hipStream_t s);
 
+// k22_augment.hip (no scratch: the program and the images are the caller's)
+int svk_augment(sv_ctx *ctx, const u8 *src, int n_src, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const sv_aug_step *steps, const int32_t *n_steps,
+                const int32_t *src_index, long n_out, uint64_t seed, long index_base, u8 *dst, hipStream_t s);
+
 // host_png.cpp: whether an sv_png_info's geometry is one sv_png_parse produces (format table, limits, derived fields)
 bool sv_png_geometry_ok(const sv_png_info *info);
 

@@ -47,6 +47,26 @@ SV_HD inline sv_philox4 sv_mc_draw(uint64_t seed, uint64_t offset, uint32_t s, u
     return sv_philox4x32_10(b, s, c2, (uint32_t)offset, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
+// ---- K22 (k22_augment.hip, sv_augment_field_host): the random block of pixel `pixel` = y*W + x of output g's step slot.
+//     key     = (seed & 0xffffffff, seed >> 32)
+//     counter = (pixel, g & 0xffffffff, (g >> 32) << 8 | slot, salt)          g < 2^56, slot < 256
+// Words 0 and 1 serve the step: the x and y field of the elastic step, (w0, w1) of the Gaussian noise, (salt, pepper) of the other.
+SV_HD inline sv_philox4 sv_aug_draw(uint64_t seed, uint64_t g, int slot, uint32_t salt, uint32_t pixel)
+{
+    return sv_philox4x32_10(pixel, (uint32_t)g, ((uint32_t)(g >> 32) << 8) | (uint32_t)(slot & 255), salt, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+// (word >> 8) * 2^-23 - 1 in [-1, 1): every step is exact in float32
+SV_HD inline float sv_aug_uniform_pm1(uint32_t w) { return (float)(w >> 8) * 1.1920928955078125e-07f - 1.0f; }
+// word * 2^-32 in [0, 1), exact in double
+SV_HD inline double sv_aug_uniform01(uint32_t w) { return (double)w * 2.3283064365386963e-10; }
+// Box-Muller: u1 = (w0 + 1) * 2^-32 in (0, 1], u2 = w1 * 2^-32; sqrt(-2 ln u1) * cos(2 pi u2), every operation a double rounding
+SV_HD inline double sv_aug_normal(uint32_t w0, uint32_t w1)
+{
+    const double u1 = ((double)w0 + 1.0) * 2.3283064365386963e-10, u2 = sv_aug_uniform01(w1);
+    const double r = sqrt(-2.0 * log(u1));
+    return r * cos(6.283185307179586 * u2);
+}
+
 // a word keeps its channel iff it is below this; 2^32 at p = 0, 0 at p = 1
 inline uint64_t sv_mc_keep_threshold(float p) { return (uint64_t)std::llrint((1.0 - (double)p) * 4294967296.0); }
 

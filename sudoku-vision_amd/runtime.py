@@ -1517,6 +1517,50 @@ class Context:
                     "sv_warp_affine_u8")
         return _back(out[0] if single else out, was_tensor)
 
+    @staticmethod
+    def augment_check_program(steps, n_steps, src_index, n_src, H, W):
+        """sv_augment_check_program on a host program: steps [n_out, AUG_MAX_STEPS] of _native.AUG_STEP_DTYPE, n_steps and src_index int32
+        [n_out].  Returns the three as contiguous arrays; NativeError (SV_ERR_BAD_ARG, naming the output and the step) for a program the
+        kernel would not run as written.  Needs no GPU."""
+        steps = np.ascontiguousarray(steps, _native.AUG_STEP_DTYPE)
+        n_steps = np.ascontiguousarray(n_steps, np.int32)
+        src_index = np.ascontiguousarray(src_index, np.int32)
+        n_out = n_steps.shape[0]
+        if steps.shape != (n_out, _native.AUG_MAX_STEPS) or src_index.shape != (n_out,):
+            raise ValueError(f"steps must be [{n_out},{_native.AUG_MAX_STEPS}] and src_index [{n_out}], got {list(steps.shape)} and {list(src_index.shape)}")
+        lib = _native.lib()
+        _native.check(lib.sv_augment_check_program(steps.ctypes.data, n_steps.ctypes.data, src_index.ctypes.data, n_out, int(n_src), int(H), int(W)),
+                      "sv_augment_check_program", lib)
+        return steps, n_steps, src_index
+
+    def augment_upload_program(self, steps, n_steps, src_index, n_src, H, W):
+        """A host program, checked (augment_check_program), as the three device tensors `augment` takes: steps as uint8 [n_out, 960]."""
+        steps, n_steps, src_index = self.augment_check_program(steps, n_steps, src_index, n_src, H, W)
+        raw = torch.from_numpy(steps.view(np.uint8).reshape(steps.shape[0], -1))
+        return raw.to(self.device), torch.from_numpy(n_steps).to(self.device), torch.from_numpy(src_index).to(self.device)
+
+    def augment(self, images, steps, n_steps, src_index, seed=0, index_base=0, out=None):
+        """K22 (sv_augment_u8): images u8 [n_src,H,W] on the device -> u8 [n_out,H,W], output i = the program steps[i][:n_steps[i]] run on
+        images[src_index[i]].  A program given as numpy arrays is checked and uploaded first; one given as device tensors (steps uint8
+        [n_out, 960], n_steps and src_index int32 [n_out]: augment_upload_program) is launched as it is -- no host work, so the call can
+        be captured in a graph and replayed after the buffers change.  seed and index_base + i key the random fields."""
+        x, pitch, fstride = _plane_layout(images, self.device, "images")
+        n_src, H, W = x.shape
+        if not (4 <= H <= _native.AUG_MAX_SIDE and 4 <= W <= _native.AUG_MAX_SIDE):
+            raise ValueError(f"images of {H} x {W}: the augmentation kernel takes sides of 4..{_native.AUG_MAX_SIDE} pixels")
+        if not isinstance(steps, torch.Tensor):
+            steps, n_steps, src_index = self.augment_upload_program(steps, n_steps, src_index, n_src, H, W)
+        n_out = n_steps.shape[0]
+        _dev_tensor(steps, "steps", torch.uint8, self.device, shape=(n_out, _native.AUG_MAX_STEPS * _native.AUG_STEP_DTYPE.itemsize))
+        _dev_tensor(n_steps, "n_steps", torch.int32, self.device, shape=(n_out,))
+        _dev_tensor(src_index, "src_index", torch.int32, self.device, shape=(n_out,))
+        if not (steps.is_contiguous() and n_steps.is_contiguous() and src_index.is_contiguous()):
+            raise ValueError("the program tensors must be contiguous")
+        dst = self._out(out, (n_out, H, W), torch.uint8, "out")
+        self._check(self._lib.sv_augment_u8(self._h, _ptr(x), n_src, H, W, pitch, fstride, _ptr(steps), _ptr(n_steps), _ptr(src_index), n_out,
+                                            int(seed) & (2 ** 64 - 1), int(index_base), _ptr(dst), _stream_ptr()), "sv_augment_u8")
+        return dst
+
 
 _default = {}
 _lock = threading.Lock()
