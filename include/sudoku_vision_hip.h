@@ -1184,6 +1184,95 @@ int sv_augment_elastic_taps(double sigma, float *taps /*host, cap*/, int cap, in
 /* The random words of one output's step slot on the host, the kernel's own generator: words[(y*W + x)*4 + k], k = 0..3. */
 int sv_augment_field_host(uint64_t seed, long index, int slot, uint32_t salt, int H, int W, uint32_t *words /*host, H*W*4*/);
 
+/* ---- K23: synthetic digit cells, ml/generate_synthetic_v2.py --------------------------------------------------------------- */
+
+/* One launch draws n_out square gray cells of `size` x `size`: output i builds its base image from cells[i] (phase A), runs
+ * steps[i][0 .. clamp(n_steps[i], 0, SV_AUG_MAX_STEPS)) on it on chip (phase B) and is stored once.  cv2 is not available, so for the
+ * cv2 calls the arithmetic stated here is the contract and parity with OpenCV itself is unpinned (as for K13 and K22); the numpy and
+ * Pillow arithmetic of the reference is reproduced bit for bit.
+ *
+ * A cell record (sv_syn_cell) is 96 bytes, 8-byte aligned: 18 int32, then double bg_d[3].
+ * Phase A, per pixel (x, y), in this order:
+ *   background (generate_paper_background, ml/generate_synthetic_v2.py:128-174), bg_kind:
+ *     SV_SYN_BG_PLAIN (:132-135)     p = bg_value.
+ *     SV_SYN_BG_TEXTURED (:137-146)  p = trunc(clip((double)bg_value + bg_d[0] * z, 0, 255)), z the pixel's normal (below).  Then, when
+ *                                    grain_stride is 2..4, every row y = k * grain_stride gets max(p - d_k, 0), d_k = bits 2k, 2k+1 of
+ *                                    the 64 bits grain_d[0] | grain_d[1] << 32 (k < 32: a side of 64 at stride 2 has 32 such rows).
+ *     SV_SYN_BG_GRADIENT (:148-167)  grad_dir 0 (horizontal, i = x) or 1 (vertical, i = y): t = i * bg_d[1] + bg_d[0], two double roundings,
+ *                                    but t = bg_d[2] at i = size - 1: np.linspace's own terms (start, step, stop);
+ *                                    p = trunc(clip((double)bg_value + t, 0, 255)).  grad_dir 2 (radial): c = size / 2 (integer),
+ *                                    t = (sqrt((double)((x-c)^2 + (y-c)^2)) / ((double)size / 2)) * bg_d[0], IEEE sqrt and division;
+ *                                    p = trunc(clip((double)bg_value - t, 0, 255)).
+ *     SV_SYN_BG_NOISY (:169-172)     as textured, without grain.
+ *     SV_SYN_BG_KEEP                 p = what dst[i] holds at (x, y) when the kernel starts: the way an existing image enters (the
+ *                                    single-image add_grid_artifacts and apply_augmentation).  A workgroup reads its own output alone.
+ *   grid-line artefacts (add_grid_artifacts, :177-206): art_edges bit 0 top, 1 bottom, 2 left, 3 right; on the band of art_width
+ *     (1..2) rows or columns at that edge p = min(p, art_dark).
+ *   smudge (generate_empty_cell, :261-270): smudge = (x, y, side, darkness); side 0 is none, else p = min(p, darkness) on the square.
+ *   glyph (generate_digit, :223-247): glyph_slot -1 is none.  m = atlas[slot][y - glyph_y][x - glyph_x] inside the slot's (w, h) mask,
+ *     0 outside it; (glyph_x, glyph_y) is the signed top-left corner of Pillow's coverage mask (font.getmask2(text, "L")) in cell
+ *     coordinates, so a mask partly or wholly outside the cell is clipped -- what the reference's padded canvas and crop do.
+ *     t = ink * m + 255 * (255 - m) + 128;  digit = (t + (t >> 8)) >> 8      (Pillow's blend of ink over white, ImageDraw.text)
+ *     p = trunc(float32(p) * float32(digit) / 255), two float32 roundings    (the multiply blend, :247)
+ * The normal of a pixel: words w0, w1 of the Philox block (K22's layout above) of (seed, g = index_base + i, slot SV_SYN_BG_SLOT, salt
+ * bg_salt, pixel y*size + x), through K22's Box-Muller.  No step has slot SV_SYN_BG_SLOT.  sv_augment_field_host gives the words.
+ *
+ * Phase B runs sv_aug_step records: every K22 op above with K22's arithmetic (the random block of step `slot` as above), and
+ *   SV_SYN_AFFINE_CONST (apply_augmentation :284-288): SV_AUG_AFFINE, but a tap outside the image reads i[0] (BORDER_CONSTANT,
+ *     borderValue; the reference passes 255).  d[0..5] the forward matrix.
+ *   SV_SYN_PERSPECTIVE_CONST (:331-341): SV_AUG_PERSPECTIVE with the same border rule, border i[0].  d[0..8] the forward matrix.
+ *   SV_SYN_SCALE_PAD (:291-305): SV_AUG_SCALE with the pad value in i[3] (the reference pads with 255): i[0] = new_w, i[1] = new_h
+ *     (down to 1), i[2] = 1 to crop, 0 to pad; the same floor-division offsets and sv_resize_linear_u8 arithmetic.
+ *   SV_SYN_GAUSS_BLUR (:308-311, cv2.GaussianBlur(img, (k, k), sigma)): i[0] = k in {3, 5}; i[1], i[2], i[3] the taps at distance 0, 1, 2
+ *     as integers in Q8.8 with i[1] + 2*i[2] + 2*i[3] = 256 (i[3] = 0 at k = 3): sv_synth_gaussian_taps_q8.  Rows are accumulated
+ *     unrounded, R(x, y) = sum_i t|i| * p(x+i, y); columns then give (sum_j t|j| * R(x, y+j) + 2^15) >> 16.  BORDER_REFLECT_101.
+ *   SV_SYN_ERODE, SV_SYN_DILATE (:344-349, a 2 x 2 kernel of ones, anchor (1, 1)): the minimum resp. maximum over (x-1..x, y-1..y), taps
+ *     outside the image ignored.
+ * An op that is neither is the identity.  These ops are valid only here: sv_augment_u8 and sv_augment_check_program keep their set.
+ *
+ * The atlas is u8 [n_slots][SV_SYN_GLYPH_SIDE][SV_SYN_GLYPH_SIDE], a slot's mask in its top-left corner, row pitch SV_SYN_GLYPH_SIDE;
+ * atlas_dims is int32 [n_slots][2] = (w, h).  Glyph rasterisation is the host's (Pillow / FreeType, once per font, size and digit).
+ * Nothing a caller uploads can make the kernel touch memory outside its buffers: a slot outside 0 .. n_slots-1 draws nothing, (w, h)
+ * are clamped to the slot, offsets, rectangles, widths, strides, taps and counts are clamped or clipped, values are clamped to 0..255.
+ * 4 <= size <= SV_AUG_MAX_SIDE, n_out >= 1, n_slots >= 0 (atlas and atlas_dims may be NULL at 0), 0 <= index_base,
+ * index_base + n_out < 2^56: SV_ERR_BAD_ARG otherwise.  Asynchronous on `stream`, graph-capturable; no allocation, no host sync. */
+#define SV_SYN_GLYPH_SIDE 32
+#define SV_SYN_BG_SLOT 255
+typedef enum sv_syn_bg { SV_SYN_BG_PLAIN = 0, SV_SYN_BG_TEXTURED = 1, SV_SYN_BG_GRADIENT = 2, SV_SYN_BG_NOISY = 3, SV_SYN_BG_KEEP = 4 } sv_syn_bg;
+typedef enum sv_syn_op {
+    SV_SYN_AFFINE_CONST = 32, SV_SYN_PERSPECTIVE_CONST = 33, SV_SYN_SCALE_PAD = 34, SV_SYN_GAUSS_BLUR = 35, SV_SYN_ERODE = 36, SV_SYN_DILATE = 37
+} sv_syn_op;
+typedef struct sv_syn_cell {
+    int32_t bg_kind;       /* sv_syn_bg */
+    int32_t bg_value;      /* the plain value, or the base */
+    int32_t bg_salt;       /* the 32 bits of the field's salt */
+    int32_t grad_dir;      /* 0 horizontal, 1 vertical, 2 radial */
+    int32_t grain_stride;  /* 0: no grain; else 2..4 */
+    uint32_t grain_d[2];   /* 2 bits per grain row */
+    int32_t art_edges, art_width, art_dark;
+    int32_t smudge[4];     /* x, y, side (0: none), darkness */
+    int32_t glyph_slot;    /* -1: none */
+    int32_t glyph_x, glyph_y, glyph_ink;
+    double bg_d[3];        /* textured, noisy: sigma;  gradient h / v: start, step, stop;  radial: strength */
+} sv_syn_cell;
+int sv_synth_cells_u8(sv_ctx *ctx, const sv_syn_cell *cells /*dev, n_out*/, const sv_aug_step *steps /*dev, n_out*SV_AUG_MAX_STEPS*/,
+                      const int32_t *n_steps /*dev, n_out*/, long n_out, int size, const uint8_t *atlas /*dev*/,
+                      const int32_t *atlas_dims /*dev, n_slots*2*/, int n_slots, uint64_t seed, long index_base,
+                      uint8_t *dst /*dev, n_out*size*size*/, void *stream);
+
+/* What the kernel cannot report, on host copies: a known background kind and gradient direction, base, value, darkness and ink in
+ * 0..255, a finite sigma, strength and linspace terms, a grain stride of 0 or 2..4 with every used d in 1..3, artefact edges in 0..15
+ * with a width of 1..2, a smudge inside the cell, a glyph slot of -1 .. n_slots-1 whose mask is 1..SV_SYN_GLYPH_SIDE on both sides;
+ * 0 <= n_steps <= SV_AUG_MAX_STEPS; a K22 op that sv_augment_check_program accepts or a K23 op with a border / pad value in 0..255, finite
+ * matrices, a scale size of 1 .. 2*size that agrees with its flag, k in {3, 5} with taps >= 0 summing to 256.  SV_ERR_BAD_ARG with
+ * a message that names the output and the field or step.  Needs no context and no GPU. */
+int sv_synth_check_program(const sv_syn_cell *cells /*host*/, const sv_aug_step *steps /*host*/, const int32_t *n_steps /*host*/, long n_out,
+                           int size, const int32_t *atlas_dims /*host, may be NULL at n_slots 0*/, int n_slots);
+/* The Q8.8 taps of SV_SYN_GAUSS_BLUR at distance 0, 1, 2: in double v[j] = exp(-(j*j) / (2*sigma*sigma)), j = 0 .. k/2,
+ * sum = v[0] + 2*v[1] (+ 2*v[2]); taps[j] = rint(v[j] / sum * 256) for j >= 1 and taps[0] = 256 - 2*taps[1] - 2*taps[2], so that they sum to
+ * 256 exactly; taps[2] = 0 at k = 3.  k not 3 or 5, or a sigma that is not positive and finite: SV_ERR_BAD_ARG. */
+int sv_synth_gaussian_taps_q8(int k, double sigma, int32_t *taps /*host, 3*/);
+
 /* ---- the whole device-resident path ----------------------------------------------------------- */
 
 /* frames + homographies -> 81 digits per frame: K2 then K3 on `stream`, no host sync.

@@ -143,6 +143,9 @@ SIGNATURES = {
     "sv_augment_perspective_matrix": [_p, _p, _p],
     "sv_augment_elastic_taps": [_d, _p, _i, _p],
     "sv_augment_field_host": [C.c_uint64, _l, _i, C.c_uint32, _i, _i, _p],
+    "sv_synth_cells_u8": [_p, _p, _p, _p, _l, _i, _p, _p, _i, C.c_uint64, _l, _p, _p],
+    "sv_synth_check_program": [_p, _p, _p, _l, _i, _p, _i],
+    "sv_synth_gaussian_taps_q8": [_i, _d, _p],
     "sv_render_overlay_u8": [_p, _p, _i, _i, _i, _pd, _pd, _p, _p, _p, _p, _i, _p, _i, _p, _pd, _pd, _p],
 }
 _RESTYPES = {"sv_last_error": C.c_char_p, "sv_sparse_bits_record_bytes": C.c_long, "sv_jpeg_encode_bound": C.c_long}
@@ -191,6 +194,13 @@ EVAL_FAILURE_DTYPE = np.dtype([("index", "<i8"), ("label", "<i4"), ("pred", "<i4
 AUG_MAX_STEPS, AUG_MAX_SIDE, AUG_MAX_RADIUS = 10, 64, 16
 AUG_STEP_DTYPE = np.dtype({"names": ["op", "i", "d", "f"], "formats": ["<i4", ("<i4", (5,)), ("<f8", (9,)), ("<f4", (18,))], "offsets": [0, 4, 24, 24],
                            "itemsize": 96})
+# sv_syn_cell of include/sudoku_vision_hip.h as a numpy record of 96 bytes, and K23's kinds and ops
+SYN_GLYPH_SIDE, SYN_BG_SLOT = 32, 255
+SYN_CELL_DTYPE = np.dtype([("bg_kind", "<i4"), ("bg_value", "<i4"), ("bg_salt", "<i4"), ("grad_dir", "<i4"), ("grain_stride", "<i4"), ("grain_d", "<u4", (2,)),
+                           ("art_edges", "<i4"), ("art_width", "<i4"), ("art_dark", "<i4"), ("smudge", "<i4", (4,)), ("glyph_slot", "<i4"), ("glyph_x", "<i4"),
+                           ("glyph_y", "<i4"), ("glyph_ink", "<i4"), ("bg_d", "<f8", (3,))])
+SYN_BG_PLAIN, SYN_BG_TEXTURED, SYN_BG_GRADIENT, SYN_BG_NOISY, SYN_BG_KEEP = range(5)
+SYN_AFFINE_CONST, SYN_PERSPECTIVE_CONST, SYN_SCALE_PAD, SYN_GAUSS_BLUR, SYN_ERODE, SYN_DILATE = range(32, 38)
 AUG_NONE, AUG_AFFINE, AUG_PERSPECTIVE, AUG_BRIGHTNESS, AUG_CONTRAST, AUG_BLUR, AUG_SCALE, AUG_FILL_RECT, AUG_ELASTIC, AUG_NOISE_GAUSS, AUG_NOISE_SP = range(11)
 
 PNG_PALETTE_STRIDE = 1024

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "sv_augment_host.h"
+#include "sv_synth_host.h"
 #include "sv_internal.h"
 #include "sv_philox.h"
 
@@ -1219,5 +1220,32 @@ extern "C" int sv_augment_field_host(uint64_t seed, long index, int slot, uint32
         const sv_philox4 w = sv_aug_draw(seed, (uint64_t)index, slot, salt, (uint32_t)p);
         for (int k = 0; k < 4; k++) words[4 * p + k] = w.v[k];
     }
+    return SV_OK;
+}
+
+// ---- K23: synthetic digit cells (k23_synth_cells.hip; the host rules live in sv_synth_host.h) ----
+extern "C" int sv_synth_cells_u8(sv_ctx *ctx, const sv_syn_cell *cells, const sv_aug_step *steps, const int32_t *n_steps, long n_out, int size, const uint8_t *atlas,
+                                 const int32_t *atlas_dims, int n_slots, uint64_t seed, long index_base, uint8_t *dst, void *stream)
+{
+    REQUIRE(ctx && cells && steps && n_steps && dst, "NULL argument");
+    REQUIRE(n_out >= 1 && n_out <= 0x7fffffffL, "n_out must be at least 1 and below 2^31");
+    REQUIRE(size >= 4 && size <= SV_AUG_MAX_SIDE, "size must be 4 .. SV_AUG_MAX_SIDE");
+    REQUIRE(n_slots >= 0 && n_slots <= (1 << 20) && (n_slots == 0 || (atlas && atlas_dims)), "n_slots must be 0 .. 2^20, with an atlas and its dims when above 0");
+    REQUIRE(index_base >= 0 && index_base < (1L << 56) - n_out, "index_base + n_out must stay below 2^56");
+    REQUIRE((uintptr_t)steps % 8 == 0 && (uintptr_t)cells % 8 == 0, "cells and steps must be 8-byte aligned");
+    return svk_synth_cells(ctx, cells, steps, n_steps, n_out, size, atlas, atlas_dims, n_slots, seed, index_base, dst, S(stream));
+}
+
+extern "C" int sv_synth_check_program(const sv_syn_cell *cells, const sv_aug_step *steps, const int32_t *n_steps, long n_out, int size, const int32_t *atlas_dims, int n_slots)
+{
+    char msg[256];
+    const int rc = sv_syn_check_program(cells, steps, n_steps, n_out, size, atlas_dims, n_slots, msg, sizeof msg);
+    return rc ? sv_fail(rc, "sv_synth_check_program: %s", msg) : SV_OK;
+}
+
+extern "C" int sv_synth_gaussian_taps_q8(int k, double sigma, int32_t *taps)
+{
+    REQUIRE(taps, "NULL argument");
+    REQUIRE(sv_syn_gaussian_taps_q8(k, sigma, taps), "k must be 3 or 5 and sigma positive and finite");
     return SV_OK;
 }

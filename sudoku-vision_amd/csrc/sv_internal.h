@@ -307,6 +307,9 @@ int svk_eval_metrics(sv_ctx *ctx, const float *input, bool prob, const void *lab
 // k22_augment.hip (no scratch: the program and the images are the caller's)
 int svk_augment(sv_ctx *ctx, const u8 *src, int n_src, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const sv_aug_step *steps, const int32_t *n_steps,
                 const int32_t *src_index, long n_out, uint64_t seed, long index_base, u8 *dst, hipStream_t s);
+// k23_synth_cells.hip (no scratch: the records, the atlas and the output are the caller's)
+int svk_synth_cells(sv_ctx *ctx, const sv_syn_cell *cells, const sv_aug_step *steps, const int32_t *n_steps, long n_out, int size, const u8 *atlas, const int32_t *dims,
+                    int n_slots, uint64_t seed, long index_base, u8 *dst, hipStream_t s);
 
 // host_png.cpp: whether an sv_png_info's geometry is one sv_png_parse produces (format table, limits, derived fields)
 bool sv_png_geometry_ok(const sv_png_info *info);

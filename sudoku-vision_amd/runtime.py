@@ -1561,6 +1561,75 @@ class Context:
                                             int(seed) & (2 ** 64 - 1), int(index_base), _ptr(dst), _stream_ptr()), "sv_augment_u8")
         return dst
 
+    @staticmethod
+    def synth_check_program(cells, steps, n_steps, size, atlas_dims):
+        """sv_synth_check_program on a host job: cells [n_out] of _native.SYN_CELL_DTYPE, steps [n_out, AUG_MAX_STEPS] of AUG_STEP_DTYPE, n_steps
+        int32 [n_out], atlas_dims int32 [n_slots, 2].  Returns the four as contiguous arrays; NativeError (SV_ERR_BAD_ARG, naming the output
+        and the field or step) for a job the kernel would not run as written.  Needs no GPU."""
+        cells = np.ascontiguousarray(cells, _native.SYN_CELL_DTYPE)
+        steps = np.ascontiguousarray(steps, _native.AUG_STEP_DTYPE)
+        n_steps = np.ascontiguousarray(n_steps, np.int32)
+        dims = np.ascontiguousarray(atlas_dims, np.int32).reshape(-1, 2)
+        n_out = n_steps.shape[0]
+        if steps.shape != (n_out, _native.AUG_MAX_STEPS) or cells.shape != (n_out,):
+            raise ValueError(f"steps must be [{n_out},{_native.AUG_MAX_STEPS}] and cells [{n_out}], got {list(steps.shape)} and {list(cells.shape)}")
+        lib = _native.lib()
+        _native.check(lib.sv_synth_check_program(cells.ctypes.data, steps.ctypes.data, n_steps.ctypes.data, n_out, int(size), dims.ctypes.data if len(dims) else None,
+                                                 len(dims)), "sv_synth_check_program", lib)
+        return cells, steps, n_steps, dims
+
+    @staticmethod
+    def synth_atlas(masks):
+        """Glyph masks (a list of u8 [h, w] coverage arrays) -> (atlas u8 [n, G, G], dims int32 [n, 2] = (w, h)), G = _native.SYN_GLYPH_SIDE.  A mask
+        larger than G on a side is refused."""
+        G = _native.SYN_GLYPH_SIDE
+        atlas, dims = np.zeros((len(masks), G, G), np.uint8), np.zeros((len(masks), 2), np.int32)
+        for k, m in enumerate(masks):
+            m = np.asarray(m, np.uint8)
+            if m.ndim != 2 or not (1 <= m.shape[0] <= G and 1 <= m.shape[1] <= G):
+                raise ValueError(f"glyph mask {k} of shape {list(m.shape)}: the atlas takes masks of 1..{G} pixels on a side")
+            atlas[k, :m.shape[0], :m.shape[1]] = m
+            dims[k] = (m.shape[1], m.shape[0])
+        return atlas, dims
+
+    def synth_upload_program(self, cells, steps, n_steps, size, atlas):
+        """A host job, checked (synth_check_program), as the device tensors `synth_cells` takes: cells as uint8 [n_out, 96], steps as uint8
+        [n_out, 960], n_steps int32 [n_out], and the atlas pair (u8 [n_slots, G, G], int32 [n_slots, 2])."""
+        a, dims = atlas
+        a = np.ascontiguousarray(a, np.uint8)
+        G = _native.SYN_GLYPH_SIDE
+        if a.shape != (len(dims), G, G):
+            raise ValueError(f"the atlas must be [{len(dims)},{G},{G}], got {list(a.shape)}")
+        cells, steps, n_steps, dims = self.synth_check_program(cells, steps, n_steps, size, dims)
+        dev = lambda x: torch.from_numpy(x).to(self.device)
+        return (dev(cells.view(np.uint8).reshape(len(cells), -1)), dev(steps.view(np.uint8).reshape(steps.shape[0], -1)), dev(n_steps),
+                (dev(a.reshape(len(dims), G, G)), dev(dims)))
+
+    def synth_cells(self, cells, steps, n_steps, size, atlas, seed=0, index_base=0, out=None):
+        """K23 (sv_synth_cells_u8): n_out cell records and step programs -> u8 [n_out, size, size] on the device in one launch.  atlas is the
+        pair (u8 [n_slots, G, G], int32 [n_slots, 2]) of synth_atlas.  A job given as numpy arrays is checked and uploaded first; one given
+        as device tensors (synth_upload_program) is launched as it is -- no host work, so the call can be captured in a graph and replayed
+        after the buffers change.  seed and index_base + i key the random fields."""
+        size = int(size)
+        if not 4 <= size <= _native.AUG_MAX_SIDE:
+            raise ValueError(f"cells of {size} x {size}: the generator kernel takes sides of 4..{_native.AUG_MAX_SIDE} pixels")
+        if not isinstance(cells, torch.Tensor):
+            cells, steps, n_steps, atlas = self.synth_upload_program(cells, steps, n_steps, size, atlas)
+        a, dims = atlas
+        n_out, n_slots, G = n_steps.shape[0], dims.shape[0], _native.SYN_GLYPH_SIDE
+        _dev_tensor(cells, "cells", torch.uint8, self.device, shape=(n_out, _native.SYN_CELL_DTYPE.itemsize))
+        _dev_tensor(steps, "steps", torch.uint8, self.device, shape=(n_out, _native.AUG_MAX_STEPS * _native.AUG_STEP_DTYPE.itemsize))
+        _dev_tensor(n_steps, "n_steps", torch.int32, self.device, shape=(n_out,))
+        _dev_tensor(a, "atlas", torch.uint8, self.device, shape=(n_slots, G, G))
+        _dev_tensor(dims, "atlas dims", torch.int32, self.device, shape=(n_slots, 2))
+        if not all(t.is_contiguous() for t in (cells, steps, n_steps, a, dims)):
+            raise ValueError("the job tensors must be contiguous")
+        dst = self._out(out, (n_out, size, size), torch.uint8, "out")
+        self._check(self._lib.sv_synth_cells_u8(self._h, _ptr(cells), _ptr(steps), _ptr(n_steps), n_out, size, _ptr(a) if n_slots else None,
+                                                _ptr(dims) if n_slots else None, n_slots, int(seed) & (2 ** 64 - 1), int(index_base), _ptr(dst), _stream_ptr()),
+                    "sv_synth_cells_u8")
+        return dst
+
 
 _default = {}
 _lock = threading.Lock()
