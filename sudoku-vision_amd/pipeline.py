@@ -363,7 +363,10 @@ def recognize_image(image, model_state_dict=None, ctx=None, glue=Context.GLUE_RU
     :365), `resolved_grid` and `paths_explored`.  `grid` and `digits` stay the uncorrected recognition.
     propagate=True: run_v2's constraint propagation (pipeline/run_v2.py:373-391) on the device, of `resolved_grid` when resolve=True and of
     `grid` otherwise, with the cells' confidences: `propagation` (is_valid, iterations, contradiction_cell as (row, col) or None,
-    cells_resolved as (row, col, digit) in the reference's order) and `propagated_grid` (what run_v2 hands to the solver).
+    cells_resolved as (row, col, digit) in the reference's order) and `propagated_grid` (what run_v2 hands to the solver).  With
+    resolve=True the confidences are run_v2's own (:374): softmax(logits) without the temperature, the repaired cells carrying their
+    alternative's.  Without it -- a path run_v2 does not have -- they are `confidence`, softmax(logits / temperature) for the v3 models.
+    They decide is_fixed only (confidence > 0.9), which no entry of the result shows.
     solve=True: run_v2's solver stage (pipeline/run_v2.py:393-407) on the device (Context.solve_sudoku), of `propagated_grid` when
     propagate=True (and only if the propagation was valid, as in run_v2), else of `resolved_grid`, else of `grid`: `solve_result` (1 solved,
     0 no solution, -1 invalid, 3 not attempted), `solution` (9x9; the input grid unless solved) and `solve_nodes`.  A frame that spends the
