@@ -1125,7 +1125,7 @@ int sv_render_overlay_u8(sv_ctx *ctx, const uint8_t *frames /*dev*/, int n, int 
  *   SV_AUG_BLUR (gaussian_blur): i[0] = k in {1, 3, 5}.  Integer taps [1,2,1] / [1,4,6,4,1] on rows and columns, BORDER_REFLECT_101,
  *     (S + 8) >> 4 resp. (S + 128) >> 8 of the exact 2-D sum S: sv_blur_u8's rounding.  k = 1 is the identity.
  *   SV_AUG_SCALE (scale): i[0] = new_w, i[1] = new_h, i[2] = 1 to crop (factor > 1), 0 to pad.  cv2.resize to (new_w, new_h) in
- *     sv_resize_linear_u8's arithmetic; crop: the H x W window at ((new_h-H)/2, (new_w-W)/2); pad: the scaled image at
+ *     sv_resize_linear_u8's arithmetic (the same device function, csrc/sv_device.h's sv_resize_px); crop: the H x W window at ((new_h-H)/2, (new_w-W)/2); pad: the scaled image at
  *     ((H-new_h)/2, (W-new_w)/2) of a plane of 128 (floor divisions).  The scaled image is never materialised.
  *   SV_AUG_FILL_RECT (random_erasing): columns i[0] .. i[0]+i[2]-1 of rows i[1] .. i[1]+i[3]-1 become i[4].
  *   SV_AUG_ELASTIC (elastic_transform): i[0] = radius r <= SV_AUG_MAX_RADIUS, i[4] = salt, f[0] = float32(alpha), f[1 + j] = the

@@ -17,7 +17,7 @@
 //   Affine warp (rotate_image, cv/grid_v2.py:371-394 = cv2.warpAffine(INTER_LINEAR, BORDER_CONSTANT)):
 //     k_warp_affine       : one thread per destination pixel.  Thread 0 of a workgroup inverts the frame's forward matrix in double
 //                           (cv2's sequence); coordinates in cv2's 10 + 5 bit fixed point; the bilinear sample is K2's
-//                           (sv_warp_sample) inside the image and the same weights with the border constant per tap outside.
+//                           (sv_warp_sample) inside the image and sv_remap_sample with the border constant outside.
 #include "sv_device.h"
 #include "sv_internal.h"
 
@@ -201,39 +201,18 @@ __global__ __launch_bounds__(1024) void k_harris_select(unsigned long long *__re
     if (tid == 0) counts[frame] = nkept;
 }
 
-// cv2's saturate_cast<int>(double): round half to even, saturating
-__device__ __forceinline__ int sat_int(double v)
-{
-    return __double2int_rn(fmax(-2147483648.0, fmin(2147483647.0, v)));
-}
-
 __global__ __launch_bounds__(256) void k_warp_affine(const u8 *__restrict__ src, int H, int W, ptrdiff_t pitch, ptrdiff_t img_stride, const double *__restrict__ fwd,
                                                      int dh, int dw, int border, u8 *__restrict__ dst)
 {
     __shared__ double M[6];
     const int frame = blockIdx.z;
-    if (threadIdx.x == 0) {
-        // cv2.warpAffine without WARP_INVERSE_MAP: invert the forward matrix, this sequence of double operations
-        const double *m = fwd + (ptrdiff_t)frame * 6;
-        double D = __dsub_rn(__dmul_rn(m[0], m[4]), __dmul_rn(m[1], m[3]));
-        D = D != 0.0 ? __ddiv_rn(1.0, D) : 0.0;
-        const double A11 = __dmul_rn(m[4], D), A22 = __dmul_rn(m[0], D);
-        const double m1 = __dmul_rn(m[1], -D), m3 = __dmul_rn(m[3], -D);
-        M[0] = A11; M[1] = m1; M[3] = m3; M[4] = A22;
-        M[2] = __dsub_rn(__dmul_rn(-A11, m[2]), __dmul_rn(m1, m[5]));
-        M[5] = __dsub_rn(__dmul_rn(-m3, m[2]), __dmul_rn(A22, m[5]));
-    }
+    if (threadIdx.x == 0) sv_affine_invert(fwd + (ptrdiff_t)frame * 6, M);
     __syncthreads();
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= dw || y >= dh) return;
-    // AB_BITS = 10: 1/1024 px coordinates, + 16 rounds the >> 5 that leaves 5 fractional bits
-    const double fx = (double)x, fy = (double)y;
-    const int adelta = sat_int(__dmul_rn(__dmul_rn(M[0], fx), 1024.0)), bdelta = sat_int(__dmul_rn(__dmul_rn(M[3], fx), 1024.0));
-    const int X0 = (int)((unsigned)sat_int(__dmul_rn(__dadd_rn(__dmul_rn(M[1], fy), M[2]), 1024.0)) + 16u);
-    const int Y0 = (int)((unsigned)sat_int(__dmul_rn(__dadd_rn(__dmul_rn(M[4], fy), M[5]), 1024.0)) + 16u);
-    const int X = (int)((unsigned)X0 + (unsigned)adelta) >> 5, Y = (int)((unsigned)Y0 + (unsigned)bdelta) >> 5;
-    const int sx = sv_clamp(X >> 5, -32768, 32767), sy = sv_clamp(Y >> 5, -32768, 32767);
-    const int a = X & 31, b = Y & 31;
+    int X, Y, sx, sy, a, b;
+    sv_affine_coord(M, x, y, X, Y);
+    sv_remap_split(X, Y, sx, sy, a, b);
     const u8 *img = src + (ptrdiff_t)frame * img_stride;
     int v;
     if ((unsigned)sx < (unsigned)(W - 1) && (unsigned)sy < (unsigned)(H - 1)) {
@@ -241,17 +220,7 @@ __global__ __launch_bounds__(256) void k_warp_affine(const u8 *__restrict__ src,
         sv_warp_sample<1>(img, H, W, pitch, sx, sy, a, b, out);
         v = out[0];
     } else {
-        // cv2's weight table is (32-a)(32-b)*32, a(32-b)*32, (32-a)b*32, ab*32 but for a = b = 0, where 32768 saturates to 32767
-        // and the table's correction puts the missing 1 on the last tap: (32767 p00 + p11 + 16384) >> 15 = p00 for 8-bit
-        // values, the same as these weights give
-        const int w00 = (32 - a) * (32 - b) * 32, w01 = a * (32 - b) * 32, w10 = (32 - a) * b * 32, w11 = a * b * 32;
-        int p[4];
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int tx = sx + (t & 1), ty = sy + (t >> 1);
-            p[t] = ((unsigned)tx < (unsigned)W && (unsigned)ty < (unsigned)H) ? img[(ptrdiff_t)ty * pitch + tx] : border;
-        }
-        v = (p[0] * w00 + p[1] * w01 + p[2] * w10 + p[3] * w11 + 16384) >> 15;
+        v = sv_remap_sample(img, H, W, pitch, sx, sy, a, b, border);
     }
     dst[((ptrdiff_t)frame * dh + y) * dw + x] = (u8)v;
 }

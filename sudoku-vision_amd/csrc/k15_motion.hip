@@ -46,13 +46,7 @@ __device__ __forceinline__ int small_px(const u8 *img, const motion_geom &g, int
     int xo, a0, a1, yo, b0, b1;
     sv_resize_axis_scaled(g.scale_x, x, xo, a0, a1);
     sv_resize_axis_scaled(g.scale_y, y, yo, b0, b1);
-    if (xo < 0) { xo = 0; a0 = 2048; a1 = 0; }
-    if (xo >= g.W - 1) { xo = g.W - 1; a0 = 2048; a1 = 0; }
-    const int x1 = xo + 1 < g.W ? xo + 1 : xo;
-    const int y0 = sv_clamp(yo, 0, g.H - 1), y1 = sv_clamp(yo + 1, 0, g.H - 1);
-    const int t0 = gray_tap<C>(img, g.pitch, xo, y0) * a0 + gray_tap<C>(img, g.pitch, x1, y0) * a1;
-    const int t1 = gray_tap<C>(img, g.pitch, xo, y1) * a0 + gray_tap<C>(img, g.pitch, x1, y1) * a1;
-    return (((b0 * (t0 >> 4)) >> 16) + ((b1 * (t1 >> 4)) >> 16) + 2) >> 2;
+    return sv_resize_px(xo, a0, a1, yo, b0, b1, g.H, g.W, [&](int tx, int ty) { return gray_tap<C>(img, g.pitch, tx, ty); });
 }
 
 // counts[frame] += the workgroup's threads with `moved` set.  Every thread of the workgroup calls it.

@@ -17,14 +17,7 @@ struct CellsLds {
 // vertical/horizontal bilinear of cv2.resize on a gray crop held in LDS
 __device__ __forceinline__ int resize_px(const u8 *crop, int cw, int sh, int sw, int xo, int xa0, int xa1, int yo, int b0, int b1)
 {
-    int sx = xo, a0 = xa0, a1 = xa1;
-    if (sx < 0) { sx = 0; a0 = 2048; a1 = 0; }
-    if (sx >= sw - 1) { sx = sw - 1; a0 = 2048; a1 = 0; }
-    const int sx1 = sx + 1 < sw ? sx + 1 : sx;
-    const int sy0 = sv_clamp(yo, 0, sh - 1), sy1 = sv_clamp(yo + 1, 0, sh - 1);
-    const int t0 = crop[sy0 * cw + sx] * a0 + crop[sy0 * cw + sx1] * a1;
-    const int t1 = crop[sy1 * cw + sx] * a0 + crop[sy1 * cw + sx1] * a1;
-    return (((b0 * (t0 >> 4)) >> 16) + ((b1 * (t1 >> 4)) >> 16) + 2) >> 2;
+    return sv_resize_px(xo, xa0, xa1, yo, b0, b1, sh, sw, [=](int x, int y) { return (int)crop[y * cw + x]; });
 }
 
 __device__ __forceinline__ void warp_cells_item(const u8 *__restrict__ frames, int H, int W, ptrdiff_t pitch, ptrdiff_t frame_stride,

@@ -83,12 +83,7 @@ __global__ void k_resize_linear(const u8 *__restrict__ src, int sh, int sw, ptrd
     int xo, a0, a1, yo, b0, b1;
     sv_resize_axis(sw, dw, x, xo, a0, a1);
     sv_resize_axis(sh, dh, y, yo, b0, b1);
-    if (xo < 0) { xo = 0; a0 = 2048; a1 = 0; }
-    if (xo >= sw - 1) { xo = sw - 1; a0 = 2048; a1 = 0; }
-    const int x1 = xo + 1 < sw ? xo + 1 : xo;
-    const u8 *r0 = src + (ptrdiff_t)sv_clamp(yo, 0, sh - 1) * pitch, *r1 = src + (ptrdiff_t)sv_clamp(yo + 1, 0, sh - 1) * pitch;
-    const int t0 = r0[xo] * a0 + r0[x1] * a1, t1 = r1[xo] * a0 + r1[x1] * a1;
-    dst[(ptrdiff_t)y * dw + x] = (u8)((((b0 * (t0 >> 4)) >> 16) + ((b1 * (t1 >> 4)) >> 16) + 2) >> 2);
+    dst[(ptrdiff_t)y * dw + x] = (u8)sv_resize_px(xo, a0, a1, yo, b0, b1, sh, sw, [=](int tx, int ty) { return (int)src[(ptrdiff_t)ty * pitch + tx]; });
 }
 
 // is_cell_empty (cv/extract.py:59-79): Otsu threshold (OpenCV's single-pass fp64 recurrence, executed by one lane

@@ -13,41 +13,15 @@ struct AugShared {
     unsigned sum;
 };
 
-// cv2's saturate_cast<int>(double): round half to even, saturating
-__device__ __forceinline__ int aug_sat_int(double v) { return __double2int_rn(fmax(-2147483648.0, fmin(2147483647.0, v))); }
-
-// the bilinear sample of cv2's remap at cell (sx, sy), fractions (a, b) / 32.  border < 0 is BORDER_REPLICATE: each tap's coordinates
-// clamped; border >= 0 is BORDER_CONSTANT: a tap outside the image reads `border`
-__device__ __forceinline__ u8 aug_sample(const u8 *in, int H, int W, int sx, int sy, int a, int b, int border = -1)
-{
-    const int w00 = (32 - a) * (32 - b) * 32, w01 = a * (32 - b) * 32, w10 = (32 - a) * b * 32, w11 = a * b * 32;
-    const int x0 = sv_clamp(sx, 0, W - 1), x1 = sv_clamp(sx + 1, 0, W - 1), y0 = sv_clamp(sy, 0, H - 1), y1 = sv_clamp(sy + 1, 0, H - 1);
-    int t00 = in[y0 * W + x0], t01 = in[y0 * W + x1], t10 = in[y1 * W + x0], t11 = in[y1 * W + x1];
-    if (border >= 0) {
-        const bool xi0 = x0 == sx, xi1 = x1 == sx + 1, yi0 = y0 == sy, yi1 = y1 == sy + 1;       // the tap lies inside iff its clamp moved nothing
-        if (!(xi0 && yi0)) t00 = border;
-        if (!(xi1 && yi0)) t01 = border;
-        if (!(xi0 && yi1)) t10 = border;
-        if (!(xi1 && yi1)) t11 = border;
-    }
-    return (u8)((t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11 + 16384) >> 15);
-}
-
 __device__ __forceinline__ u8 aug_clip_trunc(double v) { return (u8)(int)fmin(fmax(v, 0.0), 255.0); }
 
-// one pixel of cv2.resize(in, (nw, nh)) at (x, y) of the scaled image: sv_resize_linear_u8's arithmetic
+// one pixel of cv2.resize(in, (nw, nh)) at (x, y) of the scaled image
 __device__ __forceinline__ int aug_resize_px(const u8 *in, int H, int W, int nh, int nw, int x, int y)
 {
     int xo, a0, a1, yo, b0, b1;
     sv_resize_axis(W, nw, x, xo, a0, a1);
     sv_resize_axis(H, nh, y, yo, b0, b1);
-    if (xo < 0) { xo = 0; a0 = 2048; a1 = 0; }
-    if (xo >= W - 1) { xo = W - 1; a0 = 2048; a1 = 0; }
-    const int x1 = xo + 1 < W ? xo + 1 : xo;
-    const int y0 = sv_clamp(yo, 0, H - 1), y1 = sv_clamp(yo + 1, 0, H - 1);
-    const int t0 = in[y0 * W + xo] * a0 + in[y0 * W + x1] * a1;
-    const int t1 = in[y1 * W + xo] * a0 + in[y1 * W + x1] * a1;
-    return (((b0 * (t0 >> 4)) >> 16) + ((b1 * (t1 >> 4)) >> 16) + 2) >> 2;
+    return sv_resize_px(xo, a0, a1, yo, b0, b1, H, W, [=](int tx, int ty) { return (int)in[ty * W + tx]; });
 }
 
 // one separable pass of the elastic step's Gaussian along x (dx = 1) or y (dx = 0): taps t[0..r] by distance, REFLECT_101,
@@ -67,7 +41,7 @@ __device__ __forceinline__ void aug_field_pass(const float *in, float *out, int 
 }
 
 // One of K22's eleven step kinds, `op` with its arguments in sh.st, from plane `in` to plane `out` by the 256 threads of the workgroup; fx,
-// fy, ft are the three f32 planes of the elastic step.  border is the warps' border (aug_sample; K22: -1), pad the value the scale
+// fy, ft are the three f32 planes of the elastic step.  border is the warps' border (sv_remap_sample; K22: -1), pad the value the scale
 // step pads with (K22: 128).  Returns whether `out` was written (the same for every thread: st is uniform); an op it does not
 // know is the identity.  The caller has put a barrier between the write of sh.st / sh.sum = 0 and this call.
 __device__ __forceinline__ bool aug_run_step(AugShared &sh, int op, int border, int pad, const u8 *in, u8 *out, int H, int W, float *fx, float *fy, float *ft, uint64_t seed, uint64_t g, int slot, int tid)
@@ -78,27 +52,14 @@ __device__ __forceinline__ bool aug_run_step(AugShared &sh, int op, int border, 
     bool wrote = true;
     switch (op) {
     case SV_AUG_AFFINE: {
-        if (tid == 0) {
-            // cv2.warpAffine without WARP_INVERSE_MAP: invert the forward matrix, this sequence of double operations
-            const double *m = st.d;
-            double D = __dsub_rn(__dmul_rn(m[0], m[4]), __dmul_rn(m[1], m[3]));
-            D = D != 0.0 ? __ddiv_rn(1.0, D) : 0.0;
-            const double A11 = __dmul_rn(m[4], D), A22 = __dmul_rn(m[0], D);
-            const double m1 = __dmul_rn(m[1], -D), m3 = __dmul_rn(m[3], -D);
-            sh.M[0] = A11; sh.M[1] = m1; sh.M[3] = m3; sh.M[4] = A22;
-            sh.M[2] = __dsub_rn(__dmul_rn(-A11, m[2]), __dmul_rn(m1, m[5]));
-            sh.M[5] = __dsub_rn(__dmul_rn(-m3, m[2]), __dmul_rn(A22, m[5]));
-        }
+        if (tid == 0) sv_affine_invert(st.d, sh.M);
         __syncthreads();
-        const double *M = sh.M;
         for (int p = tid; p < HW; p += 256) {
             const int y = p / W, x = p - y * W;
-            const double fxd = (double)x, fyd = (double)y;
-            const int adelta = aug_sat_int(__dmul_rn(__dmul_rn(M[0], fxd), 1024.0)), bdelta = aug_sat_int(__dmul_rn(__dmul_rn(M[3], fxd), 1024.0));
-            const int X0 = (int)((unsigned)aug_sat_int(__dmul_rn(__dadd_rn(__dmul_rn(M[1], fyd), M[2]), 1024.0)) + 16u);
-            const int Y0 = (int)((unsigned)aug_sat_int(__dmul_rn(__dadd_rn(__dmul_rn(M[4], fyd), M[5]), 1024.0)) + 16u);
-            const int X = (int)((unsigned)X0 + (unsigned)adelta) >> 5, Y = (int)((unsigned)Y0 + (unsigned)bdelta) >> 5;
-            out[p] = aug_sample(in, H, W, sv_clamp(X >> 5, -32768, 32767), sv_clamp(Y >> 5, -32768, 32767), X & 31, Y & 31, border);
+            int X, Y, sx, sy, a, b;
+            sv_affine_coord(sh.M, x, y, X, Y);
+            sv_remap_split(X, Y, sx, sy, a, b);
+            out[p] = (u8)sv_remap_sample(in, H, W, W, sx, sy, a, b, border);
         }
         break;
     }
@@ -125,7 +86,7 @@ __device__ __forceinline__ bool aug_run_step(AugShared &sh, int op, int border, 
             const int y = p / W, x = p - y * W;
             int sx, sy, a, b;
             sv_warp_coord(sh.M, x, y, W, sx, sy, a, b);       // W <= 64: the image is one block of cv2's, its origin column 0
-            out[p] = aug_sample(in, H, W, sx, sy, a, b, border);
+            out[p] = (u8)sv_remap_sample(in, H, W, W, sx, sy, a, b, border);
         }
         break;
     }
@@ -204,8 +165,9 @@ __device__ __forceinline__ bool aug_run_step(AugShared &sh, int op, int border, 
         for (int p = tid; p < HW; p += 256) {
             const int y = p / W, x = p - y * W;
             const float mx = __fadd_rn((float)x, __fmul_rn(fx[p], alpha)), my = __fadd_rn((float)y, __fmul_rn(fy[p], alpha));
-            const int X = aug_sat_int((double)__fmul_rn(mx, 32.f)), Y = aug_sat_int((double)__fmul_rn(my, 32.f));
-            out[p] = aug_sample(in, H, W, sv_clamp(X >> 5, -32768, 32767), sv_clamp(Y >> 5, -32768, 32767), X & 31, Y & 31);
+            int sx, sy, a, b;
+            sv_remap_split(sv_sat_int((double)__fmul_rn(mx, 32.f)), sv_sat_int((double)__fmul_rn(my, 32.f)), sx, sy, a, b);
+            out[p] = (u8)sv_remap_sample(in, H, W, W, sx, sy, a, b, -1);
         }
         break;
     }

@@ -31,6 +31,19 @@ __device__ __forceinline__ int sv_reflect101(int p, int len)
     return p;
 }
 
+// cv2's saturate_cast<int>(double): round half to even, saturating
+__device__ __forceinline__ int sv_sat_int(double v) { return __double2int_rn(fmax(-2147483648.0, fmin(2147483647.0, v))); }
+
+// The tail of every cv2 remap: coordinates (X, Y) with INTER_BITS = 5 fractional bits -> source cell (sx, sy), saturated to
+// int16 as cv2 stores it, and the 1/32 fractions (a, b).
+__device__ __forceinline__ void sv_remap_split(int X, int Y, int &sx, int &sy, int &a, int &b)
+{
+    sx = sv_clamp(X >> 5, -32768, 32767);
+    sy = sv_clamp(Y >> 5, -32768, 32767);
+    a = X & 31;
+    b = Y & 31;
+}
+
 // Width of the column blocks cv2.warpPerspective evaluates its fp64 coordinates in.
 __host__ __device__ __forceinline__ int sv_warp_block_w(int dw, int dh)
 {
@@ -59,11 +72,7 @@ __device__ __forceinline__ void sv_warp_coord_from(const double *M, double X0, d
     double fY = __dmul_rn(__dadd_rn(Y0, __dmul_rn(M[3], fx1)), Wv);
     fX = fmax(-2147483648.0, fmin(2147483647.0, fX));
     fY = fmax(-2147483648.0, fmin(2147483647.0, fY));
-    const int X = __double2int_rn(fX), Y = __double2int_rn(fY);
-    sx = sv_clamp(X >> 5, -32768, 32767);
-    sy = sv_clamp(Y >> 5, -32768, 32767);
-    a = X & 31;
-    b = Y & 31;
+    sv_remap_split(__double2int_rn(fX), __double2int_rn(fY), sx, sy, a, b);
 }
 
 // Destination pixel (dx,dy) -> source cell (sx,sy) and 1/32 fractions (a,b)
@@ -114,6 +123,54 @@ __device__ __forceinline__ void sv_warp_sample(const u8 *img, int H, int W, ptrd
     }
 }
 
+// One single-channel bilinear sample of cv2.remap at source cell (sx, sy), fractions (a, b) / 32, wherever the cell lies.  border < 0
+// is BORDER_REPLICATE: each tap's coordinates clamped; border >= 0 is BORDER_CONSTANT: a tap outside the image reads `border`.
+// Every load is at a clamped position, so none leaves the image.  Pitch is int for a dense plane in LDS, ptrdiff_t for a
+// pitched global image.
+// cv2's weight table is (32-a)(32-b)*32, a(32-b)*32, (32-a)b*32, ab*32 but for a = b = 0, where 32768 saturates to 32767 and the
+// table's correction puts the missing 1 on the last tap: (32767 p00 + p11 + 16384) >> 15 = p00 for 8-bit values, the same as
+// these weights give.
+template <class Pitch>
+__device__ __forceinline__ int sv_remap_sample(const u8 *img, int H, int W, Pitch pitch, int sx, int sy, int a, int b, int border)
+{
+    const int w00 = (32 - a) * (32 - b) * 32, w01 = a * (32 - b) * 32, w10 = (32 - a) * b * 32, w11 = a * b * 32;
+    const int x0 = sv_clamp(sx, 0, W - 1), x1 = sv_clamp(sx + 1, 0, W - 1), y0 = sv_clamp(sy, 0, H - 1), y1 = sv_clamp(sy + 1, 0, H - 1);
+    int t00 = img[(Pitch)y0 * pitch + x0], t01 = img[(Pitch)y0 * pitch + x1], t10 = img[(Pitch)y1 * pitch + x0], t11 = img[(Pitch)y1 * pitch + x1];
+    if (border >= 0) {
+        const bool xi0 = x0 == sx, xi1 = x1 == sx + 1, yi0 = y0 == sy, yi1 = y1 == sy + 1;       // the tap lies inside iff its clamp moved nothing
+        if (!(xi0 && yi0)) t00 = border;
+        if (!(xi1 && yi0)) t01 = border;
+        if (!(xi0 && yi1)) t10 = border;
+        if (!(xi1 && yi1)) t11 = border;
+    }
+    return (t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11 + 16384) >> 15;
+}
+
+// cv2.warpAffine without WARP_INVERSE_MAP inverts the forward 2x3 matrix m by this sequence of double operations (a singular
+// matrix gives zeros) -> M[0..5]
+__device__ __forceinline__ void sv_affine_invert(const double *m, double *M)
+{
+    double D = __dsub_rn(__dmul_rn(m[0], m[4]), __dmul_rn(m[1], m[3]));
+    D = D != 0.0 ? __ddiv_rn(1.0, D) : 0.0;
+    const double A11 = __dmul_rn(m[4], D), A22 = __dmul_rn(m[0], D);
+    const double m1 = __dmul_rn(m[1], -D), m3 = __dmul_rn(m[3], -D);
+    M[0] = A11; M[1] = m1; M[3] = m3; M[4] = A22;
+    M[2] = __dsub_rn(__dmul_rn(-A11, m[2]), __dmul_rn(m1, m[5]));
+    M[5] = __dsub_rn(__dmul_rn(-m3, m[2]), __dmul_rn(A22, m[5]));
+}
+
+// Destination pixel (x, y) of cv2.warpAffine under the inverse matrix M -> source coordinates (X, Y) with 5 fractional bits, for
+// sv_remap_split.  AB_BITS = 10: 1/1024 px coordinates, + 16 rounds the >> 5 that leaves 5 fractional bits; the sums wrap as cv2's do.
+__device__ __forceinline__ void sv_affine_coord(const double *M, int x, int y, int &X, int &Y)
+{
+    const double fx = (double)x, fy = (double)y;
+    const int adelta = sv_sat_int(__dmul_rn(__dmul_rn(M[0], fx), 1024.0)), bdelta = sv_sat_int(__dmul_rn(__dmul_rn(M[3], fx), 1024.0));
+    const int X0 = (int)((unsigned)sv_sat_int(__dmul_rn(__dadd_rn(__dmul_rn(M[1], fy), M[2]), 1024.0)) + 16u);
+    const int Y0 = (int)((unsigned)sv_sat_int(__dmul_rn(__dadd_rn(__dmul_rn(M[4], fy), M[5]), 1024.0)) + 16u);
+    X = (int)((unsigned)X0 + (unsigned)adelta) >> 5;
+    Y = (int)((unsigned)Y0 + (unsigned)bdelta) >> 5;
+}
+
 // cv2.resize INTER_LINEAR 8-bit axis table entry (cv/extract.py:52): source offset + two 11-bit weights.
 // scale = 1 / (d_len / s_len), two double divisions (sv_resize_axis below, or the same two on the host: IEEE either way).
 __device__ __forceinline__ void sv_resize_axis_scaled(double scale, int d, int &ofs, int &w0, int &w1)
@@ -129,6 +186,21 @@ __device__ __forceinline__ void sv_resize_axis_scaled(double scale, int d, int &
 __device__ __forceinline__ void sv_resize_axis(int s_len, int d_len, int d, int &ofs, int &w0, int &w1)
 {
     sv_resize_axis_scaled(__ddiv_rn(1.0, __ddiv_rn((double)d_len, (double)s_len)), d, ofs, w0, w1);
+}
+
+// One pixel of 8-bit cv2.resize(INTER_LINEAR) from its axis entries (xo, a0, a1), (yo, b0, b1) over an sh x sw source whose
+// pixel (x, y) is tap(x, y): a column left of the image or on its last column takes weights (2048, 0), the rows are clamped, and
+// the blend has cv2's two stages.  Every tap lies inside the source.
+template <class Tap>
+__device__ __forceinline__ int sv_resize_px(int xo, int a0, int a1, int yo, int b0, int b1, int sh, int sw, Tap tap)
+{
+    if (xo < 0) { xo = 0; a0 = 2048; a1 = 0; }
+    if (xo >= sw - 1) { xo = sw - 1; a0 = 2048; a1 = 0; }
+    const int x1 = xo + 1 < sw ? xo + 1 : xo;
+    const int y0 = sv_clamp(yo, 0, sh - 1), y1 = sv_clamp(yo + 1, 0, sh - 1);
+    const int t0 = tap(xo, y0) * a0 + tap(x1, y0) * a1;
+    const int t1 = tap(xo, y1) * a0 + tap(x1, y1) * a1;
+    return (((b0 * (t0 >> 4)) >> 16) + ((b1 * (t1 >> 4)) >> 16) + 2) >> 2;
 }
 
 // ---- the fc2 -> argmax -> softmax[argmax] epilogue of every fc head (pipeline/run.py:139-143), in f32 on the VALU ----
