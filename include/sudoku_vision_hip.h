@@ -906,6 +906,48 @@ int sv_png_inflate_batch(const uint8_t *const *datas, const size_t *sizes, const
 int sv_png_reconstruct_bgr_u8(sv_ctx *ctx, const sv_png_info *info, const uint8_t *filtered /*dev*/, const uint8_t *row_filter /*dev*/,
                               const uint8_t *palette /*dev or NULL*/, int n, uint8_t *out /*dev*/, ptrdiff_t pitch, ptrdiff_t frame_stride,
                               uint32_t *status /*dev*/, void *stream);
+/* The same under the same contract, but the frame is what cv2.imread(path, IMREAD_GRAYSCALE) returns (ml/datasets.py:81, :153, ml/evaluate.py:67):
+ * one gray byte a pixel, pitch >= width.  Colour types 0 and 4: the sample (the high byte of 16 bits; 1, 2, 4 bits replicated), alpha dropped;
+ * exact.  Colour types 2, 3, 6: the BGR pixel of the entry above through sv_gray_u8's arithmetic, i.e. cv2.cvtColor(cv2.imread(path),
+ * COLOR_BGR2GRAY); cv2's own gray read of a colour file lets libpng convert, whose rounding is argued, not measured, here: it may differ by one
+ * level on colour files. */
+int sv_png_reconstruct_gray_u8(sv_ctx *ctx, const sv_png_info *info, const uint8_t *filtered /*dev*/, const uint8_t *row_filter /*dev*/,
+                               const uint8_t *palette /*dev or NULL*/, int n, uint8_t *out /*dev*/, ptrdiff_t pitch, ptrdiff_t frame_stride,
+                               uint32_t *status /*dev*/, void *stream);
+
+/* ---- K24: a data set of PNG cells -> model input (ml/datasets.py:18-46 preprocess_cell, :69-92 SyntheticDataset.__getitem__, :141-164
+ * RealDataset.__getitem__; ml/evaluate.py:67 for the plain gray read).  One launch takes the FILTERED bytes of n small PNG files (what
+ * sv_png_inflate wrote), each with a geometry of its own, to n cells of 28 x 28: unfilter, the gray read of sv_png_reconstruct_gray_u8,
+ * cv2.resize(img, (28, 28)) when the file is not 28 x 28 (sv_resize_linear_u8's arithmetic), then the mode; the cell never leaves the chip
+ * in between (csrc/k24_dataset_cells.hip). */
+#define SV_CELLS_GRAY 0                 /* stop after the resize: cv2.imread(path, IMREAD_GRAYSCALE) at 28 x 28 */
+#define SV_CELLS_DATASET 1              /* then datasets.preprocess_cell: CLAHE(2.0, (4,4)), adaptiveThreshold(GAUSSIAN_C, BINARY, 11, 2), 255 - x */
+#define SV_CELLS_MAX_SIDE 64            /* a cell's sides are 1 .. 64 */
+#define SV_CELLS_MAX_ROW_BYTES 512      /* 64 pixels of RGBA at 16 bits */
+#define SV_CELLS_NO_PALETTE 0xffff      /* sv_dataset_record.palette of a cell without one */
+#define SV_CELLS_STATUS_PALETTE 1u      /* status bit 0, as for sv_png_reconstruct_bgr_u8: a palette index past the palette's end (that pixel is 0) */
+#define SV_CELLS_STATUS_REFUSED 2u      /* status bit 1: the kernel refused the record; the cell's outputs are zeros */
+typedef struct sv_dataset_record {      /* 16 bytes, 8-byte aligned */
+    uint64_t offset;                    /* where the cell's filtered stream, height * (1 + row_bytes) bytes, starts inside `filtered` */
+    uint16_t width, height;             /* 1 .. SV_CELLS_MAX_SIDE */
+    uint8_t color_type, bit_depth;      /* a pair of the PNG specification; the stream is non-interlaced */
+    uint16_t palette;                   /* which of the n_palettes palettes (colour type 3), else SV_CELLS_NO_PALETTE */
+} sv_dataset_record;
+
+/* filtered (filtered_size bytes), records (n of them) and palettes (n_palettes * SV_PNG_PALETTE_STRIDE bytes, or NULL with n_palettes 0) are on
+ * the device.  out_u8 (n * 784 bytes) and out_f32 (n * 784 floats, float(u8) / 255.0f by a true division: torch.from_numpy(img).float() / 255.0
+ * to the bit) are on the device; either may be NULL, not both.  status (n uint32) is written by the kernel itself for every cell, 0 or SV_CELLS_STATUS_*.
+ * The kernel trusts no byte of a record: one that sv_dataset_check_records would refuse is refused there too (SV_CELLS_STATUS_REFUSED, outputs
+ * zero), a filter byte above 4 is None, and nothing outside filtered[0 .. filtered_size) and the palettes is ever read.  Asynchronous on
+ * `stream`; never allocates or synchronises, so it can be captured in a graph.  SV_ERR_BAD_ARG: NULL or misaligned arguments, n outside
+ * 1 .. (2^31 - 1) / 784, another mode, n_palettes outside 0 .. 65534. */
+int sv_dataset_cells(sv_ctx *ctx, const uint8_t *filtered /*dev*/, size_t filtered_size, const sv_dataset_record *records /*dev*/, long n,
+                     const uint8_t *palettes /*dev or NULL*/, int n_palettes, int mode, uint8_t *out_u8 /*dev or NULL*/, float *out_f32 /*dev or NULL*/,
+                     uint32_t *status /*dev*/, void *stream);
+/* The same rules on the host, no GPU: SV_OK, or SV_ERR_BAD_ARG with the first malformed record in sv_last_error (a side outside 1 .. 64, a
+ * (colour type, depth) pair the specification does not have, a stream that does not lie inside filtered_size, a palette index at or past
+ * n_palettes, colour type 3 without one). */
+int sv_dataset_check_records(const sv_dataset_record *records /*host*/, long n, size_t filtered_size, int n_palettes);
 
 /* ---- quality gate: the per-pixel statistics of cv/grid_quality.py (pipeline/run_v2.py:299-311) ------------------------- */
 

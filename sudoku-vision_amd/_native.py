@@ -96,6 +96,9 @@ SIGNATURES = {
     "sv_png_inflate": [_p, C.c_size_t, _p, _p, C.c_size_t, _p],
     "sv_png_inflate_batch": [_p, _p, _p, _i, _p, _p, _p, _i, _p],
     "sv_png_reconstruct_bgr_u8": [_p, _p, _p, _p, _p, _i, _p, _pd, _pd, _p, _p],
+    "sv_png_reconstruct_gray_u8": [_p, _p, _p, _p, _p, _i, _p, _pd, _pd, _p, _p],
+    "sv_dataset_cells": [_p, _p, C.c_size_t, _p, _l, _p, _i, _i, _p, _p, _p, _p],
+    "sv_dataset_check_records": [_p, _l, C.c_size_t, _i],
     "sv_softmax_topk_f32": [_p, _p, _l, _i, _p, _p, _p],
     "sv_eval_metrics": [_p, _p, _i, _p, _i, _l, _l, _f, _p, _i, _i] + [_p] * 8 + [_l, _p],
     "sv_eval_metrics_host": [_p, _p, _i, _p, _i, _l, _l, _f, _p, _i, _i] + [_p] * 8 + [_l, _p, _p],
@@ -204,6 +207,11 @@ SYN_AFFINE_CONST, SYN_PERSPECTIVE_CONST, SYN_SCALE_PAD, SYN_GAUSS_BLUR, SYN_EROD
 AUG_NONE, AUG_AFFINE, AUG_PERSPECTIVE, AUG_BRIGHTNESS, AUG_CONTRAST, AUG_BLUR, AUG_SCALE, AUG_FILL_RECT, AUG_ELASTIC, AUG_NOISE_GAUSS, AUG_NOISE_SP = range(11)
 
 PNG_PALETTE_STRIDE = 1024
+# sv_dataset_record of include/sudoku_vision_hip.h as a numpy record of 16 bytes, and K24's modes, limits and status bits
+DATASET_RECORD_DTYPE = np.dtype([("offset", "<u8"), ("width", "<u2"), ("height", "<u2"), ("color_type", "u1"), ("bit_depth", "u1"), ("palette", "<u2")])
+CELLS_GRAY, CELLS_DATASET = 0, 1
+CELLS_MAX_SIDE, CELLS_NO_PALETTE = 64, 0xffff
+CELLS_STATUS_PALETTE, CELLS_STATUS_REFUSED = 1, 2
 
 
 _lib = None

@@ -14,6 +14,7 @@
 //                   one cross-lane move (lane 0: from the LDS copy of the row above the stripe) and keeps the last 8 bytes of its own row and of
 //                   the row above in two 64-bit registers, so `left` and `above-left` are shifts.  A chunk costs its bytes + 63 steps.
 //   k_png_expand    grid (ceil(W / 256), H, n): one thread per pixel, unfiltered samples -> B, G, R.
+//   k_png_expand_gray   the same grid, one gray byte a pixel (svpng::expand_gray): the IMREAD_GRAYSCALE read, in k_png_expand's place.
 //
 // No wave waits for another: the job list is complete at the launch boundary, k_png_segments never looks at a row another workgroup writes
 // (a segment's first row needs nothing from above), and every loop is bounded by the geometry.  The scratch (ctx->png_dec) is
@@ -156,10 +157,23 @@ __global__ __launch_bounds__(256) void k_png_expand(const u8 *__restrict__ raw, 
     o[0] = (u8)px; o[1] = (u8)(px >> 8); o[2] = (u8)(px >> 16);
 }
 
+__global__ __launch_bounds__(256) void k_png_expand_gray(const u8 *__restrict__ raw, const u8 *__restrict__ palette, DecGeom g, u8 *__restrict__ out, long pitch,
+                                                         long frame_stride, uint32_t *__restrict__ status)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, img = blockIdx.z;
+    if (x >= g.W) return;
+    const u8 *pal = palette ? palette + (long)img * SV_PNG_PALETTE_STRIDE : nullptr;
+    const unsigned pal_n = pal ? min(256u, *(const uint32_t *)(pal + 768)) : 0u;
+    const svpng::Expand e = {g.color_type, g.bit_depth, g.channels};
+    const unsigned px = svpng::expand_gray(e, raw + ((long)img * g.H + y) * g.row_bytes, x, pal, pal_n);
+    if (px >> 8) atomicOr(status + img, 1u);
+    out[(long)img * frame_stride + (long)y * pitch + x] = (u8)px;
+}
+
 }  // namespace
 
 int svk_png_reconstruct(sv_ctx *ctx, const sv_png_info *info, const u8 *filtered, const u8 *row_filter, const u8 *palette, int n, u8 *out, ptrdiff_t pitch,
-                        ptrdiff_t frame_stride, uint32_t *status, hipStream_t s)
+                        ptrdiff_t frame_stride, uint32_t *status, bool gray, hipStream_t s)
 {
     DecGeom g = {};
     g.W = info->width; g.H = info->height; g.bpp = info->bpp; g.color_type = info->color_type; g.bit_depth = info->bit_depth; g.channels = info->channels;
@@ -176,8 +190,8 @@ int svk_png_reconstruct(sv_ctx *ctx, const sv_png_info *info, const u8 *filtered
     const unsigned grid = (unsigned)std::min<size_t>(rows, (size_t)ctx->num_cus * 4);
     hipLaunchKernelGGL(k_png_segments, dim3(grid), dim3(64), 0, s, filtered, row_filter, g, raw, (const uint32_t *)count, (const uint32_t *)jobs);
     SV_LAUNCH_CHECK("k_png_segments");
-    hipLaunchKernelGGL(k_png_expand, dim3((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)n), dim3(256), 0, s, (const u8 *)raw, palette, g, out, (long)pitch,
-                       (long)frame_stride, status);
-    SV_LAUNCH_CHECK("k_png_expand");
+    hipLaunchKernelGGL(gray ? k_png_expand_gray : k_png_expand, dim3((unsigned)((g.W + 255) / 256), (unsigned)g.H, (unsigned)n), dim3(256), 0, s, (const u8 *)raw, palette, g,
+                       out, (long)pitch, (long)frame_stride, status);
+    SV_LAUNCH_CHECK(gray ? "k_png_expand_gray" : "k_png_expand");
     return SV_OK;
 }

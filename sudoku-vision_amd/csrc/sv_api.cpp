@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "sv_augment_host.h"
+#include "sv_dataset_rec.h"
 #include "sv_synth_host.h"
 #include "sv_internal.h"
 #include "sv_philox.h"
@@ -1119,19 +1120,55 @@ extern "C" int sv_png_deflate_gray_u8(sv_ctx *ctx, const sv_png_enc *plan, const
     return png_deflate("sv_png_deflate_gray_u8", 1, ctx, plan, gray, n, pitch, frame_stride, stream_out, band_len, adler, status, stream);
 }
 
-// The PNG decoder's device half.  Only the geometry of the info is used, and only one sv_png_parse could have produced.
+// The PNG decoder's device half; channels 3 (BGR) or 1 (gray).  Only the geometry of the info is used, and only one sv_png_parse could have produced.
+static int png_reconstruct(const char *fn, int channels, sv_ctx *ctx, const sv_png_info *info, const uint8_t *filtered, const uint8_t *row_filter, const uint8_t *palette, int n,
+                           uint8_t *out, ptrdiff_t pitch, ptrdiff_t frame_stride, uint32_t *status, void *stream)
+{
+    REQUIRE_AS(fn, ctx && info && filtered && row_filter && out && status, "NULL argument");
+    REQUIRE_AS(fn, n > 0 && n < 65536, "n must be in 1..65535");
+    REQUIRE_AS(fn, sv_png_geometry_ok(info), "the info was not made by sv_png_parse");
+    const int type = info->color_type;
+    REQUIRE_AS(fn, type != 3 || palette, "colour type 3 needs a palette");
+    REQUIRE_AS(fn, pitch >= channels * (ptrdiff_t)info->width, "pitch smaller than a row");
+    REQUIRE_AS(fn, n == 1 || frame_stride >= pitch * (ptrdiff_t)(info->height - 1) + channels * (ptrdiff_t)info->width, "frames overlap");
+    REQUIRE_AS(fn, ((uintptr_t)status & 3) == 0 && ((uintptr_t)palette & 3) == 0, "misaligned status or palette");
+    return svk_png_reconstruct(ctx, info, filtered, row_filter, type == 3 ? palette : nullptr, n, out, pitch, frame_stride, status, channels == 1, S(stream));
+}
+
 extern "C" int sv_png_reconstruct_bgr_u8(sv_ctx *ctx, const sv_png_info *info, const uint8_t *filtered, const uint8_t *row_filter, const uint8_t *palette, int n, uint8_t *out,
                                          ptrdiff_t pitch, ptrdiff_t frame_stride, uint32_t *status, void *stream)
 {
-    REQUIRE(ctx && info && filtered && row_filter && out && status, "NULL argument");
-    REQUIRE(n > 0 && n < 65536, "n must be in 1..65535");
-    REQUIRE(sv_png_geometry_ok(info), "the info was not made by sv_png_parse");
-    const int type = info->color_type;
-    REQUIRE(type != 3 || palette, "colour type 3 needs a palette");
-    REQUIRE(pitch >= 3 * (ptrdiff_t)info->width, "pitch smaller than a row");
-    REQUIRE(n == 1 || frame_stride >= pitch * (ptrdiff_t)(info->height - 1) + 3 * (ptrdiff_t)info->width, "frames overlap");
-    REQUIRE(((uintptr_t)status & 3) == 0 && ((uintptr_t)palette & 3) == 0, "misaligned status or palette");
-    return svk_png_reconstruct(ctx, info, filtered, row_filter, type == 3 ? palette : nullptr, n, out, pitch, frame_stride, status, S(stream));
+    return png_reconstruct("sv_png_reconstruct_bgr_u8", 3, ctx, info, filtered, row_filter, palette, n, out, pitch, frame_stride, status, stream);
+}
+
+extern "C" int sv_png_reconstruct_gray_u8(sv_ctx *ctx, const sv_png_info *info, const uint8_t *filtered, const uint8_t *row_filter, const uint8_t *palette, int n, uint8_t *out,
+                                          ptrdiff_t pitch, ptrdiff_t frame_stride, uint32_t *status, void *stream)
+{
+    return png_reconstruct("sv_png_reconstruct_gray_u8", 1, ctx, info, filtered, row_filter, palette, n, out, pitch, frame_stride, status, stream);
+}
+
+// ---- K24: PNG cell data sets to model input (k24_dataset_cells.hip; the record rules live in sv_dataset_rec.h) ----
+extern "C" int sv_dataset_cells(sv_ctx *ctx, const uint8_t *filtered, size_t filtered_size, const sv_dataset_record *records, long n, const uint8_t *palettes, int n_palettes,
+                                int mode, uint8_t *out_u8, float *out_f32, uint32_t *status, void *stream)
+{
+    REQUIRE(ctx && filtered && records && status, "NULL argument");
+    REQUIRE(out_u8 || out_f32, "at least one of out_u8 and out_f32 is needed");
+    REQUIRE(n >= 1 && n <= 0x7fffffffL / 784, "n must be at least 1 and n * 784 below 2^31");
+    REQUIRE(mode == SV_CELLS_GRAY || mode == SV_CELLS_DATASET, "mode must be SV_CELLS_GRAY or SV_CELLS_DATASET");
+    REQUIRE(n_palettes >= 0 && n_palettes < SV_CELLS_NO_PALETTE && (n_palettes == 0 || palettes), "n_palettes must be 0 .. 65534, with palettes when above 0");
+    REQUIRE((uintptr_t)records % 8 == 0 && (uintptr_t)status % 4 == 0 && (uintptr_t)out_f32 % 4 == 0 && (uintptr_t)palettes % 4 == 0, "misaligned records, status, out_f32 or palettes");
+    return svk_dataset_cells(ctx, filtered, filtered_size, records, n, n_palettes ? palettes : nullptr, n_palettes, mode, out_u8, out_f32, status, S(stream));
+}
+
+extern "C" int sv_dataset_check_records(const sv_dataset_record *records, long n, size_t filtered_size, int n_palettes)
+{
+    REQUIRE(records && n >= 1, "NULL records or n below 1");
+    for (long i = 0; i < n; i++) {
+        svds::Geom g;
+        const char *why = svds::refuse(records[i], filtered_size, n_palettes, g);
+        if (why) return sv_fail(SV_ERR_BAD_ARG, "sv_dataset_check_records: record %ld: %s", i, why);
+    }
+    return SV_OK;
 }
 
 // K2 into the caller's cells (or the context's), then the forward `model` selects: 0 DigitCNN, 1 DigitCNNv3, 2 DigitCNNv3Light

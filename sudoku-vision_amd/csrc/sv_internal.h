@@ -297,7 +297,11 @@ int svk_png_deflate(sv_ctx *ctx, const sv_png_enc *plan, const u8 *src, int n, p
 
 // k19_png_decode.hip (the unfiltered samples and the job list live in ctx->png_dec)
 int svk_png_reconstruct(sv_ctx *ctx, const sv_png_info *info, const u8 *filtered, const u8 *row_filter, const u8 *palette, int n, u8 *out, ptrdiff_t pitch,
-                        ptrdiff_t frame_stride, uint32_t *status, hipStream_t s);
+                        ptrdiff_t frame_stride, uint32_t *status, bool gray, hipStream_t s);
+
+// k24_dataset_cells.hip (no scratch: the whole cell lives in LDS)
+int svk_dataset_cells(sv_ctx *ctx, const u8 *filtered, size_t filtered_size, const sv_dataset_record *records, long n, const u8 *palettes, int n_palettes, int mode,
+                      u8 *out_u8, float *out_f32, uint32_t *status, hipStream_t s);
 
 // k21_eval.hip (the failure list's scratch lives in ctx->eval)
 int svk_eval_metrics(sv_ctx *ctx, const float *input, bool prob, const void *labels, bool i64, long B, long index_base, float T, const double *bin_edges, int n_bins,

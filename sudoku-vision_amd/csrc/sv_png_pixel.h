@@ -4,6 +4,10 @@
 #pragma once
 #include <cstdint>
 
+#if defined(__HIPCC__)
+#include "sv_device.h"                 // sv_gray_px, for expand_gray (device code only)
+#endif
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define SVPNG_HD __host__ __device__ inline
 #else
@@ -59,5 +63,26 @@ SVPNG_HD uint32_t expand_pixel(const Expand &e, const uint8_t *row, long x, cons
     }
     return (uint32_t)s[2] | (uint32_t)s[1] << 8 | (uint32_t)s[0] << 16;                    // R, G, B in the file -> B, G, R
 }
+
+#if defined(__HIPCC__)
+// One pixel of the GRAY read, cv2.imread(path, IMREAD_GRAYSCALE) (ml/datasets.py:81, :153; ml/evaluate.py:67): same arguments as expand_pixel,
+// one gray byte, bit 8 set for a palette index at or past pal_n (the pixel is then 0).  Colour types 0 and 4: the sample itself (the high byte
+// of 16 bits; 1, 2 and 4 bits replicated: x255, x85, x17), alpha dropped.  Colour types 2, 3 and 6: expand_pixel's B, G, R through
+// sv_gray_px, K1's BGR -> gray: exactly cv2.cvtColor(cv2.imread(path), COLOR_BGR2GRAY).  cv2's own gray read of a COLOUR file asks libpng for
+// the conversion instead, and libpng's rounding is argued, not measured, here: it may differ by one level on colour files.  Gray files, which
+// is what every writer of the reference's data sets produces, are exact.  Device only, as sv_gray_px is; its reads are expand_pixel's or fewer, which is what the host-side checks walk.
+__device__ inline unsigned expand_gray(const Expand &e, const uint8_t *row, long x, const uint8_t *pal, unsigned pal_n)
+{
+    if (e.color_type == 0 || e.color_type == 4) {
+        if (e.bit_depth >= 8) return row[x * e.channels * (e.bit_depth >> 3)];
+        const long bit = x * e.bit_depth;
+        const unsigned v = ((unsigned)row[bit >> 3] >> (8 - e.bit_depth - (int)(bit & 7))) & ((1u << e.bit_depth) - 1u);
+        return v * (e.bit_depth == 1 ? 255u : e.bit_depth == 2 ? 85u : 17u);
+    }
+    const uint32_t px = expand_pixel(e, row, x, pal, pal_n);
+    if (px >> 24) return 1u << 8;
+    return (unsigned)sv_gray_px((int)(px & 255u), (int)(px >> 8 & 255u), (int)(px >> 16 & 255u));
+}
+#endif
 
 }  // namespace svpng

@@ -356,6 +356,97 @@ def png_inflate_batch(datas, infos=None, threads=None):
     return infos, outs, rows, np.array(list(status), np.int32)
 
 
+# ---- K24's host half: PNG cell files -> the one buffer Context.dataset_cells copies to the device (ml/datasets.py:81, :153: the serial half of
+# cv2.imread per sample) -----------
+DATASET_TOO_LARGE = 1          # PackedCells.status of a file with a side above 64: not K24's, read it through imdecode_png(gray=True) + resize_linear
+
+
+class PackedCells:
+    """What dataset_pack returns.  `pinned`: one uint8 torch tensor (pinned when a GPU is there) laid out as
+    records [n] of _native.DATASET_RECORD_DTYPE at records_at | palettes [n_palettes][1024] at palettes_at | filtered bytes at filtered_at.
+    status int32 [n]: 0, a negative sv_status (-1 SV_ERR_BAD_ARG: a file cv2 could not read; -4 SV_ERR_UNSUPPORTED: an Adam7 file) or
+    DATASET_TOO_LARGE; such a file's record has sides 0, which the kernel refuses (zeros out, SV_CELLS_STATUS_REFUSED)."""
+    __slots__ = ("n", "pinned", "records_at", "palettes_at", "n_palettes", "filtered_at", "filtered_size", "status")
+
+    @property
+    def records(self):
+        return self.pinned.numpy()[self.records_at:self.records_at + 16 * self.n].view(_native.DATASET_RECORD_DTYPE)
+
+
+def check_dataset_records(records, filtered_size, n_palettes):
+    """sv_dataset_check_records on a numpy array of _native.DATASET_RECORD_DTYPE: raises NativeError naming the first malformed record."""
+    records = np.ascontiguousarray(records, _native.DATASET_RECORD_DTYPE)
+    _native.check(_native.lib().sv_dataset_check_records(records.ctypes.data_as(C.c_void_p), records.size, int(filtered_size), int(n_palettes)),
+                  "sv_dataset_check_records")
+
+
+def dataset_pack(paths_or_buffers, threads=None):
+    """PNG cell files (paths, or bytes-like file contents) -> PackedCells: sv_png_parse per file, sv_png_inflate_batch over `threads` host
+    threads (default: the CPUs of this process, 16 at the most) straight into the packed buffer, one record and, for colour type 3, one
+    palette per file.  Nothing is raised for a bad file: see PackedCells.status."""
+    import torch
+    items = list(paths_or_buffers)
+    n = len(items)
+    if n == 0:
+        raise ValueError("dataset_pack needs at least one file")
+    status = np.zeros(n, np.int32)
+    datas, infos = [None] * n, [None] * n
+    for i, it in enumerate(items):
+        if isinstance(it, (bytes, bytearray, memoryview)):
+            datas[i] = bytes(it)
+        else:
+            try:
+                with open(os.fspath(it), "rb") as f:
+                    datas[i] = f.read()
+            except OSError:
+                status[i] = -1
+                continue
+        try:
+            infos[i] = png_parse(datas[i])
+        except _native.NativeError as e:
+            status[i] = -4 if "SV_ERR_UNSUPPORTED" in str(e) else -1
+            continue
+        if max(infos[i].width, infos[i].height) > _native.CELLS_MAX_SIDE:
+            status[i] = DATASET_TOO_LARGE
+    ok = [i for i in range(n) if status[i] == 0]
+    pal_of = {i: k for k, i in enumerate(i for i in ok if infos[i].color_type == 3)}
+    sizes = [int(infos[i].filtered_bytes) for i in ok]
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    p = PackedCells()
+    p.n, p.status, p.n_palettes, p.filtered_size = n, status, len(pal_of), int(offsets[-1])
+    p.records_at, p.palettes_at = 0, 16 * n
+    p.filtered_at = p.palettes_at + _native.PNG_PALETTE_STRIDE * p.n_palettes
+    p.pinned = torch.zeros(p.filtered_at + max(p.filtered_size, 1), dtype=torch.uint8)
+    if torch.cuda.is_available():
+        p.pinned = p.pinned.pin_memory()
+    buf = p.pinned.numpy()
+    rec = p.records
+    rec["palette"] = _native.CELLS_NO_PALETTE
+    for k, i in enumerate(ok):
+        inf = infos[i]
+        rec[i] = (offsets[k], inf.width, inf.height, inf.color_type, inf.bit_depth, pal_of.get(i, _native.CELLS_NO_PALETTE))
+        if i in pal_of:
+            at = p.palettes_at + _native.PNG_PALETTE_STRIDE * pal_of[i]
+            buf[at:at + 768] = np.frombuffer(bytes(inf.palette), np.uint8)
+            buf[at + 768:at + 772] = np.frombuffer(np.uint32(inf.palette_entries).tobytes(), np.uint8)
+    m = len(ok)
+    if m:
+        if not threads:
+            cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+            threads = max(1, min(m, cpus, 16))
+        base = buf.ctypes.data + p.filtered_at
+        VP = C.c_void_p * m
+        rcs = (C.c_int * m)()
+        _native.lib().sv_png_inflate_batch((C.c_char_p * m)(*[datas[i] for i in ok]), (C.c_size_t * m)(*[len(datas[i]) for i in ok]),
+                                           (_native.PngInfo * m)(*[infos[i] for i in ok]), m, VP(*[base + int(o) for o in offsets[:-1]]), (C.c_size_t * m)(*sizes),
+                                           None, int(threads), rcs)
+        for k, i in enumerate(ok):
+            if rcs[k]:
+                status[i] = rcs[k]
+                rec[i] = (0, 0, 0, 0, 0, _native.CELLS_NO_PALETTE)
+    return p
+
+
 def mc_dropout_masks(seed, offset, n_samples, B, p_spatial=0.1, p_fc=0.5):
     """The keep masks Context.cnn3_forward_mc draws at (seed, offset) when none are passed in (sv_mc_dropout_masks_host; the generator's
     layout is in include/sudoku_vision_hip.h): (keep1 u8 [S,B,32], keep3 [S,B,64], keepf [S,B,128]), 1 = keep.  A cell's sample has the

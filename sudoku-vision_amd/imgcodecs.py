@@ -20,7 +20,7 @@ PNG is written under names of its own: `imencode_png(img, params)` and `imwrite_
 
 PNG is read under names of its own too: `imdecode_png(buf)` and `imread_png(path)` are `cv2.imdecode(buf, IMREAD_COLOR)` and `cv2.imread(path)` for
 PNG files of every colour type and bit depth, non-interlaced: inflate on host threads (csrc/host_png.cpp), unfilter and expansion to BGR on the
-GPU (csrc/k19_png_decode.hip).  `imread` and `imdecode` themselves still take JPEG only.
+GPU (csrc/k19_png_decode.hip); `gray=True` is `IMREAD_GRAYSCALE`, a [H,W] image.  `imread` and `imdecode` themselves still take JPEG only.
 """
 import os
 
@@ -164,14 +164,17 @@ def imwrite(path, img, params=None, ctx=None, threads=1):
     return ok
 
 
-def imdecode_png(buf, device=False, ctx=None, threads=1):
+def imdecode_png(buf, device=False, ctx=None, threads=1, *, gray=False):
     """cv2.imdecode(buf, IMREAD_COLOR) for the bytes of a PNG file: a BGR uint8 image [H,W,3] whatever the file's colour type and bit depth (16-bit
     samples keep their high byte, gray is replicated, palettes are looked up, alpha is dropped), or None for a file cv2 would fail to read.
-    device=True keeps it on the GPU (CUDA uint8 tensor).  An Adam7 file raises NativeError (SV_ERR_UNSUPPORTED) instead of returning a wrong image."""
+    device=True keeps it on the GPU (CUDA uint8 tensor).  An Adam7 file raises NativeError (SV_ERR_UNSUPPORTED) instead of returning a wrong image.
+    gray=True: cv2.imdecode(buf, IMREAD_GRAYSCALE), a uint8 [H,W] image (ml/datasets.py:81, :153): exact for gray files (colour types 0 and 4);
+    a colour file gives cv2.cvtColor(cv2.imdecode(buf), COLOR_BGR2GRAY), which is argued, not measured, to be cv2's own gray read: libpng
+    converts there and may differ by one level."""
     data = bytes(buf)
     ctx = ctx or default_context()
     try:
-        img = ctx.imdecode_png(data, threads=threads)
+        img = ctx.imdecode_png(data, threads=threads, gray=bool(gray))
     except _native.NativeError as e:
         if "SV_ERR_BAD_ARG" not in str(e):                              # only a malformed file is None; a failed launch or allocation is not a bad file
             raise
@@ -179,14 +182,15 @@ def imdecode_png(buf, device=False, ctx=None, threads=1):
     return img if device else img.cpu().numpy()
 
 
-def imread_png(path, device=False, ctx=None, threads=1):
-    """cv2.imread(path) for a PNG file, whatever the path's extension; None also when the file cannot be opened."""
+def imread_png(path, device=False, ctx=None, threads=1, *, gray=False):
+    """cv2.imread(path) for a PNG file, whatever the path's extension; None also when the file cannot be opened.  gray=True:
+    cv2.imread(path, IMREAD_GRAYSCALE), see imdecode_png."""
     try:
         with open(os.fspath(path), "rb") as f:
             data = f.read()
     except OSError:
         return None
-    return imdecode_png(data, device=device, ctx=ctx, threads=threads)
+    return imdecode_png(data, device=device, ctx=ctx, threads=threads, gray=gray)
 
 
 def _png_args(params):

@@ -893,33 +893,37 @@ class Context:
     # ---- PNG decoder (cv2.imread of a .png path: pipeline/run.py:250, tools/extract_cells.py's files read back) -------------------------
     _PNG_CHUNK_BYTES = 512 << 20                                       # filtered bytes staged per set of launches of an imdecode_png_batch
 
-    def png_reconstruct(self, info, filtered, row_filter, palette=None, out=None):
+    def png_reconstruct(self, info, filtered, row_filter, palette=None, out=None, *, gray=False):
         """The device half alone (sv_png_reconstruct_bgr_u8) on the current stream.  filtered u8 [n, filtered_bytes], row_filter u8 [n, height],
         palette u8 [n, 1024] (colour type 3) on the device -> (out u8 [n,H,W,3], status i32 [n]); status[i] & 1: image i held a palette index past
-        its palette's end.  out: a caller's [n,H,W,3] view with dense pixels (row padding and gaps between frames are left untouched)."""
+        its palette's end.  out: a caller's [n,H,W,3] view with dense pixels (row padding and gaps between frames are left untouched).
+        gray=True: sv_png_reconstruct_gray_u8, the IMREAD_GRAYSCALE read; out is then u8 [n,H,W]."""
         n, H, W = filtered.shape[0], int(info.height), int(info.width)
+        ch = 1 if gray else 3
         _dev_tensor(filtered, "filtered", torch.uint8, self.device, shape=(n, int(info.filtered_bytes)))
         _dev_tensor(row_filter, "row_filter", torch.uint8, self.device, shape=(n, H))
         if palette is not None:
             _dev_tensor(palette, "palette", torch.uint8, self.device, shape=(n, _native.PNG_PALETTE_STRIDE))
         if not (filtered.is_contiguous() and row_filter.is_contiguous() and (palette is None or palette.is_contiguous())):
             raise ValueError("filtered, row_filter and palette must be contiguous")
+        shape = (n, H, W) if gray else (n, H, W, 3)
         if out is None:
-            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
-        _dev_tensor(out, "out", torch.uint8, self.device, shape=(n, H, W, 3))
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        _dev_tensor(out, "out", torch.uint8, self.device, shape=shape)
         st = out.stride()
-        pitch = st[1] if H > 1 else max(st[1], 3 * W)
+        pitch = st[1] if H > 1 else max(st[1], ch * W)
         stride = st[0] if n > 1 else pitch * H
-        if st[3] != 1 or st[2] != 3 or pitch < 3 * W or (n > 1 and stride < pitch * (H - 1) + 3 * W):
-            raise ValueError("out must be a [n,H,W,3] view with dense pixels and rows and frames that do not overlap")
+        if (not gray and st[3] != 1) or st[2] != ch or pitch < ch * W or (n > 1 and stride < pitch * (H - 1) + ch * W):
+            raise ValueError(f"out must be a {list(shape)} view with dense pixels and rows and frames that do not overlap")
         status = torch.empty(n, dtype=torch.int32, device=self.device)
-        self._check(self._lib.sv_png_reconstruct_bgr_u8(self._h, C.byref(info), _ptr(filtered), _ptr(row_filter), _opt_ptr(palette), n, _ptr(out), pitch, stride,
-                                                        _ptr(status), _stream_ptr()), "sv_png_reconstruct_bgr_u8")
+        fn, name = (self._lib.sv_png_reconstruct_gray_u8, "sv_png_reconstruct_gray_u8") if gray else (self._lib.sv_png_reconstruct_bgr_u8, "sv_png_reconstruct_bgr_u8")
+        self._check(fn(self._h, C.byref(info), _ptr(filtered), _ptr(row_filter), _opt_ptr(palette), n, _ptr(out), pitch, stride, _ptr(status), _stream_ptr()), name)
         return out, status
 
-    def imdecode_png_batch(self, datas, threads=16, out=None):
+    def imdecode_png_batch(self, datas, threads=16, out=None, *, gray=False):
         """PNG files of ONE geometry (size, bit depth, colour type; anything else is a ValueError) -> uint8 CUDA tensor [n,H,W,3], each frame what
-        cv2.imdecode(buf, IMREAD_COLOR) returns.  `threads` host threads inflate into pinned memory (csrc/host_png.cpp), the filtered bytes cross
+        cv2.imdecode(buf, IMREAD_COLOR) returns; gray=True: [n,H,W], what cv2.imdecode(buf, IMREAD_GRAYSCALE) returns (colour files: see
+        sv_png_reconstruct_gray_u8).  `threads` host threads inflate into pinned memory (csrc/host_png.cpp), the filtered bytes cross
         PCIe in one copy and one set of launches unfilters and expands them (csrc/k19_png_decode.hip); batches above 512 MiB of filtered bytes go
         in several such sets.  NativeError for a file that is malformed (SV_ERR_BAD_ARG) or not decoded here (SV_ERR_UNSUPPORTED: Adam7).  Returns
         after the last launch, but for palette files, whose indices the GPU checks: those synchronise the current stream."""
@@ -934,9 +938,10 @@ class Context:
         if any(key(i) != key(info) for i in infos):
             raise ValueError("imdecode_png_batch: the files differ in size, bit depth or colour type")
         H, W, fb, ps = int(info.height), int(info.width), int(info.filtered_bytes), _native.PNG_PALETTE_STRIDE
+        shape = (n, H, W) if gray else (n, H, W, 3)
         if out is None:
-            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
-        _dev_tensor(out, "out", torch.uint8, self.device, shape=(n, H, W, 3))
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        _dev_tensor(out, "out", torch.uint8, self.device, shape=shape)
         paletted = info.color_type == 3
         step = max(1, min(n, self._PNG_CHUNK_BYTES // (fb + H + ps)))
         stream = torch.cuda.current_stream(self.device)
@@ -962,7 +967,7 @@ class Context:
                     host_pal[i, 768:772] = np.frombuffer(np.uint32(inf.palette_entries).tobytes(), np.uint8)
                 pal = dev[pal_at:total].view(m, ps)
             dev[:total].copy_(pin[:total], non_blocking=True)
-            _, st = self.png_reconstruct(info, dev[:rows_at].view(m, fb), dev[rows_at:rows_at + m * H].view(m, H), pal, out[at:at + m])
+            _, st = self.png_reconstruct(info, dev[:rows_at].view(m, fb), dev[rows_at:rows_at + m * H].view(m, H), pal, out[at:at + m], gray=gray)
             ev.record(stream)
             flags.append(st)
         if paletted:
@@ -971,9 +976,57 @@ class Context:
                 raise _native.NativeError(f"imdecode_png: SV_ERR_BAD_ARG: image {int(bad.nonzero()[0])} holds a palette index past its palette's end")
         return out
 
-    def imdecode_png(self, data: bytes, threads=1, out=None):
-        """cv2.imdecode / cv2.imread of a PNG file -> BGR uint8 CUDA tensor [H,W,3] (imdecode_png_batch of one file; out: a [H,W,3] view)."""
-        return self.imdecode_png_batch([data], threads, None if out is None else out[None])[0]
+    def imdecode_png(self, data: bytes, threads=1, out=None, *, gray=False):
+        """cv2.imdecode / cv2.imread of a PNG file -> BGR uint8 CUDA tensor [H,W,3] (imdecode_png_batch of one file; out: a [H,W,3] view);
+        gray=True: the IMREAD_GRAYSCALE read, [H,W]."""
+        return self.imdecode_png_batch([data], threads, None if out is None else out[None], gray=gray)[0]
+
+    # ---- K24: a data set of PNG cells -> model input (ml/datasets.py:18-46, :69-92, :141-164; ml/evaluate.py:67) --------------------------------
+    def dataset_cells(self, packed, mode="dataset", want=("f32",)):
+        """One K24 launch over what host.dataset_pack made: one H2D copy of the packed bytes, then sv_dataset_cells on the current stream.
+        mode "dataset" (datasets.preprocess_cell after the gray read) or "gray" (the gray read at 28 x 28 alone); want: "f32", "u8" or both.
+        -> dict with "f32" f32 [n,1,28,28] and / or "u8" u8 [n,28,28], and "status" i32 [n] (bit 0: a palette index past the palette's end,
+        bit 1: the kernel refused the record), all on the device.  Files dataset_pack could not pack (packed.status != 0) have their slot
+        refused.  Does not synchronise."""
+        modes = {"gray": _native.CELLS_GRAY, "dataset": _native.CELLS_DATASET}
+        if mode not in modes:
+            raise ValueError(f"mode must be 'gray' or 'dataset', got {mode!r}")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in ("f32", "u8") for w in want):
+            raise ValueError(f"want must name 'f32', 'u8' or both, got {want!r}")
+        n = packed.n
+        dev = packed.pinned.to(self.device, non_blocking=True)
+        out = {}
+        if "u8" in want:
+            out["u8"] = torch.empty((n, 28, 28), dtype=torch.uint8, device=self.device)
+        if "f32" in want:
+            out["f32"] = torch.empty((n, 1, 28, 28), dtype=torch.float32, device=self.device)
+        out["status"] = torch.empty(n, dtype=torch.int32, device=self.device)
+        # max(., 1): a pack without one decodable file still has a byte there, so that `filtered` is a pointer; every record is then refused
+        self.dataset_cells_raw(dev[packed.filtered_at:packed.filtered_at + max(packed.filtered_size, 1)], dev[packed.records_at:packed.records_at + 16 * n],
+                               dev[packed.palettes_at:packed.palettes_at + _native.PNG_PALETTE_STRIDE * packed.n_palettes] if packed.n_palettes else None,
+                               modes[mode], out.get("u8"), out.get("f32"), out["status"])
+        return out
+
+    def dataset_cells_raw(self, filtered, records, palettes, mode, out_u8, out_f32, status):
+        """sv_dataset_cells itself on the current stream, every argument a device tensor: filtered u8 [filtered_size], records u8 [16 n]
+        (_native.DATASET_RECORD_DTYPE), palettes u8 [1024 k] or None, mode _native.CELLS_*, out_u8 u8 [n,28,28] or None, out_f32 f32 [n,1,28,28]
+        or None, status i32 [n].  The kernel refuses what sv_dataset_check_records would; nothing here reads the records."""
+        n = status.numel()
+        _dev_tensor(filtered, "filtered", torch.uint8, self.device, ndim=1)
+        _dev_tensor(records, "records", torch.uint8, self.device, shape=(16 * n,))
+        _dev_tensor(status, "status", torch.int32, self.device, shape=(n,))
+        if palettes is not None:
+            _dev_tensor(palettes, "palettes", torch.uint8, self.device, ndim=1)
+        if out_u8 is not None:
+            self._out(out_u8, (n, 28, 28), torch.uint8, "out_u8")
+        if out_f32 is not None:
+            self._out(out_f32, (n, 1, 28, 28), torch.float32, "out_f32")
+        if not (filtered.is_contiguous() and records.is_contiguous() and status.is_contiguous() and (palettes is None or palettes.is_contiguous())):
+            raise ValueError("filtered, records, palettes and status must be contiguous")
+        n_pal = 0 if palettes is None else palettes.numel() // _native.PNG_PALETTE_STRIDE
+        self._check(self._lib.sv_dataset_cells(self._h, _ptr(filtered), filtered.numel(), _ptr(records), n, _opt_ptr(palettes), n_pal, int(mode), _opt_ptr(out_u8),
+                                               _opt_ptr(out_f32), _ptr(status), _stream_ptr()), "sv_dataset_cells")
 
     def softmax_topk(self, logits, k=3):
         """F.softmax(logits, 1).topk(k) (pipeline/run_v2.py:165-178): (index u8 [B,k], prob f32 [B,k]), best first."""
