@@ -573,7 +573,8 @@ typedef struct sv_eval_failure {
  *   p = softmax(input / temperature) by k_softmax_topk's sequence of operations -- z = input / T, m = max z, e = expf(z - m),
  *   den = e0 + ... + e9 in class order, p = e / den -- so probs is bit-identical to what sv_softmax_topk_f32 returns for the same
  *   logits at T = 1; in probability mode p = input;
- *   pred = argmax of the input, ties to the lowest class; conf = p[pred]; true_prob = p[label];
+ *   pred = argmax of the input, ties to the lowest class, a NaN entry counting as the largest and the first NaN winning (np.argmax,
+ *   torch.argmax); conf = p[pred]; true_prob = p[label];
  *   nll = logsumexp(z) - z[label] = logf(den) - (z[label] - m)   (probability mode: -logf(p[label]));  correct = pred == label.
  * Per-cell outputs, each [dev] and each may be NULL: probs [B*10], pred [B], conf [B], true_prob [B], nll [B], correct [B].  A cell
  * that is not finite gets whatever the arithmetic gives (NaN probabilities) and correct 0; a bad label gets true_prob = nll = NaN.
@@ -587,7 +588,9 @@ typedef struct sv_eval_failure {
  * failures [dev, max_failures records, or NULL with max_failures 0]: record r is the r-th wrong valid cell in sample order counted
  * from the last clear of stats (ml/evaluate_v2.py:203-206: the list stops at max_failures); its place comes from a prefix sum over
  * the wrong flags (per workgroup counts, one scan launch), not from an atomic append.  stats->n_wrong is the total whatever
- * max_failures is.  Records past min(n_wrong, max_failures) are not written.
+ * max_failures is.  Records past min(n_wrong, max_failures) are not written.  Every accumulating call's wrong cells take their places,
+ * whatever its own max_failures: a call with max_failures 0 between two others writes nothing, the later call's records start behind
+ * the places of its wrong cells, and the records of those places stay unwritten.
  * Asynchronous on `stream`; reads nothing back.  Scratch (only with max_failures > 0) lives in the context and only grows: a first
  * call at a larger B allocates, so warm up before capturing into a graph.
  * SV_ERR_BAD_ARG: NULL ctx / input / labels / stats / bin_edges, B < 0 or B * 2^30 >= 2^62, index_base < 0, temperature not finite

@@ -44,6 +44,11 @@ __device__ __forceinline__ void eval_cell(const float *__restrict__ in, const vo
 #pragma unroll
     for (int j = 1; j < 10; j++)
         if (l[j] > top) { top = l[j]; c.pred = j; }
+    if (!c.finite) {                                        // rare: a NaN is the maximum, the first one (np.argmax, torch.argmax)
+#pragma unroll
+        for (int j = 9; j >= 0; j--)
+            if (l[j] != l[j]) { top = l[j]; c.pred = j; }
+    }
     const long label = i64 ? (long)((const long long *)labels)[cell] : (long)((const int *)labels)[cell];
     c.label = label >= 0 && label < 10 ? (int)label : -1;
     c.zl = 0.f;

@@ -10,6 +10,8 @@ lines do it.
   failures            ml/evaluate_v2.py:194-220 from per-batch probabilities
   train_evaluate      ml/train.py:157-190 from per-batch logits
   aggregates          sv_eval_stats as Context.eval_stats_dict shows it, in Python integers, from per-cell pred / conf / labels
+  aggregates_fast     the same dictionary from np.searchsorted and np.bincount, for the large size
+  per_cell_prob       the probability-input mode: pred, conf, true_prob from the given f32 rows, nll = -log in float64, the finite rule
 
 and the inputs the GPU tests use (tests/test_eval_ref.py checks each does what it was built for)."""
 import numpy as np
@@ -151,6 +153,51 @@ def aggregates(pred, conf, labels, n_bins, finite=None, edges=None):
     return out
 
 
+def per_cell_prob(probs, labels):
+    """Probability-input mode (compute_calibration's argument, ml/evaluate_v2.py:152-154; the sv_eval_metrics comment): probs f32 [B,10],
+    labels int [B] in 0..9 -> dict: pred (np.argmax of the f32 rows: first maximum, a NaN counting as the largest), conf and true_prob
+    (the f32 input entries themselves), nll (-log in float64 of true_prob: +inf at 0, NaN below 0), correct, finite (all ten entries
+    finite and 0 <= max <= 1)."""
+    p = np.asarray(probs, np.float32)
+    labels = np.asarray(labels).astype(np.int64)
+    rows = np.arange(len(p))
+    pred = np.argmax(p, 1)
+    conf, true_prob = p[rows, pred], p[rows, labels]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nll = -np.log(true_prob.astype(np.float64))
+        top = p.max(1)
+        finite = np.isfinite(p).all(1) & (top >= 0) & (top <= 1)
+    return {"pred": pred, "conf": conf, "true_prob": true_prob, "nll": nll, "correct": pred == labels, "finite": finite}
+
+
+def aggregates_fast(pred, conf, labels, n_bins, finite=None, edges=None):
+    """aggregates' vectorised twin for the large size: the same dictionary from np.searchsorted (the first edge >= conf, so bin k - 1 when
+    1 <= k <= n_bins) and np.bincount.  tests/test_eval_ref.py holds it to aggregates for every entry of EDGE_SETS."""
+    pred, labels = np.asarray(pred).astype(np.int64), np.asarray(labels).astype(np.int64)
+    conf = np.asarray(conf, np.float32)
+    finite = np.ones(len(pred), bool) if finite is None else np.asarray(finite, bool)
+    edges = np.linspace(0, 1, n_bins + 1) if edges is None else np.asarray(edges, np.float64)
+    bad = finite & ((labels < 0) | (labels > 9))
+    valid = finite & ~bad
+    pred, labels, c = pred[valid], labels[valid], conf[valid].astype(np.float64)
+    ok = pred == labels
+    fx = (c * CONF_ONE).astype(np.int64)                                   # towards zero, as int() of a float; the sums stay below 2^62
+    k = np.searchsorted(edges, c, side="left")
+    binned = (k >= 1) & (k <= n_bins)
+    b = k[binned] - 1
+
+    def per_bin(weights):
+        out = np.zeros(n_bins, np.int64)
+        np.add.at(out, b, weights[binned])
+        return [int(v) for v in out]
+
+    groups = (np.ones(len(ok), bool), ok, ~ok)
+    return {"confusion": np.bincount(labels * 10 + pred, minlength=100).reshape(10, 10).tolist(), "n": int(valid.sum()), "n_correct": int(ok.sum()),
+            "n_wrong": int((~ok).sum()), "bad_labels": int(bad.sum()), "nonfinite": int((~finite).sum()),
+            "bin_count": per_bin(np.ones(len(ok), np.int64)), "bin_correct": per_bin(ok.astype(np.int64)), "bin_conf": per_bin(fx),
+            "tot_count": [int(g.sum()) for g in groups], "tot_correct": [int((g & ok).sum()) for g in groups], "tot_conf": [int(fx[g].sum()) for g in groups]}
+
+
 def ece_of(agg):
     """The expected calibration error of an aggregates() / eval_stats_dict dictionary, in float64 (ml/evaluate_v2.py:171-173)."""
     total = 0.0
@@ -246,3 +293,96 @@ def edge_cells():
     out["nonfinite"] = (zn, lab)
     out["mixed"] = (z, lab)
     return out
+
+
+# ---- inputs of tests/test_gpu_eval_modes.py: probability mode, caller bin edges, the long failure list -------------------------------------
+EDGE_SETS = {                                  # name -> (bin_edges as doubles, n_bins)
+    "uniform10": (np.linspace(0, 1, 11), 10),                               # the default
+    "decimal": (np.array([0, 0.1, 0.3, 0.7, 1.0]), 4),                      # f32(0.1), f32(0.3) lie above their double edge, f32(0.7) below
+    "repeated": (np.array([0, 0.5, 0.5, 0.5, 1.0]), 4),                     # bins 1 and 2 are empty whatever the cells
+    "inner": (np.array([0.2, 0.4, 0.9]), 2),                                # cells below 0.2 and above 0.9 are in no bin
+    "one": (np.array([0.125, 1.0]), 1),                                     # a conf of 0.125 sits on the open lower edge: no bin
+    "fine64": (np.linspace(0, 1, 65) ** 2, 64),                             # 65 non-uniform edges: all of the LDS copy
+}
+
+
+def _prob_row(top, at, rest):
+    r = np.full(10, rest, np.float32)
+    r[at] = top
+    return r
+
+
+def prob_cells():
+    """Rows for the probability-input mode -> (probs f32 [N,10], labels int64 [N], marks: name -> row index).  The first 2 * 257 rows are
+    the torch-CPU f32 softmax of the first 257 random_cells at scale 1 and at scale 30 (many rows with conf == 1.0, entries that are
+    denormal or zero), with their labels.  Then the crafted rows, each named in marks for what it is there for:
+      tiny          all ten 1e-12: valid, the fixed-point term is 0, bin 0 of uniform edges
+      zeros         all ten 0: pred 0, counted in n, in no bin of edges that start at 0; label 0: true_prob 0, nll +inf
+      sub_unit      all ten 0.75 * 2^-30: the fixed-point term truncates to 0 (rounding would give 1)
+      small         top f32(0.001): 0.001 * 2^30 is no integer, the term truncates
+      negatives     top 0.6, the others between -3 and -1, a wrong cell: its top-3 is 0.6, then two entries of -1.0, lowest class first
+      neg_label     a valid wrong cell whose label points at -0.05: true_prob < 0, nll NaN
+      above_one     top nextafter(1, 2): not finite by the mode's rule;  neg_top: top -0.25, all others lower: the same
+      nan, inf      one NaN entry (class 3, not the first: np.argmax gives 3), one +inf entry: not finite
+      on_0.1, on_0.3, on_0.7, on_0.125, below_0.5   the maximum is exactly f32(0.1), f32(0.3), f32(0.7), 0.125, nextafter(f32(0.5), 0)
+    Made once, not writable."""
+    if "prob" not in _POOL:
+        import torch
+        parts, labels = [], []
+        for scale in SCALES:
+            z, lab = random_cells(scale)
+            parts.append(torch.softmax(torch.from_numpy(z[:257].copy()), 1).numpy())
+            labels.append(lab[:257])
+        f = np.float32
+        crafted = [
+            ("tiny", _prob_row(1e-12, 0, 1e-12), 0),
+            ("zeros", np.zeros(10, f), 0),
+            ("sub_unit", _prob_row(0.75 * 2.0 ** -30, 0, 0.75 * 2.0 ** -30), 4),
+            ("small", _prob_row(0.001, 6, 0.0005), 6),
+            ("negatives", np.array([-2.5, -1.0, -3.0, -1.5, 0.6, -1.0, -2.0, -1.25, -2.75, -1.75], f), 7),
+            ("neg_label", np.array([0.9, 0.05, -0.05, 0.1, 0, 0, 0, 0, 0, 0], f), 2),
+            ("above_one", _prob_row(np.nextafter(f(1), f(2)), 2, 0.0), 2),
+            ("neg_top", _prob_row(-0.25, 5, -0.5), 5),
+            ("nan", np.array([0.1, 0.2, 0.05, np.nan, 0.3, 0.05, 0.1, 0.1, 0.05, 0.05], f), 4),
+            ("inf", np.array([0.1, 0.2, 0.05, 0.05, 0.3, 0.05, np.inf, 0.1, 0.05, 0.05], f), 6),
+            ("on_0.1", _prob_row(f(0.1), 9, 0.05), 9),
+            ("on_0.3", _prob_row(f(0.3), 1, 0.07), 0),
+            ("on_0.7", _prob_row(f(0.7), 8, 0.03), 8),
+            ("on_0.125", _prob_row(0.125, 3, 0.0625), 3),
+            ("below_0.5", _prob_row(np.nextafter(f(0.5), f(0)), 7, 0.05), 2),
+        ]
+        at = 2 * 257
+        marks = {name: at + i for i, (name, _, _) in enumerate(crafted)}
+        probs = np.concatenate(parts + [np.stack([r for _, r, _ in crafted])]).astype(np.float32)
+        lab = np.concatenate(labels + [np.array([c for _, _, c in crafted], np.int64)])
+        probs.setflags(write=False)
+        lab.setflags(write=False)
+        _POOL["prob"] = (probs, lab, marks)
+    return _POOL["prob"]
+
+
+LONG_TILE = 300                                # the all-wrong tile: cells 76,800 .. 77,055, past the seam between scan chunks at tile 256
+LONG_SEAMS = (0, 255, 256, 65535, 65536, 65791, 131071, 131072, 262143, 262144, 262145)
+
+
+def long_list_cells():
+    """The SIZES[-1] = 262,146 random_cells(1.0) with each label set to the row's argmax, but for 300 wrong cells: LONG_SEAMS (the ends of
+    tile 0; both sides of cell 65,536, where k_eval_scan goes from its first chunk of 256 tiles to the second, and the end of that
+    chunk's first tile; both sides of 131,072; the last cell of a workgroup's first tile, 262,143, and the two cells of workgroup 0's
+    second tile), cell 100 (tile 0 then holds another count of wrong cells than tile 1,024, the tile whose count a workgroup-indexed write
+    would put in its place), all 256 cells of tile LONG_TILE, and 32 more drawn from the whole range.
+    -> logits f32, labels int64, the wrong indices in order.  Made once, not writable."""
+    if "long" not in _POOL:
+        z, _ = random_cells(1.0)
+        n = len(z)
+        pred = z.argmax(1).astype(np.int64)
+        fixed = set(LONG_SEAMS) | {100} | set(range(LONG_TILE * 256, LONG_TILE * 256 + 256))
+        rs = np.random.RandomState(2121)
+        extra = [int(i) for i in rs.permutation(n) if int(i) not in fixed][:300 - len(fixed)]
+        wrong = np.array(sorted(fixed | set(extra)), np.int64)
+        labels = pred.copy()
+        labels[wrong] = (pred[wrong] + 1 + wrong % 8) % 10                  # any class but the prediction
+        labels.setflags(write=False)
+        wrong.setflags(write=False)
+        _POOL["long"] = (z, labels, wrong)
+    return _POOL["long"]

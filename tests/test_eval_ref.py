@@ -184,3 +184,122 @@ def test_edge_cells_are_edges():
     assert sorted(lab[(lab < 0) | (lab > 9)].tolist()) == [-1, 10]
     z, lab = e["nonfinite"]
     assert np.isnan(z).sum() == 1 and np.isinf(z).sum() == 1 and (~np.isfinite(z)).any(1).sum() == 2
+
+
+# ---- the inputs of tests/test_gpu_eval_modes.py ----------------------------------------------------------------------------------------------
+def test_decimal_edges_fall_on_the_side_they_were_chosen_for():
+    """f32(0.1) and f32(0.3) lie above the double edge of the same name, f32(0.7) below: comparing in float would move each cell."""
+    edges, n_bins = er.EDGE_SETS["decimal"]
+    assert n_bins == 4 and edges.dtype == np.float64 and edges.tolist() == [0, 0.1, 0.3, 0.7, 1.0]
+    for v, above in ((0.1, True), (0.3, True), (0.7, False)):
+        c = float(np.float32(v))
+        print(f"f32({v}) = {c!r}: {'above' if c > v else 'below'} the double edge {v!r}")
+        assert (c > v) == above and c != v and np.float32(v) == np.float32(c)
+    for name, (edges, n_bins) in er.EDGE_SETS.items():
+        assert len(edges) == n_bins + 1 and (np.diff(edges) >= 0).all() and 1 <= n_bins <= 64, name
+    assert er.EDGE_SETS["uniform10"][0].tolist() == np.linspace(0, 1, 11).tolist() and er.EDGE_SETS["fine64"][1] == 64
+    assert len(set(np.diff(er.EDGE_SETS["fine64"][0]).round(12).tolist())) == 64, "fine64 is not uniform"
+
+
+def test_prob_cells_are_what_they_are_for():
+    probs, labels, marks = er.prob_cells()
+    r = er.per_cell_prob(probs, labels)
+    f = np.float32
+    assert probs.dtype == np.float32 and len(probs) == 2 * 257 + len(marks) and len(set(marks.values())) == len(marks) == 15
+    soft = probs[:514]
+    assert r["finite"][:514].all() and (soft[257:].max(1) == 1.0).sum() > 10, "scale 30 saturates"
+    tiny = np.abs(soft[257:])
+    assert (tiny == 0).any() and ((tiny > 0) & (tiny < 2.0 ** -126)).any(), "scale 30 gives zero and denormal entries"
+    assert 0 < r["correct"][:514].sum() < 514
+
+    def row(name):
+        i = marks[name]
+        return {k: v[i] for k, v in r.items()}, probs[i], int(labels[i])
+
+    c, p, lab = row("tiny")
+    assert c["finite"] and c["pred"] == 0 and int(float(c["conf"]) * er.CONF_ONE) == 0 and 0 < float(c["conf"]) <= 0.1
+    c, p, lab = row("zeros")
+    assert c["finite"] and c["pred"] == 0 == lab and c["conf"] == 0 and c["true_prob"] == 0 and c["nll"] == np.inf and c["correct"]
+    c, p, lab = row("sub_unit")
+    assert c["finite"] and float(c["conf"]) * er.CONF_ONE == 0.75
+    c, p, lab = row("small")
+    fx = float(c["conf"]) * er.CONF_ONE
+    assert c["finite"] and fx - int(fx) > 0.5 and float(c["conf"]) < 2.0 ** -7, "rounding the fixed-point term would add one"
+    c, p, lab = row("negatives")
+    order = np.argsort(-p, kind="stable")[:3]
+    assert c["finite"] and not c["correct"] and p.max() == f(0.6) and (np.delete(p, c["pred"]) <= -1).all() and (p >= -3).all()
+    assert order.tolist() == [4, 1, 5] and p[1] == p[5] == -1.0 and c["true_prob"] < 0 and np.isnan(c["nll"])
+    c, p, lab = row("neg_label")
+    assert c["finite"] and not c["correct"] and c["true_prob"] < 0 and np.isnan(c["nll"]) and p.max() == f(0.9)
+    c, p, lab = row("above_one")
+    assert not c["finite"] and np.isfinite(p).all() and p.max() == np.nextafter(f(1), f(2)) > 1
+    c, p, lab = row("neg_top")
+    assert not c["finite"] and np.isfinite(p).all() and p.max() == f(-0.25) and c["pred"] == 5 and (np.delete(p, 5) < -0.25).all()
+    c, p, lab = row("nan")
+    assert not c["finite"] and np.isnan(p).sum() == 1 and c["pred"] == 3 != np.nanargmax(p), "np.argmax takes the NaN, not the largest number"
+    c, p, lab = row("inf")
+    assert not c["finite"] and np.isinf(p).sum() == 1 and c["pred"] == 6
+    for name, top in (("on_0.1", f(0.1)), ("on_0.3", f(0.3)), ("on_0.7", f(0.7)), ("on_0.125", f(0.125)), ("below_0.5", np.nextafter(f(0.5), f(0)))):
+        c, p, lab = row(name)
+        assert c["finite"] and c["conf"] == top and (np.delete(p, c["pred"]) < top).all(), name
+    assert f(0.125) == 0.125 and float(np.nextafter(f(0.5), f(0))) < 0.5
+    wrong_valid = r["finite"] & ~r["correct"]
+    assert {marks[k] for k in ("negatives", "neg_label", "on_0.3", "below_0.5")} <= set(np.nonzero(wrong_valid)[0].tolist())
+    assert sorted(np.nonzero(~r["finite"])[0].tolist()) == sorted(marks[k] for k in ("above_one", "neg_top", "nan", "inf"))
+    # where the crafted cells land: derived by hand from evaluate_v2.py:163, `conf > edges[i] and conf <= edges[i + 1]`
+    where = {name: {} for name in er.EDGE_SETS}
+    for name, (edges, n_bins) in er.EDGE_SETS.items():
+        for k, i in marks.items():
+            if r["finite"][i]:
+                one = er.aggregates(r["pred"][i:i + 1], r["conf"][i:i + 1], labels[i:i + 1], n_bins, edges=edges)["bin_count"]
+                where[name][k] = one.index(1) if 1 in one else None
+    assert where["uniform10"]["tiny"] == 0 and where["uniform10"]["zeros"] is None and where["uniform10"]["on_0.1"] == 1 and where["uniform10"]["below_0.5"] == 4
+    assert [where["decimal"][k] for k in ("on_0.1", "on_0.3", "on_0.7", "on_0.125", "negatives")] == [1, 2, 2, 1, 2]
+    assert where["repeated"]["below_0.5"] == 0 and where["repeated"]["negatives"] == 3 and where["repeated"]["zeros"] is None
+    assert where["inner"]["on_0.1"] is None and where["inner"]["on_0.3"] == 0 and where["inner"]["neg_label"] == 1
+    assert where["one"]["on_0.125"] is None and where["one"]["on_0.1"] is None and where["one"]["on_0.3"] == 0
+    for name, (edges, n_bins) in er.EDGE_SETS.items():
+        agg = er.aggregates(r["pred"], r["conf"], labels, n_bins, finite=r["finite"], edges=edges)
+        assert agg["nonfinite"] == 4 and agg["n"] == len(probs) - 4
+        if name == "fine64":
+            assert agg["bin_count"][63] > 10, "the last bin of fine64 holds the saturated cells: a missing last edge changes a count"
+        if name == "repeated":
+            assert agg["bin_count"][1] == agg["bin_count"][2] == 0 and agg["bin_count"][0] > 0 and agg["bin_count"][3] > 0
+        if name == "inner":
+            assert 0 < sum(agg["bin_count"]) < agg["n"] and (r["conf"][r["finite"]] < 0.2).any() and (r["conf"][r["finite"]] > 0.9).any()
+
+
+def test_vectorised_aggregates_equal_the_loop():
+    """aggregates_fast against aggregates on 3,000 logits cells at both scales, with bad labels and non-finite cells, and on prob_cells(),
+    for every edge set and the default edges."""
+    cases = []
+    for scale in er.SCALES:
+        z, labels = er.random_cells(scale)
+        r = er.per_cell(z[:3000], labels[:3000])
+        lab = labels[:3000].copy()
+        lab[[7, 1500]] = [10, -1]
+        finite = np.ones(3000, bool)
+        finite[[3, 8, 2999]] = False
+        cases.append((r["pred"], r["conf"].astype(np.float32), lab, finite))
+    probs, labels, _ = er.prob_cells()
+    r = er.per_cell_prob(probs, labels)
+    cases.append((r["pred"], r["conf"], labels, r["finite"]))
+    for pred, conf, lab, finite in cases:
+        for name, (edges, n_bins) in er.EDGE_SETS.items():
+            assert er.aggregates_fast(pred, conf, lab, n_bins, finite=finite, edges=edges) == er.aggregates(pred, conf, lab, n_bins, finite=finite, edges=edges), name
+        for n_bins in er.BIN_COUNTS:
+            assert er.aggregates_fast(pred, conf, lab, n_bins, finite=finite) == er.aggregates(pred, conf, lab, n_bins, finite=finite)
+
+
+def test_long_list_cells_are_placed():
+    z, labels, wrong = er.long_list_cells()
+    assert len(z) == er.SIZES[-1] == 262146 and len(wrong) == 300 and (np.diff(wrong) > 0).all()
+    pred = z.argmax(1)
+    assert (np.nonzero(pred != labels)[0] == wrong).all() and ((labels >= 0) & (labels <= 9)).all()
+    have = set(wrong.tolist())
+    assert {0, 255, 256, 65535, 65536, 65791, 131071, 131072, 262143, 262144, 262145} <= have
+    tile = wrong // 256
+    assert (tile == er.LONG_TILE).sum() == 256 and er.LONG_TILE > 256, "one whole tile past the seam between scan chunks is wrong"
+    assert (tile < 256).any() and ((tile >= 256) & (tile < 512)).any() and (tile == 1024).sum() == 2
+    assert (tile >= 512).sum() > 5 and len(set(tile.tolist())) > 30
+    assert (tile == 0).sum() != (tile == 1024).sum(), "workgroup 0's two tiles hold different counts"
